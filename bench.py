@@ -82,6 +82,9 @@ def parse_args(argv=None):
     ap.add_argument("--roofline-only", action="store_true",
                     help="only the isolated launches of the dominant (layer-2) kernel: run under `rocprofv3 --kernel-trace "
                          "--stats` to get a per-kernel average that is directly comparable with roofline.avg_launch_us")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the [group, 4] ELBO sums, the per-pair scalars "
+                         "and the logits) as DIR/<name>.npy in float32, at most 64 MB in all (larger arrays: a fixed seeded sample)")
     return ap.parse_args(argv)
 
 
@@ -257,6 +260,30 @@ def run_groups(main_ev, full, warm, tail_ev, dist=None, collective_every_eval=Fa
         dt = float(tmax.item())
     run_groups.last_reduced = slots
     return dt
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays, limit=DUMP_LIMIT_BYTES):
+    """`arrays` {name: tensor} -> d/<name>.npy in float32, smallest first.  An array that does not fit in what is left of
+    `limit` is written as `<name>_sampled.npy`: the flat elements at a fixed set of indices (numpy default_rng(0), sorted),
+    the same for every run with the same shapes."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    left = limit
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):
+        t = t.detach().float()
+        cap = max(0, (left - 4096) // 4)                           # (npy header allowance)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=cap, replace=False))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+            name += "_sampled"
+        else:
+            a = t.cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), a)
+        left -= a.nbytes + 4096
 
 
 # ------------------------------------------------------------------------------------------ GPU side
@@ -681,6 +708,7 @@ def main():
     ev = make_evaluator(engine, net, x, y, S_global, G, graph=not args.no_graph)
     assert ev.s_local == S_local and ev.n_local == G * S_local
     tail = make_evaluator(engine, net, x, y, S_global, rem, graph=not args.no_graph) if rem else None
+    counter0 = ev.counter.clone()                       # the Philox sample counter the first replay draws from
     if args.roofline_only:
         torch.cuda.synchronize()
         roof = layer2_roofline(ev, net, dims, args.batch, lr, args.math)
@@ -696,7 +724,12 @@ def main():
     if args.settle_ms > 0 and full > 0:
         n_settle = max(1, int(args.settle_ms * 1e-3 / (dt_cold / full) + 0.999))
         run_groups(ev, n_settle, 0, None, dist)
+        # rewound: the measured W + K steps draw the epsilon of the cold ones, whatever number of settle replays ran before
+        ev.counter.copy_(counter0)
         dt = run_groups(ev, full, warm, tail, dist)
+    if args.dump_outputs and rank == 0 and full > 0:
+        sums = run_groups.last_reduced[(full + warm - 1) & 1] if dist is not None else ev.sums
+        dump_outputs(args.dump_outputs, {"sums": sums, "logits": ev.logits, **ev.out})
     if dist is not None and run_groups.last_reduced is not None and full > 0:
         got = run_groups.last_reduced[(full + warm - 1) & 1][..., 3]         # every all-reduced row: the GLOBAL sample count
         assert bool((got == float(S_global)).all()), f"all-reduced sample counts {got.flatten().tolist()} != {S_global}"

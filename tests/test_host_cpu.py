@@ -297,6 +297,27 @@ def test_bench_times_any_step_count_exactly():
     assert bench.plan_groups(20, 5, 256) == (20, 1, 0, 1) and bench.plan_groups(8192, 512, 256) == (256, 32, 0, 2)
 
 
+def test_bench_dump_outputs_stays_under_its_limit(tmp_path):
+    '''bench.dump_outputs: every array as float32 .npy, whole while it fits; one that does not fit the rest of the limit
+    is a fixed seeded sample of its elements, identical from call to call.'''
+    import bench
+    import torch
+    big = torch.arange(300_000, dtype=torch.float64).reshape(3, 100_000)
+    arrays = {"sums": torch.ones(8, 4), "nll": torch.arange(8, dtype=torch.bfloat16), "logits": big}
+    limit = 1 << 20
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["logits_sampled.npy", "nll.npy", "sums.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= limit
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "sums.npy"), np.ones((8, 4), np.float32))
+    s = np.load(tmp_path / "a" / "logits_sampled.npy")
+    assert 0 < s.size < big.numel() and np.all(np.diff(s) > 0)      # distinct elements of the flat array, in order
+
+
 def test_bench_gpus_flag_is_honoured_or_refused():
     '''`bench.py --gpus N` never reports a run of another size: under a launcher whose WORLD_SIZE disagrees it exits 2
     before touching a device, and without a launcher it starts N rank processes itself (here, with no GPU, every
