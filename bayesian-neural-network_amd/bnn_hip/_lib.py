@@ -7,7 +7,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BNN_HIP_LIB") or os.path.join(_HERE, "libbnn_hip.so")   # env: diagnostic builds only
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 # enums of include/bnn_hip.h
 F32, BF16 = 0, 1
@@ -26,7 +26,7 @@ EXPORTS = (
     "bnn_lr_linear_fwd_workspace_bytes", "bnn_lr_split_scratch_bytes", "bnn_lr_split_scratch_zero_bytes", "bnn_lr_linear_fwd", "bnn_lr_final_fwd", "bnn_lr_plan", "bnn_bbb_plan", "bnn_lr_prepare_bytes", "bnn_lr_prepare", "bnn_lr_prepare_x3_bytes", "bnn_lr_prepare_x3", "bnn_lr_prepare_many",
     "bnn_gauss_kl_workspace_bytes", "bnn_gauss_kl",
     "bnn_elbo_finalize", "bnn_bbb_final_fwd", "bnn_bbb_final_scratch_bytes", "bnn_philox_normal", "bnn_cast_bf16", "bnn_softplus", "bnn_eval_prepare",
-    "bnn_ece_workspace_bytes", "bnn_ece", "bnn_snr_db", "bnn_snr_prune",
+    "bnn_ece_workspace_bytes", "bnn_ece", "bnn_snr_db", "bnn_snr_prune", "bnn_mc_predictive",
 )
 
 
@@ -200,6 +200,22 @@ class PrepareArgs(C.Structure):
                 ("cast_dst_lo", C.c_void_p)]
 
 
+PREDICTIVE_MAX_QUANTILES = 8
+PREDICTIVE_MAX_QUANTILE_SAMPLES = 1024
+
+
+class McPredictiveArgs(C.Structure):
+    """bnn_mc_predictive_args (include/bnn_hip.h)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("mode", C.c_int32),
+                ("groups", C.c_int32), ("n_samples", C.c_int32), ("batch", C.c_int32), ("classes", C.c_int32),
+                ("logits", C.c_void_p), ("scale", C.c_float), ("sigma", C.c_float),
+                ("probs", C.c_void_p), ("preds", C.c_void_p), ("predictive_entropy", C.c_void_p),
+                ("expected_entropy", C.c_void_p), ("mutual_information", C.c_void_p),
+                ("mean", C.c_void_p), ("variance", C.c_void_p), ("predictive_variance", C.c_void_p),
+                ("n_quantiles", C.c_int32), ("reserved", C.c_int32),
+                ("quantile", C.c_double * PREDICTIVE_MAX_QUANTILES), ("quantiles", C.c_void_p)]
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -326,6 +342,8 @@ def _load_real():
     lib.bnn_snr_db.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     lib.bnn_snr_prune.restype = C.c_int
     lib.bnn_snr_prune.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
+    lib.bnn_mc_predictive.restype = C.c_int
+    lib.bnn_mc_predictive.argtypes = [C.POINTER(McPredictiveArgs), C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

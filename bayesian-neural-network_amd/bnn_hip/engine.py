@@ -14,6 +14,7 @@ import torch
 from . import _lib as L
 from . import ops
 from .functional import AllReduceSumFn, BBBLinearFn, ElboFn, LayerCall, LRLinearFn, NetCall, NLLFn
+from .ops import Predictive
 from .runtime import state, take_samples
 
 
@@ -500,6 +501,62 @@ def mc_predict(layers: Sequence[LayerSpec], x: torch.Tensor, samples: int):
     return preds, probs
 
 
+def _first_minibatch(p: Predictive) -> Predictive:
+    """The [B, ...] views of a Predictive of [1, B, ...] tensors (quantiles [Q, 1, B, out] -> [Q, B, out])."""
+    return Predictive(*(None if t is None else (t[:, 0] if f == "quantiles" else t[0]) for f, t in zip(p._fields, p)))
+
+
+def combine_predictive(out: Predictive, mode: str, samples: int, world: int, sigma: float = 1.0) -> Predictive:
+    """The predictive summaries of a sample-sharded job from every rank's partials (bnn_mc_predictive, partial=True), in
+    place in `out`, on every rank.  Classification: the sums probs = sum_s p_s / S and expected_entropy = sum_s H(p_s) / S
+    are sum-all-reduced, then preds, predictive_entropy and mutual_information are formed from them.  Regression: the
+    per-rank (count, mean, variance) are all-gathered and merged with Chan et al.'s pairwise formula in fp64,
+        mean = sum_r n_r m_r / n,   M2 = sum_r n_r v_r + sum_r n_r (m_r - mean)^2,   variance = M2 / n."""
+    import torch.distributed as dist
+    if mode == "classification":
+        dist.all_reduce(out.probs, op=dist.ReduceOp.SUM)
+        dist.all_reduce(out.expected_entropy, op=dist.ReduceOp.SUM)
+        out.preds.copy_(torch.argmax(out.probs, dim=-1))
+        out.predictive_entropy.copy_(-torch.special.xlogy(out.probs, out.probs).sum(-1))
+        out.mutual_information.copy_(torch.clamp(out.predictive_entropy - out.expected_entropy, min=0.0))
+        return out
+    counts = [shard_range(samples, r, world)[1] for r in range(world)]
+    mine = torch.stack([out.mean, out.variance])
+    parts = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(parts, mine)
+    n = float(sum(counts))
+    mean = sum(c * p[0].double() for c, p in zip(counts, parts)) / n
+    m2 = sum(c * (p[1].double() + (p[0].double() - mean) ** 2) for c, p in zip(counts, parts))
+    out.mean.copy_(mean)
+    out.variance.copy_(m2 / n)
+    out.predictive_variance.copy_(m2 / n + float(sigma) ** 2)
+    return out
+
+
+def mc_predictive(layers: Sequence[LayerSpec], x: torch.Tensor, samples: int, mode: str, quantiles=(), sigma: float = 1.0) -> Predictive:
+    """F3: the predictive summaries of `samples` stochastic passes of one minibatch (bnn_mc_predictive over mc_forward's
+    outputs); with sample sharding on, every rank summarises its share and combine_predictive merges them."""
+    if mode not in ("classification", "regression"):
+        raise Exception("Training mode must be either 'regression' or 'classification'")
+    if mode == "classification" and quantiles:
+        raise ops.BnnHipError("predictive: quantiles are a regression summary")
+    q = ops.quantile_levels(quantiles)
+    rank, world = dist_info()
+    if world > 1 and q:
+        raise ops.BnnHipError("predictive: quantiles need every MC sample on one rank (sample sharding is on)")
+    logits = mc_forward(layers, x, samples)
+    if world == 1:
+        return _first_minibatch(ops.mc_predictive(logits, mode, sigma=sigma, quantiles=q))
+    out = ops.predictive_buffers(mode, 1, x.shape[0], layers[-1].in_out[1], x.device)
+    if logits.shape[0]:
+        ops.mc_predictive(logits, mode, scale=1.0 / samples, sigma=sigma, partial=True, out=out)
+    else:                                                # a rank without samples contributes zero sums / zero weight
+        for t in (out.probs, out.expected_entropy, out.mean, out.variance):
+            if t is not None:
+                t.zero_()
+    return _first_minibatch(combine_predictive(out, mode, samples, world, sigma))
+
+
 class GraphedElbo:
     """Forward-only ELBO evaluations with static buffers: one launch per layer for ALL local MC samples (the last
     BBB layer carries the finalize), captured once as a hipGraph and replayed.  The Philox sample index has a
@@ -870,6 +927,50 @@ class GraphedPredict(GraphedElbo):
             dist.all_reduce(self.probs, op=dist.ReduceOp.SUM)
             self.preds.copy_(torch.argmax(self.probs, dim=1))
         return self.preds, self.probs
+
+
+class GraphedPredictive(GraphedElbo):
+    """F3 as a captured evaluation: the predictive summaries (bnn_mc_predictive) of one minibatch, or of G stacked minibatches
+    (`stacked`: x [G, B, ...], all with the same B -- a short last minibatch is not padded), with static buffers and FRESH
+    epsilon on every replay.  It is GraphedElbo's launch chain with the summary launch behind it; the ELBO scalars it also
+    produces are computed against an all-zero target and mean nothing.  Minibatch g of a stacked evaluation draws the global
+    sample indices [c + g * samples, c + (g + 1) * samples) of an evaluation that starts at counter c.
+    Classification: probs, preds, predictive / expected entropy, mutual information.  Regression: mean, variance,
+    predictive_variance = variance + sigma^2 and, at up to 8 `quantiles` levels in [0, 1], numpy.percentile's linear
+    quantiles (samples <= 1024).  `capture` as for GraphedElbo.  `replay()` returns the static Predictive ([B, ...], or
+    [G, B, ...] stacked); with sample sharding on, every rank runs its share of the samples and replay() merges the
+    partials (combine_predictive, outside the graph).  Quantiles under sample sharding raise BnnHipError."""
+
+    def __init__(self, net, x: torch.Tensor, samples: int, quantiles=None, sigma: float = 1.0, capture=True,
+                 stream: Optional[torch.cuda.Stream] = None, stacked: bool = False):
+        mode = net.mode
+        if mode not in ("classification", "regression"):
+            raise Exception("Training mode must be either 'regression' or 'classification'")
+        if mode == "classification" and quantiles:
+            raise ops.BnnHipError("GraphedPredictive: quantiles are a regression summary")
+        self.mode, self.quantile_levels, self.pred_sigma = mode, ops.quantile_levels(quantiles), float(sigma)
+        if self.quantile_levels and dist_info()[1] > 1:
+            raise ops.BnnHipError("GraphedPredictive: quantiles need every MC sample on one rank (sample sharding is on)")
+        G = int(x.shape[0]) if stacked else 1
+        B = net._flat(x[0] if stacked else x).shape[0]
+        Cc = net._specs()[-1].in_out[1]
+        lead = (G, B) if stacked else (B,)
+        target = (torch.zeros(lead, dtype=torch.int64, device=x.device) if mode == "classification"
+                  else torch.zeros(lead + (Cc,), dtype=torch.float32, device=x.device))
+        self._pred = ops.predictive_buffers(mode, G, B, Cc, x.device, self.quantile_levels)
+        self.result = self._pred if stacked else _first_minibatch(self._pred)
+        super().__init__(net, x, target, samples, sigma=sigma, capture=capture, stream=stream, stacked=stacked)
+
+    def _enqueue(self):
+        super()._enqueue()
+        ops.mc_predictive(self.logits, self.mode, groups=self.G, scale=1.0 / self.samples, sigma=self.pred_sigma,
+                          quantiles=self.quantile_levels, partial=self.world > 1, out=self._pred)
+
+    def replay(self) -> Predictive:
+        super().replay()
+        if self.world > 1:
+            combine_predictive(self._pred, self.mode, self.samples, self.world, self.pred_sigma)
+        return self.result
 
 
 def elbo_many(net, x: torch.Tensor, target: torch.Tensor, samples: int, sigma: float = 1.0) -> torch.Tensor:

@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -845,6 +845,106 @@ def mc_softmax_mean(logits: torch.Tensor, scale: float, want_preds: bool = True,
     L.check(lib.bnn_mc_softmax_mean(lg.data_ptr(), S, B, Cc, float(scale), probs.data_ptr(), _ptr(preds), _stream()),
             "bnn_mc_softmax_mean")
     return probs, preds
+
+
+class Predictive(NamedTuple):
+    """Predictive summaries of MC outputs (bnn_mc_predictive).  Classification fills probs / preds / the three entropies,
+    regression mean / variance / predictive_variance / quantiles; the other mode's fields are None (quantiles too when no
+    level was asked for).  Shapes [B, ...] for one minibatch, [G, B, ...] for G stacked ones; quantiles [Q, (G,) B, out]."""
+    probs: Optional[torch.Tensor] = None
+    preds: Optional[torch.Tensor] = None
+    predictive_entropy: Optional[torch.Tensor] = None
+    expected_entropy: Optional[torch.Tensor] = None
+    mutual_information: Optional[torch.Tensor] = None
+    mean: Optional[torch.Tensor] = None
+    variance: Optional[torch.Tensor] = None
+    predictive_variance: Optional[torch.Tensor] = None
+    quantiles: Optional[torch.Tensor] = None
+
+
+def quantile_levels(quantiles) -> tuple:
+    """The quantile levels as floats, checked as bnn_mc_predictive checks them (ahead of any allocation)."""
+    q = tuple(float(v) for v in (quantiles or ()))
+    if len(q) > L.PREDICTIVE_MAX_QUANTILES:
+        raise BnnHipError(f"at most {L.PREDICTIVE_MAX_QUANTILES} quantile levels")
+    if not all(0.0 <= v <= 1.0 for v in q):             # (NaN fails)
+        raise BnnHipError(f"quantile levels must lie in [0, 1], got {q}")
+    return q
+
+
+def predictive_buffers(mode: str, G: int, B: int, Cc: int, device, quantiles=(), partial: bool = False) -> Predictive:
+    """Output tensors of bnn_mc_predictive for logits [G, S, B, Cc].  `partial`: a rank's share of a sample-sharded job --
+    the buffers for the optional outputs too (they receive the combined values: engine.combine_predictive)."""
+    f = dict(dtype=torch.float32, device=device)
+    if mode == "classification":
+        return Predictive(probs=torch.empty((G, B, Cc), **f), preds=torch.empty((G, B), dtype=torch.int64, device=device),
+                          predictive_entropy=torch.empty((G, B), **f), expected_entropy=torch.empty((G, B), **f),
+                          mutual_information=torch.empty((G, B), **f))
+    if mode == "regression":
+        q = quantile_levels(quantiles)
+        return Predictive(mean=torch.empty((G, B, Cc), **f), variance=torch.empty((G, B, Cc), **f),
+                          predictive_variance=torch.empty((G, B, Cc), **f),
+                          quantiles=torch.empty((len(q), G, B, Cc), **f) if q else None)
+    raise Exception("Training mode must be either 'regression' or 'classification'")
+
+
+def mc_predictive(logits: torch.Tensor, mode: str, *, groups: int = 1, scale: Optional[float] = None, sigma: float = 1.0,
+                  quantiles=(), partial: bool = False, out: Optional[Predictive] = None) -> Predictive:
+    """F3: bnn_mc_predictive over logits [groups * S, B, C] (g-major, the layout of a stacked evaluation's output).
+    Returns a Predictive of [groups, B, ...] tensors (`out`: static buffers of a captured evaluation, from
+    predictive_buffers).  `scale`: classification's weight of the sums, 1 / S by default.  `partial`: only what a rank of
+    a sample-sharded job contributes -- classification probs and expected_entropy (pass scale = 1 / global samples),
+    regression mean and variance of the local samples; the other fields are left for engine.combine_predictive."""
+    lib = L.load()
+    require_device(logits)
+    lg = _f32c(logits, "logits")
+    if lg.dim() != 3 or lg.shape[0] % groups:
+        raise BnnHipError("mc_predictive: logits must be [groups * samples, batch, outputs]")
+    G = int(groups)
+    S, B, Cc = lg.shape[0] // G, lg.shape[1], lg.shape[2]
+    q = quantile_levels(quantiles) if mode == "regression" else ()
+    if partial and q:
+        raise BnnHipError("mc_predictive: quantiles of sample-sharded outputs are not supported")
+    if out is None:
+        out = predictive_buffers(mode, G, B, Cc, lg.device, q)
+    want = dict(probs=(G, B, Cc), preds=(G, B), predictive_entropy=(G, B), expected_entropy=(G, B), mutual_information=(G, B),
+                mean=(G, B, Cc), variance=(G, B, Cc), predictive_variance=(G, B, Cc), quantiles=(len(q), G, B, Cc))
+    for name, tns in zip(out._fields, out):
+        if tns is None:
+            continue
+        require_device(tns)
+        dt = torch.int64 if name == "preds" else torch.float32
+        if tuple(tns.shape) != want[name] or tns.dtype != dt or not tns.is_contiguous():
+            raise BnnHipError(f"mc_predictive: out.{name} must be a contiguous {dt} tensor of shape {want[name]}")
+    a = L.McPredictiveArgs()
+    a.struct_bytes = C.sizeof(L.McPredictiveArgs)
+    a.groups, a.n_samples, a.batch, a.classes = G, S, B, Cc
+    a.logits = lg.data_ptr()
+    if mode == "classification":
+        a.mode = L.NLL_CLASSIFICATION
+        a.scale = float(1.0 / S if scale is None else scale)
+        a.probs, a.expected_entropy = out.probs.data_ptr(), out.expected_entropy.data_ptr()
+        if not partial:
+            a.preds, a.predictive_entropy, a.mutual_information = (_ptr(out.preds), _ptr(out.predictive_entropy),
+                                                                   _ptr(out.mutual_information))
+    elif mode == "regression":
+        a.mode = L.NLL_REGRESSION
+        a.sigma = float(sigma)
+        a.mean, a.variance = out.mean.data_ptr(), out.variance.data_ptr()
+        if not partial:
+            a.predictive_variance = _ptr(out.predictive_variance)
+        a.n_quantiles = len(q)
+        for i, v in enumerate(q):
+            a.quantile[i] = v
+        if q:
+            if out.quantiles is None:
+                raise BnnHipError("mc_predictive: quantile levels need out.quantiles")
+            a.quantiles = out.quantiles.data_ptr()
+    else:
+        raise Exception("Training mode must be either 'regression' or 'classification'")
+    a._keep = (lg, out)               # (the structure owns what its pointers refer to: engine.GraphedElbo(capture="calls") replays it)
+    L.check(lib.bnn_mc_predictive(C.byref(a), _stream()), "bnn_mc_predictive")
+    return out
 
 
 def elbo_loss(a, b, nll, beta, total_samples: int, local_reparam: bool, grad_scale: float = 1.0):

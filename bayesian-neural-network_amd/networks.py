@@ -266,6 +266,29 @@ class BayesianNetwork(nn.Module):
         launch list instead of a hipGraph (a few us less per replay at up to ~16 samples)."""
         return _engine.GraphedPredict(self, x, int(samples), capture=capture)
 
+    def predictive(self, x, samples, *, quantiles=None, sigma=1., stacked=False):
+        """Extension (not in the reference): the predictive summaries of `samples` stochastic passes, computed on the
+        device -- a bnn_hip.ops.Predictive.  Classification: probs (the mean softmax, as predict_mc), preds, and the
+        entropy decomposition predictive_entropy = expected_entropy (aleatoric) + mutual_information (epistemic, BALD;
+        clamped at 0).  Regression: mean, variance (ddof 0), predictive_variance = variance + sigma^2 (sigma: the NLL's
+        noise_tolerance, regression/reg_task.py:68-70) and, for up to 8 `quantiles` levels in [0, 1], np.percentile's
+        linear quantiles over the samples (what utils/plot_utils.py:8-29 draws), [Q, batch, out].
+        `stacked`: x is [G, batch, ...], G minibatches of one batch size in one launch per layer; every field gains a
+        leading G (eps is drawn on the device then, never injected)."""
+        if stacked:
+            with torch.no_grad():
+                return _engine.GraphedPredictive(self, x, int(samples), quantiles=quantiles, sigma=float(sigma), capture=False,
+                                                 stacked=True).replay()
+        return _engine.mc_predictive(self._specs(), self._flat(x), int(samples), self.mode, quantiles=quantiles,
+                                     sigma=float(sigma))
+
+    def predictive_graph(self, x, samples, *, quantiles=None, sigma=1., stacked=False, capture=True):
+        """Extension (not in the reference): predictive for this input shape as a replayable evaluation --
+        `p = net.predictive_graph(x, samples)`, then `p.x.copy_(next_input); out = p.replay()` (static buffers, fresh
+        epsilon each replay: bnn_hip.engine.GraphedPredictive).  `capture`: True (hipGraph), "calls" or False."""
+        return _engine.GraphedPredictive(self, x, int(samples), quantiles=quantiles, sigma=float(sigma), capture=capture,
+                                         stacked=stacked)
+
     def elbo_many(self, inputs, targets, samples, sigma=1.):
         """Extension (not in the reference): the forward-only ELBO terms of G independent minibatches -- inputs
         [G, batch, ...], targets [G, batch] -- in one launch per layer instead of G sample_elbo calls under

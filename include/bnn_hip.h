@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define BNN_HIP_ABI_VERSION 7
+#define BNN_HIP_ABI_VERSION 8
 #define BNN_EPS_MAP_VERSION 2     /* 1: Philox4x32-10 (rounds 1-2); 2: Philox4x32-7 */
 #ifndef BNN_PHILOX_ROUNDS          /* build-time choice (csrc/Makefile: make PHILOX_ROUNDS=10): 7 = map version 2 (the product), */
 #define BNN_PHILOX_ROUNDS 7        /* 10 = rocRAND's PHILOX4_32_10 / map version 1.  bnn_philox_rounds() tells what a library runs */
@@ -734,6 +734,53 @@ int bnn_stage_inputs_cast(const void* src0, void* dst0, size_t bytes0, const voi
  * ---------------------------------------------------------------------------------- */
 int bnn_mc_softmax_mean(const float* logits, int32_t n_samples, int32_t batch, int32_t classes, float scale,
                         float* probs, long long* preds, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * F3  bnn_mc_predictive — the predictive summaries of S MC outputs (what a user of the network reads off the samples
+ * the reference collects in regression/reg_task.py:76-83 and classification/class_task.py:81-87).
+ * logits fp32 [groups, n_samples, batch, classes], g-major: G minibatches of S local samples each, the layout of a
+ * stacked evaluation's output.  Every output is per (g, b) [groups, batch] or per (g, b, c) [groups, batch, classes].
+ *   BNN_NLL_CLASSIFICATION, p_s = softmax(z_s):
+ *     probs              = scale * sum_s p_s                          (required; scale = 1 / n_samples for the mean)
+ *     expected_entropy   = scale * sum_s H(p_s), H = logsumexp(z) - sum_c p_c z_c       (required: the aleatoric part)
+ *     preds              int64 argmax_c probs, lowest index on ties    (optional)
+ *     predictive_entropy = -sum_c probs_c log probs_c, 0 log 0 = 0     (optional)
+ *     mutual_information = max(predictive_entropy - expected_entropy, 0)   (optional: the epistemic part, BALD.  It is
+ *                          >= 0 in exact arithmetic; the clamp removes the rounding-level negatives)
+ *     A rank of a sample-sharded job passes its local samples and scale = 1 / (global samples), sum-all-reduces probs
+ *     and expected_entropy, and forms the optional outputs from the sums.
+ *   BNN_NLL_REGRESSION, over the S samples of each (g, b, c):
+ *     mean, variance (ddof 0; two passes in fp64)                      (required)
+ *     predictive_variance = variance + sigma^2                         (optional; sigma: the NLL's noise scale)
+ *     quantiles [n_quantiles, groups, batch, classes] at the levels quantile[] in [0, 1] (n_quantiles 0 .. 8;
+ *       n_samples <= BNN_PREDICTIVE_MAX_QUANTILE_SAMPLES): numpy.percentile(y, 100 q, axis=0) with its linear
+ *       interpolation -- sort, pos = q (S - 1), v[floor pos] + frac (v[floor pos + 1] - v[floor pos]) -- and NaN for a
+ *       column with a NaN sample.
+ * Output buffers must not overlap logits.  One launch (two with quantiles).
+ * ---------------------------------------------------------------------------------- */
+#define BNN_PREDICTIVE_MAX_QUANTILES 8
+#define BNN_PREDICTIVE_MAX_QUANTILE_SAMPLES 1024   /* a column's samples are sorted in LDS */
+typedef struct bnn_mc_predictive_args {
+  uint32_t struct_bytes;
+  int32_t mode;                   /* bnn_nll_mode */
+  int32_t groups, n_samples, batch, classes;
+  const float* logits;
+  float scale;                    /* classification */
+  float sigma;                    /* regression, with predictive_variance */
+  float* probs;
+  int64_t* preds;
+  float* predictive_entropy;
+  float* expected_entropy;
+  float* mutual_information;
+  float* mean;
+  float* variance;
+  float* predictive_variance;
+  int32_t n_quantiles;
+  int32_t reserved;
+  double quantile[BNN_PREDICTIVE_MAX_QUANTILES];
+  float* quantiles;
+} bnn_mc_predictive_args;
+int bnn_mc_predictive(const bnn_mc_predictive_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * F3  bnn_ece — ECELoss.forward of compute_ece.py:14-57 over the MC-averaged class probabilities the predict path
