@@ -7,7 +7,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BNN_HIP_LIB") or os.path.join(_HERE, "libbnn_hip.so")   # env: diagnostic builds only
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 # enums of include/bnn_hip.h
 F32, BF16 = 0, 1
@@ -27,6 +27,7 @@ EXPORTS = (
     "bnn_gauss_kl_workspace_bytes", "bnn_gauss_kl",
     "bnn_elbo_finalize", "bnn_bbb_final_fwd", "bnn_bbb_final_scratch_bytes", "bnn_philox_normal", "bnn_cast_bf16", "bnn_softplus", "bnn_eval_prepare",
     "bnn_ece_workspace_bytes", "bnn_ece", "bnn_snr_db", "bnn_snr_prune", "bnn_mc_predictive",
+    "bnn_bandit_rows", "bnn_bandit_act", "bnn_bandit_replay",
 )
 
 
@@ -216,6 +217,32 @@ class McPredictiveArgs(C.Structure):
                 ("quantile", C.c_double * PREDICTIVE_MAX_QUANTILES), ("quantiles", C.c_void_p)]
 
 
+BANDIT_MAX_ACTIONS = 64
+BANDIT_MAX_BUFFER = 8192
+
+
+class BanditActArgs(C.Structure):
+    """bnn_bandit_act_args (include/bnn_hip.h): the argument block of bnn_bandit_rows and bnn_bandit_act"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_actions", C.c_int32), ("n_labels", C.c_int32), ("n_samples", C.c_int32),
+                ("output_sample_stride", C.c_int32), ("context_dim", C.c_int32), ("n_contexts", C.c_int64),
+                ("buffer_size", C.c_int32), ("sample_counter_inc", C.c_uint32), ("max_steps", C.c_int64),
+                ("n_indices", C.c_int64), ("epsilon", C.c_float), ("reserved", C.c_uint32), ("seed", C.c_uint64),
+                ("x", C.c_void_p), ("labels", C.c_void_p), ("rewards", C.c_void_p), ("oracle", C.c_void_p),
+                ("indices", C.c_void_p), ("outputs", C.c_void_p), ("step", C.c_void_p), ("cur_index", C.c_void_p),
+                ("rows", C.c_void_p), ("actions", C.c_void_p), ("reward_out", C.c_void_p), ("regrets", C.c_void_p),
+                ("counts", C.c_void_p), ("ring_index", C.c_void_p), ("ring_action", C.c_void_p), ("ring_reward", C.c_void_p),
+                ("sample_counter", C.c_void_p)]
+
+
+class BanditReplayArgs(C.Structure):
+    """bnn_bandit_replay_args (include/bnn_hip.h)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("batch_size", C.c_int32), ("num_batches", C.c_int32), ("buffer_size", C.c_int32),
+                ("context_dim", C.c_int32), ("n_actions", C.c_int32), ("n_contexts", C.c_int64), ("seed", C.c_uint64),
+                ("step", C.c_void_p), ("x", C.c_void_p), ("ring_index", C.c_void_p), ("ring_action", C.c_void_p),
+                ("ring_reward", C.c_void_p), ("workspace", C.c_void_p), ("slab", C.c_void_p), ("targets", C.c_void_p),
+                ("n_batches", C.c_void_p)]
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -344,6 +371,11 @@ def _load_real():
     lib.bnn_snr_prune.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
     lib.bnn_mc_predictive.restype = C.c_int
     lib.bnn_mc_predictive.argtypes = [C.POINTER(McPredictiveArgs), C.c_void_p]
+    for name in ("bnn_bandit_rows", "bnn_bandit_act"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(BanditActArgs), C.c_void_p]
+    lib.bnn_bandit_replay.restype = C.c_int
+    lib.bnn_bandit_replay.argtypes = [C.POINTER(BanditReplayArgs), C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

@@ -1,0 +1,340 @@
+"""F5: the mushroom contextual bandit of the reference (reinforcement_learning/base_bandit.py, bandits.py:17-54) with the
+whole loop on the device.
+
+One reference step (base_bandit.py:75-99) decides with 2 x n_samples batch-1 forwards that each end in `.item()`, appends
+to Python lists, rebuilds up to buffer_size rows from them through a numpy permutation and then runs up to num_batches
+dependent training steps, each launch-bound.  Here a step is
+
+    decision   bnn_bandit_rows -> the network's forward of the A rows -> bnn_bandit_act     (one hipGraph / recorded calls)
+    replay     bnn_bandit_replay: pool, shuffle (bitonic sort in LDS), gather into the minibatch slab (a second graph)
+    training   nb(t) replays of train.GraphedTrainStep on slab[j] with beta_j, then scheduler.step()
+
+and nothing is read back: the step number, the replay ring, the regrets and the counts live on the device, and the host
+knows nb(t) from t alone (`n_batches`).  Semantics are include/bnn_hip.h F5's; the random decisions (the epsilon-greedy
+coin, the reward coin, a drawn context, the permutation) come from the bandit's own Philox stream (word 3 = 1), the
+network's epsilon from the usual one (word 3 = 0), so the two never share a counter.
+
+The MUSHROOM table reproduces base_bandit.py:26-35 BY LABEL VALUE, as the reference reads its labels: read_data_rl's
+LabelEncoder maps 'e' -> 0, 'p' -> 1 and the reference calls that value `edible`, so label 1 earns +5 for eating and label
+0 earns +5 or -35 (probability 1/2 each); rejecting earns 0 and the oracle is 5 * label.  Kept as the reference has it.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import ops
+from .ops import BnnHipError
+from .optim import FusedAdam
+from .runtime import state, take_samples
+
+
+class RewardTable(NamedTuple):
+    """rewards[k][a] = (hi, lo, thr): the reward of action a on label k is hi when the step's coin u > thr, else lo;
+    oracle[k] is the best expected reward of label k (the regret's reference)."""
+    rewards: tuple
+    oracle: tuple
+
+
+# base_bandit.py:26-35 by label value (module docstring): action 0 = eat, 1 = reject
+MUSHROOM = RewardTable(rewards=(((5.0, -35.0, 0.5), (0.0, 0.0, 0.5)),      # label 0: eat 5 if rand > 0.5 else -35
+                                ((5.0, 5.0, 0.5), (0.0, 0.0, 0.5))),       # label 1: eat 5
+                       oracle=(0.0, 5.0))
+
+
+# ---------------------------------------------------------------------------------------------------- host schedule
+def pool_size(l: int, batch_size: int, buffer_size: int) -> int:
+    """Entries of the replay pool after l appends (base_bandit.py:77-84)."""
+    if l <= 0:
+        return 0
+    if l <= batch_size:
+        return batch_size
+    if l < buffer_size:
+        return l // batch_size * batch_size
+    return buffer_size
+
+
+def n_batches(t: int, batch_size: int, buffer_size: int) -> int:
+    """Training minibatches of bandit step t (0-based): a function of t alone, so the host never reads it back."""
+    return pool_size(t + 1, batch_size, buffer_size) // batch_size
+
+
+def pool_entries(l: int, batch_size: int, buffer_size: int) -> np.ndarray:
+    """Buffer entries (0-based append order) at the pool positions, before the shuffle."""
+    P = pool_size(l, batch_size, buffer_size)
+    p = np.arange(P, dtype=np.int64)
+    if l <= batch_size:
+        m = batch_size // l + 1
+        return (m * l - batch_size + p) % l
+    return l - P + p
+
+
+def beta(j: int, num_batches: int) -> float:
+    """KL weight of minibatch j (bandits.py:44); num_batches is the configured value, not nb."""
+    return 2 ** (num_batches - (j + 1)) / (2 ** num_batches - 1)
+
+
+# ---------------------------------------------------------------------------------------------------- the agent
+class BNNBandit:
+    """BNN_Bandit (bandits.py:17-54) on the device.  `bandit_params` takes the keys of main.py:76-87 (+ n_samples, epsilon);
+    `x` [N, d] contexts, `y` [N] labels in [0, K).
+
+    policy="mean": the reference's rule -- every one of the n_samples outputs is the deterministic forward (net(x) in eval
+    mode, base_bandit.py:44-46), so n_samples only scales the sum.  policy="thompson": output s is the forward under posterior
+    draw s (one weight draw for all A action rows of the decision, a fresh global MC-sample index per draw, taken from the
+    counter the training step shares).  A local-reparameterisation network draws activation noise per row, not a function,
+    so it serves policy="mean" only.
+
+    Mirrors bandits.py:23-37: `net` (networks.BayesianNetwork, local_reparam filled in), `optimiser` (FusedAdam,
+    capturable), `scheduler` (StepLR(step_size=5000, gamma=0.5), stepped by update()).  `cumulative_regrets`, `tp`, `tn`,
+    `fp`, `fn`, `counts` read device state: EACH READ SYNCHRONISES with the device once.  update() never does.
+    `capture`: True (hipGraphs), "calls" (recorded launch lists) or False (eager launches)."""
+
+    def __init__(self, label, bandit_params, x, y, *, policy: str = "thompson", rewards: RewardTable = MUSHROOM,
+                 seed: Optional[int] = None, max_steps: int = 50000, local_reparam: bool = False, capture=True):
+        import networks
+        from .engine import effective_math
+        from .train import GraphedTrainStep
+        if state.shard_samples:
+            raise BnnHipError("BNNBandit: sample sharding is not supported (one device runs the whole loop)")
+        if policy not in ("mean", "thompson"):
+            raise BnnHipError(f"BNNBandit: policy must be 'mean' or 'thompson', got {policy!r}")
+        if policy == "thompson" and local_reparam:
+            raise BnnHipError("BNNBandit: Thompson sampling needs weight draws; a local-reparameterisation network draws "
+                              "activation noise per row -- use policy='mean'")
+        p = bandit_params
+        self.label = label
+        self.n_samples, self.buffer_size = int(p["n_samples"]), int(p["buffer_size"])
+        self.batch_size, self.num_batches = int(p["batch_size"]), int(p["num_batches"])
+        self.lr, self.epsilon = float(p["lr"]), float(p["epsilon"])
+        self.policy, self.max_steps = policy, int(max_steps)
+        if self.buffer_size % self.batch_size:
+            raise BnnHipError("BNNBandit: buffer_size must be a multiple of batch_size (the reference's last minibatch is short)")
+        if not 0 < self.buffer_size <= L.BANDIT_MAX_BUFFER:
+            raise BnnHipError(f"BNNBandit: buffer_size must lie in [1, {L.BANDIT_MAX_BUFFER}]")
+        if self.n_samples < 1 or self.max_steps < 1:
+            raise BnnHipError("BNNBandit: n_samples and max_steps must be positive")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.x = torch.as_tensor(np.asarray(x), dtype=torch.float32).to(dev).contiguous()
+        yh = np.asarray(y).astype(np.int64)
+        tab = np.asarray(rewards.rewards, dtype=np.float32)
+        if tab.ndim != 3 or tab.shape[2] != 3 or tab.shape[1] < 2 or len(rewards.oracle) != tab.shape[0]:
+            raise BnnHipError("BNNBandit: rewards must be [K][A][(hi, lo, thr)] with A >= 2 and K oracle values")
+        self.K, self.A = tab.shape[0], tab.shape[1]
+        if self.x.dim() != 2 or yh.shape != (self.x.shape[0],) or yh.min() < 0 or yh.max() >= self.K:
+            raise BnnHipError("BNNBandit: x must be [N, d] and y [N] labels in [0, K)")
+        self.N, self.d = self.x.shape
+        self.y = torch.from_numpy(yh).to(dev)
+        self.table = torch.from_numpy(tab).to(dev)
+        self.oracle = torch.tensor(rewards.oracle, dtype=torch.float32, device=dev)
+        self.seed = state.seed if seed is None else int(seed)
+
+        # bandits.py:23-37
+        model_params = {
+            'input_shape': self.d + self.A, 'classes': 1, 'batch_size': self.batch_size,
+            'hidden_units': p['hidden_units'], 'mode': p['mode'], 'mixture_prior': p['mixture_prior'],
+            'mu_init': p['mu_init'], 'rho_init': p['rho_init'], 'prior_init': p['prior_init'],
+            'local_reparam': bool(local_reparam),
+        }
+        if model_params['mode'] != 'regression':
+            raise BnnHipError("BNNBandit: the bandit's network regresses the reward (mode='regression')")
+        self.net = networks.BayesianNetwork(model_params).to(dev)
+        self.optimiser = FusedAdam(self.net.parameters(), lr=self.lr, capturable=True)
+        self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimiser, step_size=5000, gamma=0.5)
+
+        # device state
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        T, B, W = self.max_steps, self.buffer_size, self.d + self.A
+        self.step_word = torch.zeros(1, **i32)
+        self.cur_index = torch.zeros(1, **i32)
+        self.indices = torch.full((T,), -1, dtype=torch.int64, device=dev)         # -1: draw the context on the device
+        self.actions = torch.zeros(T, dtype=torch.int64, device=dev)
+        self.rewards = torch.zeros(T, **f32)
+        self.regrets = torch.zeros(T + 1, dtype=torch.float64, device=dev)
+        self._counts = torch.zeros((self.K, self.A), dtype=torch.int64, device=dev)
+        self.ring_index, self.ring_action, self.ring_reward = torch.zeros(B, **i32), torch.zeros(B, **i32), torch.zeros(B, **f32)
+        self.perm = torch.zeros(B, **i32)
+        self.nb_slab = B // self.batch_size
+        self.slab = torch.zeros((self.nb_slab, self.batch_size, W), **f32)
+        self.targets = torch.zeros((self.nb_slab, self.batch_size, 1), **f32)
+        self.rows = torch.zeros((self.A, W), **f32)
+        self.t = 0
+        self.loss_info = None
+
+        self.train = GraphedTrainStep(self.net, self.optimiser, self.slab[0], self.targets[0], self.n_samples)
+
+        # the decision forward: S draws (thompson) or the one deterministic forward (mean) of the A rows
+        self.math = effective_math(bool(local_reparam))
+        hid = torch.bfloat16 if (self.math == L.MATH_BF16 and not local_reparam) else torch.float32
+        self.specs = self.net._specs()
+        n = self.n_samples if policy == "thompson" else 1
+        self.dec_samples = n
+        self.h = [torch.empty((n, self.A, sp.in_out[1]), dtype=torch.float32 if i == len(self.specs) - 1 else hid, device=dev)
+                  for i, sp in enumerate(self.specs)]
+        self.act_args = ops.bandit_act_args(
+            x=self.x, labels=self.y, rewards=self.table, oracle=self.oracle, outputs=self.h[-1], n_samples=self.n_samples,
+            output_sample_stride=self.A if policy == "thompson" else 0, step=self.step_word, cur_index=self.cur_index,
+            rows=self.rows, actions=self.actions, reward_out=self.rewards, regrets=self.regrets, counts=self._counts,
+            ring_index=self.ring_index, ring_action=self.ring_action, ring_reward=self.ring_reward, epsilon=self.epsilon,
+            seed=self.seed, indices=self.indices, sample_counter=self.train.counter if policy == "thompson" else None,
+            sample_counter_inc=n if policy == "thompson" else 0)
+        self.replay_args = ops.bandit_replay_args(
+            x=self.x, step=self.step_word, ring_index=self.ring_index, ring_action=self.ring_action, ring_reward=self.ring_reward,
+            workspace=self.perm, slab=self.slab, targets=self.targets, batch_size=self.batch_size, n_actions=self.A, seed=self.seed)
+
+        # warm-up (validates every argument block eagerly; "calls" records it), then the state words are reset
+        self.capture = capture
+        self.calls_decide = self.calls_replay = None
+        self.g_decide = self.g_replay = None
+        self.train._sync_counter()
+        mirror = self.train._shared["mirror"]
+        if capture == "calls":
+            with L.recording() as calls:
+                self._decide()
+            self.calls_decide = list(calls)
+            with L.recording() as calls:
+                self._replay()
+            self.calls_replay = list(calls)
+        else:
+            self._decide()
+            self._replay()
+        torch.cuda.synchronize()
+        self._reset_words(mirror)
+        if capture is True:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self.g_decide = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.g_decide, stream=side):
+                    self._decide()
+                self.g_replay = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.g_replay, stream=side):
+                    self._replay()
+            torch.cuda.current_stream().wait_stream(side)
+        elif capture not in ("calls", False):
+            raise BnnHipError(f"BNNBandit: capture must be True, 'calls' or False, got {capture!r}")
+        torch.cuda.synchronize()
+
+    def _reset_words(self, mirror: int):
+        self.step_word.zero_()
+        self._counts.zero_()
+        self.regrets.zero_()
+        self.train._set_counter(mirror)
+
+    def _decide(self):
+        """bnn_bandit_rows -> forward of the A rows -> bnn_bandit_act, on the current stream."""
+        ops.bandit_rows(self.act_args)
+        thompson = self.policy == "thompson"
+        eps_mode = L.EPS_PHILOX if thompson else L.EPS_ZERO
+        h = self.rows
+        for i, sp in enumerate(self.specs):
+            m = sp.m
+            pd = (m.weight_mu.detach(), m.weight_rho.detach(), m.bias_mu.detach(), m.bias_rho.detach())
+            kw = dict(n_samples=self.dec_samples, math_mode=self.math, relu=sp.relu, y_dtype=self.h[i].dtype, eps_mode=eps_mode,
+                      seed=state.seed, layer_id=sp.layer_id, sample_offset=self.train.base if thompson else 0,
+                      sample_counter=self.train.counter if thompson else None, form=state.form, out=self.h[i])
+            if sp.lr:
+                ops.lr_linear_fwd(h, *pd, sigma_p=m._prior_spec.sigma_p, want_kl=False, **kw)
+            else:
+                ops.bbb_linear_fwd(h, *pd, prior=m._prior_spec, want_stats=False, **kw)
+            h = self.h[i]
+        ops.bandit_act(self.act_args)
+
+    def _replay(self):
+        ops.bandit_replay(self.replay_args)
+
+    @staticmethod
+    def _run_calls(calls):
+        for fn, args, name in calls:
+            rc = fn(*args)
+            if rc:
+                L.check(rc, name)
+
+    def _step(self):
+        if state.shard_samples:
+            raise BnnHipError("BNNBandit: sample sharding is not supported")
+        t = self.t
+        thompson = self.policy == "thompson"
+        if thompson:
+            self.train._sync_counter()
+        if self.g_decide is not None:
+            self.g_decide.replay()
+            if thompson:
+                self._advance_mirror()
+            self.g_replay.replay()
+        elif self.calls_decide is not None:
+            self._run_calls(self.calls_decide)
+            if thompson:
+                self._advance_mirror()
+            self._run_calls(self.calls_replay)
+        else:
+            self._decide()
+            if thompson:
+                self._advance_mirror()
+            self._replay()
+        for j in range(n_batches(t, self.batch_size, self.buffer_size)):
+            self.loss_info = self.train.step(self.slab[j], self.targets[j], beta(j, self.num_batches))
+        self.scheduler.step()
+        self.t = t + 1
+
+    def _advance_mirror(self):
+        take_samples(self.dec_samples)
+        sh = self.train._shared
+        sh["mirror"] = (sh["mirror"] + self.dec_samples) & 0xFFFFFFFF
+
+    def update(self, mushroom: Optional[int] = None):
+        """One bandit step (base_bandit.py:75-84 + the training of bandits.py:43-51 + main.py:103's scheduler.step()) on
+        context `mushroom`, or on a context drawn on the device when None.  Does not synchronise with the host."""
+        if self.t >= self.max_steps:
+            raise BnnHipError(f"BNNBandit: max_steps={self.max_steps} reached")
+        if mushroom is not None:
+            i = int(mushroom)
+            if not 0 <= i < self.N:
+                raise BnnHipError(f"BNNBandit: context index {i} outside [0, {self.N})")
+            self.indices[self.t].fill_(i)
+        self._step()
+
+    def run(self, indices: Sequence[int]):
+        """update(i) for every i of `indices`, the sequence uploaded once."""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if self.t + idx.size > self.max_steps:
+            raise BnnHipError(f"BNNBandit: {idx.size} steps from step {self.t} pass max_steps={self.max_steps}")
+        if idx.size and (idx.min() < 0 or idx.max() >= self.N):
+            raise BnnHipError(f"BNNBandit: context indices must lie in [0, {self.N})")
+        self.indices[self.t:self.t + idx.size].copy_(torch.from_numpy(idx))
+        for _ in range(idx.size):
+            self._step()
+
+    # ---- reads (each one synchronises)
+    @property
+    def cumulative_regrets(self) -> list:
+        """[0, r_1, ..., r_t] as base_bandit.py:20, :99 keep it (fp64)."""
+        return self.regrets[:self.t + 1].tolist()
+
+    @property
+    def counts(self) -> np.ndarray:
+        """counts[label, action] (int64)."""
+        return self._counts.cpu().numpy()
+
+    @property
+    def tp(self) -> int:
+        return int(self._counts[1, 0].item())
+
+    @property
+    def fn(self) -> int:
+        return int(self._counts[1, 1].item())
+
+    @property
+    def fp(self) -> int:
+        return int(self._counts[0, 0].item())
+
+    @property
+    def tn(self) -> int:
+        return int(self._counts[0, 1].item())
+
+    def history(self):
+        """(actions [t] int64, rewards [t] fp32) of the steps taken, as numpy arrays."""
+        return self.actions[:self.t].cpu().numpy(), self.rewards[:self.t].cpu().numpy()

@@ -1168,3 +1168,90 @@ def snr_prune_(mu: torch.Tensor, rho: torch.Tensor, threshold: float, kept: Opti
         raise BnnHipError("snr_prune_: contiguous float32 mu and rho of one size")
     L.check(lib.bnn_snr_prune(mu.data_ptr(), rho.data_ptr(), mu.numel(), float(threshold), _ptr(kept), _stream()),
             "bnn_snr_prune")
+
+
+# ---------------------------------------------------------------------------------------------------------------- F5 bandit
+def _typed(t: torch.Tensor, dtype: torch.dtype, name: str, numel: Optional[int] = None) -> torch.Tensor:
+    require_device(t)
+    if t.dtype != dtype or not t.is_contiguous():
+        raise BnnHipError(f"{name} must be a contiguous {dtype} tensor")
+    if numel is not None and t.numel() != numel:
+        raise BnnHipError(f"{name} must have {numel} elements, got {t.numel()}")
+    return t
+
+
+def bandit_act_args(*, x, labels, rewards, oracle, outputs, n_samples: int, output_sample_stride: int, step, cur_index, rows,
+                    actions, reward_out, regrets, counts, ring_index, ring_action, ring_reward, epsilon: float, seed: int,
+                    indices=None, sample_counter=None, sample_counter_inc: int = 0) -> L.BanditActArgs:
+    """The argument block of bnn_bandit_rows / bnn_bandit_act (include/bnn_hip.h F5), built once: the launches of a bandit
+    step read everything that changes (t, i_t, the outputs) from device memory, so the same block serves every step.
+    x [N, d] fp32, labels [N] int64, rewards [K, A, 3] fp32 (hi, lo, thr), oracle [K] fp32, outputs [S, A] (stride A) or
+    [A] (stride 0), rows [A, d + A], actions / reward_out [max_steps], regrets [max_steps + 1] fp64, counts [K, A] int64,
+    the ring [buffer_size] (int32 index, int32 action, fp32 reward), step / cur_index one int32 word each."""
+    N, d = x.shape
+    K, A = rewards.shape[0], rewards.shape[1]
+    T = actions.numel()
+    a = L.BanditActArgs()
+    a.struct_bytes = C.sizeof(L.BanditActArgs)
+    a.n_actions, a.n_labels, a.n_samples, a.output_sample_stride = A, K, int(n_samples), int(output_sample_stride)
+    a.context_dim, a.n_contexts, a.buffer_size = d, N, ring_index.numel()
+    a.max_steps, a.epsilon, a.seed = T, float(epsilon), int(seed) & 0xFFFFFFFFFFFFFFFF
+    keep = [_typed(x, torch.float32, "x"), _typed(labels, torch.int64, "labels", N), _typed(rewards, torch.float32, "rewards", K * A * 3),
+            _typed(oracle, torch.float32, "oracle", K), _typed(outputs, torch.float32, "outputs"),
+            _typed(step, torch.int32, "step", 1), _typed(cur_index, torch.int32, "cur_index", 1),
+            _typed(rows, torch.float32, "rows", A * (d + A)), _typed(actions, torch.int64, "actions"),
+            _typed(reward_out, torch.float32, "reward_out", T), _typed(regrets, torch.float64, "regrets", T + 1),
+            _typed(counts, torch.int64, "counts", K * A), _typed(ring_index, torch.int32, "ring_index"),
+            _typed(ring_action, torch.int32, "ring_action", ring_index.numel()),
+            _typed(ring_reward, torch.float32, "ring_reward", ring_index.numel())]
+    (a.x, a.labels, a.rewards, a.oracle, a.outputs, a.step, a.cur_index, a.rows, a.actions, a.reward_out, a.regrets, a.counts,
+     a.ring_index, a.ring_action, a.ring_reward) = (t.data_ptr() for t in keep)
+    if outputs.numel() < (n_samples - 1) * output_sample_stride + A:
+        raise BnnHipError("outputs is smaller than its samples and stride say")
+    if indices is not None:
+        keep.append(_typed(indices, torch.int64, "indices"))
+        a.indices, a.n_indices = indices.data_ptr(), indices.numel()
+    if sample_counter is not None:
+        keep.append(_typed(sample_counter, torch.int32, "sample_counter", 1))
+        a.sample_counter, a.sample_counter_inc = sample_counter.data_ptr(), int(sample_counter_inc) & 0xFFFFFFFF
+    a._keep = keep
+    return a
+
+
+def bandit_rows(a: L.BanditActArgs):
+    """bnn_bandit_rows: i_t (the index sequence's entry t, or drawn) and the A decision rows x[i_t] ++ one_hot(a)."""
+    L.check(L.load().bnn_bandit_rows(C.byref(a), _stream()), "bnn_bandit_rows")
+
+
+def bandit_act(a: L.BanditActArgs):
+    """bnn_bandit_act: decision, reward, regret, counts and ring append of step t; advances the step word."""
+    L.check(L.load().bnn_bandit_act(C.byref(a), _stream()), "bnn_bandit_act")
+
+
+def bandit_replay_args(*, x, step, ring_index, ring_action, ring_reward, workspace, slab, targets, batch_size: int,
+                       n_actions: int, seed: int, n_batches=None) -> L.BanditReplayArgs:
+    """The argument block of bnn_bandit_replay: slab [num_batches, batch_size, d + A] fp32, targets [num_batches, batch_size]
+    fp32, workspace int32 [buffer_size], n_batches (optional) one int32 word."""
+    N, d = x.shape
+    buf = ring_index.numel()
+    nbm = slab.shape[0]
+    a = L.BanditReplayArgs()
+    a.struct_bytes = C.sizeof(L.BanditReplayArgs)
+    a.batch_size, a.num_batches, a.buffer_size = int(batch_size), nbm, buf
+    a.context_dim, a.n_actions, a.n_contexts, a.seed = d, int(n_actions), N, int(seed) & 0xFFFFFFFFFFFFFFFF
+    keep = [_typed(step, torch.int32, "step", 1), _typed(x, torch.float32, "x"), _typed(ring_index, torch.int32, "ring_index"),
+            _typed(ring_action, torch.int32, "ring_action", buf), _typed(ring_reward, torch.float32, "ring_reward", buf),
+            _typed(workspace, torch.int32, "workspace", buf),
+            _typed(slab, torch.float32, "slab", nbm * int(batch_size) * (d + int(n_actions))),
+            _typed(targets, torch.float32, "targets", nbm * int(batch_size))]
+    (a.step, a.x, a.ring_index, a.ring_action, a.ring_reward, a.workspace, a.slab, a.targets) = (t.data_ptr() for t in keep)
+    if n_batches is not None:
+        keep.append(_typed(n_batches, torch.int32, "n_batches", 1))
+        a.n_batches = n_batches.data_ptr()
+    a._keep = keep
+    return a
+
+
+def bandit_replay(a: L.BanditReplayArgs):
+    """bnn_bandit_replay: the shuffled replay pool of the step just taken, gathered into the minibatch slab."""
+    L.check(L.load().bnn_bandit_replay(C.byref(a), _stream()), "bnn_bandit_replay")

@@ -56,3 +56,27 @@ def synth_eps(shapes, sample, seed=SEED_EPS):
     subset of samples can be regenerated independently (multi-GPU shards)."""
     rs = np.random.RandomState(seed + 7919 * int(sample))
     return [rs.standard_normal(s).astype(np.float32) for s in shapes]
+
+
+# read_data_rl's one-hot layout of agaricus-lepiota.data (utils/data_utils.py:31-57 of the reference): the number of
+# distinct values of each of the 22 attributes, in column order (117 columns; stalk-root counts its '?')
+MUSHROOM_CARDINALITIES = (6, 4, 10, 2, 9, 2, 2, 2, 12, 2, 5, 4, 4, 9, 9, 1, 4, 3, 5, 9, 6, 7)
+MUSHROOM_ODOR = 4             # attribute index of odor
+
+
+def mushroom_like(n, seed=SEED_DATA):
+    """(x [n, 117] float32 one-hot, y [n] int64): shaped like read_data_rl's output (the real file cannot be fetched here).
+    Every attribute is uniform over its values except odor, and the label is a deterministic function of odor, as it
+    nearly is in the real data: odor values 0-3 <-> label 1, 4-8 <-> label 0.  Labels are balanced (n even: exactly)."""
+    rs = np.random.RandomState(seed)
+    y = rs.permutation(np.arange(n) % 2).astype(np.int64)
+    x = np.zeros((n, sum(MUSHROOM_CARDINALITIES)), dtype=np.float32)
+    col = 0
+    for f, card in enumerate(MUSHROOM_CARDINALITIES):
+        if f == MUSHROOM_ODOR:
+            v = np.where(y == 1, rs.randint(0, 4, n), rs.randint(4, card, n))
+        else:
+            v = rs.randint(0, card, n)
+        x[np.arange(n), col + v] = 1.0
+        col += card
+    return x, y

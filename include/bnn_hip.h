@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define BNN_HIP_ABI_VERSION 8
+#define BNN_HIP_ABI_VERSION 9
 #define BNN_EPS_MAP_VERSION 2     /* 1: Philox4x32-10 (rounds 1-2); 2: Philox4x32-7 */
 #ifndef BNN_PHILOX_ROUNDS          /* build-time choice (csrc/Makefile: make PHILOX_ROUNDS=10): 7 = map version 2 (the product), */
 #define BNN_PHILOX_ROUNDS 7        /* 10 = rocRAND's PHILOX4_32_10 / map version 1.  bnn_philox_rounds() tells what a library runs */
@@ -806,6 +806,92 @@ int bnn_ece(const float* probs, const long long* labels, int64_t n, int32_t clas
  * ---------------------------------------------------------------------------------- */
 int bnn_snr_db(const float* mu, const float* rho, int64_t n, float* out, void* stream);
 int bnn_snr_prune(float* mu, float* rho, int64_t n, float threshold, unsigned long long* kept, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * F5  contextual bandit — the device half of Bandit.update (reinforcement_learning/base_bandit.py:37-99): decide, reward,
+ * regret, replay buffer, shuffle and minibatch gather, with nothing read back by the host.  Per bandit step t:
+ *   bnn_bandit_rows    i_t = indices[t] when indices != NULL, t < n_indices and indices[t] >= 0, else drawn
+ *                      (min(floor(u(r3) N), N - 1)); writes *cur_index = i_t and the A decision rows
+ *                      rows[a] = x[i_t] ++ one_hot(a)  ([A, d + A] fp32: action a's encoding, base_bandit.py:39-40)
+ *   (the caller's forward of the rows: outputs[S, A])
+ *   bnn_bandit_act     v_a = o_0(a) + o_1(a) + ... + o_{S-1}(a), left to right in fp32 (Python's sum, :45-46), with
+ *                      o_s = outputs + s * output_sample_stride (stride 0: the one deterministic forward, S times);
+ *                      action = argmax_a v_a, ties to the HIGHEST index (the reference eats only when eat > reject);
+ *                      u(r0) < epsilon: action = min(floor(u(r1) A), A - 1) (:48-50);
+ *                      with k = labels[i_t] and (hi, lo, thr) = rewards[k][action]: reward = u(r2) > thr ? hi : lo;
+ *                      regrets[t + 1] = regrets[t] + (oracle[k] - reward) in fp64 (regrets[0] = 0 is the caller's);
+ *                      counts[k][action] += 1; ring slot t mod buffer_size <- (i_t, action, reward); *step = t + 1;
+ *                      *sample_counter += sample_counter_inc (the MC-sample indices a sampled decision used).
+ *   bandit random stream: (r0, r1, r2, r3) = Philox4x32-R((0, t, 0, 1), key = (seed_lo, seed_hi)), u() as for eps: word 3
+ *   is 1, every eps counter's is 0.  t = *step, read on the device; a step at or past max_steps writes nothing.
+ * Both launches take the same argument block; one block each. */
+#define BNN_BANDIT_MAX_ACTIONS 64
+#define BNN_BANDIT_MAX_BUFFER 8192     /* the replay permutation sorts (key, position) pairs in 64 KiB of LDS */
+typedef struct bnn_bandit_act_args {
+  uint32_t struct_bytes;
+  int32_t n_actions;              /* A, 2 .. BNN_BANDIT_MAX_ACTIONS */
+  int32_t n_labels;               /* K >= 1 */
+  int32_t n_samples;              /* S >= 1 */
+  int32_t output_sample_stride;   /* A (one output row per draw) or 0 */
+  int32_t context_dim;            /* d */
+  int64_t n_contexts;             /* N */
+  int32_t buffer_size;            /* ring entries, 1 .. BNN_BANDIT_MAX_BUFFER */
+  uint32_t sample_counter_inc;
+  int64_t max_steps;              /* entries of actions / reward_out, max_steps + 1 of regrets */
+  int64_t n_indices;
+  float epsilon;
+  uint32_t reserved;
+  uint64_t seed;
+  const float* x;                 /* [N, d] */
+  const int64_t* labels;          /* [N], values in [0, K) */
+  const float* rewards;           /* [K, A, 3]: (hi, lo, thr) */
+  const float* oracle;            /* [K] */
+  const int64_t* indices;         /* optional [n_indices] */
+  const float* outputs;           /* act: [S, A] (stride A) or [A] (stride 0) */
+  uint32_t* step;                 /* device word t */
+  int32_t* cur_index;             /* device word i_t */
+  float* rows;                    /* rows: [A, d + A] */
+  int64_t* actions;               /* act: [max_steps] */
+  float* reward_out;              /* act: [max_steps] */
+  double* regrets;                /* act: [max_steps + 1] */
+  int64_t* counts;                /* act: [K, A] */
+  int32_t* ring_index;            /* act: [buffer_size] */
+  int32_t* ring_action;           /* act: [buffer_size] */
+  float* ring_reward;             /* act: [buffer_size] */
+  uint32_t* sample_counter;       /* optional */
+} bnn_bandit_act_args;
+int bnn_bandit_rows(const bnn_bandit_act_args* args, void* stream);
+int bnn_bandit_act(const bnn_bandit_act_args* args, void* stream);
+
+/* bnn_bandit_replay — the replay pool of base_bandit.py:77-84 after step t's append (l = t + 1 = *step entries):
+ *   l <= bs:               pool position p in [0, bs) holds entry (m l - bs + p) mod l, m = bs / l + 1
+ *   bs < l < buffer_size:  the last floor(l / bs) bs entries;  otherwise the last buffer_size entries
+ * shuffled by sorting the positions by (key, p), key of p = word (p & 3) of Philox4x32-R((p >> 2, t, 1, 1), seed), and
+ * gathered into minibatches: row q of the shuffled pool is x[i] ++ one_hot(action) of its entry, its target the reward.
+ *   slab [num_batches, bs, d + A], targets [num_batches, bs]; *n_batches = pool / bs (optional).  Rows past the pool
+ *   are left as they were.  workspace: int32 [buffer_size] (the shuffled ring slots).
+ * buffer_size % batch_size == 0 (else the reference's last minibatch is short), buffer_size <= BNN_BANDIT_MAX_BUFFER,
+ * num_batches * batch_size >= buffer_size.  Two launches: the sort (one block), the gather. */
+typedef struct bnn_bandit_replay_args {
+  uint32_t struct_bytes;
+  int32_t batch_size;
+  int32_t num_batches;            /* slab capacity */
+  int32_t buffer_size;
+  int32_t context_dim;            /* d */
+  int32_t n_actions;              /* A */
+  int64_t n_contexts;             /* N */
+  uint64_t seed;
+  const uint32_t* step;           /* device word l = t + 1 (what bnn_bandit_act left) */
+  const float* x;                 /* [N, d] */
+  const int32_t* ring_index;
+  const int32_t* ring_action;
+  const float* ring_reward;
+  int32_t* workspace;             /* [buffer_size] */
+  float* slab;
+  float* targets;
+  int32_t* n_batches;             /* optional device word */
+} bnn_bandit_replay_args;
+int bnn_bandit_replay(const bnn_bandit_replay_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * bnn_philox_normal — materialise the on-chip epsilon stream (map at the top) into
