@@ -2488,10 +2488,13 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
     const int S = a->n_samples, B = a->batch, N = a->out_features, K = a->in_features;
     // (S: a grid of S x (ceil(B / 16) + 1) small blocks; 64 until round 4 -- the launch group of 256 minibatches takes this form
     // behind its own sampling launch since: 28.6 + 4.1 us of one-block-per-pair K1c + the sums launch against ~17 us)
+    // (no ticket: only without a loss tail -- the follow-up sums launch does not assemble the loss, and the kernel's own
+    // assembly runs behind the ticket)
     const bool rows = a->y_dtype == BNN_F32 && N <= 16 && B <= 128 && S <= 4096 && !f->local_reparam &&
                       nl >= 1 && f->n_samples == S && f->classes == N && f->batch == B && f->logits == a->y && f->nll &&
                       f->scratch && f->scratch_bytes >= bnn_bbb_final_scratch_bytes(S) &&
-                      !(reinterpret_cast<uintptr_t>(f->scratch) & 15) && (S == 1 || S > kRowsTicketMaxSamples || f->ticket) && !a->rider &&
+                      !(reinterpret_cast<uintptr_t>(f->scratch) & 15) &&
+                      (S == 1 || f->ticket || (S > kRowsTicketMaxSamples && !f->loss)) && !a->rider &&
                       (N % 4 != 0 || !(reinterpret_cast<uintptr_t>(a->y) & 15));
     if (!rows) {
       rc = bnn_bbb_linear_fwd(a, stream_);

@@ -2446,7 +2446,8 @@ extern "C" int bnn_lr_final_fwd(const bnn_lr_fwd_args* a, const bnn_finalize_arg
                     f->local_reparam && nl >= 1 && nl <= 8 && f->n_samples == S && f->classes == N && f->batch == B &&
                     f->logits == a->y && f->nll && f->kl && f->layer_in[nl - 1] == K && f->layer_out[nl - 1] == N &&
                     f->scratch && f->scratch_bytes >= bnn_bbb_final_scratch_bytes(S) &&
-                    !(reinterpret_cast<uintptr_t>(f->scratch) & 15) && (S == 1 || S > kLrRowsTicketMaxSamples || f->ticket) &&
+                    !(reinterpret_cast<uintptr_t>(f->scratch) & 15) &&
+                    (S == 1 || f->ticket || (S > kLrRowsTicketMaxSamples && !f->loss)) &&      // (no ticket: no loss tail, as in bnn_bbb_final_fwd)
                     (N % 4 != 0 || !(reinterpret_cast<uintptr_t>(a->y) & 15));
   if (!rows) {
     rc = bnn_lr_linear_fwd(a, stream_);
