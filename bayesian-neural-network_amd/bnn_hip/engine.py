@@ -43,8 +43,7 @@ FINAL_ROWS_MAX_SAMPLES = 16
 # (Letting the FIRST layer's launch carry the sampling of every later layer -- hidden layers matmul-only too -- was
 # built and measured slower at every size: one evaluation 36.8 against 35.4 us at one sample, 58.8 against 43.6 at three:
 # the rider blocks inherit the layer's 768-thread / 98 KB-LDS block shape, one per CU, and queue behind the layer's own.
-# PRESAMPLE_HIDDEN_MAX_SAMPLES = 0 keeps that form off; tools/few_sample_sweep.py re-measures it.)
-PRESAMPLE_HIDDEN_MAX_SAMPLES = 0
+# Only the output layer is ever pre-sampled.)
 
 
 def final_rows_ok(specs, n_samples: int, batch: int, hidden_dtype) -> bool:
@@ -62,18 +61,13 @@ def final_rows_ok(specs, n_samples: int, batch: int, hidden_dtype) -> bool:
 # >= 512 batch rows): 2 * batch flops per sampled weight make the matrix cores the bound, and the fused kernels would
 # redo the sampling for every 128-row batch block
 BLOCK_GEMM_MIN_BATCH = 512
-# GraphedElbo: those layers' sampling launches on a side stream, beside the earlier layers' matmuls.  Measured and left OFF
-# (tools/side_stream_ab.py, profiles/r04_side_stream_ab.log: 580 against 573 us per 4-sample evaluation at batch 1024, 1640
-# against 1617 at batch 4096): a K1g block takes 2 x 216 of a SIMD's 512 registers and 128 KiB of LDS, so a sampling block
-# only ever runs where a matmul block has not started yet -- the launches take turns on a CU instead of sharing it, and the
-# cross-stream edges cost more than the little that overlaps.  The bits are the same either way (tests).
-SAMPLE_BESIDE_MATMUL = False
-# LR, one minibatch: the prepare launch (fragments of the layers after the first) depends on no activation and the first layer (K3s
-# on the shared input, 152 blocks) leaves a hundred CUs idle -- it can run on a side stream beside that layer (a fork / join inside
-# the evaluation, so a captured graph keeps the edges).  Measured SLOWER by 9 us at every sample count (7 ... 64 samples: 88 against
-# 79 us at 8; profiles/r04_prepare_side_stream.log): a cross-stream edge inside a hipGraph costs more than the 5 us launch it
-# hides -- the same lesson as SAMPLE_BESIDE_MATMUL.  Off.
-PREPARE_BESIDE_FIRST_LAYER = False
+# GraphedElbo enqueues every launch on one stream.  Those layers' sampling launches on a side stream, beside the earlier layers'
+# matmuls, were measured slower (profiles/r04_side_stream_ab.log: 580 against 573 us per 4-sample evaluation at batch 1024, 1640
+# against 1617 at batch 4096): a K1g block takes 2 x 216 of a SIMD's 512 registers and 128 KiB of LDS, so a sampling block only
+# ever runs where a matmul block has not started yet -- the launches take turns on a CU instead of sharing it, and the
+# cross-stream edges cost more than the little that overlaps.  So was the LR prepare launch on a side stream beside the first
+# layer (K3s on the shared input, 152 blocks): 9 us slower at every sample count (7 ... 64 samples: 88 against 79 us at 8;
+# profiles/r04_prepare_side_stream.log) -- a cross-stream edge inside a hipGraph costs more than the 5 us launch it hides.
 
 
 def use_block_gemm(sp, batch: int, hidden_dtype) -> bool:
@@ -81,32 +75,17 @@ def use_block_gemm(sp, batch: int, hidden_dtype) -> bool:
         state.form == L.FORM_AUTO and state.math == L.MATH_BF16
 
 
-# BBB, bf16 math: from this many (minibatch, sample) pairs per launch on, the output layer + finalize can run in the row-split form
-# (K1r) behind a sampling launch of their own (K1s for the output layer's few weights) instead of one block per pair that samples,
-# multiplies and finalizes (K1c: 28.6 us at 256 pairs + 4 us for the sums launch).  Built, oracle-checked at (256, 1), and measured
-# SLOWER: 621 against 613 us per launch group of 256 minibatches (tools/rows_alone_ab.py, profiles/r04_rows_alone_ab.log) -- the
-# sampling launch and 2304 small blocks cost more than the one chain per pair they replace.  Off (set to 64 to try it).
-FINAL_ROWS_ALONE_MIN_SAMPLES = 10 ** 9
-FINAL_ROWS_ALONE_MAX_SAMPLES = 4096
-
-
-def final_rows_alone(specs, n_samples: int, batch: int, hidden_dtype) -> bool:
-    if len(specs) < 2 or any(sp.lr for sp in specs) or hidden_dtype != torch.bfloat16 or state.form != L.FORM_AUTO or \
-            state.math != L.MATH_BF16:
-        return False
-    k_last, n_last = specs[-1].in_out
-    return FINAL_ROWS_ALONE_MIN_SAMPLES <= n_samples <= FINAL_ROWS_ALONE_MAX_SAMPLES and n_last <= 16 and batch <= 128 and k_last % 8 == 0
+# (BBB, bf16 math, more pairs than FINAL_ROWS_MAX_SAMPLES: the output layer + finalize in the row-split form (K1r) behind a
+# sampling launch of their own (K1s for the output layer's few weights) instead of one block per pair that samples, multiplies
+# and finalizes (K1c: 28.6 us at 256 pairs + 4 us for the sums launch) was built, oracle-checked at (256, 1), and measured
+# SLOWER: 621 against 613 us per launch group of 256 minibatches (profiles/r04_rows_alone_ab.log) -- the sampling launch and
+# 2304 small blocks cost more than the one chain per pair they replace.)
 
 
 def presample_from(specs, n_samples: int, batch: int, hidden_dtype) -> int:
-    """Index of the layer whose launch carries the sampling job of all layers after it (they run matmul-only), or -1:
-    the layer before the output layer, or the first layer for very few (minibatch, sample) pairs."""
-    if not final_rows_ok(specs, n_samples, batch, hidden_dtype):
-        return -1
-    last = len(specs) - 1
-    if n_samples <= PRESAMPLE_HIDDEN_MAX_SAMPLES and all(sp.in_out[0] % 8 == 0 for sp in specs[1:]):
-        return 0
-    return last - 1
+    """Index of the layer whose launch carries the sampling job of the output layer (which then runs matmul-only), or -1:
+    the layer before the output layer."""
+    return len(specs) - 2 if final_rows_ok(specs, n_samples, batch, hidden_dtype) else -1
 
 
 def use_split(fin: int, fout: int, n_samples: int, batch: int = 128) -> bool:
@@ -264,7 +243,7 @@ def run_layers(layers: Sequence[LayerSpec], x: torch.Tensor, n_local: int, first
     # forward-only ELBO with on-chip eps: the output layer may take the pre-sampled row-split form (final_rows_ok)
     pre_from = presample_from(layers, n_local, x.shape[-2], hidden_dtype) \
         if (not differentiable and fin_kw is not None and want_stats and sample and injected is None) else -1
-    presampled = {}                                   # layer index -> dict(w, b, workspace) drawn by an earlier launch
+    presampled = {}                                   # layer index -> dict(w, b, workspace) drawn by an earlier launch (the output layer)
     for i, sp in enumerate(layers):
         last = i == len(layers) - 1
         if not sample:
@@ -344,13 +323,8 @@ def run_layers(layers: Sequence[LayerSpec], x: torch.Tensor, n_local: int, first
                     else:
                         out, fin = ops.bbb_final_fwd((h,) + pd, kw, dict(workspaces=stats, **fin_kw))
                     return out["y"], fin
-                if i in presampled:                   # a hidden layer whose weights an earlier launch has drawn
-                    ps = presampled[i]
-                    h = ops.bbb_sampled_matmul(h, ps["w"], ps["b"], n_samples=n_local, relu=sp.relu, y_dtype=call.y_dtype)
-                    stats.append(ps["workspace"])
-                    continue
                 if i == pre_from:
-                    # the later layers' weights are drawn beside this layer (a sampling job riding on its launch)
+                    # the output layer's weights are drawn beside this layer (a sampling job riding on its launch)
                     kw["rider"] = ops.build_sample_job(
                         [dict(w_mu=q.m.weight_mu.detach(), w_rho=q.m.weight_rho.detach(), b_mu=q.m.bias_mu.detach(),
                               b_rho=q.m.bias_rho.detach(), prior=q.m._prior_spec, layer_id=q.layer_id)
@@ -694,29 +668,15 @@ class GraphedElbo:
             self.lr_rider = dict(w_mu=sp.m.weight_mu.detach(), w_rho=sp.m.weight_rho.detach(), b_mu=sp.m.bias_mu.detach(),
                                  b_rho=sp.m.bias_rho.detach(), workspace=self.ws[nl - 1],
                                  w_frag=torch.empty(L.load().bnn_lr_prepare_bytes(*sp.in_out) // 4, dtype=torch.float32, device=dev))
-        self.pre_from = presample_from(self.specs, S, B, hid)      # the layer whose launch samples all layers after it
+        self.pre_from = presample_from(self.specs, S, B, hid)      # the layer whose launch samples the output layer
         self.rows = self.pre_from >= 0
         self.w_pre, self.b_pre = [None] * len(self.specs), [None] * len(self.specs)
-        # many pairs: the output layer's weights from a sampling launch of its own, then the row-split final form
-        self.rows_alone = (not self.rows) and self.scratch is not None and not self.lib[-1] and final_rows_alone(self.specs, S, B, hid)
-        if self.rows_alone:
-            k_i, n_i = self.specs[-1].in_out
-            self.w_pre[-1] = torch.empty((S, n_i, k_i), dtype=torch.bfloat16, device=dev)
-            self.b_pre[-1] = torch.empty((S, n_i), dtype=torch.float32, device=dev)
-            self.ws[-1] = ops.sample_workspace(S, k_i, n_i, dev)
         if self.rows:
             for i in range(self.pre_from + 1, len(self.specs)):
                 k_i, n_i = self.specs[i].in_out
                 self.w_pre[i] = torch.empty((S, n_i, k_i), dtype=torch.bfloat16, device=dev)
                 self.b_pre[i] = torch.empty((S, n_i), dtype=torch.float32, device=dev)
                 self.ws[i] = ops.sample_workspace(S, k_i, n_i, dev)
-        # large-batch layers (K1s + K1g): the sampling launches depend on no activation -- they run on a SIDE stream beside the
-        # matmuls of the layers before them (vector / memory work next to matrix-core work on the same CUs: layer l's K1g
-        # waits for layer l's K1s only), forked and joined inside the evaluation so that a captured graph keeps the edges
-        self.side = torch.cuda.Stream(device=dev) if (SAMPLE_BESIDE_MATMUL and sum(self.lib) >= 1 and not self.lr) else None
-        self.prep_side = (torch.cuda.Stream(device=dev)
-                          if (PREPARE_BESIDE_FIRST_LAYER and self.lr and self.wfrag[0] is None and any(w is not None for w in self.wfrag))
-                          else None)
         self.graph = None
         self.calls = None
         if capture == "calls":
@@ -766,32 +726,13 @@ class GraphedElbo:
             if self.x16 is not None:
                 h, h_sq, h_lo = self.x16, self.x16_sq, self.x16_lo
         last = len(self.specs) - 1
-        prepared = None                                  # event: the side stream's prepare launch has been enqueued
         if self.lr and any(w is not None for w in self.wfrag):
             # the prepared operands of every layer that takes them, in ONE launch (they depend on no activation)
             jobs = [dict(w_mu=sp.m.weight_mu.detach(), w_rho=sp.m.weight_rho.detach(), b_mu=sp.m.bias_mu.detach(),
                          b_rho=sp.m.bias_rho.detach(), workspace=self.ws[i], out=self.wfrag[i])
                     for i, sp in enumerate(self.specs) if self.wfrag[i] is not None]
-            if self.prep_side is not None:
-                main = torch.cuda.current_stream()
-                self.prep_side.wait_stream(main)         # fork: behind the previous evaluation's finalize (it read these buffers)
-                with torch.cuda.stream(self.prep_side):
-                    ops.lr_prepare_many(jobs, x3=self.lr_x3)
-                    prepared = torch.cuda.Event()
-                    prepared.record(self.prep_side)
-            else:
-                ops.lr_prepare_many(jobs, x3=self.lr_x3)
+            ops.lr_prepare_many(jobs, x3=self.lr_x3)
         grp = dict(sample_group=self.group, sample_group_stride=self.samples) if self.G > 1 else {}
-        sampled = {}                                     # layer -> event: its K1s launch (side stream) has been enqueued
-        if self.side is not None:
-            main = torch.cuda.current_stream()
-            self.side.wait_stream(main)                  # fork: behind everything this stream has enqueued (the last finalize)
-            with torch.cuda.stream(self.side):
-                for i, sp in enumerate(self.specs):
-                    if self.lib[i]:
-                        self._sample_layer(i, grp)
-                        sampled[i] = torch.cuda.Event()
-                        sampled[i].record(self.side)
         fin_kw = dict(layer_in=[sp.in_out[0] for sp in self.specs], layer_out=[sp.in_out[1] for sp in self.specs],
                       local_reparam=self.lr, prior=self.specs[0].m._prior_spec, n_samples=self.n_local,
                       target=self.target, mode=self.net.mode, nll_sigma=self.sigma, sample_counter=self.counter,
@@ -799,16 +740,10 @@ class GraphedElbo:
                       ticket=self.ticket, scratch=self.scratch, group_samples=self.group)
         for i, sp in enumerate(self.specs):
             p = tuple(t.detach() for t in (sp.m.weight_mu, sp.m.weight_rho, sp.m.bias_mu, sp.m.bias_rho))
-            if i == last and self.side is not None:
-                torch.cuda.current_stream().wait_stream(self.side)      # join: ahead of the launch that finalizes (it advances
-                                                                        # the sample counter the sampling launches read)
             common = dict(n_samples=self.n_local, math_mode=math_mode, relu=sp.relu, y_dtype=self.bufs[i].dtype,
                           eps_mode=L.EPS_PHILOX, seed=state.seed, layer_id=sp.layer_id, sample_offset=self.lo,
                           sample_counter=self.counter, workspace=self.ws[i], out=self.bufs[i], form=state.form, **grp)
             if self.lr:
-                if prepared is not None and self.wfrag[i] is not None:
-                    torch.cuda.current_stream().wait_event(prepared)      # join: the first layer that reads prepared operands
-                    prepared = None
                 if self.lr_x3 and i == last:
                     common["math_mode"] = L.MATH_F32          # the narrow output layer: exact fp32 on the fp32 activations
                 if i == last and self.scratch is not None and not wide_nll(self.specs, self.x.shape[-2]):
@@ -823,10 +758,7 @@ class GraphedElbo:
                                   x_lo=h_lo if self.lr_x3 else None, out_lo=self.bufs_lo[i] if self.lr_x3 else None, **common)
                 h_sq = self.bufs_sq[i]
             elif self.lib[i]:
-                if i in sampled:
-                    torch.cuda.current_stream().wait_event(sampled[i])
-                else:
-                    self._sample_layer(i, grp)
+                self._sample_layer(i, grp)
                 ops.bbb_sampled_matmul(h, self.lib_w[i], self.lib_b[i], n_samples=self.n_local, relu=sp.relu,
                                        y_dtype=self.bufs[i].dtype, out=self.bufs[i])
                 if i == last:
@@ -835,11 +767,7 @@ class GraphedElbo:
                 kw = dict(prior=sp.m._prior_spec, want_stats=True, split_scratch=self.split[i], w_sigma=self.wsigma[i], **common)
                 if self.x3:
                     kw.update(x_lo=h_lo if h.dtype == torch.bfloat16 else None, out_lo=self.bufs_lo[i])
-                if i == last and self.rows_alone:
-                    ops.bbb_sample_weights([dict(w_mu=p[0], w_rho=p[1], b_mu=p[2], b_rho=p[3], prior=sp.m._prior_spec, layer_id=sp.layer_id,
-                                                 workspace=self.ws[i], w_out=self.w_pre[i], b_out=self.b_pre[i])],
-                                           n_samples=self.n_local, seed=state.seed, sample_offset=self.lo, sample_counter=self.counter, **grp)
-                if i == last and (self.rows or self.rows_alone):
+                if i == last and self.rows:
                     ops.bbb_final_fwd((h, None, None, None, None),
                                       dict(n_samples=self.n_local, prior=sp.m._prior_spec, math_mode=math_mode, relu=sp.relu,
                                            y_dtype=self.bufs[i].dtype, eps_mode=L.EPS_ZERO, want_stats=False, out=self.bufs[i],
@@ -847,11 +775,8 @@ class GraphedElbo:
                                       dict(workspaces=self.ws, **fin_kw))
                 elif i == last:
                     ops.bbb_final_fwd((h,) + p, kw, dict(workspaces=self.ws[:last], **fin_kw))
-                elif self.w_pre[i] is not None:              # a hidden layer whose weights an earlier launch has drawn
-                    ops.bbb_sampled_matmul(h, self.w_pre[i], self.b_pre[i], n_samples=self.n_local, relu=sp.relu,
-                                           y_dtype=self.bufs[i].dtype, out=self.bufs[i])
                 else:
-                    if i == self.pre_from:                   # the later layers' weights are drawn beside this layer
+                    if i == self.pre_from:                   # the output layer's weights are drawn beside this layer
                         kw["rider"] = ops.build_sample_job(
                             [dict(w_mu=q.m.weight_mu.detach(), w_rho=q.m.weight_rho.detach(), b_mu=q.m.bias_mu.detach(),
                                   b_rho=q.m.bias_rho.detach(), prior=q.m._prior_spec, layer_id=q.layer_id,

@@ -1334,58 +1334,28 @@ __global__ __launch_bounds__(NW * 64, 4) void bbb_fwd_gemm_kernel(const BbbK p) 
 // bf16(w - wa)), and every (batch tile, k-step) takes three MFMAs: wa . xh + wl . xh + wa . xl.  The staging buffers then
 // would hold 48 KiB each -- 96 KiB per block, one 8-wave block per CU, two waves per SIMD: measured 636 us per 256-pair
 // launch of the 1200 x 1200 layer against the bf16 form's 322 (both forms' steps take ~4000 cycles per WAVE: what a launch
-// delivers is waves per SIMD over that latency).  So the X3 form keeps its PARAMETERS IN ONE BUFFER (PS): a step reads its
+// delivers is waves per SIMD over that latency).  So the X3 form keeps its PARAMETERS IN ONE BUFFER: a step reads its
 // (mu, sigma) fragments into registers first, the block meets (a second, cheap barrier right behind the step's start), and
 // only then are the next step's parameter pieces requested into the same 16 KiB; x stays double-buffered, the bias goes
 // through lane shuffles instead of LDS: 16 + 2 x 32 KiB = 80 KiB, two blocks per CU, four waves per SIMD like the bf16 form.
-#ifndef BNN_K1B2_PS
-#define BNN_K1B2_PS 0       // build knob: the bf16 form with single-buffered parameters too (48 KiB: three blocks per CU)
-#endif
-#ifndef BNN_K1B2_WPS
-#define BNN_K1B2_WPS 4      // build knob: waves per SIMD the register allocation aims at
-#endif
-#ifndef BNN_K1B2_STAG
-#define BNN_K1B2_STAG 0     // the second pair's waves one MFMA phase behind the first pair's (see STAG in the kernel); 0: in lockstep
-#endif
-#ifndef BNN_K1B2_SPREAD
-#define BNN_K1B2_SPREAD 0   // build knob: the four staging pieces of a step spread over the previous step (K2_STAGE_PIECE) instead of all at its top.  Measured (profiles/r04_k1b2_spread.log): eps = 0 launches 304 -> 294 us, launches with the generator 348 -> 353: off
-#endif
+// The bf16 form double-buffers everything: two staging buffers (one k-step of DMA run-ahead) of 32 KiB + the bias table.
 template <int NF, int SB, int EPS, int NB = 2, bool X3 = false>
-__global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd_gemm2_kernel(const BbbK p) {
+__global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const BbbK p) {
   constexpr int NW = NF * SB;
-  static_assert(NB == 2 || NB == 3, "staging buffers (NB - 1 k-steps of DMA run-ahead)");
+  static_assert(NB == 2, "two staging buffers");
   constexpr int WPW = 4 / SB;                 // parameter pieces (of a tile's four) each of the SB waves of a tile brings
   constexpr int XPW = 8 / NF;                 // x pieces (batch tiles of its pair) each of the NF waves of a pair brings
   constexpr int XT = X3 ? 1024 : 512;         // float4s of one pair's x tile (X3: the hi plane's 8 pieces, then the lo plane's)
   static_assert(SB == 1 || SB == 2 || SB == 4, "pairs per block");
   static_assert(NF == 2 || NF == 4 || NF == 8, "feature waves per block");
-  static_assert(!X3 || NB == 2, "split-bf16 form: two x buffers");
-  constexpr bool PS = X3 || (BNN_K1B2_PS && NB == 2);   // parameters single-buffered (see above)
-  // x buffers of the PS form: two, or (build knob BNN_K1B2_PS = 2, bf16 form) a ring of three -- the x pieces of step t + 2 are
-  // requested during step t, behind the parameters of step t + 1, and stay in flight over the step's closing wait
-  constexpr int XB = (PS && !X3 && BNN_K1B2_PS == 2) ? 3 : 2;
-  constexpr int RB = PS ? XB : NB;            // buffers the step index cycles through
-  constexpr int BUF = NF * 256 + SB * XT;     // float4s of one staging buffer of the double-buffered-everything layout
-  // STAG (bf16 form, two pairs): the waves of the block's SECOND pair run their x reads + MFMAs of step t - 1 at the START of step
-  // t.  A CU's SIMD holds wave fw of the first pair and wave fw of the second: in lockstep both queue for the vector-memory pipe
-  // at the top of a step (half of a wave's step, tools/stamps_k1b2.py), both run their generator next, both their MFMAs last.
-  // One phase apart, the second pair's LDS reads and MFMAs run beside the first pair's staging burst, its staging beside the
-  // first pair's parameter reads, its generator beside the first pair's MFMAs.  The late pair keeps its weight fragment over the
-  // barrier (4 registers) and its x tile one step longer: a ring of THREE x slots for that pair (the two in the staging buffers
-  // + one more 8 KiB behind the bias table), since its waves request x of step t + 1 while others of them still read x of step
-  // t - 1.  Same arithmetic in the same order per accumulator: same bits.
-#if defined(BNN_TUNE) || defined(BNN_STAMPS)
-  constexpr bool STAG = false;
-#else
-  constexpr bool STAG = BNN_K1B2_STAG && !X3 && !(BNN_K1B2_PS && NB == 2) && NB == 2 && SB == 2;
-#endif
-  // LDS image, in float4s.  !PS: [buffer][NF tiles' parameter pieces | SB pairs' x tiles], then the bias table.
-  //                          PS: [parameter pieces][x buffer 0][x buffer 1].
-  auto p_idx = [](int buf) { return PS ? 0 : buf * BUF; };
-  auto x_idx = [](int buf) { return PS ? NF * 256 + buf * (SB * XT) : buf * BUF + NF * 256; };
+  constexpr int BUF = NF * 256 + SB * XT;     // float4s of one staging buffer of the bf16 form
+  // LDS image, in float4s.  bf16: [buffer][NF tiles' parameter pieces | SB pairs' x tiles], then the bias table.
+  //                          X3: [parameter pieces][x buffer 0][x buffer 1].
+  auto p_idx = [](int buf) { return X3 ? 0 : buf * BUF; };
+  auto x_idx = [](int buf) { return X3 ? NF * 256 + buf * (SB * XT) : buf * BUF + NF * 256; };
   // ONE shared object (the guide's second-__shared__-object trap), the staging buffers first
-  __shared__ __attribute__((aligned(16))) float4 sm_all[PS ? NF * 256 + XB * SB * XT : NB * BUF + NW * 4 + (STAG ? XT : 0)];
-  float (*bias_s)[16] = reinterpret_cast<float (*)[16]>(sm_all + (PS ? 0 : NB * BUF));          // (!PS only)
+  __shared__ __attribute__((aligned(16))) float4 sm_all[X3 ? NF * 256 + 2 * SB * XT : NB * BUF + NW * 4];
+  float (*bias_s)[16] = reinterpret_cast<float (*)[16]>(sm_all + (X3 ? 0 : NB * BUF));          // (bf16 only)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: the staging bases below live in SGPRs)
   const int fw = wave % NF, sb = wave / NF;
   const int r = lane & 15, q = lane >> 4;
@@ -1432,12 +1402,10 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
 #pragma unroll
   for (int i = 0; i < XPW; ++i) voff_x[i] = ((uint32_t)xrow[i] + (uint32_t)(q * 8)) * 2u;
   const uint32_t lds0 = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)&sm_all[0];
-  // float4 index of this wave's pair's x tile `slot`: the pair's region of staging buffer `slot`, or (STAG, the late pair's
-  // third slot) the region behind the bias table
-  const bool late = STAG && sb == 1;                            // wave-uniform
-  auto x_slot = [&](int slot) { return (STAG && slot == 2) ? NB * BUF + NW * 4 : x_idx(slot) + sb * XT; };
+  // float4 index of this wave's pair's x tile in staging buffer `slot`
+  auto x_slot = [&](int slot) { return x_idx(slot) + sb * XT; };
   // (the plan takes this form only where the tensors' byte spans fit 32 bits)
-  // WP / WX (compile-time): stage the parameter pieces / the x pieces of step t (the PS form requests them at different points
+  // WP / WX (compile-time): stage the parameter pieces / the x pieces of step t (the X3 form requests them at different points
   // of a step, into different buffer indices)
   auto stage_fast = [&](int t, int pbuf, int xbuf, auto wp_, auto wx_) __attribute__((always_inline)) {
     if (decltype(wp_)::value) {
@@ -1466,26 +1434,6 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
       }
     }
   };
-  // ONE piece of step t's staging (full steps only), pinned in the instruction stream by `tie`: a value computed just before and
-  // consumed just after.  All four pieces of a wave issued back to back at the top of a step queue behind the other fifteen
-  // waves' pieces in the CU's one vector-memory pipe (64 B per clock: the 64 KiB the CU's two blocks request per step take it
-  // ~1000 cycles) and the wave cannot issue anything else meanwhile -- in-kernel stamps: 1370 of a wave-step's ~2800 cycles
-  // between the top of a step and its parameter fragments (tools/stamps_k1b2.py, profiles/r04_k1b2_stamps.log).  Spread over
-  // the step -- top, behind the parameter reads, behind the generator, behind the packing of w -- a piece meets a drained pipe.
-  // (a macro, not a generic lambda: `tie` is a float, a uint32_t or a 4-register vector; IDX is a literal)
-#define K2_STAGE_PIECE(T, BUF, IDX, TIE)                                                                                                   \
-  do {                                                                                                                                     \
-    if ((IDX) < WPW) {                                                                                                                     \
-      const int j_ = sb * WPW + (IDX);                                                                                                     \
-      const char* base_ = reinterpret_cast<const char*>((j_ & 2) ? p.w_sigma : p.w_mu) + (size_t)(T) * 128 + (j_ & 1) * 16;               \
-      const uint32_t m0v_ = lds0 + (uint32_t)((p_idx(BUF) + (fw * 4 + j_) * 64) * 16);                                                     \
-      asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : "+v"(TIE) : "v"(voff_w), "s"(base_), "s"(m0v_) : "memory", "m0"); \
-    } else {                                                                                                                               \
-      const char* base_ = reinterpret_cast<const char*>(xs) + (size_t)(T) * 64;                                                            \
-      const uint32_t m0v_ = lds0 + (uint32_t)((x_idx(BUF) + sb * XT + (fw + ((IDX) - WPW) * NF) * 64) * 16);                               \
-      asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : "+v"(TIE) : "v"(voff_x[((IDX) - WPW) % XPW]), "s"(base_), "s"(m0v_) : "memory", "m0"); \
-    }                                                                                                                                      \
-  } while (0)
   auto stage_slow = [&](int t, int pbuf, int xbuf, auto wp_, auto wx_) __attribute__((always_inline)) {
     const int kk = min(t * 32 + q * 8, K - 8);
     if (decltype(wp_)::value) {
@@ -1530,18 +1478,7 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
     beps_pre = bias_eps(p, n, s, gs, do_dump);
   }
   stage(0, 0);
-  if (PS && XB == 3) {
-    stage_sel(ksteps > 1 ? 1 : 0, 0, 1, std::false_type{}, std::true_type{});      // x of step 1 (a one-step layer: a clamped re-read)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  } else if (NB == 3) {
-    // two k-steps of run-ahead (build knob BNN_GEMM_RING=3, tools/build_k1b2_variants.sh): step 1 is in flight while step
-    // 0's pieces are waited for (a one-step layer issues a clamped re-read of step 0 into the idle buffer 1 so that the
-    // counted wait holds on every path)
-    stage(ksteps > 1 ? 1 : 0, 1);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WPW + XPW) : "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   f32x4 acc[8];
@@ -1619,38 +1556,26 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
       }
     }
   };
-  bf16x8 wa_prev = {};                                             // (STAG) the late pair's weight fragment of the step before
-  // cur: the staging buffer of step t (t % RB); c3 (STAG): t % 3, the late pair's x slot of step t
-  auto step = [&](int t, int cur, int c3, auto full_) __attribute__((always_inline)) {
+  // cur: the staging buffer of step t (t % NB).  (mfma_phase is captured explicitly, ahead of the implicit captures: the order
+  // of the closure's members steers the optimizer's value order and with it the register allocation of the loop -- this one
+  // reproduces the code that profiles/ measured.)
+  auto step = [&, &mfma_phase = mfma_phase](int t, int cur, auto full_) __attribute__((always_inline)) {
     constexpr bool FULL = decltype(full_)::value;
     const int k = t * 32 + q * 8;
     const bool lane_ok = FULL || (n_ok && k < K);
     K2_T(st0);
-    if (STAG) {
-      if (late && t > 0) mfma_phase(wa_prev, wa_prev, x_slot(c3 == 0 ? 2 : c3 - 1), f32x4{0.f, 0.f, 0.f, 0.f});   // wave-uniform branch
-    }
     // the buffer staged here was last read in step t - 1 (barrier since)
-    const bool staged = t + NB - 1 < ksteps;                     // block-uniform
+    const bool staged = t + 1 < ksteps;                          // block-uniform
 #ifdef BNN_TUNE
     // tuning build only (wrong results; tools/k1b_ablate.py): BNN_TUNE_K1B bit 0 = no barrier, 1 = no waits, 3 = no DMA (the LDS
     // reads of the parameters stay: stale bytes, the same vector work), 4 = no x reads, 5 = no MFMAs
     if (staged && !(p.tune & 8)) {
-      if (PS && XB == 2) stage_sel(t + 1, 0, cur ^ 1, std::false_type{}, std::true_type{});
-      else if (!PS) stage(t + NB - 1, NB == 2 ? (cur ^ 1) : (cur == 0 ? 2 : cur - 1));
-    }
 #else
-    // (spread: the four pieces of step t + 1 at four points of this step instead of here -- see stage_piece)
-    const bool spread = BNN_K1B2_SPREAD && !STAG && !PS && NB == 2 && WPW + XPW == 4 && staged && (t + 2) * 32 <= K;     // block-uniform
-    if (staged && !spread) {
-      if (PS && XB == 2) stage_sel(t + 1, 0, cur ^ 1, std::false_type{}, std::true_type{});      // x of step t + 1 now, its parameters below
-      else if (STAG) stage_sel(t + 1, cur ^ 1, late ? (c3 == 2 ? 0 : c3 + 1) : (cur ^ 1), std::true_type{}, std::true_type{});
-      else if (!PS) stage(t + NB - 1, NB == 2 ? (cur ^ 1) : (cur == 0 ? 2 : cur - 1));
-    }
-    uint32_t tie0 = voff_w;
-    if (spread) K2_STAGE_PIECE(t + 1, cur ^ 1, 2, tie0);            // an x piece first: the pieces longest in flight are the ones the
-                                                                 // next step reads last
+    if (staged) {
 #endif
-    const bool x_ahead = PS && XB == 3 && t + 2 < ksteps;        // block-uniform: this step requests the x pieces of step t + 2
+      if (X3) stage_sel(t + 1, 0, cur ^ 1, std::false_type{}, std::true_type{});      // x of step t + 1 now, its parameters below
+      else stage(t + 1, cur ^ 1);
+    }
     // LDS reads by hand (ds_read_b128 in asm): a compiler-visible read of `sm` would be ordered behind EVERY LDS-DMA in
     // flight that may alias it -- s_waitcnt vmcnt(0) right behind the prefetch this step has just issued -- although
     // buffer t & 1 was complete at the last barrier.  The "+v" operands of the wait tie the consumers to it; the outputs
@@ -1660,22 +1585,17 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
     asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
                  : "=&v"(m_lo), "=&v"(m_hi), "=&v"(g_lo), "=&v"(g_hi) : "v"(pa));
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(m_lo), "+v"(m_hi), "+v"(g_lo), "+v"(g_hi));
-    if (PS) {
+    if (X3) {
       // every wave of the block holds its (mu, sigma) fragments in registers: the one parameter buffer is free for step t + 1
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
 #ifdef BNN_TUNE
       if (t + 1 < ksteps && !(p.tune & 8)) stage_sel(t + 1, 0, 0, std::true_type{}, std::false_type{});
-      if (x_ahead && !(p.tune & 8)) stage_sel(t + 2, 0, cur == 0 ? 2 : cur - 1, std::false_type{}, std::true_type{});
 #else
       if (t + 1 < ksteps) stage_sel(t + 1, 0, 0, std::true_type{}, std::false_type{});
-      if (x_ahead) stage_sel(t + 2, 0, cur == 0 ? 2 : cur - 1, std::false_type{}, std::true_type{});   // slot (cur + 2) % 3, behind the parameters
 #endif
     }
     K2_T(st1);
-#ifndef BNN_TUNE
-    if (spread) K2_STAGE_PIECE(t + 1, cur ^ 1, 3, m_lo);
-#endif
     const f32x2 mu2[4] = {{m_lo[0], m_lo[1]}, {m_lo[2], m_lo[3]}, {m_hi[0], m_hi[1]}, {m_hi[2], m_hi[3]}};
     const f32x2 sg2[4] = {{g_lo[0], g_lo[1]}, {g_lo[2], g_lo[3]}, {g_hi[0], g_hi[1]}, {g_hi[2], g_hi[3]}};
     float e[8];
@@ -1683,9 +1603,6 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
       const uint32_t g = (uint32_t)n * (uint32_t)gpr + (uint32_t)(k >> 2);
       uint4 pa_, pb_;
       philox_pair<>(g, gs, wid, p.k0, p.k1, pa_, pb_);
-#ifndef BNN_TUNE
-      if (spread) K2_STAGE_PIECE(t + 1, cur ^ 1, 0, pa_.x);          // between the integer and the transcendental half
-#endif
       box_muller8(pa_, pb_, e);
     } else if (EPS == BNN_EPS_MEMORY) {
       load8<true>(p.eps_w + ((size_t)s * N + n) * K + k, lane_ok ? 8 : 0, e);
@@ -1694,10 +1611,6 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
       for (int j = 0; j < 8; ++j) e[j] = 0.f;
     }
     if (p.eps_w_dump && do_dump) store8<true>(p.eps_w_dump + ((size_t)s * N + n) * K + k, lane_ok ? 8 : 0, e);
-#ifndef BNN_TUNE
-    if (spread) K2_STAGE_PIECE(t + 1, cur ^ 1, 1, e[0]);             // behind the generator (EPS != PHILOX: the third and fourth piece
-    if (spread && EPS != BNN_EPS_PHILOX) K2_STAGE_PIECE(t + 1, cur ^ 1, 0, e[1]);   // both here)
-#endif
     f32x2 w2[4], e2v = {0.f, 0.f}, av = {0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1758,27 +1671,18 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
     asm volatile("" :: "v"(wa));
 #endif
     K2_T(st2);
-    if (STAG && late) wa_prev = wa;                                // its products at the top of the next step
-    else mfma_phase(wa, wl, x_idx(cur) + sb * XT, m_lo);
+    mfma_phase(wa, wl, x_idx(cur) + sb * XT, m_lo);
     // this wave's DMA pieces of step t + 1 have landed and its LDS reads of buffer `cur` are back; then the block meets
-    // (a bare s_barrier: __syncthreads()'s fence would add the same vmcnt(0)).  With three buffers the pieces of step
-    // t + 2, issued at the top of this step, stay in flight: vector-memory operations complete in issue order, and
-    // WPW + XPW of them are younger than step t + 1's pieces whenever this step staged anything.
+    // (a bare s_barrier: __syncthreads()'s fence would add the same vmcnt(0))
 #ifdef BNN_TUNE
-    if (!(p.tune & 2)) {
-      if (x_ahead) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(XPW) : "memory");
-      else if (!PS && NB == 3 && staged) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WPW + XPW) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    }
+    if (!(p.tune & 2)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if (!(p.tune & 1)) __builtin_amdgcn_s_barrier();
 #else
 #ifdef BNN_STAMPS
     asm volatile("" :: "v"(acc[0]), "v"(acc[7]));
     K2_T(st3);
 #endif
-    if (x_ahead) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(XPW) : "memory");     // the x pieces of step t + 2 stay in flight
-    else if (!PS && NB == 3 && staged) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WPW + XPW) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     K2_T(st4);
     __builtin_amdgcn_s_barrier();
 #endif
@@ -1791,14 +1695,11 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
   {
     const bool tiles_full = (tb * NF + NF) * 16 <= N;           // block-uniform
     const int full_steps = tiles_full ? (K >> 5) : 0;           // steps whose 32 k are all inside K
-    int t = 0, cur = 0, c3 = 0;
+    int t = 0, cur = 0;
 #pragma nounroll
-    for (; t < full_steps; ++t, cur = (cur + 1 == RB ? 0 : cur + 1), c3 = (c3 == 2 ? 0 : c3 + 1)) step(t, cur, c3, std::true_type{});
+    for (; t < full_steps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, std::true_type{});
 #pragma nounroll
-    for (; t < ksteps; ++t, cur = (cur + 1 == RB ? 0 : cur + 1), c3 = (c3 == 2 ? 0 : c3 + 1)) step(t, cur, c3, std::false_type{});
-    if (STAG) {
-      if (late) mfma_phase(wa_prev, wa_prev, x_slot(c3 == 0 ? 2 : c3 - 1), f32x4{0.f, 0.f, 0.f, 0.f});   // the late pair's last step (ksteps >= 1)
-    }
+    for (; t < ksteps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, std::false_type{});
   }
 
 #ifdef BNN_STAMPS
@@ -1808,19 +1709,18 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
   }
 #endif
 #undef K2_T
-#undef K2_STAGE_PIECE
   // ---- epilogue: bias, stats, store (no cross-wave reduction)
   float b_own = 0.f;                                           // lanes 0 .. 15 (q == 0): the sampled bias of feature r
   if (q == 0) {
     if (n_ok) b_own = sample_bias(p, bmu_pre, brho_pre, beps_pre, do_stats, do_ls, s_e2, s_a, s_ls);
-    if (!PS) bias_s[wave][r] = b_own;
+    if (!X3) bias_s[wave][r] = b_own;
   }
   if (do_stats) {
     const float a = wave_sum(s_e2), b = wave_sum(s_a), cc = wave_sum(s_ls);
     if (lane == 0 && tile < T) p.ws[1 + (size_t)s * T + tile] = make_float4(a, b, cc, 0.f);
   }
   float bq[4];
-  if (PS) {                                                    // the PS form has no LDS left for a bias table: lane shuffles
+  if (X3) {                                                    // the X3 form has no LDS left for a bias table: lane shuffles
 #pragma unroll
     for (int i = 0; i < 4; ++i) bq[i] = __shfl(b_own, q * 4 + i, 64);
   } else {
@@ -1829,7 +1729,7 @@ __global__ __launch_bounds__(NF * SB * 64, (X3 ? 4 : BNN_K1B2_WPS)) void bbb_fwd
   if (!active) return;
   const int nb = tile * 16 + q * 4;
   const bool vec_ok = (N & 3) == 0;
-  if (!PS) {
+  if (!X3) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) bq[i] = bias_s[wave][q * 4 + i];
   }
@@ -1974,14 +1874,8 @@ struct BbbPlan {
 
 constexpr size_t kL2WeightBudget = 2560 * 1024;   // of an XCD's 4 MiB L2: the (mu, rho | sigma) of the feature groups a class of the
                                                   // 2-D work order keeps resident while the units' x tiles stream through
-#ifndef BNN_GEMM_PAIRS
-#define BNN_GEMM_PAIRS 2
-#endif
-#ifndef BNN_GEMM_RING
-#define BNN_GEMM_RING 2
-#endif
-constexpr int kGemmPairs = BNN_GEMM_PAIRS;   // K1b2: units that share a block's parameter tiles
-constexpr int kGemmRing = BNN_GEMM_RING;     // K1b2: LDS staging buffers (k-steps of DMA run-ahead + 1); 2 x 2 is the measured
+constexpr int kGemmPairs = 2;                // K1b2: units that share a block's parameter tiles
+constexpr int kGemmRing = 2;                 // K1b2: LDS staging buffers (k-steps of DMA run-ahead + 1); 2 x 2 is the measured
                                              // best of {2, 4} pairs x {2, 3} buffers (profiles/r03_k1b2_variants.log)
 constexpr int kGemmPairsX3 = 2;              // ... of the split-bf16 variant (48 KiB per staging buffer)
 constexpr int kGemmMinBlocks = 450;          // block-GEMM form from this many (64-feature group x sample x batch block) items
@@ -2147,8 +2041,7 @@ static int bbb_plan(const bnn_bbb_fwd_args* a, bool al, BbbPlan& pl, bool allow_
     pl.nw = 4 * pairs;
     pl.blocks = (long)((N + 63) / 64) * (((long)S * mbs + pairs - 1) / pairs);
     // (split-bf16 form: one parameter buffer + two x buffers of a (hi, lo) plane pair per unit, no bias table)
-    pl.lds = x3 ? (4 * 256 + 2 * pairs * 1024) * 16 : kGemmRing * (4 * 256 + pairs * 512) * 16 + pl.nw * 16 * sizeof(float) +
-                      ((BNN_K1B2_STAG && !BNN_K1B2_PS && kGemmRing == 2 && pairs == 2) ? 512 * 16 : 0);   // (the late pair's third x slot)
+    pl.lds = x3 ? (4 * 256 + 2 * pairs * 1024) * 16 : kGemmRing * (4 * 256 + pairs * 512) * 16 + pl.nw * 16 * sizeof(float);
   }
   if (x3 && pl.pairs == 1) {                 // (the plain block-GEMM kernel has no split-bf16 variant)
     tile_plan(S, B, K, N, al, 8, pl);

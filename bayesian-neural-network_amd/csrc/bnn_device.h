@@ -95,11 +95,6 @@ __device__ __forceinline__ void box_muller8(const uint4& a, const uint4& b, floa
 template <int ROUNDS = BNN_PHILOX_ROUNDS>
 __device__ __forceinline__ void philox_normal8(uint32_t group, uint32_t gsample, uint32_t tensor_id, uint32_t k0, uint32_t k1,
                                                float out[8]) {
-#ifdef BNN_PHILOX_SEQ       // A/B build knob (tools/): the two calls one after the other, as rounds 1-3 wrote them
-  philox_normal4(group, gsample, tensor_id, k0, k1, out);
-  philox_normal4(group + 1u, gsample, tensor_id, k0, k1, out + 4);
-  return;
-#endif
   uint4 a, b;
   philox_pair<ROUNDS>(group, gsample, tensor_id, k0, k1, a, b);
   box_muller8(a, b, out);

@@ -2059,10 +2059,7 @@ extern "C" int bnn_lr_prepare_x3(const float* w_mu, const float* w_rho, const fl
 // set of three prefetched fragments in flight the compiler spills INSIDE the k loop -- scratch loads and stores count in vmcnt
 // like every vector-memory operation, so the ring's counted waits ("all but this step's operations have landed") would no
 // longer say what they mean.  With one step of prefetch every wait in the loop is vmcnt(0).
-#ifndef BNN_LR_X3_DEPTH
-#define BNN_LR_X3_DEPTH 1
-#endif
-static constexpr int kLrX3Depth = BNN_LR_X3_DEPTH;
+static constexpr int kLrX3Depth = 1;
 
 // validate the arguments and fill the kernel parameter block
 static int lr_fill(const bnn_lr_fwd_args* a, LrK& k) {
@@ -2417,14 +2414,10 @@ extern "C" int bnn_loss_tail_(const bnn_finalize_args* f, void* stream_);   // r
 
 // Last LR layer + ELBO finalize: ONE launch (K3r) for a few-sample evaluation with a narrow output layer, else
 // bnn_lr_linear_fwd followed by bnn_elbo_finalize.
-#ifndef BNN_LR_ROWS_PREPARED_MAX
-#define BNN_LR_ROWS_PREPARED_MAX 4096   // build knob (A/B): 16 = the row-split form for few pairs only, as until round 4
-#endif
-#ifndef BNN_LR_ROWS_RT_MAX
-#define BNN_LR_ROWS_RT_MAX 2            // build knob (A/B): 1 = one 16-row tile per block whatever the launch.  The LR launch group of
-                                        // 256 minibatches, one box, alternating: 573-576 us at 1, 552-557 at 2, 559-563 at 4 (profiles/r04_lr_rows_ab.log)
-#endif
-static_assert(BNN_LR_ROWS_RT_MAX >= 1 && BNN_LR_ROWS_RT_MAX <= bnn::kRowsMaxTiles, "LrRows.rt is at most kRowsMaxTiles");
+static constexpr int kLrRowsPreparedMax = 4096;   // K3r over prepared fragments: up to this many pairs (16 without them)
+static constexpr int kLrRowsRtMax = 2;            // K3r: 16-row tiles per block at most.  The LR launch group of 256 minibatches,
+                                                  // one box, alternating: 573-576 us at 1, 552-557 at 2, 559-563 at 4 (profiles/r04_lr_rows_ab.log)
+static_assert(kLrRowsRtMax >= 1 && kLrRowsRtMax <= bnn::kRowsMaxTiles, "LrRows.rt is at most kRowsMaxTiles");
 static constexpr int kLrRowsTicketMaxSamples = 64;   // K3r: up to here the last sample's last block folds the sums
 extern "C" int bnn_elbo_sums_(const bnn_finalize_args* f, void* stream_);
 extern "C" int bnn_lr_final_fwd(const bnn_lr_fwd_args* a, const bnn_finalize_args* f, void* stream_) {
@@ -2440,7 +2433,7 @@ extern "C" int bnn_lr_final_fwd(const bnn_lr_fwd_args* a, const bnn_finalize_arg
   // (S: up to 16 pairs when every row block has to park the layer itself; over PREPARED fragments (bnn_lr_prepare[_many], the
   // rider) any launch group -- its grid is S x (ceil(B / 16) + 1) small blocks that need no LDS)
   const bool prepared = a->w_frag && a->want_kl && a->workspace && !(reinterpret_cast<uintptr_t>(a->w_frag) & 15);
-  const bool rows = a->math == BNN_MATH_BF16 && a->x_dtype == BNN_BF16 && a->y_dtype == BNN_F32 && N <= 16 && B <= 128 && S <= (prepared ? BNN_LR_ROWS_PREPARED_MAX : 16) &&
+  const bool rows = a->math == BNN_MATH_BF16 && a->x_dtype == BNN_BF16 && a->y_dtype == BNN_F32 && N <= 16 && B <= 128 && S <= (prepared ? kLrRowsPreparedMax : 16) &&
                     (K % 8) == 0 && K <= 2048 && !(reinterpret_cast<uintptr_t>(a->x) & 15) && a->eps_mode == BNN_EPS_PHILOX &&
                     !a->eps_act_dump && !a->eps_b_dump && !a->y_sq && !a->y_bf16_copy && !a->hfac_out && !a->kl_out && a->form == BNN_FORM_AUTO &&
                     f->local_reparam && nl >= 1 && nl <= 8 && f->n_samples == S && f->classes == N && f->batch == B &&
@@ -2477,7 +2470,7 @@ extern "C" int bnn_lr_final_fwd(const bnn_lr_fwd_args* a, const bnn_finalize_arg
   const int RB = (B + 15) / 16;
   // many pairs over prepared fragments: two 16-row tiles per block (two blocks of ~200 registers fit a CU: S x 9 one-tile blocks
   // of a 256-pair launch ran as five rounds); few pairs: one tile per block, the shortest chain
-  r.rt = (r.w_frag && (long)S * (RB + 1) > 512) ? (RB < BNN_LR_ROWS_RT_MAX ? RB : BNN_LR_ROWS_RT_MAX) : 1;
+  r.rt = (r.w_frag && (long)S * (RB + 1) > 512) ? (RB < kLrRowsRtMax ? RB : kLrRowsRtMax) : 1;
   const int NBLK = (RB + r.rt - 1) / r.rt;
   const size_t lds = r.w_frag ? 0 : (size_t)2 * ((K + 31) / 32) * 4 * 16 * 8 * 2;       // bf16 M and sigma^2 fragments of the whole layer (parked by the block itself)
   if (lds > 64 * 1024) {

@@ -1556,13 +1556,11 @@ def test_row_split_output_layer_equals_the_two_launch_form(dev, monkeypatch, dim
     (a1, b1, o1, lg1, c1), (a2, b2, o2, lg2, c2) = res
     assert c1 == c2 == 40 + 3 * G * S and not torch.equal(a1, b1)
     scale = float(lg2.abs().max()) + 1e-6
-    # the output layer alone pre-sampled: same bf16 operands, fp32 summation order only.  Hidden layers pre-sampled too
-    # (n <= engine.PRESAMPLE_HIDDEN_MAX_SAMPLES): their matmul-only launches sum in another order, and a hidden
-    # activation that lands on the other side of a bf16 rounding boundary moves by 2^-8 of its value
-    # (and so does a hidden layer that takes the K-sliced block GEMM under FORM_AUTO: from 4 pairs per launch)
-    hidden_pre = G * S <= engine.PRESAMPLE_HIDDEN_MAX_SAMPLES and len(dims) == 3
+    # the output layer alone pre-sampled: same bf16 operands, fp32 summation order only.  A hidden layer that takes the
+    # K-sliced block GEMM under FORM_AUTO (from 4 pairs per launch) sums in another order, and a hidden activation that
+    # lands on the other side of a bf16 rounding boundary moves by 2^-8 of its value
     hidden_other_form = any(sp is not None for sp in ev0_split)
-    lg_tol, nll_tol = (2e-3, 1e-3) if (hidden_pre or hidden_other_form) else (2e-5, 2e-5)
+    lg_tol, nll_tol = (2e-3, 1e-3) if hidden_other_form else (2e-5, 2e-5)
     err = float((lg1 - lg2).abs().max())
     assert err <= lg_tol * scale, (err, scale)
     for k in o1:
@@ -1586,7 +1584,6 @@ def test_large_batch_layers_take_the_block_gemm(dev, monkeypatch):
     for form in (L.FORM_AUTO, L.FORM_TILE):
         monkeypatch.setattr(bnn_hip.runtime.state, "form", form)
         bnn_hip.manual_seed(4, counter=10)
-        monkeypatch.setattr(engine, "SAMPLE_BESIDE_MATMUL", True)   # (the side-stream form of the sampling launches: checked below)
         ev = engine.GraphedElbo(net, xd, yd, S)
         assert all(ev.lib) == (form == L.FORM_AUTO)
         sums = ev.replay().clone()
@@ -1598,17 +1595,15 @@ def test_large_batch_layers_take_the_block_gemm(dev, monkeypatch):
             close(tup[1] * S, float(sums[0]), rtol=1e-6)
             close(tup[2] * S, float(sums[1]), rtol=1e-6)
             close(tup[3] * S, float(sums[2]), rtol=1e-5)
-    # the sampling launches run on a side stream beside the matmuls (forked and joined inside the captured evaluation): the
-    # same evaluation with everything on one stream gives the same bits, replay after replay
+    # two evaluations per replay (evals_per_replay=2) give the same bits as one evaluation per replay replayed twice,
+    # replay after replay
     monkeypatch.setattr(bnn_hip.runtime.state, "form", L.FORM_AUTO)
-    monkeypatch.setattr(engine, "SAMPLE_BESIDE_MATMUL", False)
     bnn_hip.manual_seed(4, counter=10)
     ev1 = engine.GraphedElbo(net, xd, yd, S)
-    assert ev1.side is None and all(ev1.lib)
-    monkeypatch.setattr(engine, "SAMPLE_BESIDE_MATMUL", True)
+    assert all(ev1.lib)
     bnn_hip.manual_seed(4, counter=10)
     ev2 = engine.GraphedElbo(net, xd, yd, S, evals_per_replay=2)
-    assert ev2.side is not None
+    assert all(ev2.lib)
     for rep_ in range(3):
         a = ev1.replay().clone(); ev1.replay()                   # two evaluations per step on either side
         b = ev2.replay().clone()
