@@ -28,6 +28,7 @@ EXPORTS = (
     "bnn_elbo_finalize", "bnn_bbb_final_fwd", "bnn_bbb_final_scratch_bytes", "bnn_philox_normal", "bnn_cast_bf16", "bnn_softplus", "bnn_eval_prepare",
     "bnn_ece_workspace_bytes", "bnn_ece", "bnn_snr_db", "bnn_snr_prune", "bnn_mc_predictive",
     "bnn_bandit_rows", "bnn_bandit_act", "bnn_bandit_replay",
+    "bnn_dense_fwd", "bnn_dense_plan", "bnn_dropout_mask",
 )
 
 
@@ -243,6 +244,15 @@ class BanditReplayArgs(C.Structure):
                 ("n_batches", C.c_void_p)]
 
 
+class DenseFwdArgs(C.Structure):
+    """bnn_dense_fwd_args (include/bnn_hip.h): one nn.Linear of MLP_Dropout for S MC-dropout samples"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("batch", C.c_int32), ("in_features", C.c_int32),
+                ("out_features", C.c_int32), ("x_shared", C.c_int32), ("x", C.c_void_p), ("x_dtype", C.c_int32),
+                ("math", C.c_int32), ("w", C.c_void_p), ("b", C.c_void_p), ("relu", C.c_int32), ("layer_id", C.c_int32),
+                ("drop_p", C.c_double), ("seed", C.c_uint64), ("sample_offset", C.c_uint32), ("sample_counter_inc", C.c_uint32),
+                ("sample_counter", C.c_void_p), ("y", C.c_void_p), ("y_dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -376,6 +386,13 @@ def _load_real():
         getattr(lib, name).argtypes = [C.POINTER(BanditActArgs), C.c_void_p]
     lib.bnn_bandit_replay.restype = C.c_int
     lib.bnn_bandit_replay.argtypes = [C.POINTER(BanditReplayArgs), C.c_void_p]
+    lib.bnn_dense_fwd.restype = C.c_int
+    lib.bnn_dense_fwd.argtypes = [C.POINTER(DenseFwdArgs), C.c_void_p]
+    lib.bnn_dense_plan.restype = C.c_int
+    lib.bnn_dense_plan.argtypes = [C.POINTER(DenseFwdArgs), C.POINTER(Plan)]
+    lib.bnn_dropout_mask.restype = C.c_int
+    lib.bnn_dropout_mask.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_double, C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

@@ -1255,3 +1255,81 @@ def bandit_replay_args(*, x, step, ring_index, ring_action, ring_reward, workspa
 def bandit_replay(a: L.BanditReplayArgs):
     """bnn_bandit_replay: the shuffled replay pool of the step just taken, gathered into the minibatch slab."""
     L.check(L.load().bnn_bandit_replay(C.byref(a), _stream()), "bnn_bandit_replay")
+
+
+def dropout_params(p: float) -> tuple:
+    """(thr, scale) of the kind-3 dropout map (include/bnn_hip.h) for a drop probability p in [0, 1), in fp64 as the
+    library forms them.  Raises BnnHipError outside that range."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:                               # (NaN fails)
+        raise BnnHipError(f"dropout probability must lie in [0, 1), got {p}")
+    return min(math.floor(p * 2.0 ** 32), 2 ** 32 - 1), C.c_float(1.0 / (1.0 - p)).value
+
+
+def dropout_mask(seed: int, layer_id: int, sample_offset: int, n_samples: int, rows: int, cols: int, p: float,
+                 device) -> torch.Tensor:
+    """The kind-3 dropout stream of layer `layer_id`, materialised (bnn_dropout_mask): float32[n_samples, rows, cols]
+    holding 1 / (1 - p) where an element is kept and 0 where it is dropped."""
+    lib = L.load()
+    dropout_params(p)
+    if torch.device(device).type != "cuda":
+        raise BnnHipError("bnn_hip.dropout_mask needs a ROCm device")
+    mask = torch.empty((n_samples, rows, cols), dtype=torch.float32, device=device)
+    L.check(lib.bnn_dropout_mask(mask.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF, int(layer_id), sample_offset & 0xFFFFFFFF,
+                                 n_samples, rows, cols, float(p), _stream()), "bnn_dropout_mask")
+    return mask
+
+
+def _dense_build(x, w, b, *, n_samples: int, math_mode: int, relu: bool, drop_p: float, layer_id: int, seed: int,
+                 sample_offset: int = 0, sample_counter=None, sample_counter_inc: int = 0, y_dtype=torch.float32, out=None):
+    """(args, keep-alive, y) of one bnn_dense_fwd launch: x [B, in] (shared by the samples) or [S, B, in]."""
+    require_device(x, w, b, out, sample_counter)
+    dropout_params(drop_p)
+    w = _f32c(w, "weight")
+    b = None if b is None else _f32c(b, "bias")
+    if x.dim() == 2:
+        shared, B, K = 1, x.shape[0], x.shape[1]
+    elif x.dim() == 3 and x.shape[0] == n_samples:
+        shared, B, K = 0, x.shape[1], x.shape[2]
+    else:
+        raise BnnHipError(f"dense_fwd: x must be [batch, in] or [{n_samples}, batch, in], got {tuple(x.shape)}")
+    x = x if x.is_contiguous() else x.contiguous()
+    N = w.shape[0]
+    if w.dim() != 2 or w.shape[1] != K or (b is not None and tuple(b.shape) != (N,)):
+        raise BnnHipError(f"dense_fwd: weight {tuple(w.shape)} / bias do not fit x of {K} features")
+    if out is None:
+        out = torch.empty((n_samples, B, N), dtype=y_dtype, device=x.device)
+    elif tuple(out.shape) != (n_samples, B, N) or not out.is_contiguous():
+        raise BnnHipError(f"dense_fwd: out must be a contiguous [{n_samples}, {B}, {N}] tensor")
+    if sample_counter is not None and (sample_counter.dtype != torch.int32 or sample_counter.numel() != 1):
+        raise BnnHipError("dense_fwd: sample_counter must be a one-element int32 device tensor")
+    a = L.DenseFwdArgs()
+    a.struct_bytes = C.sizeof(L.DenseFwdArgs)
+    a.n_samples, a.batch, a.in_features, a.out_features = int(n_samples), B, K, N
+    a.x_shared, a.x, a.x_dtype = shared, x.data_ptr(), _dt(x)
+    a.math = int(math_mode)
+    a.w, a.b = w.data_ptr(), _ptr(b)
+    a.relu, a.layer_id, a.drop_p = int(bool(relu)), int(layer_id), float(drop_p)
+    a.seed, a.sample_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset) & 0xFFFFFFFF
+    a.sample_counter, a.sample_counter_inc = _ptr(sample_counter), int(sample_counter_inc)
+    a.y, a.y_dtype = out.data_ptr(), _dt(out)
+    return a, (x, w, b, out, sample_counter), out
+
+
+def dense_fwd(x, w, b, **kw) -> torch.Tensor:
+    """K5: y[s] = drop_s(act(x[s'] . w^T + b)) for n_samples MC-dropout samples in one launch (bnn_dense_fwd).  The kind-3
+    mask of `layer_id` at global sample index sample_offset + *sample_counter + s; drop_p = 0 applies none."""
+    lib = L.load()
+    a, keep, y = _dense_build(x, w, b, **kw)
+    a._keep = keep                    # (the structure owns what its pointers refer to: a recorded launch list replays it)
+    L.check(lib.bnn_dense_fwd(C.byref(a), _stream()), "bnn_dense_fwd")
+    return y
+
+
+def dense_plan(x, w, b, **kw) -> dict:
+    """What bnn_dense_fwd would launch for these arguments (bnn_dense_plan)."""
+    lib = L.load()
+    a, _, _ = _dense_build(x, w, b, **kw)
+    pl = L.Plan()
+    L.check(lib.bnn_dense_plan(C.byref(a), C.byref(pl)), "bnn_dense_plan")
+    return _plan_dict(pl)

@@ -25,6 +25,7 @@ from torch import nn
 from config import *  # noqa: F401,F403  (DEVICE, RegConfig, RLConfig, ClassConfig)
 from bnn_hip import _lib as _L
 from bnn_hip import engine as _engine
+from bnn_hip import mcdropout as _mcdropout
 from bnn_hip.functional import BBBLinearFn as _BBBLinearFn
 from bnn_hip.functional import LayerCall as _LayerCall
 from bnn_hip.functional import LRLinearFn as _LRLinearFn
@@ -378,3 +379,27 @@ class MLP_Dropout(_PlainMLP):
         for m in self.modules():
             if m.__class__.__name__.startswith('Dropout'):
                 m.train()
+
+    def mc_forward(self, x, samples):
+        """Extension (not in the reference): the outputs of `samples` MC-dropout passes, [samples, batch, classes] fp32,
+        one launch per layer (bnn_hip.mcdropout) -- what regression/reg_task.py:186-195 collects by calling the network
+        with enable_dropout() in a Python loop.  Fresh masks per call (the global sample counter, bnn_hip.manual_seed)."""
+        return _mcdropout.mc_forward(self, x, int(samples))
+
+    def predict_mc(self, x, samples):
+        """Extension (not in the reference): (preds[batch], probs[batch, classes]) with probs the mean softmax over `samples`
+        MC-dropout passes (classification/class_task.py:230-236)."""
+        return _mcdropout.predict_mc(self, x, int(samples))
+
+    def predictive(self, x, samples, *, quantiles=None, sigma=1.):
+        """Extension (not in the reference): the predictive summaries of `samples` MC-dropout passes -- the same
+        bnn_hip.ops.Predictive as BayesianNetwork.predictive (entropy decomposition for classification; mean, variance,
+        predictive_variance and np.percentile quantiles for regression)."""
+        return _mcdropout.predictive(self, x, int(samples), quantiles=quantiles, sigma=float(sigma))
+
+    def predictive_graph(self, x, samples, *, quantiles=None, sigma=1., capture=True):
+        """Extension (not in the reference): predictive for this input shape as a replayable evaluation -- `p =
+        mlp.predictive_graph(x, samples)`, then `p.x.copy_(next_input_flattened); out = p.replay()` (static buffers, fresh
+        masks per replay: bnn_hip.mcdropout.GraphedDropoutPredictive).  `capture=False`: the same chain, eager."""
+        return _mcdropout.GraphedDropoutPredictive(self, x, int(samples), quantiles=quantiles, sigma=float(sigma),
+                                                   capture=capture)

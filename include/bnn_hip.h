@@ -39,6 +39,14 @@
  *       slot 0,1 = sqrt(-2 ln u(r0)) * {cos, sin}(2 pi u(r1)); slot 2,3 likewise from r2,r3
  *       eps[row, col] = slot (col & 3)
  *   oracle/bnn_oracle.py:philox_normal restates this on the CPU.
+ *   Kind 3: the MC-dropout uniform of the activations that leave Linear layer l (an MLP_Dropout's nn.Dropout after the
+ *   ReLU of Linear l), logical shape [batch, features], same counter layout, t = 4*l + 3:
+ *       (r0,r1,r2,r3) = Philox4x32-R((group, g, 4*l + 3, 0), key)
+ *       keep[row, col] = r_(col & 3) >= thr,   thr = min(floor(p * 2^32), 2^32 - 1)   (host, fp64; p in [0, 1))
+ *       out = keep ? a * scale : 0,            scale = (float)(1.0 / (1.0 - p))
+ *   (p = 0.5: thr = 2^31, scale = 2.)  No other stream uses word 2 = 4l + 3 with word 3 = 0 (the bandit's stream has
+ *   word 3 = 1), so adding kind 3 left every earlier stream, and the map version, as they were.  bnn_dropout_mask
+ *   materialises it; tests/test_mc_dropout_cpu.py restates it on the CPU.
  */
 #ifndef BNN_HIP_H_
 #define BNN_HIP_H_
@@ -900,6 +908,56 @@ int bnn_bandit_replay(const bnn_bandit_replay_args* args, void* stream);
  * ---------------------------------------------------------------------------------- */
 int bnn_philox_normal(float* eps, uint64_t seed, uint32_t tensor_id, uint32_t sample_offset,
                       int32_t n_samples, int32_t rows, int32_t cols, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * K5  MC dropout of MLP_Dropout (networks.py:253-285 kept in train mode at test time, main.py:42/:138,
+ * regression/reg_task.py:186-195, classification/class_task.py:230-236): S stochastic passes of
+ *     y[s] = drop_s(act(x[s'] . W^T + b))
+ * for one nn.Linear (W fp32 [out,in], b fp32 [out], SHARED by all samples) in ONE launch.
+ *   x_shared = 1: x [batch, in] for every sample (the first layer: the dropout acts after it): the block computes its
+ *                 output tile once and writes the masked copies of a run of samples.
+ *   x_shared = 0: x [n_samples, batch, in]: one GEMM of n_samples * batch rows against W; row r is sample r / batch.
+ *   drop_p in [0, 1): the kind-3 mask of layer layer_id (map at the top) for global sample index
+ *                 g = sample_offset + *sample_counter + s; drop_p = 0 applies none (keep all, scale 1: the same values).
+ *   relu: ReLU before the dropout.  y [n_samples, batch, out] of y_dtype (bf16 between layers in bf16 math).
+ * Math: BNN_MATH_BF16: x and W rounded to bf16 (RNE) while they are staged, fp32 accumulate (v_mfma_f32_16x16x32_bf16);
+ * BNN_MATH_F32 and BNN_MATH_BF16X3: exact fp32 (v_mfma_f32_16x16x4_f32; x and y fp32).  An output element's reduction
+ * runs K in 32-wide steps in one fixed order whatever n_samples, batch and the tile: results do not depend on how the
+ * samples are split over calls.  Parameters are read on every call (no cached copies).  Any shape >= 1.
+ * sample_counter_inc: added to *sample_counter by the launch (so a captured chain advances its own counter); only with
+ * drop_p == 0, i.e. by a launch that does not read the counter (the output layer).
+ * bnn_dense_plan returns what bnn_dense_fwd launches: form BNN_FORM_GEMM, batch_rows x features_per_block output tiles
+ * (64 x 64, or 128 x 128 for bf16 math when they still give >= 512 blocks), k_slices = the sample runs of a shared-x
+ * launch (1 otherwise), blocks, lds_bytes; a pure function of the shape, math, dtypes and alignment.
+ * ---------------------------------------------------------------------------------- */
+typedef struct bnn_dense_fwd_args {
+  uint32_t struct_bytes;
+  int32_t n_samples, batch, in_features, out_features;
+  int32_t x_shared;         /* 1: x [batch,in] for all samples; 0: x [n_samples,batch,in] */
+  const void* x;
+  int32_t x_dtype;          /* bnn_dtype; BNN_BF16 only with BNN_MATH_BF16 */
+  int32_t math;             /* bnn_math */
+  const float* w;           /* [out,in] */
+  const float* b;           /* [out], or NULL for no bias */
+  int32_t relu;
+  int32_t layer_id;         /* >= 0: the mask's tensor id is 4 * layer_id + 3 */
+  double drop_p;            /* in [0, 1) */
+  uint64_t seed;
+  uint32_t sample_offset;
+  uint32_t sample_counter_inc;
+  uint32_t* sample_counter; /* optional DEVICE word, as in bnn_bbb_fwd_args */
+  void* y;                  /* [n_samples,batch,out] */
+  int32_t y_dtype;          /* bnn_dtype; BNN_BF16 only with BNN_MATH_BF16 */
+  int32_t reserved;
+} bnn_dense_fwd_args;
+int bnn_dense_fwd(const bnn_dense_fwd_args* args, void* stream);
+int bnn_dense_plan(const bnn_dense_fwd_args* args, bnn_plan* plan);
+
+/* bnn_dropout_mask — the kind-3 stream of layer layer_id, materialised: mask[n_samples, rows, cols] = scale where
+ * the element is kept and 0 where it is dropped, samples sample_offset .. sample_offset + n_samples - 1.  p in [0, 1)
+ * (else BNN_ERR_SHAPE).  For tests; bnn_dense_fwd never reads it. */
+int bnn_dropout_mask(float* mask, uint64_t seed, uint32_t layer_id, uint32_t sample_offset, int32_t n_samples,
+                     int32_t rows, int32_t cols, double p, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
