@@ -29,7 +29,11 @@ result does not depend on N), and the only collective is ONE RCCL sum all-reduce
 scalars per launch group.  `c4` in the output is BASELINE configs[3] as SURVEY §8(e) words it: one minibatch, 64 (and
 512) MC samples split over the ranks, one all-reduce of the 4-vector PER EVALUATION.
 
-Prints ONE JSON line (rank 0).  value = total MC samples / s over all ranks; `roofline` is the dominant kernel (layer
+Prints ONE JSON line (rank 0).  value = total MC samples / s over all ranks.  A plain run stops there: it builds the
+evaluator, runs the steps above (cold pass, settle, measured pass), writes `--dump-outputs` and prints the line.  Everything
+else -- `roofline`, `cpu_baseline`, `extras` and the figures beside them -- takes runs of its own and needs `--full`.
+
+With `--full`: `roofline` is the dominant kernel (layer
 2, 1200x1200 weights) against the roof that binds it -- vector issue for K1b2, whose on-chip generator is most of the
 ~160 VALU instructions per 8 sampled weights (instruction mix: profiles/isa_mix.json; counters: profiles/pmc.json), with the
 ALGORITHMIC lane-op count of the epsilon map beside the compiled loop's (`valu.algorithmic`: derived from the map in
@@ -77,8 +81,11 @@ def parse_args(argv=None):
                          "state under this load (the first ~40 launch groups after idle run up to 12 %% slower: tools/warmup_probe.py); "
                          "0 = time the K steps straight after the W warm-up steps of a cold device (reported as `cold_start` otherwise)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the dominant kernel's roofline and board power, "
+                         "the CPU baseline and the extras (other configurations, sizes and math modes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no extras")
     ap.add_argument("--roofline-only", action="store_true",
                     help="only the isolated launches of the dominant (layer-2) kernel: run under `rocprofv3 --kernel-trace "
                          "--stats` to get a per-kernel average that is directly comparable with roofline.avg_launch_us")
@@ -764,7 +771,7 @@ def main():
                                "further untimed launch groups and W more warm-up steps"},
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
         out["roofline"] = attach_traffic(layer2_roofline(ev, net, dims, args.batch, lr, args.math))
         if world == 1 and not rehearsal:
             out["roofline"]["board_power"] = board_power_while(ev.replay)
@@ -773,7 +780,7 @@ def main():
             out["speedup_vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
     del ev, tail
 
-    if not args.no_extras and args.net == "mnist" and not lr:
+    if args.full and not args.no_extras and args.net == "mnist" and not lr:
         extras = {}
         if world == 1:
             # the training loop's regime: one minibatch, one MC sample, every evaluation waits for the previous one
@@ -866,7 +873,7 @@ def main():
             r10 = os.path.join(REPO, "bayesian-neural-network_amd", "bnn_hip", "libbnn_hip_r10.so")
             if os.path.exists(r10) and not os.environ.get("BNN_HIP_LIB"):
                 try:
-                    cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-extras", "--no-cpu-baseline", "--steps", str(args.steps),
+                    cp = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-extras", "--no-cpu-baseline", "--steps", str(args.steps),
                                          "--warmup", str(args.warmup), "--group", str(G), "--batch", str(args.batch)],
                                         env=dict(os.environ, BNN_HIP_LIB=r10), capture_output=True, text=True, timeout=300)
                     d10 = json.loads(cp.stdout.strip().splitlines()[-1])

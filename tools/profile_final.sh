@@ -28,7 +28,7 @@ $P pmc bbb256 bbb_g256 "$PMC" &&
 $P pmc bbb256x3 bbb_g256_x3 "$PMC" --math bf16x3 &&
 $P pmc lr256 lr_g256 "$PMC" --variant lr &&
 $P pmc wide4096 wide_B4096 "$PMC" --net wide --batch 4096 --samples 4 --group 1 &&
-$P statsfull steps20 --steps 20 --warmup 5 --no-extras --no-cpu-baseline    # last: its bench line carries the traffic / counters collected above
+$P statsfull steps20 --steps 20 --warmup 5 --full --no-extras --no-cpu-baseline    # last: its bench line carries the traffic / counters collected above
 # harness logs behind DESIGN.md 4 (development binaries are built in the container and travel with the snapshot)
 PROF=gpurun_out/profiles
 ( tools/ubench.out > $PROF/${TAG}_ubench_generator.log 2>&1 ) || true
