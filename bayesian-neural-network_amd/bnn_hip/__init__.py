@@ -5,8 +5,9 @@
 `functional` autograd bridges (forward = HIP kernels)
 `engine`     batched-samples launcher + MC-sample sharding over torch.distributed
 `runtime`    process-wide knobs: math mode, Philox seed / sample counter, sharding switch
-`optim`      FusedAdam: torch.optim.Adam's update in one launch (F2)
+`optim`      FusedAdam / FusedSGD: torch.optim.Adam's / SGD's update in one launch (F2, K6)
 `train`      GraphedTrainStep: zero_grad -> sample_elbo -> backward -> Adam as one hipGraph
+`dense_train` GraphedDenseTrainStep: the same for MLP / MLP_Dropout (forward, loss, backward, SGD / Adam) (K6)
 `synth`      synthetic inputs with the reference's distributions (numpy only)
 """
 from .runtime import get_math, manual_seed, set_host_eps, set_math, shard_samples  # noqa: F401

@@ -29,6 +29,7 @@ EXPORTS = (
     "bnn_ece_workspace_bytes", "bnn_ece", "bnn_snr_db", "bnn_snr_prune", "bnn_mc_predictive",
     "bnn_bandit_rows", "bnn_bandit_act", "bnn_bandit_replay",
     "bnn_dense_fwd", "bnn_dense_plan", "bnn_dropout_mask",
+    "bnn_dense_loss", "bnn_dense_bwd", "bnn_sgd_step",
 )
 
 
@@ -253,6 +254,31 @@ class DenseFwdArgs(C.Structure):
                 ("sample_counter", C.c_void_p), ("y", C.c_void_p), ("y_dtype", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DenseLossArgs(C.Structure):
+    """bnn_dense_loss_args (include/bnn_hip.h): cross_entropy / mse_loss (sum) and the logits' gradient"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("batch", C.c_int32), ("classes", C.c_int32), ("loss_mode", C.c_int32),
+                ("logits", C.c_void_p), ("target", C.c_void_p), ("grad_scale", C.c_float), ("reserved", C.c_int32),
+                ("loss", C.c_void_p), ("g_logits", C.c_void_p)]
+
+
+class DenseBwdArgs(C.Structure):
+    """bnn_dense_bwd_args (include/bnn_hip.h): the backward of one Linear -> [ReLU] -> [Dropout] group"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("batch", C.c_int32), ("in_features", C.c_int32), ("out_features", C.c_int32),
+                ("math", C.c_int32), ("gx_mask", C.c_int32), ("x", C.c_void_p), ("gy", C.c_void_p), ("y", C.c_void_p),
+                ("y_scale", C.c_float), ("gx_scale", C.c_float), ("w", C.c_void_p), ("g_w", C.c_void_p), ("g_b", C.c_void_p),
+                ("g_x", C.c_void_p)]
+
+
+SGD_MAX_TENSORS = 16
+
+
+class SgdArgs(C.Structure):
+    """bnn_sgd_args (include/bnn_hip.h)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_tensors", C.c_int32), ("param", C.c_void_p * SGD_MAX_TENSORS),
+                ("grad", C.c_void_p * SGD_MAX_TENSORS), ("numel", C.c_int64 * SGD_MAX_TENSORS), ("lr", C.c_double),
+                ("weight_decay", C.c_double), ("lr_device", C.c_void_p)]
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -393,6 +419,12 @@ def _load_real():
     lib.bnn_dropout_mask.restype = C.c_int
     lib.bnn_dropout_mask.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_double, C.c_void_p]
+    lib.bnn_dense_loss.restype = C.c_int
+    lib.bnn_dense_loss.argtypes = [C.POINTER(DenseLossArgs), C.c_void_p]
+    lib.bnn_dense_bwd.restype = C.c_int
+    lib.bnn_dense_bwd.argtypes = [C.POINTER(DenseBwdArgs), C.c_void_p]
+    lib.bnn_sgd_step.restype = C.c_int
+    lib.bnn_sgd_step.argtypes = [C.POINTER(SgdArgs), C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

@@ -1,0 +1,214 @@
+"""K6: one training step of MLP / MLP_Dropout (the reference's train_step, classification/class_task.py:150-157,
+regression/reg_task.py:176-183: zero_grad -> forward -> cross_entropy / mse_loss (sum) -> backward -> optimiser step)
+as a fixed chain of HIP launches, captured once as a hipGraph:
+
+  bnn_dense_fwd per layer (one sample, fp32 outputs, the kind-3 dropout mask of the step's global sample index; the
+  output layer's launch advances the device sample counter)  ->  bnn_dense_loss (loss + logits gradient)  ->
+  bnn_dense_bwd per layer, top down (weight and bias gradients; the input gradient, already multiplied by the layer
+  below's mask read off its saved output, except at layer 0)  ->  bnn_sgd_step / bnn_adam_step.
+
+Three layers: 3 + 1 + 3 + 1 = 8 launches.  The step always trains in train-mode semantics (dropout on), as the
+reference's train_step does after net.train()."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib as L
+from . import ops
+from .mcdropout import _math, flat_input, layers_of
+from .ops import BnnHipError
+from .optim import FusedAdam, FusedSGD, _sgd_supported
+from .runtime import state, take_samples
+
+LOSSES = ("cross_entropy", "mse")
+
+
+class GraphedDenseTrainStep:
+    def __init__(self, mlp, optimizer, x: torch.Tensor, y: torch.Tensor, loss=None, capture: bool = True):
+        """`x`, `y`: an example minibatch (the shape and dtype of every later one): classification x [B, 1, h, w] with
+        int64 labels [B], regression x [B, in] with float32 targets of B * out elements.  `optimizer`: FusedSGD or
+        FusedAdam with capturable=True over the network's parameters.  `loss`: 'cross_entropy' or 'mse' (sum reduction),
+        by default the reference's for mlp.mode.  `capture=False`: the same launches, run eagerly on every step.
+
+        Building the step runs one real warm-up step and then restores the parameters, the optimiser state and the
+        sample counter, so the model and the optimiser are left as they were."""
+        if not isinstance(optimizer, (FusedSGD, FusedAdam)):
+            raise BnnHipError("GraphedDenseTrainStep needs FusedSGD or FusedAdam (capturable=True)")
+        if not all(g.get("capturable") for g in optimizer.param_groups):
+            raise BnnHipError("GraphedDenseTrainStep needs a capturable optimiser (capturable=True)")
+        if isinstance(optimizer, FusedSGD):
+            for g in optimizer.param_groups:
+                _sgd_supported(g)
+        if state.shard_samples:
+            raise BnnHipError("GraphedDenseTrainStep: MC-sample sharding is not supported; switch it off")
+        if loss is None:
+            loss = "cross_entropy" if mlp.mode == "classification" else "mse"
+        if loss not in LOSSES:
+            raise BnnHipError(f"GraphedDenseTrainStep: loss must be one of {LOSSES}, got {loss!r}")
+        self.layers = layers_of(mlp)
+        for d in self.layers[:-1]:
+            if d.p and not d.relu:
+                raise BnnHipError("GraphedDenseTrainStep: a Dropout needs a ReLU before it (the backward reads the mask "
+                                  "off the layer's saved output)")
+        self.loss_mode = "classification" if loss == "cross_entropy" else "regression"
+        self.mlp, self.opt = mlp, optimizer
+        self.x = flat_input(mlp, x).clone().contiguous()
+        ops.require_device(y)
+        B, dev = self.x.shape[0], self.x.device
+        C_out = self.layers[-1].linear.out_features
+        if self.loss_mode == "classification":
+            if y.dtype != torch.int64 or y.numel() != B:
+                raise BnnHipError("GraphedDenseTrainStep: cross-entropy targets must be int64 labels, one per row")
+        elif y.dtype != torch.float32 or y.numel() != B * C_out:
+            raise BnnHipError(f"GraphedDenseTrainStep: mse targets must be float32 with {B * C_out} elements")
+        self.y = y.clone().contiguous()
+        self.math = _math()[0]
+
+        # the parameters, in layer order, and one flat gradient bucket (each slice 256-byte aligned); p.grad are views
+        self.params = [t for d in self.layers for t in (d.linear.weight, d.linear.bias) if t is not None]
+        in_opt = {id(p) for g in optimizer.param_groups for p in g["params"]}
+        if any(id(p) not in in_opt for p in self.params):
+            raise BnnHipError("GraphedDenseTrainStep: the optimiser must hold every parameter of the network")
+        offs, tot = [], 0
+        for p in self.params:
+            offs.append(tot)
+            tot += (p.numel() + 63) // 64 * 64
+        self.bucket = torch.zeros(tot, dtype=torch.float32, device=dev)
+        self.grad_views = [self.bucket[o:o + p.numel()].view(p.shape) for o, p in zip(offs, self.params)]
+        self._grad_of = dict(zip(map(id, self.params), self.grad_views))
+
+        # activations (fp32 for every layer: the backward reads them), the logits' gradient, the input gradients
+        self.acts = [torch.empty((1, B, d.linear.out_features), dtype=torch.float32, device=dev) for d in self.layers]
+        self.g_logits = torch.empty((B, C_out), dtype=torch.float32, device=dev)
+        self.g_hidden = [torch.empty((B, d.linear.out_features), dtype=torch.float32, device=dev) for d in self.layers[:-1]]
+        self.loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.scales = [ops.dropout_params(d.p)[1] for d in self.layers]
+
+        # ONE device sample counter per optimiser, shared by every step object built on it (the 128-row and the 96-row
+        # last batch of an MNIST epoch): a step draws global sample index base + counter, the output layer's forward
+        # advances it, and the host's counter is kept in step (take_samples), so later evaluations draw past it
+        sh = getattr(optimizer, "_sample_words", None)
+        if sh is None or sh["counter"].device != dev:
+            sh = optimizer._sample_words = dict(counter=torch.zeros(1, dtype=torch.int32, device=dev), base=take_samples(0),
+                                                mirror=0)
+        self._shared = sh
+        self.counter, self.base = sh["counter"], sh["base"]
+        self._sync_counter()
+
+        self.graph = None
+        if capture:
+            self._warm_up()
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self._enqueue()
+
+    # ---- the chain
+    def _enqueue(self):
+        with torch.no_grad():
+            last = len(self.layers) - 1
+            h = self.x
+            for i, d in enumerate(self.layers):
+                lin = d.linear
+                ops.dense_fwd(h, lin.weight.detach(), None if lin.bias is None else lin.bias.detach(), n_samples=1,
+                              math_mode=self.math, relu=d.relu, drop_p=d.p, layer_id=d.layer_id, seed=state.seed,
+                              sample_offset=self.base, sample_counter=self.counter, sample_counter_inc=1 if i == last else 0,
+                              y_dtype=torch.float32, out=self.acts[i])
+                h = self.acts[i][0]
+            ops.dense_loss(self.acts[-1][0], self.y, self.loss_mode, loss=self.loss, g_logits=self.g_logits)
+            for i in range(last, -1, -1):
+                d = self.layers[i]
+                lin = d.linear
+                below = self.layers[i - 1] if i > 0 else None
+                ops.dense_bwd(self.x if i == 0 else self.acts[i - 1][0], self.g_logits if i == last else self.g_hidden[i],
+                              lin.weight.detach(), g_w=self._grad_of[id(lin.weight)],
+                              g_b=None if lin.bias is None else self._grad_of[id(lin.bias)],
+                              g_x=self.g_hidden[i - 1] if i > 0 else None, gx_mask=below is not None and below.relu,
+                              gx_scale=self.scales[i - 1] if i > 0 else 1.0, math_mode=self.math)
+        self._attach_grads()
+        if isinstance(self.opt, FusedAdam):
+            self.opt._bump = None                # the sample counter advances in the forward, not in Adam's launch
+        self.opt.step()
+
+    def _attach_grads(self):
+        for p, g in zip(self.params, self.grad_views):
+            p.grad = g
+
+    # ---- the sample counter (as train.GraphedTrainStep keeps it)
+    def _set_counter(self, value: int):
+        value &= 0xFFFFFFFF
+        self.counter.fill_(value - (1 << 32) if value >= (1 << 31) else value)     # the kernels add it as a uint32
+        self._shared["mirror"] = value
+
+    def _sync_counter(self):
+        """Before a step: the device counter must equal the host's count of indices drawn since `base` (evaluations
+        between steps draw from the host counter); one small fill when they differ, nothing otherwise."""
+        want = (state.counter - self.base) & 0xFFFFFFFF
+        if want != self._shared["mirror"]:
+            self._set_counter(want)
+
+    def _warm_up(self):
+        """One real step on a side stream (allocator pools, the optimiser's lazily created state and device words),
+        then its effects undone: parameters, optimiser state, device step / learning-rate words, sample counter."""
+        opt = self.opt
+        params = [p for g in opt.param_groups for p in g["params"]]
+        saved_p = [p.detach().clone() for p in params]
+        had_state = {p for p in params if p in opt.state and len(opt.state[p])}
+        saved_state = {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in opt.state[p].items()} for p in had_state}
+        saved_dev = {gi: [w.clone() if torch.is_tensor(w) else w for w in d] for gi, d in opt._dev.items()}
+        mirror, host_counter = self._shared["mirror"], state.counter
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._enqueue()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        state.counter = host_counter
+        with torch.no_grad():
+            for p, q in zip(params, saved_p):
+                p.copy_(q)
+            for p in params:
+                st = opt.state.get(p)
+                if not st:
+                    continue
+                if p in had_state:
+                    for k, v in saved_state[p].items():
+                        st[k].copy_(v) if torch.is_tensor(st.get(k)) and torch.is_tensor(v) else st.__setitem__(k, v)
+                else:                            # the warm-up created it: back to a fresh optimiser's values
+                    for k, v in st.items():
+                        if torch.is_tensor(v):
+                            v.zero_()
+        for gi, d in opt._dev.items():
+            if gi in saved_dev:
+                for w, s in zip(d, saved_dev[gi]):
+                    if torch.is_tensor(w):
+                        w.copy_(s)
+            elif isinstance(opt, FusedAdam):     # created by the warm-up: start from the host-side step
+                steps = [int(saved_state[p]["step"]) for p in opt.param_groups[gi]["params"] if p in saved_state]
+                d[0].fill_(max(steps) if steps else 0)
+        self._set_counter(mirror)
+        torch.cuda.synchronize()
+
+    # ---- the public step
+    def step(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """One optimiser step on minibatch (x, y); returns the static 0-dim loss tensor (the reference's loss_info: read
+        it before the next call)."""
+        xf = flat_input(self.mlp, x)
+        ops.require_device(y)
+        if xf.numel() != self.x.numel() or y.numel() != self.y.numel() or y.dtype != self.y.dtype:
+            raise BnnHipError("GraphedDenseTrainStep.step: the minibatch must have the example's shape and dtype")
+        if xf.is_contiguous() and y.is_contiguous():
+            ops.stage_inputs(xf, self.x, y, self.y)                       # one launch instead of two
+        else:
+            self.x.copy_(xf.reshape(self.x.shape), non_blocking=True)
+            self.y.copy_(y.reshape(self.y.shape), non_blocking=True)
+        self.opt.sync_lr()
+        self._sync_counter()
+        if self.graph is not None:
+            self._attach_grads()
+            self.graph.replay()
+        else:
+            self._enqueue()
+        take_samples(1)
+        self._shared["mirror"] = (self._shared["mirror"] + 1) & 0xFFFFFFFF
+        return self.loss

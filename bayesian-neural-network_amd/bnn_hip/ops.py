@@ -1333,3 +1333,84 @@ def dense_plan(x, w, b, **kw) -> dict:
     pl = L.Plan()
     L.check(lib.bnn_dense_plan(C.byref(a), C.byref(pl)), "bnn_dense_plan")
     return _plan_dict(pl)
+
+
+def dense_loss(logits, target, mode: str, *, grad_scale: float = 1.0, loss=None, g_logits=None):
+    """K6 bnn_dense_loss: (loss 0-dim, g_logits [B, C]) of cross_entropy(logits, target, reduction='sum') (classification,
+    int64 labels [B]) or mse_loss(logits, target, reduction='sum') (regression, fp32 target of B * C elements), the
+    gradient times grad_scale, in one launch.  An out-of-range label gives a NaN loss and NaN gradient row."""
+    lib = L.load()
+    require_device(logits, target, loss, g_logits)
+    logits = _f32c(logits, "logits")
+    if logits.dim() != 2:
+        raise BnnHipError(f"dense_loss: logits must be [batch, classes], got {tuple(logits.shape)}")
+    B, Cc = logits.shape
+    if mode == "classification":
+        if target.dtype != torch.int64 or target.numel() != B:
+            raise BnnHipError("dense_loss: classification targets must be int64 labels, one per row")
+        lm = L.NLL_CLASSIFICATION
+    elif mode == "regression":
+        if target.dtype != torch.float32 or target.numel() != B * Cc:
+            raise BnnHipError(f"dense_loss: regression targets must be float32 with {B * Cc} elements")
+        lm = L.NLL_REGRESSION
+    else:
+        raise BnnHipError(f"dense_loss: unknown mode {mode!r}")
+    target = target if target.is_contiguous() else target.contiguous()
+    if loss is None:
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    if g_logits is None:
+        g_logits = torch.empty_like(logits)
+    elif tuple(g_logits.shape) != (B, Cc) or g_logits.dtype != torch.float32 or not g_logits.is_contiguous():
+        raise BnnHipError("dense_loss: g_logits must be a contiguous float32 tensor of the logits' shape")
+    a = L.DenseLossArgs()
+    a.struct_bytes = C.sizeof(L.DenseLossArgs)
+    a.batch, a.classes, a.loss_mode = B, Cc, lm
+    a.logits, a.target, a.grad_scale = logits.data_ptr(), target.data_ptr(), float(grad_scale)
+    a.loss, a.g_logits = loss.data_ptr(), g_logits.data_ptr()
+    L.check(lib.bnn_dense_loss(C.byref(a), _stream()), "bnn_dense_loss")
+    return loss, g_logits
+
+
+def dense_bwd(x, gy, w, *, g_w, g_b=None, g_x=None, y=None, y_scale: float = 1.0, gx_mask: bool = False,
+              gx_scale: float = 1.0, math_mode: int = L.MATH_F32):
+    """K6 bnn_dense_bwd: the backward of one Linear -> [ReLU] -> [Dropout] group into the given buffers.  gz = gy, or
+    (y > 0 ? gy * y_scale : 0) with the saved output y; g_w = gz^T x, g_b = colsum(gz), g_x = gz W (optional) times
+    (x > 0 ? gx_scale : 0) when gx_mask.  All fp32 contiguous device tensors."""
+    lib = L.load()
+    require_device(x, gy, w, g_w, g_b, g_x, y)
+    B, K = x.shape
+    N = w.shape[0]
+    shapes = ((x, (B, K)), (gy, (B, N)), (w, (N, K)), (g_w, (N, K)), (g_b, (N,)), (g_x, (B, K)), (y, (B, N)))
+    for t, shp in shapes:
+        if t is not None and (tuple(t.shape) != shp or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise BnnHipError(f"dense_bwd: expected a contiguous float32 tensor of shape {shp}, got {tuple(t.shape)} {t.dtype}")
+    a = L.DenseBwdArgs()
+    a.struct_bytes = C.sizeof(L.DenseBwdArgs)
+    a.batch, a.in_features, a.out_features = B, K, N
+    a.math, a.gx_mask = _exact_unless_bf16(math_mode), int(bool(gx_mask))
+    a.x, a.gy, a.y, a.w = x.data_ptr(), gy.data_ptr(), _ptr(y), w.data_ptr()
+    a.y_scale, a.gx_scale = float(y_scale), float(gx_scale)
+    a.g_w, a.g_b, a.g_x = g_w.data_ptr(), _ptr(g_b), _ptr(g_x)
+    L.check(lib.bnn_dense_bwd(C.byref(a), _stream()), "bnn_dense_bwd")
+
+
+def sgd_step(params, grads, *, lr: float, weight_decay: float = 0.0, lr_device=None):
+    """K6 bnn_sgd_step: p -= lr * (g + weight_decay * p) over lists of fp32 tensors, 16 per launch; `lr_device` (device
+    float[1]) overrides lr."""
+    lib = L.load()
+    n = len(params)
+    require_device(lr_device)
+    for lo in range(0, n, L.SGD_MAX_TENSORS):
+        hi = min(n, lo + L.SGD_MAX_TENSORS)
+        a = L.SgdArgs()
+        a.struct_bytes = C.sizeof(L.SgdArgs)
+        a.n_tensors = hi - lo
+        for j in range(lo, hi):
+            p, g = params[j], grads[j]
+            require_device(p, g)
+            if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous() or \
+                    g.numel() != p.numel():
+                raise BnnHipError("sgd_step: parameters and gradients must be contiguous float32 of one size")
+            a.param[j - lo], a.grad[j - lo], a.numel[j - lo] = p.data_ptr(), g.data_ptr(), p.numel()
+        a.lr, a.weight_decay, a.lr_device = float(lr), float(weight_decay), _ptr(lr_device)
+        L.check(lib.bnn_sgd_step(C.byref(a), _stream()), "bnn_sgd_step")

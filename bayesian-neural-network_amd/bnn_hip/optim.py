@@ -140,3 +140,84 @@ class FusedAdam(torch.optim.Optimizer):
                     self.state[p]["step"] = step
                 ops.adam_step(ps, gs, ms, vs, step=step, **kw)
         return loss
+
+
+class FusedSGD(torch.optim.Optimizer):
+    """K6: a drop-in for the `torch.optim.SGD(params, lr)` of the reference's classification trainers
+    (classification/class_task.py:149) without momentum: p -= lr * (g + weight_decay * p), every parameter tensor in one
+    HIP launch (bnn_sgd_step).  The parameter groups carry torch.optim.SGD's keys (plus `capturable`), so state_dict() /
+    load_state_dict() interoperate with it; momentum, dampening, nesterov and maximize are refused, not ignored.
+
+    `capturable=True` keeps each group's learning rate in a device word that a captured hipGraph of the training step
+    (dense_train.GraphedDenseTrainStep) reads; StepLR keeps working through sync_lr()."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, *, maximize=False,
+                 capturable=False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        _sgd_supported(dict(momentum=momentum, dampening=dampening, nesterov=nesterov, maximize=maximize))
+        super().__init__(params, dict(lr=lr, momentum=0, dampening=0, weight_decay=weight_decay, nesterov=False,
+                                      maximize=False, foreach=None, differentiable=False, fused=None, capturable=capturable))
+        self._dev = {}            # group index -> [lr float32[1], last lr written]
+
+    def _group_lr(self, gi, group, device):
+        if gi not in self._dev:
+            self._dev[gi] = [torch.tensor([group["lr"]], dtype=torch.float32, device=device), group["lr"]]
+        return self._dev[gi][0]
+
+    def sync_lr(self):
+        """Push param_groups[i]['lr'] (what an lr scheduler changed) into the device words a captured graph reads.  Call
+        outside capture, before replaying."""
+        for gi, group in enumerate(self.param_groups):
+            if gi in self._dev and self._dev[gi][1] != group["lr"]:
+                self._dev[gi][0].fill_(group["lr"])
+                self._dev[gi][1] = group["lr"]
+
+    def load_state_dict(self, state_dict):
+        """torch.optim.SGD's format (a state dict of either optimiser).  Loaded groups keep this optimiser's `capturable`
+        unless they carry one; a group with momentum, nesterov or maximize is refused.  The device learning-rate words
+        are updated in place (a captured graph holds their addresses)."""
+        for g in state_dict["param_groups"]:
+            _sgd_supported(g)
+        caps = [g["capturable"] for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for g, cap in zip(self.param_groups, caps):
+            g.setdefault("capturable", cap)
+        for gi, group in enumerate(self.param_groups):
+            if gi in self._dev:
+                self._dev[gi][0].fill_(group["lr"])
+                self._dev[gi][1] = group["lr"]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for gi, group in enumerate(self.param_groups):
+            ps, gs = [], []
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("FusedSGD does not support sparse gradients")
+                ps.append(p)
+                gs.append(p.grad if p.grad.is_contiguous() else p.grad.contiguous())
+            if not ps:
+                continue
+            lr_dev = None
+            if group["capturable"]:
+                lr_dev = self._group_lr(gi, group, ps[0].device)
+                if not torch.cuda.is_current_stream_capturing():
+                    self.sync_lr()
+            ops.sgd_step(ps, gs, lr=group["lr"], weight_decay=group["weight_decay"], lr_device=lr_dev)
+        return loss
+
+
+def _sgd_supported(group):
+    """momentum, dampening, nesterov and maximize are torch.optim.SGD features FusedSGD does not implement: refuse them."""
+    if group.get("momentum", 0) != 0 or group.get("dampening", 0) != 0 or group.get("nesterov", False) or \
+            group.get("maximize", False):
+        raise ops.BnnHipError("FusedSGD: momentum, dampening, nesterov and maximize are not supported")

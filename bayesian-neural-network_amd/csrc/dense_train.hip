@@ -1,0 +1,426 @@
+// K6 training of MLP / MLP_Dropout: bnn_dense_loss (loss value + logits gradient), bnn_dense_bwd (one Linear ->
+// [ReLU] -> [Dropout] group's weight, bias and input gradients in one launch) and bnn_sgd_step.  The forward is K5's
+// bnn_dense_fwd (mlp_dropout.hip) with one sample and fp32 outputs.
+//
+// bnn_dense_bwd.  Two GEMMs share one grid: blocks [0, tiles_x) own 64 x 64 tiles of g_x = gz . W (K = out), the rest
+// 64 x 64 tiles of g_w = gz^T . x (K = batch).  The g_x tiles come first: at the MNIST shape they have ~10 x the k
+// stages of a weight-gradient tile, so they start in the first dispatch wave.  The GEMM core is K5's: a 256-thread block
+// of 2 x 2 waves, 2 x 2 accumulators of 16 x 16 per wave, K walked in 32-wide stages through two LDS buffers (next
+// stage loaded into registers during the current stage's MFMAs), the same XOR-swizzled [row][k] image.  What differs is
+// the operands' memory order: gz^T, x and W are read along their contiguous (row) dimension -- a thread loads 8
+// consecutive rows of one k and writes them into the [row][k] image element by element -- and gz is formed on load
+// from gy (and the layer's saved output y: gz = y > 0 ? gy * y_scale : 0), so no masked copy is materialised.
+// g_b = colsum(gz) rides on the weight-gradient blocks of tile column 0: four strided partial sums per column, added in
+// a fixed order.  No float atomics, no K-split: every element is one fixed chain, whatever the grid.
+#include <math.h>
+
+#include "bnn_device.h"
+#include "../../include/bnn_hip.h"
+
+namespace bnn {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kBK = 32;      // k per LDS stage
+constexpr int kT = 64;       // tile rows and columns (2 waves x 2 accumulators x 16)
+constexpr int kSgdChunk = 4096;
+
+// An operand of C[m, n] = sum_k A(m, k) B(n, k): element (r, k) at p[r * ld + k] (kc: k contiguous) or p[k * ld + r].
+// msk (optional): the value is p[.] * (msk[.] > 0 ? s : 0) -- gz formed from gy and the saved output y.
+struct Opnd {
+  const float* p;
+  const float* msk;
+  float s;
+  int ld, rows, vec;
+};
+
+__device__ __forceinline__ float gz_of(float g, const float* msk, long i, float s) {
+  return msk ? (msk[i] > 0.f ? g * s : 0.f) : g;
+}
+
+template <typename T>
+__device__ __forceinline__ int swz(int row, int chunk) {
+  constexpr int CH = kBK * (int)sizeof(T) / 16;
+  return row * CH + (chunk ^ ((row >> 1) & (CH - 1)));
+}
+
+// the element index (in T) of (row, k) in the stage image
+template <typename T>
+__device__ __forceinline__ int elem(int row, int k) {
+  constexpr int PER = 16 / (int)sizeof(T);
+  return swz<T>(row, k / PER) * PER + (k % PER);
+}
+
+// 8 elements p[base + j * step] (j < valid; zero beyond), masked; vec: two 16-byte loads (step 1, valid == 8)
+__device__ __forceinline__ void load8(const Opnd& o, long base, long step, int valid, bool vec, float v[8]) {
+  if (vec && valid == 8) {
+    const float4 a = *reinterpret_cast<const float4*>(o.p + base), b = *reinterpret_cast<const float4*>(o.p + base + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    if (o.msk) {
+      const float4 c = *reinterpret_cast<const float4*>(o.msk + base), d = *reinterpret_cast<const float4*>(o.msk + base + 4);
+      const float m[8] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = m[j] > 0.f ? v[j] * o.s : 0.f;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = j < valid ? gz_of(o.p[base + j * step], o.msk, base + j * step, o.s) : 0.f;
+  }
+}
+
+// One thread's segment of an operand's stage: 8 elements.  kc: row r = s / 4, k = 8 (s % 4) .. +7 (along k);
+// otherwise k = s / 8, rows 8 (s % 8) .. +7 (along the rows).  r0: the tile's first row, k0: the stage's first k.
+template <bool KC>
+__device__ __forceinline__ void fetch_seg(const Opnd& o, int K, int r0, int k0, int s, float v[8]) {
+  if constexpr (KC) {
+    const int r = r0 + (s >> 2), k = k0 + 8 * (s & 3);
+    const int valid = r < o.rows ? min(8, max(0, K - k)) : 0;
+    load8(o, (long)r * o.ld + k, 1, valid, o.vec, v);
+  } else {
+    const int k = k0 + (s >> 3), r = r0 + 8 * (s & 7);
+    const int valid = k < K ? min(8, max(0, o.rows - r)) : 0;
+    load8(o, (long)k * o.ld + r, 1, valid, o.vec, v);
+  }
+}
+
+template <typename T, bool KC>
+__device__ __forceinline__ void stash_seg(T* img, int s, const float v[8]) {
+  if constexpr (KC) {
+    const int r = s >> 2, k = 8 * (s & 3);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) img[elem<T>(r, k + j)] = (T)v[j];
+  } else {
+    const int k = s >> 3, r = 8 * (s & 7);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) img[elem<T>(r + j, k)] = (T)v[j];
+  }
+}
+
+// acc[i][j] (rows wm 32 + 16 i, columns wn 32 + 16 j of the tile) = sum_k A(m0 + ., k) B(n0 + ., k) over k < K
+template <typename T, bool AKC, bool BKC>
+__device__ __forceinline__ void gemm_tile(const Opnd& A, const Opnd& Bo, int m0, int n0, int K, uint4* lds, f32x4 acc[2][2]) {
+  constexpr int ROW_CHUNKS = kBK * (int)sizeof(T) / 16;
+  constexpr int STAGE = 2 * kT * ROW_CHUNKS;                  // uint4 per stage buffer (A rows, then B rows)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int fr = lane & 15, fg = lane >> 4;
+  float ra[8], rb[8];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto stash = [&](int buf) {
+    T* img = reinterpret_cast<T*>(lds + buf * STAGE);
+    stash_seg<T, AKC>(img, tid, ra);
+    stash_seg<T, BKC>(img + kT * ROW_CHUNKS * (16 / (int)sizeof(T)), tid, rb);
+  };
+  const int nk = (K + kBK - 1) / kBK;
+  fetch_seg<AKC>(A, K, m0, 0, tid, ra);
+  fetch_seg<BKC>(Bo, K, n0, 0, tid, rb);
+  stash(0);
+  __syncthreads();
+#pragma unroll 1
+  for (int kt = 0; kt < nk; ++kt) {
+    if (kt + 1 < nk) {
+      fetch_seg<AKC>(A, K, m0, (kt + 1) * kBK, tid, ra);
+      fetch_seg<BKC>(Bo, K, n0, (kt + 1) * kBK, tid, rb);
+    }
+    const uint4* img = lds + (kt & 1) * STAGE;
+    if constexpr (sizeof(T) == 2) {
+      bf16x8 af[2], bf[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) af[i] = __builtin_bit_cast(bf16x8, img[swz<T>(wm * 32 + i * 16 + fr, fg)]);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) bf[j] = __builtin_bit_cast(bf16x8, img[kT * ROW_CHUNKS + swz<T>(wn * 32 + j * 16 + fr, fg)]);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
+    } else {
+      f32x4 af[2][2], bf[2][2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int r = wm * 32 + i * 16 + fr;
+        af[i][0] = __builtin_bit_cast(f32x4, img[swz<T>(r, fg)]);
+        af[i][1] = __builtin_bit_cast(f32x4, img[swz<T>(r, fg + 4)]);
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int r = wn * 32 + j * 16 + fr;
+        bf[j][0] = __builtin_bit_cast(f32x4, img[kT * ROW_CHUNKS + swz<T>(r, fg)]);
+        bf[j][1] = __builtin_bit_cast(f32x4, img[kT * ROW_CHUNKS + swz<T>(r, fg + 4)]);
+      }
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][e >> 2][e & 3], bf[j][e >> 2][e & 3], acc[i][j], 0, 0, 0);
+    }
+    if (kt + 1 < nk) stash((kt + 1) & 1);
+    __syncthreads();
+  }
+}
+
+struct BwdParams {
+  const float* x;
+  const float* gy;
+  const float* y;
+  const float* w;
+  float* gw;
+  float* gb;
+  float* gx;
+  int B, IN, OUT;
+  float y_scale, gx_scale;
+  int gx_mask;
+  int tiles_x, tiles_x_n, tiles_w_n;
+  int vec_x, vec_g, vec_w, vec_out;
+};
+
+constexpr int kOutLd = kT + 4;                                  // the epilogue's fp32 tile row, 16-byte rows
+constexpr int kLdsUint4 = 2 * 2 * kT * (kBK * 4 / 16);          // two fp32 stages (the larger image)
+static_assert(kLdsUint4 * 4 >= kT * kOutLd, "the epilogue tile fits the stage buffers");
+
+// the tile through LDS (lane: column lane & 15, rows 4 (lane >> 4) + e of each 16 x 16 accumulator), then 4 consecutive
+// columns of a row per thread: out[row, col] (row pitch IN) = v, times (x[row, col] > 0 ? s : 0) when mask
+__device__ __forceinline__ void store_tile(const BwdParams& p, uint4* lds, f32x4 acc[2][2], int m0, int n0, int rows,
+                                           float* out, bool mask) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, fr = lane & 15, fg = lane >> 4;
+  float* t = reinterpret_cast<float*>(lds);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) t[(wm * 32 + i * 16 + fg * 4 + e) * kOutLd + wn * 32 + j * 16 + fr] = acc[i][j][e];
+  __syncthreads();
+#pragma unroll 1
+  for (int q = tid; q < kT * (kT / 4); q += kThreads) {
+    const int r = q / (kT / 4), c4 = (q % (kT / 4)) * 4;
+    const int row = m0 + r, col0 = n0 + c4;
+    if (row >= rows || col0 >= p.IN) continue;
+    const float4 a4 = *reinterpret_cast<const float4*>(t + r * kOutLd + c4);
+    float o[4] = {a4.x, a4.y, a4.z, a4.w};
+    const int ncol = min(4, p.IN - col0);
+    const long at = (long)row * p.IN + col0;
+    if (mask) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (c < ncol) o[c] = p.x[at + c] > 0.f ? o[c] * p.gx_scale : 0.f;
+    }
+    if (ncol == 4 && p.vec_out) {
+      *reinterpret_cast<float4*>(out + at) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+      for (int c = 0; c < ncol; ++c) out[at + c] = o[c];
+    }
+  }
+}
+
+template <typename TX>
+__global__ __launch_bounds__(kThreads) void dense_bwd_kernel(BwdParams p) {
+  __shared__ uint4 lds[kLdsUint4];
+  f32x4 acc[2][2];
+  int item = blockIdx.x;
+  if (item < p.tiles_x) {
+    // g_x [B, IN] = gz [B, OUT] . W [OUT, IN]: A(b, o) = gz, k (= o) contiguous; B(i, o) = W[o, i], i contiguous
+    const int tm = item / p.tiles_x_n, tn = item - tm * p.tiles_x_n;
+    const Opnd A{p.gy, p.y, p.y_scale, p.OUT, p.B, p.vec_g};
+    const Opnd Bo{p.w, nullptr, 1.f, p.IN, p.IN, p.vec_w};
+    gemm_tile<TX, true, false>(A, Bo, tm * kT, tn * kT, p.OUT, lds, acc);
+    store_tile(p, lds, acc, tm * kT, tn * kT, p.B, p.gx, p.gx_mask != 0);
+    return;
+  }
+  item -= p.tiles_x;
+  // g_w [OUT, IN] = gz^T . x: A(o, b) = gz[b, o], o contiguous; B(i, b) = x[b, i], i contiguous; K = B
+  const int tm = item / p.tiles_w_n, tn = item - tm * p.tiles_w_n;
+  const int m0 = tm * kT;
+  const Opnd A{p.gy, p.y, p.y_scale, p.OUT, p.OUT, p.vec_g};
+  const Opnd Bo{p.x, nullptr, 1.f, p.IN, p.IN, p.vec_x};
+  gemm_tile<float, false, false>(A, Bo, m0, tn * kT, p.B, lds, acc);
+  store_tile(p, lds, acc, m0, tn * kT, p.OUT, p.gw, false);
+  if (tn != 0 || !p.gb) return;
+  // g_b[o] = sum_b gz[b, o] for the tile's 64 rows: partial g sums rows b = g, g + 4, ... in order; then ((0 + 1) + 2) + 3
+  __syncthreads();
+  float* part = reinterpret_cast<float*>(lds);
+  const int c = threadIdx.x & 63, g = threadIdx.x >> 6, o = m0 + c;
+  float s = 0.f;
+  if (o < p.OUT) {
+#pragma unroll 4
+    for (int b = g; b < p.B; b += 4) s += gz_of(p.gy[(long)b * p.OUT + o], p.y, (long)b * p.OUT + o, p.y_scale);
+  }
+  part[g * 64 + c] = s;
+  __syncthreads();
+  if (threadIdx.x < 64 && o < p.OUT) p.gb[o] = ((part[c] + part[64 + c]) + part[128 + c]) + part[192 + c];
+}
+
+// one block; thread t owns rows t, t + 256, ...; the per-thread sums then meet in a fixed-order tree
+__global__ __launch_bounds__(kThreads) void dense_loss_kernel(const float* __restrict__ z, const void* __restrict__ target, int B,
+                                                              int C, int mode, float gs, float* __restrict__ loss,
+                                                              float* __restrict__ g) {
+  __shared__ float part[kThreads];
+  float acc = 0.f;
+#pragma unroll 1
+  for (int b = threadIdx.x; b < B; b += kThreads) {
+    const float* row = z + (long)b * C;
+    float* grow = g + (long)b * C;
+    if (mode == BNN_NLL_CLASSIFICATION) {
+      const long long tc = reinterpret_cast<const long long*>(target)[b];
+      const bool ok = tc >= 0 && tc < C;
+      float mx = row[0];
+      for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
+      float se = 0.f;
+      for (int c = 0; c < C; ++c) se += expf(row[c] - mx);
+      // an out-of-range label: NaN loss and row gradient, and z[label] is never read
+      acc += ok ? (mx + logf(se)) - row[ok ? tc : 0] : __builtin_nanf("");
+      const float inv = ok ? 1.0f / se : __builtin_nanf("");
+      for (int c = 0; c < C; ++c) grow[c] = (expf(row[c] - mx) * inv - (c == tc ? 1.f : 0.f)) * gs;
+    } else {
+      const float* tg = reinterpret_cast<const float*>(target) + (long)b * C;
+      for (int c = 0; c < C; ++c) {
+        const float d = row[c] - tg[c];
+        acc = __builtin_fmaf(d, d, acc);
+        grow[c] = 2.f * d * gs;
+      }
+    }
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int h = kThreads / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *loss = part[0];
+}
+
+struct SgdK {
+  float* p[BNN_SGD_MAX_TENSORS];
+  const float* g[BNN_SGD_MAX_TENSORS];
+  long numel[BNN_SGD_MAX_TENSORS];
+  int first_chunk[BNN_SGD_MAX_TENSORS + 1];
+  int n;
+  float lr, wd;
+  const float* lr_dev;
+};
+
+// one block = one 4096-element chunk of one tensor; 16-byte accesses
+__global__ __launch_bounds__(kThreads) void sgd_kernel(const SgdK k) {
+  int t = 0;
+#pragma unroll 1
+  while (t + 1 < k.n && (int)blockIdx.x >= k.first_chunk[t + 1]) ++t;
+  const long base = (long)((int)blockIdx.x - k.first_chunk[t]) * kSgdChunk;
+  const long n = k.numel[t];
+  float* __restrict__ p = k.p[t];
+  const float* __restrict__ g = k.g[t];
+  const float nlr = -(k.lr_dev ? *k.lr_dev : k.lr);
+  const float wd = k.wd;
+#pragma unroll
+  for (int it = 0; it < kSgdChunk / (kThreads * 4); ++it) {
+    const long i = base + ((long)it * kThreads + threadIdx.x) * 4;
+    if (i >= n) break;
+    if (i + 3 < n) {
+      const float4 a = *reinterpret_cast<const float4*>(p + i), b = *reinterpret_cast<const float4*>(g + i);
+      float pv[4] = {a.x, a.y, a.z, a.w};
+      const float gv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) pv[j] = __builtin_fmaf(nlr, wd != 0.f ? __builtin_fmaf(wd, pv[j], gv[j]) : gv[j], pv[j]);
+      *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
+    } else {
+      for (long j = i; j < n; ++j) p[j] = __builtin_fmaf(nlr, wd != 0.f ? __builtin_fmaf(wd, p[j], g[j]) : g[j], p[j]);
+    }
+  }
+}
+
+bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
+
+}  // namespace
+}  // namespace bnn
+
+using namespace bnn;
+
+extern "C" int bnn_dense_loss(const bnn_dense_loss_args* a, void* stream_) {
+  if (!a) return BNN_ERR_NULL;
+  if (a->struct_bytes != sizeof(bnn_dense_loss_args)) return BNN_ERR_ABI;
+  if (a->batch <= 0 || a->classes <= 0) return BNN_ERR_SHAPE;
+  if ((long)a->batch * a->classes > ((long)1 << 31)) return BNN_ERR_SHAPE;
+  if (a->loss_mode != BNN_NLL_CLASSIFICATION && a->loss_mode != BNN_NLL_REGRESSION) return BNN_ERR_ENUM;
+  if (!a->logits || !a->target || !a->loss || !a->g_logits) return BNN_ERR_NULL;
+  if (misaligned(a->logits, 4) || misaligned(a->loss, 4) || misaligned(a->g_logits, 4) ||
+      misaligned(a->target, a->loss_mode == BNN_NLL_CLASSIFICATION ? 8 : 4))
+    return BNN_ERR_ALIGN;
+  hipLaunchKernelGGL(dense_loss_kernel, dim3(1), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream_), a->logits, a->target,
+                     a->batch, a->classes, a->loss_mode, a->grad_scale, a->loss, a->g_logits);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? BNN_OK : (int)err;
+}
+
+extern "C" int bnn_dense_bwd(const bnn_dense_bwd_args* a, void* stream_) {
+  if (!a) return BNN_ERR_NULL;
+  if (a->struct_bytes != sizeof(bnn_dense_bwd_args)) return BNN_ERR_ABI;
+  if (a->batch <= 0 || a->in_features <= 0 || a->out_features <= 0) return BNN_ERR_SHAPE;
+  if ((long)a->batch * a->in_features > ((long)1 << 31) || (long)a->batch * a->out_features > ((long)1 << 31) ||
+      (long)a->in_features * a->out_features > ((long)1 << 31))
+    return BNN_ERR_SHAPE;
+  if (a->math != BNN_MATH_F32 && a->math != BNN_MATH_BF16 && a->math != BNN_MATH_BF16X3) return BNN_ERR_ENUM;
+  if (!a->x || !a->gy || !a->w || !a->g_w) return BNN_ERR_NULL;
+  if (misaligned(a->x, 4) || misaligned(a->gy, 4) || misaligned(a->y, 4) || misaligned(a->w, 4) || misaligned(a->g_w, 4) ||
+      misaligned(a->g_b, 4) || misaligned(a->g_x, 4))
+    return BNN_ERR_ALIGN;
+  BwdParams p;
+  p.x = a->x; p.gy = a->gy; p.y = a->y; p.w = a->w;
+  p.gw = a->g_w; p.gb = a->g_b; p.gx = a->g_x;
+  p.B = a->batch; p.IN = a->in_features; p.OUT = a->out_features;
+  p.y_scale = a->y_scale; p.gx_scale = a->gx_scale; p.gx_mask = a->gx_mask ? 1 : 0;
+  const int tin = (p.IN + kT - 1) / kT, tout = (p.OUT + kT - 1) / kT, tb = (p.B + kT - 1) / kT;
+  p.tiles_x_n = tin;
+  p.tiles_x = a->g_x ? tb * tin : 0;
+  p.tiles_w_n = tin;
+  const long blocks = (long)p.tiles_x + (long)tout * tin;
+  if (blocks > INT32_MAX) return BNN_ERR_SHAPE;
+  // 16-byte loads / stores: rows of a multiple of 4 floats from 16-byte aligned bases
+  p.vec_x = p.IN % 4 == 0 && !misaligned(a->x, 16);
+  p.vec_w = p.IN % 4 == 0 && !misaligned(a->w, 16);
+  p.vec_g = p.OUT % 4 == 0 && !misaligned(a->gy, 16) && !misaligned(a->y, 16);
+  p.vec_out = p.IN % 4 == 0 && !misaligned(a->g_w, 16) && !misaligned(a->g_x, 16);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+  if (a->math == BNN_MATH_BF16)
+    hipLaunchKernelGGL(dense_bwd_kernel<__bf16>, dim3((unsigned)blocks), dim3(kThreads), 0, st, p);
+  else
+    hipLaunchKernelGGL(dense_bwd_kernel<float>, dim3((unsigned)blocks), dim3(kThreads), 0, st, p);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? BNN_OK : (int)err;
+}
+
+extern "C" int bnn_sgd_step(const bnn_sgd_args* a, void* stream_) {
+  if (!a) return BNN_ERR_NULL;
+  if (a->struct_bytes != sizeof(bnn_sgd_args)) return BNN_ERR_ABI;
+  if (a->n_tensors <= 0 || a->n_tensors > BNN_SGD_MAX_TENSORS) return BNN_ERR_SHAPE;
+  if (!(a->lr >= 0.0) || !(a->weight_decay >= 0.0)) return BNN_ERR_SHAPE;
+  SgdK k;
+  long chunks = 0;
+  for (int t = 0; t < a->n_tensors; ++t) {
+    if (!a->param[t] || !a->grad[t]) return BNN_ERR_NULL;
+    if (a->numel[t] <= 0) return BNN_ERR_SHAPE;
+    if (misaligned(a->param[t], 16) || misaligned(a->grad[t], 16)) return BNN_ERR_ALIGN;
+    k.p[t] = a->param[t];
+    k.g[t] = a->grad[t];
+    k.numel[t] = (long)a->numel[t];
+    k.first_chunk[t] = (int)chunks;
+    chunks += (a->numel[t] + kSgdChunk - 1) / kSgdChunk;
+    if (chunks > 0x3fffffff) return BNN_ERR_SHAPE;
+  }
+  if (misaligned(a->lr_device, 4)) return BNN_ERR_ALIGN;
+  for (int t = a->n_tensors; t <= BNN_SGD_MAX_TENSORS; ++t) k.first_chunk[t] = (int)chunks;
+  for (int t = a->n_tensors; t < BNN_SGD_MAX_TENSORS; ++t) {
+    k.p[t] = nullptr; k.g[t] = nullptr; k.numel[t] = 0;
+  }
+  k.n = a->n_tensors;
+  k.lr = (float)a->lr;
+  k.wd = (float)a->weight_decay;
+  k.lr_dev = a->lr_device;
+  hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)chunks), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream_), k);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? BNN_OK : (int)err;
+}

@@ -25,6 +25,7 @@ from torch import nn
 from config import *  # noqa: F401,F403  (DEVICE, RegConfig, RLConfig, ClassConfig)
 from bnn_hip import _lib as _L
 from bnn_hip import engine as _engine
+from bnn_hip import dense_train as _dense_train
 from bnn_hip import mcdropout as _mcdropout
 from bnn_hip.functional import BBBLinearFn as _BBBLinearFn
 from bnn_hip.functional import LayerCall as _LayerCall
@@ -341,8 +342,10 @@ class BayesianNetwork(nn.Module):
 
 
 class _PlainMLP(nn.Module):
-    """Deterministic baselines (reference networks.py:227-285): stock nn.Linear stacks, out
-    of the hot path; kept so `from networks import MLP, MLP_Dropout` keeps working."""
+    """Deterministic baselines (reference networks.py:227-285): stock nn.Linear stacks, so `from networks import MLP,
+    MLP_Dropout` keeps working and forward() is torch's nn.Sequential.  Training them runs on the device through
+    graphed_train_step (bnn_hip.dense_train: forward with the Philox dropout mask, loss, backward and the optimiser as
+    one captured chain of HIP launches); MLP_Dropout's MC-dropout prediction likewise (bnn_hip.mcdropout)."""
     _p_drop = None
 
     def __init__(self, model_params):
@@ -365,6 +368,14 @@ class _PlainMLP(nn.Module):
         else:
             assert len(x.shape) == 2, "Input dimensions incorrect, expected shape = (batch_size, sample,...)"
         return self.net(x)
+
+    def graphed_train_step(self, optimizer, x, y, **kw):
+        """Extension (not in the reference): the reference's train_step body (zero_grad, forward, cross_entropy /
+        mse_loss with reduction='sum', backward, optimiser step) for minibatches shaped like (x, y), as one replayable
+        hipGraph -- `s = mlp.graphed_train_step(opt, x, y)`, then `loss = s.step(x, y)` per minibatch.  `optimizer`:
+        bnn_hip.optim.FusedSGD or FusedAdam with capturable=True; keywords: loss ('cross_entropy' | 'mse'), capture.
+        Dropout is always on (train mode), with fresh masks every step (bnn_hip.dense_train.GraphedDenseTrainStep)."""
+        return _dense_train.GraphedDenseTrainStep(self, optimizer, x, y, **kw)
 
 
 class MLP(_PlainMLP):

@@ -960,6 +960,75 @@ int bnn_dropout_mask(float* mask, uint64_t seed, uint32_t layer_id, uint32_t sam
                      int32_t rows, int32_t cols, double p, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * K6  Training MLP / MLP_Dropout (networks.py:227-285 under the reference's train_step: zero_grad, forward, loss,
+ * backward, optimiser step; classification/class_task.py:150-157, regression/reg_task.py:176-183).  The forward is
+ * bnn_dense_fwd with n_samples = 1 and fp32 outputs; these three finish the step.
+ *
+ * bnn_dense_loss — the loss value and the logits' gradient in ONE launch (one block; no float atomics):
+ *   BNN_NLL_CLASSIFICATION: cross_entropy(z, y, reduction='sum'):  loss = sum_b (logsumexp z_b - z_b[y_b]),
+ *                           g_logits = (softmax(z) - onehot(y)) * grad_scale.  target int64 [batch].  A label outside
+ *                           [0, classes) makes the loss and its row's gradient NaN (never read out of bounds).
+ *   BNN_NLL_REGRESSION:     mse_loss(z, y, reduction='sum'):  loss = sum (z - y)^2,  g_logits = 2 (z - y) * grad_scale.
+ *                           target fp32 [batch, classes].
+ * The loss is a per-thread sum over a fixed set of rows, then a fixed-order tree: the same bits on every call. */
+typedef struct bnn_dense_loss_args {
+  uint32_t struct_bytes;
+  int32_t batch, classes;
+  int32_t loss_mode;        /* bnn_nll_mode */
+  const float* logits;      /* [batch, classes] */
+  const void* target;       /* int64 [batch] (classification) or fp32 [batch, classes] (regression) */
+  float grad_scale;
+  int32_t reserved;
+  float* loss;              /* device scalar (unscaled) */
+  float* g_logits;          /* [batch, classes] */
+} bnn_dense_loss_args;
+int bnn_dense_loss(const bnn_dense_loss_args* args, void* stream);
+
+/* bnn_dense_bwd — the backward of one Linear -> [ReLU] -> [Dropout] group in ONE launch:
+ *   gz   = gy                                   (y == NULL: the output layer, or gy already masked by the layer above)
+ *        = y > 0 ? gy * y_scale : 0             (y: this layer's saved output; with ReLU then Dropout, y > 0 exactly
+ *                                                where the element was kept and the ReLU open; y_scale = 1 / (1 - p))
+ *   g_w  = gz^T . x  [out, in],   g_b = colsum(gz)  [out]: always the exact-fp32 matrix core (v_mfma_f32_16x16x4_f32)
+ *   g_x  = gz . W    [batch, in]  (optional; BNN_MATH_BF16: gz and W rounded to bf16 (RNE), fp32 accumulate; other
+ *                                  modes exact fp32), times (x > 0 ? gx_scale : 0) when gx_mask: the gradient mask of the
+ *                                  layer below (x is that layer's output), so its backward takes g_x as gy directly.
+ * x fp32 [batch, in] (this layer's input), gy / y fp32 [batch, out], W fp32 [out, in].  No K-split: every output element
+ * is one fixed chain of MFMAs over 32-wide k stages (g_b: four fixed strided partial sums, added in order), so results
+ * do not depend on the grid.  Any shape >= 1; 4-byte aligned pointers. */
+typedef struct bnn_dense_bwd_args {
+  uint32_t struct_bytes;
+  int32_t batch, in_features, out_features;
+  int32_t math;             /* bnn_math of the g_x product */
+  int32_t gx_mask;
+  const float* x;
+  const float* gy;
+  const float* y;           /* optional */
+  float y_scale;
+  float gx_scale;
+  const float* w;
+  float* g_w;
+  float* g_b;               /* optional */
+  float* g_x;               /* optional */
+} bnn_dense_bwd_args;
+int bnn_dense_bwd(const bnn_dense_bwd_args* args, void* stream);
+
+/* bnn_sgd_step — torch.optim.SGD.step() without momentum (the optimiser of classification/class_task.py:149) over up to
+ * BNN_SGD_MAX_TENSORS fp32 tensors in ONE launch:  p -= lr * (g + weight_decay * p)  (two fmas in fp32).  lr_device
+ * (optional device float) overrides lr, so StepLR can change the rate of a captured graph.  Contiguous tensors,
+ * 16-byte aligned. */
+#define BNN_SGD_MAX_TENSORS 16
+typedef struct bnn_sgd_args {
+  uint32_t struct_bytes;
+  int32_t n_tensors;
+  float* param[BNN_SGD_MAX_TENSORS];
+  const float* grad[BNN_SGD_MAX_TENSORS];
+  int64_t numel[BNN_SGD_MAX_TENSORS];
+  double lr, weight_decay;
+  const float* lr_device;
+} bnn_sgd_args;
+int bnn_sgd_step(const bnn_sgd_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
