@@ -28,6 +28,7 @@ EXPORTS = (
     "bnn_elbo_finalize", "bnn_bbb_final_fwd", "bnn_bbb_final_scratch_bytes", "bnn_philox_normal", "bnn_cast_bf16", "bnn_softplus", "bnn_eval_prepare",
     "bnn_ece_workspace_bytes", "bnn_ece", "bnn_snr_db", "bnn_snr_prune", "bnn_mc_predictive",
     "bnn_bandit_rows", "bnn_bandit_act", "bnn_bandit_replay",
+    "bnn_bandit_rows_group", "bnn_bandit_act_group", "bnn_bandit_replay_group", "bnn_mlp_group_fwd", "bnn_mlp_group_train",
     "bnn_dense_fwd", "bnn_dense_plan", "bnn_dropout_mask",
     "bnn_dense_loss", "bnn_dense_bwd", "bnn_sgd_step",
 )
@@ -245,6 +246,35 @@ class BanditReplayArgs(C.Structure):
                 ("n_batches", C.c_void_p)]
 
 
+MLP_GROUP_MAX_IN = 128
+MLP_GROUP_MAX_HIDDEN = 128
+MLP_GROUP_MAX_OUT = 1
+MLP_GROUP_MAX_BATCH = 64
+MLP_GROUP_MAX_BATCHES = 128
+MLP_GROUP_MAX_AGENTS = 4096
+
+
+class BanditGroupArgs(C.Structure):
+    """bnn_bandit_group_args (include/bnn_hip.h F6): G F5 argument blocks, the host copy and its device copy"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_agents", C.c_int32), ("blocks_host", C.c_void_p), ("blocks", C.c_void_p),
+                ("blocks_bytes", C.c_int64)]
+
+
+class MlpGroupAgent(C.Structure):
+    """bnn_mlp_group_agent (include/bnn_hip.h F6): one agent's pointers"""
+    _fields_ = [("param", C.c_void_p * 6), ("exp_avg", C.c_void_p * 6), ("exp_avg_sq", C.c_void_p * 6), ("step", C.c_void_p),
+                ("lr", C.c_void_p), ("slab", C.c_void_p), ("targets", C.c_void_p), ("n_batches", C.c_void_p), ("loss", C.c_void_p),
+                ("rows", C.c_void_p), ("outputs", C.c_void_p)]
+
+
+class MlpGroupArgs(C.Structure):
+    """bnn_mlp_group_args (include/bnn_hip.h F6): the shared shape and hyperparameters, the agent blocks host + device"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_agents", C.c_int32), ("in_features", C.c_int32), ("hidden", C.c_int32),
+                ("out_features", C.c_int32), ("batch", C.c_int32), ("max_batches", C.c_int32), ("n_rows", C.c_int32),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("agents_host", C.c_void_p), ("agents", C.c_void_p), ("agents_bytes", C.c_int64)]
+
+
 class DenseFwdArgs(C.Structure):
     """bnn_dense_fwd_args (include/bnn_hip.h): one nn.Linear of MLP_Dropout for S MC-dropout samples"""
     _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("batch", C.c_int32), ("in_features", C.c_int32),
@@ -412,6 +442,12 @@ def _load_real():
         getattr(lib, name).argtypes = [C.POINTER(BanditActArgs), C.c_void_p]
     lib.bnn_bandit_replay.restype = C.c_int
     lib.bnn_bandit_replay.argtypes = [C.POINTER(BanditReplayArgs), C.c_void_p]
+    for name in ("bnn_bandit_rows_group", "bnn_bandit_act_group", "bnn_bandit_replay_group"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(BanditGroupArgs), C.c_void_p]
+    for name in ("bnn_mlp_group_fwd", "bnn_mlp_group_train"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(MlpGroupArgs), C.c_void_p]
     lib.bnn_dense_fwd.restype = C.c_int
     lib.bnn_dense_fwd.argtypes = [C.POINTER(DenseFwdArgs), C.c_void_p]
     lib.bnn_dense_plan.restype = C.c_int

@@ -338,3 +338,276 @@ class BNNBandit:
     def history(self):
         """(actions [t] int64, rewards [t] fp32) of the steps taken, as numpy arrays."""
         return self.actions[:self.t].cpu().numpy(), self.rewards[:self.t].cpu().numpy()
+
+
+# ---------------------------------------------------------------------------------------------------- F6 greedy agents
+class GreedyBanditGroup:
+    """G independent Greedy_Bandit agents (bandits.py:59-85: an MLP in-(hidden)-(hidden)-1 trained with Adam on
+    mse_loss(net(x).squeeze(), y, reduction='sum'), epsilon-greedy decisions) advanced together on the device.  One update
+    of the whole group is six launches whatever G (include/bnn_hip.h F6), one workgroup per agent in each:
+
+        bnn_bandit_rows_group -> bnn_mlp_group_fwd -> bnn_bandit_act_group -> bnn_bandit_replay_group (2)
+        -> bnn_mlp_group_train (all nb minibatch steps of every agent)
+
+    captured as one hipGraph (`capture=True`) or launched eagerly (`capture=False`); the host never reads anything back.
+
+    G = len(epsilons).  Agent g builds networks.MLP exactly as Greedy_Bandit.init_net does, in order under torch's RNG, with
+    a capturable FusedAdam(lr=bandit_params['lr']) and StepLR(step_size=5000, gamma=0.5), and has its own bandit Philox
+    stream (seeds[g]; by default the global seed + g), ring, regrets, counts, actions and rewards.  update(mushroom) and
+    run(indices) give every agent the same context, as main.py does; update() without an index lets each agent draw its
+    context from its own stream.  `group[g]` is agent g's view (the BNNBandit read surface); every read synchronises."""
+
+    def __init__(self, label, bandit_params, x, y, *, epsilons, seeds=None, rewards: RewardTable = MUSHROOM,
+                 max_steps: int = 50000, capture: bool = True):
+        import networks
+        p = bandit_params
+        if state.shard_samples:
+            raise BnnHipError("GreedyBanditGroup: sample sharding is not supported (one device runs the whole loop)")
+        if p["mode"] != "regression":
+            raise BnnHipError("GreedyBanditGroup: the bandit's network regresses the reward (mode='regression')")
+        self.label = label
+        self.buffer_size, self.batch_size = int(p["buffer_size"]), int(p["batch_size"])
+        self.num_batches, self.lr, self.hidden = int(p["num_batches"]), float(p["lr"]), int(p["hidden_units"])
+        self.max_steps = int(max_steps)
+        if self.batch_size < 1 or self.buffer_size % self.batch_size:
+            raise BnnHipError("GreedyBanditGroup: buffer_size must be a multiple of batch_size (the reference's last "
+                              "minibatch is short)")
+        eps = [float(e) for e in epsilons]
+        if not eps or any(not 0.0 <= e <= 1.0 for e in eps):                    # NaN fails the comparison
+            raise BnnHipError(f"GreedyBanditGroup: epsilons must be a non-empty list of values in [0, 1], got {epsilons!r}")
+        self.G = len(eps)
+        if seeds is not None and len(seeds) != self.G:
+            raise BnnHipError(f"GreedyBanditGroup: {len(seeds)} seeds for {self.G} epsilons")
+        tab = np.asarray(rewards.rewards, dtype=np.float32)
+        if tab.ndim != 3 or tab.shape[2] != 3 or tab.shape[1] < 2 or len(rewards.oracle) != tab.shape[0]:
+            raise BnnHipError("GreedyBanditGroup: rewards must be [K][A][(hi, lo, thr)] with A >= 2 and K oracle values")
+        self.K, self.A = tab.shape[0], tab.shape[1]
+        xh, yh = np.asarray(x, dtype=np.float32), np.asarray(y).astype(np.int64)
+        if xh.ndim != 2 or yh.shape != (xh.shape[0],) or yh.min() < 0 or yh.max() >= self.K:
+            raise BnnHipError("GreedyBanditGroup: x must be [N, d] and y [N] labels in [0, K)")
+        self.N, self.d = xh.shape
+        W = self.d + self.A
+        nbm = self.buffer_size // self.batch_size
+        if (W > L.MLP_GROUP_MAX_IN or not 1 <= self.hidden <= L.MLP_GROUP_MAX_HIDDEN or self.batch_size > L.MLP_GROUP_MAX_BATCH
+                or nbm > L.MLP_GROUP_MAX_BATCHES or self.A > min(L.BANDIT_MAX_ACTIONS, L.MLP_GROUP_MAX_BATCH)
+                or self.buffer_size > L.BANDIT_MAX_BUFFER or self.G > L.MLP_GROUP_MAX_AGENTS or self.max_steps < 1):
+            raise BnnHipError(f"GreedyBanditGroup: beyond the kernels' limits (input {W} <= {L.MLP_GROUP_MAX_IN}, hidden <= "
+                              f"{L.MLP_GROUP_MAX_HIDDEN}, batch <= {L.MLP_GROUP_MAX_BATCH}, buffer / batch <= "
+                              f"{L.MLP_GROUP_MAX_BATCHES}, buffer <= {L.BANDIT_MAX_BUFFER}, agents <= {L.MLP_GROUP_MAX_AGENTS})")
+        self.epsilons = eps
+        self.seeds = [state.seed + g if seeds is None else int(seeds[g]) for g in range(self.G)]
+
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.x = torch.from_numpy(xh).to(dev).contiguous()
+        self.y = torch.from_numpy(yh).to(dev)
+        self.table = torch.from_numpy(tab).to(dev)
+        self.oracle = torch.tensor(rewards.oracle, dtype=torch.float32, device=dev)
+
+        # bandits.py:64-74, agent by agent
+        model_params = {'input_shape': W, 'classes': 1, 'batch_size': self.batch_size, 'hidden_units': self.hidden,
+                        'mode': p['mode']}
+        self.nets, self.optimisers, self.schedulers = [], [], []
+        for g in range(self.G):
+            net = networks.MLP(model_params).to(dev)
+            opt = FusedAdam(net.parameters(), lr=self.lr, capturable=True)
+            self.nets.append(net)
+            self.optimisers.append(opt)
+            self.schedulers.append(torch.optim.lr_scheduler.StepLR(opt, step_size=5000, gamma=0.5))
+
+        # device state, [G, ...] with one contiguous row per agent
+        G, T, B = self.G, self.max_steps, self.buffer_size
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        self.step_word = torch.zeros((G, 1), **i32)
+        self.cur_index = torch.zeros((G, 1), **i32)
+        self.indices = torch.full((T,), -1, dtype=torch.int64, device=dev)       # shared: -1 = each agent draws its own
+        self.actions = torch.zeros((G, T), dtype=torch.int64, device=dev)
+        self.rewards = torch.zeros((G, T), **f32)
+        self.regrets = torch.zeros((G, T + 1), dtype=torch.float64, device=dev)
+        self._counts = torch.zeros((G, self.K, self.A), dtype=torch.int64, device=dev)
+        self.ring_index, self.ring_action, self.ring_reward = torch.zeros((G, B), **i32), torch.zeros((G, B), **i32), \
+            torch.zeros((G, B), **f32)
+        self.perm = torch.zeros((G, B), **i32)
+        self.nb_slab = nbm
+        self.slab = torch.zeros((G, nbm, self.batch_size, W), **f32)
+        self.targets = torch.zeros((G, nbm, self.batch_size), **f32)
+        self.n_batches_word = torch.zeros((G, 1), **i32)
+        self.loss = torch.zeros((G, 1), **f32)
+        self.rows = torch.zeros((G, self.A, W), **f32)
+        self.outputs = torch.zeros((G, self.A), **f32)
+        self.t = 0
+
+        act, rep, mlp = [], [], []
+        for g in range(G):
+            act.append(ops.bandit_act_args(
+                x=self.x, labels=self.y, rewards=self.table, oracle=self.oracle, outputs=self.outputs[g], n_samples=1,
+                output_sample_stride=0, step=self.step_word[g], cur_index=self.cur_index[g], rows=self.rows[g],
+                actions=self.actions[g], reward_out=self.rewards[g], regrets=self.regrets[g], counts=self._counts[g],
+                ring_index=self.ring_index[g], ring_action=self.ring_action[g], ring_reward=self.ring_reward[g],
+                epsilon=eps[g], seed=self.seeds[g], indices=self.indices))
+            rep.append(ops.bandit_replay_args(
+                x=self.x, step=self.step_word[g], ring_index=self.ring_index[g], ring_action=self.ring_action[g],
+                ring_reward=self.ring_reward[g], workspace=self.perm[g], slab=self.slab[g], targets=self.targets[g],
+                batch_size=self.batch_size, n_actions=self.A, seed=self.seeds[g], n_batches=self.n_batches_word[g]))
+            opt = self.optimisers[g]
+            params = [t.detach() for t in self.nets[g].parameters()]              # w1 b1 w2 b2 w3 b3
+            for q in self.nets[g].parameters():                                   # Adam's state, as its first step makes it
+                st = opt.state[q]
+                st["step"] = 0
+                st["exp_avg"] = torch.zeros_like(q, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(q, memory_format=torch.preserve_format)
+            step_dev, lr_dev, _, _ = opt._group_dev(0, opt.param_groups[0], dev)
+            qs = list(self.nets[g].parameters())
+            mlp.append(ops.mlp_group_agent(
+                params=params, exp_avg=[opt.state[q]["exp_avg"] for q in qs], exp_avg_sq=[opt.state[q]["exp_avg_sq"] for q in qs],
+                step=step_dev, lr=lr_dev, slab=self.slab[g], targets=self.targets[g], n_batches=self.n_batches_word[g],
+                loss=self.loss[g], rows=self.rows[g], outputs=self.outputs[g]))
+        grp = self.optimisers[0].param_groups[0]
+        self.g_act = ops.bandit_group_args(act, dev)
+        self.g_replay = ops.bandit_group_args(rep, dev)
+        shape = dict(in_features=W, hidden=self.hidden, device=dev, betas=grp["betas"], eps=grp["eps"],
+                     weight_decay=grp["weight_decay"])
+        self.g_fwd = ops.mlp_group_args(mlp, n_rows=self.A, **shape)
+        self.g_train = ops.mlp_group_args(mlp, batch=self.batch_size, max_batches=nbm, **shape)
+
+        # warm-up: every launch once, eagerly (this validates every block); the training launch with nb = 0 touches nothing.
+        # Then the words the warm-up moved are reset, and the update is captured.
+        self.capture = bool(capture)
+        self.graph = None
+        self._enqueue(train=False)
+        self.n_batches_word.zero_()
+        ops.mlp_group_train(self.g_train)
+        torch.cuda.synchronize()
+        self.step_word.zero_()
+        self._counts.zero_()
+        self.regrets.zero_()
+        if capture:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph, stream=side):
+                    self._enqueue()
+            torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+
+    def _enqueue(self, train: bool = True):
+        """The six launches of one group update, on the current stream."""
+        ops.bandit_rows_group(self.g_act)
+        ops.mlp_group_fwd(self.g_fwd)
+        ops.bandit_act_group(self.g_act)
+        ops.bandit_replay_group(self.g_replay)
+        if train:
+            ops.mlp_group_train(self.g_train)
+
+    def _step(self):
+        if state.shard_samples:
+            raise BnnHipError("GreedyBanditGroup: sample sharding is not supported")
+        for opt in self.optimisers:
+            opt.sync_lr()                        # what StepLR changed, into the device words (a fill, no host read)
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._enqueue()
+        for s in self.schedulers:
+            s.step()
+        self.t += 1
+
+    def update(self, mushroom: Optional[int] = None):
+        """One bandit step of every agent (base_bandit.py:75-88 + main.py:103's scheduler.step()) on context `mushroom`,
+        the same for all agents, or, when None, on a context each agent draws from its own stream.  Does not synchronise."""
+        if self.t >= self.max_steps:
+            raise BnnHipError(f"GreedyBanditGroup: max_steps={self.max_steps} reached")
+        if mushroom is not None:
+            i = int(mushroom)
+            if not 0 <= i < self.N:
+                raise BnnHipError(f"GreedyBanditGroup: context index {i} outside [0, {self.N})")
+            self.indices[self.t].fill_(i)
+        self._step()
+
+    def run(self, indices: Sequence[int]):
+        """update(i) for every i of `indices`, the sequence uploaded once."""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if self.t + idx.size > self.max_steps:
+            raise BnnHipError(f"GreedyBanditGroup: {idx.size} steps from step {self.t} pass max_steps={self.max_steps}")
+        if idx.size and (idx.min() < 0 or idx.max() >= self.N):
+            raise BnnHipError(f"GreedyBanditGroup: context indices must lie in [0, {self.N})")
+        self.indices[self.t:self.t + idx.size].copy_(torch.from_numpy(idx))
+        for _ in range(idx.size):
+            self._step()
+
+    def __len__(self):
+        return self.G
+
+    def __getitem__(self, g: int) -> "GreedyAgentView":
+        if not -self.G <= g < self.G:
+            raise IndexError(g)
+        return GreedyAgentView(self, g % self.G)
+
+
+class GreedyAgentView:
+    """Agent g of a GreedyBanditGroup with BNNBandit's read surface.  Every read synchronises with the device once."""
+
+    def __init__(self, group: GreedyBanditGroup, g: int):
+        self.group, self.g = group, g
+        self.label = f"{group.label}[{g}]"
+        self.epsilon, self.seed = group.epsilons[g], group.seeds[g]
+        self.net, self.optimiser, self.scheduler = group.nets[g], group.optimisers[g], group.schedulers[g]
+
+    @property
+    def t(self) -> int:
+        return self.group.t
+
+    @property
+    def loss_info(self):
+        """The loss of the last minibatch of the last update (mse_loss, sum): a float, or None before the first update."""
+        return float(self.group.loss[self.g].item()) if self.group.t else None
+
+    @property
+    def cumulative_regrets(self) -> list:
+        return self.group.regrets[self.g, :self.group.t + 1].tolist()
+
+    @property
+    def counts(self) -> np.ndarray:
+        return self.group._counts[self.g].cpu().numpy()
+
+    @property
+    def tp(self) -> int:
+        return int(self.group._counts[self.g, 1, 0].item())
+
+    @property
+    def fn(self) -> int:
+        return int(self.group._counts[self.g, 1, 1].item())
+
+    @property
+    def fp(self) -> int:
+        return int(self.group._counts[self.g, 0, 0].item())
+
+    @property
+    def tn(self) -> int:
+        return int(self.group._counts[self.g, 0, 1].item())
+
+    def history(self):
+        """(actions [t] int64, rewards [t] fp32) of the steps taken, as numpy arrays."""
+        t = self.group.t
+        return self.group.actions[self.g, :t].cpu().numpy(), self.group.rewards[self.g, :t].cpu().numpy()
+
+
+class GreedyBandit(GreedyAgentView):
+    """Greedy_Bandit (bandits.py:59-85) on the device: a GreedyBanditGroup of one, with the reference's constructor arguments
+    (epsilon from bandit_params) -- a drop-in where main.py:91-93 builds one.  update() / run() as the group's."""
+
+    def __init__(self, label, bandit_params, x, y, *, seed: Optional[int] = None, rewards: RewardTable = MUSHROOM,
+                 max_steps: int = 50000, capture: bool = True):
+        group = GreedyBanditGroup(label, bandit_params, x, y, epsilons=[bandit_params["epsilon"]],
+                                  seeds=None if seed is None else [seed], rewards=rewards, max_steps=max_steps, capture=capture)
+        super().__init__(group, 0)
+        self.label = label
+        self.n_samples = int(bandit_params.get("n_samples", 1))
+        self.buffer_size, self.batch_size = group.buffer_size, group.batch_size
+        self.num_batches, self.lr = group.num_batches, group.lr
+
+    def update(self, mushroom: Optional[int] = None):
+        self.group.update(mushroom)
+
+    def run(self, indices: Sequence[int]):
+        self.group.run(indices)

@@ -1257,6 +1257,114 @@ def bandit_replay(a: L.BanditReplayArgs):
     L.check(L.load().bnn_bandit_replay(C.byref(a), _stream()), "bnn_bandit_replay")
 
 
+# ---------------------------------------------------------------------------------------------------------------- F6 groups
+def _device_copy(arr, device) -> torch.Tensor:
+    """The bytes of a ctypes array as a device uint8 tensor (the copy the group kernels read)."""
+    return torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(device)
+
+
+def bandit_group_args(blocks: Sequence, device) -> L.BanditGroupArgs:
+    """The argument block of bnn_bandit_*_group over G F5 blocks (all BanditActArgs or all BanditReplayArgs): the host
+    array the entry validates and its device copy, made once here, that the kernels read."""
+    if not blocks:
+        raise BnnHipError("bandit_group_args: at least one block")
+    cls = type(blocks[0])
+    if cls not in (L.BanditActArgs, L.BanditReplayArgs) or any(type(b) is not cls for b in blocks):
+        raise BnnHipError("bandit_group_args: blocks must all be BanditActArgs or all BanditReplayArgs")
+    host = (cls * len(blocks))(*blocks)
+    dev = _device_copy(host, device)
+    g = L.BanditGroupArgs()
+    g.struct_bytes = C.sizeof(L.BanditGroupArgs)
+    g.n_agents, g.blocks_host, g.blocks, g.blocks_bytes = len(blocks), C.addressof(host), dev.data_ptr(), dev.numel()
+    g._keep = (host, dev, [b._keep for b in blocks])
+    return g
+
+
+def bandit_rows_group(g: L.BanditGroupArgs):
+    """bnn_bandit_rows_group: bnn_bandit_rows of every agent, one launch."""
+    L.check(L.load().bnn_bandit_rows_group(C.byref(g), _stream()), "bnn_bandit_rows_group")
+
+
+def bandit_act_group(g: L.BanditGroupArgs):
+    """bnn_bandit_act_group: bnn_bandit_act of every agent, one launch."""
+    L.check(L.load().bnn_bandit_act_group(C.byref(g), _stream()), "bnn_bandit_act_group")
+
+
+def bandit_replay_group(g: L.BanditGroupArgs):
+    """bnn_bandit_replay_group: bnn_bandit_replay of every agent, two launches."""
+    L.check(L.load().bnn_bandit_replay_group(C.byref(g), _stream()), "bnn_bandit_replay_group")
+
+
+def mlp_group_agent(*, params: Sequence[torch.Tensor], exp_avg=None, exp_avg_sq=None, step=None, lr=None, slab=None,
+                    targets=None, n_batches=None, loss=None, rows=None, outputs=None) -> L.MlpGroupAgent:
+    """One agent's block of bnn_mlp_group_*: params = (w1, b1, w2, b2, w3, b3) fp32 (nn.Linear layout), Adam's moments in the
+    same order, step (int32 word), lr (fp32 word), slab [max_batches, batch, in], targets [max_batches * batch], n_batches
+    (int32 word), loss (fp32 scalar) for training; rows [n_rows, in] and outputs [n_rows] for the decision forward."""
+    a = L.MlpGroupAgent()
+    keep = []
+    a._named = dict(params=list(params), slab=slab, targets=targets, rows=rows, outputs=outputs)
+    if len(params) != 6:
+        raise BnnHipError("mlp_group_agent: six parameter tensors (w1, b1, w2, b2, w3, b3)")
+    for f, ts in (("param", params), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if ts is None:
+            continue
+        if len(ts) != 6:
+            raise BnnHipError(f"mlp_group_agent: six {f} tensors")
+        arr = getattr(a, f)
+        for i, t in enumerate(ts):
+            keep.append(_typed(t, torch.float32, f"{f}[{i}]", params[i].numel()))
+            arr[i] = t.data_ptr()
+    for f, t, dt in (("step", step, torch.int32), ("lr", lr, torch.float32), ("slab", slab, torch.float32),
+                     ("targets", targets, torch.float32), ("n_batches", n_batches, torch.int32), ("loss", loss, torch.float32),
+                     ("rows", rows, torch.float32), ("outputs", outputs, torch.float32)):
+        if t is not None:
+            keep.append(_typed(t, dt, f))
+            setattr(a, f, t.data_ptr())
+    a._keep = keep
+    return a
+
+
+def mlp_group_args(agents: Sequence, *, in_features: int, hidden: int, device, batch: int = 0, max_batches: int = 0,
+                   n_rows: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0) -> L.MlpGroupArgs:
+    """The argument block of bnn_mlp_group_fwd / _train over G agent blocks (mlp_group_agent), with the device copy of the
+    blocks made once here.  Shapes are checked against the blocks' tensors: the training form (max_batches > 0) needs slab
+    [max_batches, batch, in], the forward form (n_rows > 0) rows [n_rows, in]."""
+    if not agents:
+        raise BnnHipError("mlp_group_args: at least one agent")
+    I, H = int(in_features), int(hidden)
+    shapes = (H * I, H, H * H, H, H, 1)
+    for ag in agents:
+        if tuple(t.numel() for t in ag._named["params"]) != shapes:
+            raise BnnHipError(f"mlp_group_args: the parameters must be an {I}-{H}-{H}-1 MLP's")
+        named = ag._named
+        if int(max_batches) and (named["slab"] is None or named["slab"].numel() != int(max_batches) * int(batch) * I or
+                                          named["targets"] is None or named["targets"].numel() != int(max_batches) * int(batch)):
+            raise BnnHipError("mlp_group_args: slab must be [max_batches, batch, in] and targets [max_batches, batch]")
+        if int(n_rows) and (named["rows"] is None or named["rows"].numel() != int(n_rows) * I or named["outputs"] is None or
+                                          named["outputs"].numel() != int(n_rows)):
+            raise BnnHipError("mlp_group_args: rows must be [n_rows, in] and outputs [n_rows]")
+    host = (L.MlpGroupAgent * len(agents))(*agents)
+    dev = _device_copy(host, device)
+    a = L.MlpGroupArgs()
+    a.struct_bytes = C.sizeof(L.MlpGroupArgs)
+    a.n_agents, a.in_features, a.hidden, a.out_features = len(agents), int(in_features), int(hidden), 1
+    a.batch, a.max_batches, a.n_rows = int(batch), int(max_batches), int(n_rows)
+    a.beta1, a.beta2, a.eps, a.weight_decay = float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
+    a.agents_host, a.agents, a.agents_bytes = C.addressof(host), dev.data_ptr(), dev.numel()
+    a._keep = (host, dev, [ag._keep for ag in agents])
+    return a
+
+
+def mlp_group_fwd(a: L.MlpGroupArgs):
+    """bnn_mlp_group_fwd: every agent's forward of its rows, one launch."""
+    L.check(L.load().bnn_mlp_group_fwd(C.byref(a), _stream()), "bnn_mlp_group_fwd")
+
+
+def mlp_group_train(a: L.MlpGroupArgs):
+    """bnn_mlp_group_train: every agent's nb minibatch steps (forward, mse_loss(sum), backward, Adam), one launch."""
+    L.check(L.load().bnn_mlp_group_train(C.byref(a), _stream()), "bnn_mlp_group_train")
+
+
 def dropout_params(p: float) -> tuple:
     """(thr, scale) of the kind-3 dropout map (include/bnn_hip.h) for a drop probability p in [0, 1), in fp64 as the
     library forms them.  Raises BnnHipError outside that range."""

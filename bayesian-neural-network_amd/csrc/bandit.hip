@@ -22,7 +22,9 @@ __device__ __forceinline__ long pick(uint32_t r, long n) {
   return v < n - 1 ? v : n - 1;
 }
 
-__global__ __launch_bounds__(kRowsBlock) void bandit_rows_kernel(bnn_bandit_act_args a) {
+// The kernel bodies take the argument block by reference: the F5 kernels pass their by-value argument, the F6 group kernels
+// (bnn_bandit_*_group) block g of the device array -- the same code on either.
+__device__ __forceinline__ void bandit_rows_body(const bnn_bandit_act_args& a) {
   __shared__ long s_idx;
   const uint32_t t = *a.step;
   if ((int64_t)t >= a.max_steps) return;                                          // block-uniform
@@ -43,8 +45,13 @@ __global__ __launch_bounds__(kRowsBlock) void bandit_rows_kernel(bnn_bandit_act_
   }
 }
 
+__global__ __launch_bounds__(kRowsBlock) void bandit_rows_kernel(bnn_bandit_act_args a) { bandit_rows_body(a); }
+__global__ __launch_bounds__(kRowsBlock) void bandit_rows_group_kernel(const bnn_bandit_act_args* g) {
+  bandit_rows_body(g[blockIdx.x]);
+}
+
 // One wave: lane a sums its action's S outputs, the wave takes the argmax (ties to the highest index), lane 0 does the rest.
-__global__ __launch_bounds__(64) void bandit_act_kernel(bnn_bandit_act_args a) {
+__device__ __forceinline__ void bandit_act_body(const bnn_bandit_act_args& a) {
   const uint32_t t = *a.step;
   if ((int64_t)t >= a.max_steps) return;                                          // wave-uniform
   const int lane = threadIdx.x, A = a.n_actions;
@@ -85,6 +92,9 @@ __global__ __launch_bounds__(64) void bandit_act_kernel(bnn_bandit_act_args a) {
   if (a.sample_counter) *a.sample_counter += a.sample_counter_inc;
 }
 
+__global__ __launch_bounds__(64) void bandit_act_kernel(bnn_bandit_act_args a) { bandit_act_body(a); }
+__global__ __launch_bounds__(64) void bandit_act_group_kernel(const bnn_bandit_act_args* g) { bandit_act_body(g[blockIdx.x]); }
+
 // The pool of base_bandit.py:77-84 for l entries: its size, and the entry at position p.
 __device__ __forceinline__ uint32_t pool_size(uint32_t l, uint32_t bs, uint32_t buf) {
   if (l <= bs) return l ? bs : 0u;
@@ -101,7 +111,7 @@ __device__ __forceinline__ uint32_t pool_entry(uint32_t p, uint32_t l, uint32_t 
 
 // One block: keys (Philox word of the position) ++ position, bitonic-sorted ascending in LDS, then the ring slot of every
 // shuffled position into the workspace.
-__global__ __launch_bounds__(kSortBlock) void bandit_shuffle_kernel(bnn_bandit_replay_args a) {
+__device__ __forceinline__ void bandit_shuffle_body(const bnn_bandit_replay_args& a) {
   __shared__ unsigned long long kv[BNN_BANDIT_MAX_BUFFER];                        // 64 KiB
   const uint32_t l = *a.step, t = l - 1u;
   const uint32_t bs = (uint32_t)a.batch_size, buf = (uint32_t)a.buffer_size;
@@ -141,11 +151,16 @@ __global__ __launch_bounds__(kSortBlock) void bandit_shuffle_kernel(bnn_bandit_r
   }
 }
 
+__global__ __launch_bounds__(kSortBlock) void bandit_shuffle_kernel(bnn_bandit_replay_args a) { bandit_shuffle_body(a); }
+__global__ __launch_bounds__(kSortBlock) void bandit_shuffle_group_kernel(const bnn_bandit_replay_args* g) {
+  bandit_shuffle_body(g[blockIdx.x]);
+}
+
 // A wave per slab row q < pool: x[i] ++ one_hot(action) and the reward of the entry in ring slot workspace[q].
-__global__ __launch_bounds__(kGatherBlock) void bandit_gather_kernel(bnn_bandit_replay_args a) {
+__device__ __forceinline__ void bandit_gather_body(const bnn_bandit_replay_args& a, uint32_t bx) {
   const uint32_t l = *a.step;
   const uint32_t P = pool_size(l, (uint32_t)a.batch_size, (uint32_t)a.buffer_size);
-  const uint32_t q = blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6);
+  const uint32_t q = bx * (kGatherBlock / 64) + (threadIdx.x >> 6);
   if (q >= P) return;                                                             // wave-uniform
   const int lane = threadIdx.x & 63, d = a.context_dim, A = a.n_actions, w = d + A;
   const int slot = a.workspace[q];
@@ -155,6 +170,12 @@ __global__ __launch_bounds__(kGatherBlock) void bandit_gather_kernel(bnn_bandit_
   float* dst = a.slab + (size_t)q * w;
   for (int c = lane; c < w; c += 64) dst[c] = c < d ? src[c] : (c - d == act ? 1.f : 0.f);
   if (lane == 0) a.targets[q] = a.ring_reward[slot];
+}
+
+__global__ __launch_bounds__(kGatherBlock) void bandit_gather_kernel(bnn_bandit_replay_args a) { bandit_gather_body(a, blockIdx.x); }
+// grid (blocks of the largest agent's buffer, G): row g gathers agent g
+__global__ __launch_bounds__(kGatherBlock) void bandit_gather_group_kernel(const bnn_bandit_replay_args* g) {
+  bandit_gather_body(g[blockIdx.y], blockIdx.x);
 }
 
 }  // namespace bnn
@@ -203,7 +224,7 @@ extern "C" int bnn_bandit_act(const bnn_bandit_act_args* a, void* stream_) {
   return err == hipSuccess ? BNN_OK : (int)err;
 }
 
-extern "C" int bnn_bandit_replay(const bnn_bandit_replay_args* a, void* stream_) {
+static int check_replay(const bnn_bandit_replay_args* a) {
   if (!a) return BNN_ERR_NULL;
   if (a->struct_bytes != sizeof(bnn_bandit_replay_args)) return BNN_ERR_ABI;
   if (a->batch_size < 1 || a->num_batches < 1 || a->buffer_size < 1 || a->buffer_size > BNN_BANDIT_MAX_BUFFER) return BNN_ERR_SHAPE;
@@ -217,12 +238,71 @@ extern "C" int bnn_bandit_replay(const bnn_bandit_replay_args* a, void* stream_)
   const void* w4[] = {a->step, a->x, a->ring_index, a->ring_action, a->ring_reward, a->workspace, a->slab, a->targets, a->n_batches};
   for (const void* p : w4)
     if (misaligned(p, 4)) return BNN_ERR_ALIGN;
+  return BNN_OK;
+}
+
+extern "C" int bnn_bandit_replay(const bnn_bandit_replay_args* a, void* stream_) {
+  const int rc = check_replay(a);
+  if (rc) return rc;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   hipLaunchKernelGGL(bandit_shuffle_kernel, dim3(1), dim3(kSortBlock), 0, stream, *a);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) return (int)err;
   const unsigned blocks = (unsigned)((a->buffer_size + kGatherBlock / 64 - 1) / (kGatherBlock / 64));
   hipLaunchKernelGGL(bandit_gather_kernel, dim3(blocks), dim3(kGatherBlock), 0, stream, *a);
+  err = hipGetLastError();
+  return err == hipSuccess ? BNN_OK : (int)err;
+}
+
+// ---------------------------------------------------------------------------------------------------- F6 group forms
+// The host copy of the blocks is validated block by block; the kernels read the device copy (include/bnn_hip.h F6).
+template <class Block>
+static int check_group(const bnn_bandit_group_args* g, int (*check)(const Block*)) {
+  if (!g) return BNN_ERR_NULL;
+  if (g->struct_bytes != sizeof(bnn_bandit_group_args)) return BNN_ERR_ABI;
+  if (g->n_agents < 1 || g->n_agents > BNN_MLP_GROUP_MAX_AGENTS) return BNN_ERR_SHAPE;
+  if (!g->blocks_host || !g->blocks) return BNN_ERR_NULL;
+  if (g->blocks_bytes != (int64_t)g->n_agents * (int64_t)sizeof(Block)) return BNN_ERR_SHAPE;
+  if (misaligned(g->blocks, 8)) return BNN_ERR_ALIGN;
+  const Block* h = static_cast<const Block*>(g->blocks_host);
+  for (int i = 0; i < g->n_agents; ++i) {
+    const int rc = check(h + i);
+    if (rc) return rc;
+  }
+  return BNN_OK;
+}
+
+extern "C" int bnn_bandit_rows_group(const bnn_bandit_group_args* g, void* stream_) {
+  const int rc = check_group<bnn_bandit_act_args>(g, check_act);
+  if (rc) return rc;
+  hipLaunchKernelGGL(bandit_rows_group_kernel, dim3((unsigned)g->n_agents), dim3(kRowsBlock), 0,
+                     reinterpret_cast<hipStream_t>(stream_), static_cast<const bnn_bandit_act_args*>(g->blocks));
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? BNN_OK : (int)err;
+}
+
+extern "C" int bnn_bandit_act_group(const bnn_bandit_group_args* g, void* stream_) {
+  const int rc = check_group<bnn_bandit_act_args>(g, check_act);
+  if (rc) return rc;
+  hipLaunchKernelGGL(bandit_act_group_kernel, dim3((unsigned)g->n_agents), dim3(64), 0,
+                     reinterpret_cast<hipStream_t>(stream_), static_cast<const bnn_bandit_act_args*>(g->blocks));
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? BNN_OK : (int)err;
+}
+
+extern "C" int bnn_bandit_replay_group(const bnn_bandit_group_args* g, void* stream_) {
+  const int rc = check_group<bnn_bandit_replay_args>(g, check_replay);
+  if (rc) return rc;
+  const bnn_bandit_replay_args* h = static_cast<const bnn_bandit_replay_args*>(g->blocks_host);
+  int32_t buf = 1;
+  for (int i = 0; i < g->n_agents; ++i) buf = h[i].buffer_size > buf ? h[i].buffer_size : buf;
+  const bnn_bandit_replay_args* d = static_cast<const bnn_bandit_replay_args*>(g->blocks);
+  hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+  hipLaunchKernelGGL(bandit_shuffle_group_kernel, dim3((unsigned)g->n_agents), dim3(kSortBlock), 0, stream, d);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return (int)err;
+  const unsigned blocks = (unsigned)((buf + kGatherBlock / 64 - 1) / (kGatherBlock / 64));
+  hipLaunchKernelGGL(bandit_gather_group_kernel, dim3(blocks, (unsigned)g->n_agents), dim3(kGatherBlock), 0, stream, d);
   err = hipGetLastError();
   return err == hipSuccess ? BNN_OK : (int)err;
 }

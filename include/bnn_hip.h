@@ -902,6 +902,85 @@ typedef struct bnn_bandit_replay_args {
 int bnn_bandit_replay(const bnn_bandit_replay_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F6  groups of epsilon-greedy MLP bandits — Greedy_Bandit (reinforcement_learning/bandits.py:59-85: an MLP
+ * in-(hidden)-(hidden)-1 trained by torch.optim.Adam on mse_loss(net(x).squeeze(), y, reduction='sum')) for G independent
+ * agents, each update a fixed number of launches whatever G: rows, fwd, act, replay (2), train.
+ *
+ * Grouped F5 entries: bnn_bandit_rows_group / bnn_bandit_act_group run exactly bnn_bandit_rows / bnn_bandit_act on each of
+ * n_agents bnn_bandit_act_args blocks (block g of the grid on block g), bnn_bandit_replay_group exactly bnn_bandit_replay on
+ * n_agents bnn_bandit_replay_args blocks (sort: block g; gather: grid row g).  Per agent the semantics are F5's.
+ * Validation without a device: the caller passes the blocks twice -- `blocks_host`, a HOST array the entry validates block
+ * by block with F5's checks, and `blocks`, a DEVICE copy of the same bytes that the kernels read (the caller copies it once;
+ * the launches read it on every replay, so a captured graph keeps working as long as the copy is left in place).
+ * blocks_bytes must be n_agents * sizeof(block) (else BNN_ERR_SHAPE); the library does not compare the two copies.
+ *
+ * bnn_mlp_group_fwd — the decision forward: for each agent g, outputs[r] = net_g(rows[r]) for the n_rows rows
+ *   [n_rows, in] (what bnn_bandit_rows wrote): Linear, ReLU, Linear, ReLU, Linear.  One launch, one workgroup per agent.
+ * bnn_mlp_group_train — the training half of one update (base_bandit.py:86-88 with bandits.py:77-83) for every agent in
+ *   ONE launch, one workgroup per agent: nb = min(*n_batches, max_batches) (the word bnn_bandit_replay writes); for
+ *   j = 0 .. nb - 1 on slab[j] [batch, in] / targets[j] [batch]:
+ *     forward; loss = sum_b (z_b - y_b)^2, dz_b = 2 (z_b - y_b); backward (weight, bias and hidden-input gradients);
+ *     Adam (F2's arithmetic, torch.optim.Adam): t = *step + j + 1, lr = *lr (device words: a captured graph counts by
+ *     itself, StepLR reaches it), bias corrections in fp64, then every parameter of the agent updated.
+ *   *step += nb, and *loss = the loss of minibatch nb - 1 (the reference's loss_info).  nb == 0 writes nothing.
+ *   The minibatches are separated by workgroup barriers only: agents never wait on each other.
+ * Math: exact fp32 in every math mode (fp32 FMA; bnn_set_math / BNN_MATH_* do not apply: the shapes are per-CU latency-bound
+ *   chains, where bf16 operands would buy little and cost the reference's arithmetic).  Every sum runs in one fixed order
+ *   (no float atomics): a replay is bit-reproducible, and an agent's results do not depend on G or on its place in the group.
+ * Limits: in <= BNN_MLP_GROUP_MAX_IN, hidden <= BNN_MLP_GROUP_MAX_HIDDEN, out == 1, batch and n_rows <=
+ *   BNN_MLP_GROUP_MAX_BATCH (x, both hidden activations and one gradient live in LDS: 4 x 32 KiB of the CU's 160),
+ *   max_batches <= BNN_MLP_GROUP_MAX_BATCHES, n_agents <= BNN_MLP_GROUP_MAX_AGENTS; else BNN_ERR_SHAPE.
+ * Per-agent data lives in an array of bnn_mlp_group_agent blocks, passed host + device as above (agents_host validated,
+ *   agents read by the kernel, agents_bytes = n_agents * sizeof(bnn_mlp_group_agent)).  Parameters in nn.Linear's layout
+ *   (weight [out, in], bias [out]); param / exp_avg / exp_avg_sq in the order w1 b1 w2 b2 w3 b3.  fwd reads param, rows,
+ *   outputs only; train everything but rows / outputs.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_MLP_GROUP_MAX_IN 128
+#define BNN_MLP_GROUP_MAX_HIDDEN 128
+#define BNN_MLP_GROUP_MAX_OUT 1
+#define BNN_MLP_GROUP_MAX_BATCH 64
+#define BNN_MLP_GROUP_MAX_BATCHES 128
+#define BNN_MLP_GROUP_MAX_AGENTS 4096
+typedef struct bnn_bandit_group_args {
+  uint32_t struct_bytes;
+  int32_t n_agents;               /* G, 1 .. BNN_MLP_GROUP_MAX_AGENTS */
+  const void* blocks_host;        /* HOST: G bnn_bandit_act_args blocks for rows / act, G bnn_bandit_replay_args for replay */
+  const void* blocks;             /* DEVICE copy of blocks_host */
+  int64_t blocks_bytes;           /* bytes of the device copy */
+} bnn_bandit_group_args;
+int bnn_bandit_rows_group(const bnn_bandit_group_args* args, void* stream);
+int bnn_bandit_act_group(const bnn_bandit_group_args* args, void* stream);
+int bnn_bandit_replay_group(const bnn_bandit_group_args* args, void* stream);
+
+typedef struct bnn_mlp_group_agent {
+  float* param[6];                /* w1 [hidden, in], b1 [hidden], w2 [hidden, hidden], b2 [hidden], w3 [1, hidden], b3 [1] */
+  float* exp_avg[6];              /* train: Adam's moments, same shapes */
+  float* exp_avg_sq[6];
+  uint32_t* step;                 /* train: Adam's device step word */
+  const float* lr;                /* train: device learning rate */
+  const float* slab;              /* train: [max_batches, batch, in] */
+  const float* targets;           /* train: [max_batches, batch] */
+  const int32_t* n_batches;       /* train: device word nb */
+  float* loss;                    /* train: device scalar */
+  const float* rows;              /* fwd: [n_rows, in] */
+  float* outputs;                 /* fwd: [n_rows] */
+} bnn_mlp_group_agent;
+typedef struct bnn_mlp_group_args {
+  uint32_t struct_bytes;
+  int32_t n_agents;               /* G, 1 .. BNN_MLP_GROUP_MAX_AGENTS */
+  int32_t in_features, hidden, out_features;
+  int32_t batch;                  /* train: minibatch rows */
+  int32_t max_batches;            /* train: slab capacity */
+  int32_t n_rows;                 /* fwd: rows per agent */
+  double beta1, beta2, eps, weight_decay;
+  const bnn_mlp_group_agent* agents_host;   /* HOST array of G blocks (validated) */
+  const bnn_mlp_group_agent* agents;        /* DEVICE copy (read by the kernel) */
+  int64_t agents_bytes;                     /* bytes of the device copy */
+} bnn_mlp_group_args;
+int bnn_mlp_group_fwd(const bnn_mlp_group_args* args, void* stream);
+int bnn_mlp_group_train(const bnn_mlp_group_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_philox_normal — materialise the on-chip epsilon stream (map at the top) into
  * eps[n_samples, rows, cols]: used by the backward pass to regenerate eps instead of
  * storing it, and by tests to check the frozen counter->element map.
