@@ -29,6 +29,7 @@ EXPORTS = (
     "bnn_ece_workspace_bytes", "bnn_ece", "bnn_snr_db", "bnn_snr_prune", "bnn_mc_predictive",
     "bnn_bandit_rows", "bnn_bandit_act", "bnn_bandit_replay",
     "bnn_bandit_rows_group", "bnn_bandit_act_group", "bnn_bandit_replay_group", "bnn_mlp_group_fwd", "bnn_mlp_group_train",
+    "bnn_bbb_group_workspace_bytes", "bnn_bbb_group_fwd", "bnn_bbb_group_train",
     "bnn_dense_fwd", "bnn_dense_plan", "bnn_dropout_mask",
     "bnn_dense_loss", "bnn_dense_bwd", "bnn_sgd_step",
 )
@@ -275,6 +276,28 @@ class MlpGroupArgs(C.Structure):
                 ("agents_host", C.c_void_p), ("agents", C.c_void_p), ("agents_bytes", C.c_int64)]
 
 
+BBB_GROUP_MAX_SAMPLES = 8
+
+
+class BbbGroupAgent(C.Structure):
+    """bnn_bbb_group_agent (include/bnn_hip.h F7): one agent's pointers, its epsilon key and its decision rule"""
+    _fields_ = [("param", C.c_void_p * 12), ("exp_avg", C.c_void_p * 12), ("exp_avg_sq", C.c_void_p * 12), ("step", C.c_void_p),
+                ("lr", C.c_void_p), ("slab", C.c_void_p), ("targets", C.c_void_p), ("n_batches", C.c_void_p),
+                ("loss_info", C.c_void_p), ("rows", C.c_void_p), ("outputs", C.c_void_p), ("sample_counter", C.c_void_p),
+                ("workspace", C.c_void_p), ("eps_seed", C.c_uint64), ("eps_mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BbbGroupArgs(C.Structure):
+    """bnn_bbb_group_args (include/bnn_hip.h F7): the shared shape, prior, Adam's hyperparameters and the KL weights, the
+    agent blocks host + device"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_agents", C.c_int32), ("in_features", C.c_int32), ("hidden", C.c_int32),
+                ("out_features", C.c_int32), ("batch", C.c_int32), ("max_batches", C.c_int32), ("n_rows", C.c_int32),
+                ("n_samples", C.c_int32), ("prior", Prior),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("beta", C.c_float * MLP_GROUP_MAX_BATCHES), ("workspace_bytes", C.c_int64),
+                ("agents_host", C.c_void_p), ("agents", C.c_void_p), ("agents_bytes", C.c_int64)]
+
+
 class DenseFwdArgs(C.Structure):
     """bnn_dense_fwd_args (include/bnn_hip.h): one nn.Linear of MLP_Dropout for S MC-dropout samples"""
     _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("batch", C.c_int32), ("in_features", C.c_int32),
@@ -448,6 +471,11 @@ def _load_real():
     for name in ("bnn_mlp_group_fwd", "bnn_mlp_group_train"):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(MlpGroupArgs), C.c_void_p]
+    lib.bnn_bbb_group_workspace_bytes.restype = C.c_size_t
+    lib.bnn_bbb_group_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+    for name in ("bnn_bbb_group_fwd", "bnn_bbb_group_train"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(BbbGroupArgs), C.c_void_p]
     lib.bnn_dense_fwd.restype = C.c_int
     lib.bnn_dense_fwd.argtypes = [C.POINTER(DenseFwdArgs), C.c_void_p]
     lib.bnn_dense_plan.restype = C.c_int

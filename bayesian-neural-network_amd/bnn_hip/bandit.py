@@ -592,6 +592,290 @@ class GreedyAgentView:
         return self.group.actions[self.g, :t].cpu().numpy(), self.group.rewards[self.g, :t].cpu().numpy()
 
 
+# ---------------------------------------------------------------------------------------------------- F7 BNN agents
+def _per_agent(value, G: int, name: str) -> list:
+    """`value` as a list of G: one value for all agents, or one per agent."""
+    if isinstance(value, (str, bytes)) or not hasattr(value, "__len__"):
+        return [value] * G
+    if len(value) != G:
+        raise BnnHipError(f"BNNBanditGroup: {len(value)} {name} for {G} seeds (one value, or one per agent)")
+    return list(value)
+
+
+class BNNBanditGroup:
+    """G independent BNN_Bandit agents (bandits.py:17-54: a Bayes-by-Backprop network in-(hidden)-(hidden)-1 trained with
+    Adam on sample_elbo, Thompson-sampling decisions) advanced together on the device.  One update of the whole group is
+    six launches whatever G (include/bnn_hip.h F7), one workgroup per agent in each:
+
+        bnn_bandit_rows_group -> bnn_bbb_group_fwd -> bnn_bandit_act_group -> bnn_bandit_replay_group (2)
+        -> bnn_bbb_group_train (all nb minibatch steps of every agent)
+
+    captured as one hipGraph (`capture=True`), kept as a recorded launch list (`"calls"`) or launched eagerly (`False`); the
+    host never reads anything back.  The kernels are exact fp32 whatever bnn_hip.set_math says.
+
+    G = len(seeds).  Agent g builds networks.BayesianNetwork exactly as BNN_Bandit.init_net does, in order under torch's RNG
+    (a group of one after torch.manual_seed(k) starts where a BNNBandit built after the same call starts), with a capturable
+    FusedAdam and StepLR(step_size=5000, gamma=0.5).  Its parameters and Adam's moments are views into the group's storage:
+    `group[g].net` is a real network whose tensors the kernels update.  Per agent: the bandit's Philox stream (seeds[g]), the
+    key of the network's epsilon stream (eps_seeds[g]; by default the global seed + g) with its own MC-sample counter starting
+    at 0 (a sampled decision takes n_samples indices, then every minibatch n_samples: BNNBandit's sequence), epsilon, the
+    decision rule (`policy`: "thompson" or "mean", as BNNBandit's) and the learning rate (bandit_params['lr']: one value or
+    G).  n_samples, the prior and the shapes are the launch's: one for the group.
+    update(mushroom) and run(indices) give every agent the same context, as main.py does; update() without an index lets each
+    agent draw its context from its own stream.  `group[g]` is agent g's view (the BNNBandit read surface); every read
+    synchronises."""
+
+    def __init__(self, label, bandit_params, x, y, *, seeds, eps_seeds=None, epsilons=None, policy="thompson",
+                 rewards: RewardTable = MUSHROOM, max_steps: int = 50000, local_reparam: bool = False, capture=True):
+        p = bandit_params
+        if state.shard_samples:
+            raise BnnHipError("BNNBanditGroup: sample sharding is not supported (one device runs the whole loop)")
+        if local_reparam or p.get("local_reparam", False):
+            raise BnnHipError("BNNBanditGroup: local reparameterisation is not supported (its activation noise needs a "
+                              "kernel of its own); BNNBandit(local_reparam=True, policy='mean') runs such a network")
+        if p["mode"] != "regression":
+            raise BnnHipError("BNNBanditGroup: the bandit's network regresses the reward (mode='regression')")
+        if not (capture is True or capture is False or capture == "calls"):
+            raise BnnHipError(f"BNNBanditGroup: capture must be True, 'calls' or False, got {capture!r}")
+        self.label = label
+        self.buffer_size, self.batch_size = int(p["buffer_size"]), int(p["batch_size"])
+        self.num_batches, self.hidden, self.n_samples = int(p["num_batches"]), int(p["hidden_units"]), int(p["n_samples"])
+        self.max_steps = int(max_steps)
+        if self.batch_size < 1 or self.buffer_size % self.batch_size:
+            raise BnnHipError("BNNBanditGroup: buffer_size must be a multiple of batch_size (the reference's last minibatch "
+                              "is short)")
+        if not hasattr(seeds, "__len__") or len(seeds) < 1:
+            raise BnnHipError("BNNBanditGroup: seeds must be a non-empty list (one agent per seed)")
+        self.G = len(seeds)
+        self.seeds = [int(v) for v in seeds]
+        if eps_seeds is not None and not hasattr(eps_seeds, "__len__"):
+            raise BnnHipError("BNNBanditGroup: eps_seeds must be a list, one epsilon key per agent")
+        self.eps_seeds = ([state.seed + g for g in range(self.G)] if eps_seeds is None
+                          else [int(v) for v in _per_agent(eps_seeds, self.G, "eps_seeds")])
+        self.epsilons = [float(e) for e in _per_agent(p["epsilon"] if epsilons is None else epsilons, self.G, "epsilons")]
+        if any(not 0.0 <= e <= 1.0 for e in self.epsilons):                      # NaN fails the comparison
+            raise BnnHipError(f"BNNBanditGroup: epsilons must lie in [0, 1], got {self.epsilons!r}")
+        self.policies = _per_agent(policy, self.G, "policies")
+        if any(q not in ("mean", "thompson") for q in self.policies):
+            raise BnnHipError(f"BNNBanditGroup: policy must be 'mean' or 'thompson', got {policy!r}")
+        self.lrs = [float(v) for v in _per_agent(p["lr"], self.G, "learning rates")]
+        tab = np.asarray(rewards.rewards, dtype=np.float32)
+        if tab.ndim != 3 or tab.shape[2] != 3 or tab.shape[1] < 2 or len(rewards.oracle) != tab.shape[0]:
+            raise BnnHipError("BNNBanditGroup: rewards must be [K][A][(hi, lo, thr)] with A >= 2 and K oracle values")
+        self.K, self.A = tab.shape[0], tab.shape[1]
+        xh, yh = np.asarray(x, dtype=np.float32), np.asarray(y).astype(np.int64)
+        if xh.ndim != 2 or yh.shape != (xh.shape[0],) or yh.min() < 0 or yh.max() >= self.K:
+            raise BnnHipError("BNNBanditGroup: x must be [N, d] and y [N] labels in [0, K)")
+        self.N, self.d = xh.shape
+        W, H, S = self.d + self.A, self.hidden, self.n_samples
+        nbm = self.buffer_size // self.batch_size
+        if (W > L.MLP_GROUP_MAX_IN or not 1 <= H <= L.MLP_GROUP_MAX_HIDDEN or self.batch_size > L.MLP_GROUP_MAX_BATCH
+                or nbm > L.MLP_GROUP_MAX_BATCHES or self.A > min(L.BANDIT_MAX_ACTIONS, L.MLP_GROUP_MAX_BATCH)
+                or not 0 < self.buffer_size <= L.BANDIT_MAX_BUFFER or self.G > L.MLP_GROUP_MAX_AGENTS or self.max_steps < 1
+                or not 1 <= S <= L.BBB_GROUP_MAX_SAMPLES):
+            raise BnnHipError(f"BNNBanditGroup: beyond the kernels' limits (input {W} <= {L.MLP_GROUP_MAX_IN}, hidden <= "
+                              f"{L.MLP_GROUP_MAX_HIDDEN}, batch <= {L.MLP_GROUP_MAX_BATCH}, buffer / batch <= "
+                              f"{L.MLP_GROUP_MAX_BATCHES}, buffer <= {L.BANDIT_MAX_BUFFER}, agents <= {L.MLP_GROUP_MAX_AGENTS}, "
+                              f"1 <= n_samples <= {L.BBB_GROUP_MAX_SAMPLES})")
+
+        import networks
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.x = torch.from_numpy(xh).to(dev).contiguous()
+        self.y = torch.from_numpy(yh).to(dev)
+        self.table = torch.from_numpy(tab).to(dev)
+        self.oracle = torch.tensor(rewards.oracle, dtype=torch.float32, device=dev)
+
+        # bandits.py:23-37, agent by agent; the parameters and Adam's moments become views of one [G, P] tensor each
+        model_params = {'input_shape': W, 'classes': 1, 'batch_size': self.batch_size, 'hidden_units': H, 'mode': p['mode'],
+                        'mixture_prior': p['mixture_prior'], 'mu_init': p['mu_init'], 'rho_init': p['rho_init'],
+                        'prior_init': p['prior_init'], 'local_reparam': False}
+        G, T, B = self.G, self.max_steps, self.buffer_size
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        self.nets = [networks.BayesianNetwork(model_params) for _ in range(G)]
+        P = sum(q.numel() for q in self.nets[0].parameters())
+        self.param_store, self.exp_avg, self.exp_avg_sq = torch.zeros((G, P), **f32), torch.zeros((G, P), **f32), \
+            torch.zeros((G, P), **f32)
+        self.prior = self.nets[0].l1._prior_spec
+        self.optimisers, self.schedulers = [], []
+        for g, net in enumerate(self.nets):
+            off = 0
+            for q in net.parameters():
+                n = q.numel()
+                view = self.param_store[g, off:off + n].view(q.shape)
+                view.copy_(q.data)
+                q.data = view
+                off += n
+            opt = FusedAdam(net.parameters(), lr=self.lrs[g], capturable=True)
+            off = 0
+            for q in net.parameters():                                            # Adam's state, as its first step makes it
+                n = q.numel()
+                st = opt.state[q]
+                st["step"] = 0
+                st["exp_avg"] = self.exp_avg[g, off:off + n].view(q.shape)
+                st["exp_avg_sq"] = self.exp_avg_sq[g, off:off + n].view(q.shape)
+                off += n
+            self.optimisers.append(opt)
+            self.schedulers.append(torch.optim.lr_scheduler.StepLR(opt, step_size=5000, gamma=0.5))
+
+        # device state, [G, ...] with one contiguous row per agent
+        self.step_word = torch.zeros((G, 1), **i32)
+        self.cur_index = torch.zeros((G, 1), **i32)
+        self.indices = torch.full((T,), -1, dtype=torch.int64, device=dev)       # shared: -1 = each agent draws its own
+        self.actions = torch.zeros((G, T), dtype=torch.int64, device=dev)
+        self.rewards = torch.zeros((G, T), **f32)
+        self.regrets = torch.zeros((G, T + 1), dtype=torch.float64, device=dev)
+        self._counts = torch.zeros((G, self.K, self.A), dtype=torch.int64, device=dev)
+        self.ring_index, self.ring_action, self.ring_reward = torch.zeros((G, B), **i32), torch.zeros((G, B), **i32), \
+            torch.zeros((G, B), **f32)
+        self.perm = torch.zeros((G, B), **i32)
+        self.nb_slab = nbm
+        self.slab = torch.zeros((G, nbm, self.batch_size, W), **f32)
+        self.targets = torch.zeros((G, nbm, self.batch_size), **f32)
+        self.n_batches_word = torch.zeros((G, 1), **i32)
+        self.loss = torch.zeros((G, 4), **f32)                                   # (loss, log_p, log_q, nll) per agent
+        self.rows = torch.zeros((G, self.A, W), **f32)
+        self.outputs = torch.zeros((G, S, self.A), **f32)
+        self.sample_counter = torch.zeros((G, 1), **i32)
+        self.workspace = torch.zeros((G, ops.bbb_group_workspace_bytes(W, H) // 4), **f32)
+        self.t = 0
+
+        act, rep, bbb = [], [], []
+        for g in range(G):
+            thompson = self.policies[g] == "thompson"
+            act.append(ops.bandit_act_args(
+                x=self.x, labels=self.y, rewards=self.table, oracle=self.oracle, outputs=self.outputs[g], n_samples=S,
+                output_sample_stride=self.A if thompson else 0, step=self.step_word[g], cur_index=self.cur_index[g],
+                rows=self.rows[g], actions=self.actions[g], reward_out=self.rewards[g], regrets=self.regrets[g],
+                counts=self._counts[g], ring_index=self.ring_index[g], ring_action=self.ring_action[g],
+                ring_reward=self.ring_reward[g], epsilon=self.epsilons[g], seed=self.seeds[g], indices=self.indices,
+                sample_counter=self.sample_counter[g] if thompson else None, sample_counter_inc=S if thompson else 0))
+            rep.append(ops.bandit_replay_args(
+                x=self.x, step=self.step_word[g], ring_index=self.ring_index[g], ring_action=self.ring_action[g],
+                ring_reward=self.ring_reward[g], workspace=self.perm[g], slab=self.slab[g], targets=self.targets[g],
+                batch_size=self.batch_size, n_actions=self.A, seed=self.seeds[g], n_batches=self.n_batches_word[g]))
+            opt = self.optimisers[g]
+            qs = list(self.nets[g].parameters())
+            step_dev, lr_dev, _, _ = opt._group_dev(0, opt.param_groups[0], dev)
+            bbb.append(ops.bbb_group_agent(
+                params=[q.detach() for q in qs], exp_avg=[opt.state[q]["exp_avg"] for q in qs],
+                exp_avg_sq=[opt.state[q]["exp_avg_sq"] for q in qs], step=step_dev, lr=lr_dev, slab=self.slab[g],
+                targets=self.targets[g], n_batches=self.n_batches_word[g], loss_info=self.loss[g], rows=self.rows[g],
+                outputs=self.outputs[g], sample_counter=self.sample_counter[g], workspace=self.workspace[g],
+                eps_seed=self.eps_seeds[g], eps_mode=L.EPS_PHILOX if thompson else L.EPS_ZERO))
+        grp = self.optimisers[0].param_groups[0]
+        self.g_act = ops.bandit_group_args(act, dev)
+        self.g_replay = ops.bandit_group_args(rep, dev)
+        shape = dict(in_features=W, hidden=H, n_samples=S, device=dev, prior=self.prior, betas=grp["betas"], eps=grp["eps"],
+                     weight_decay=grp["weight_decay"])
+        self.g_fwd = ops.bbb_group_args(bbb, n_rows=self.A, **shape)
+        self.g_train = ops.bbb_group_args(bbb, batch=self.batch_size, max_batches=nbm,
+                                          kl_weights=[beta(j, self.num_batches) for j in range(nbm)], **shape)
+
+        # warm-up: every launch once, eagerly (this validates every block), recorded for capture="calls"; the training
+        # launch runs with nb = 0 and touches nothing.  Then the words the warm-up moved are reset, and the update is captured.
+        self.capture = capture
+        self.graph = self.calls = None
+        with L.recording() as calls:
+            self._enqueue(train=False)
+        recorded = list(calls)
+        self.n_batches_word.zero_()
+        with L.recording() as calls:
+            ops.bbb_group_train(self.g_train)
+        recorded += list(calls)
+        if capture == "calls":
+            self.calls = recorded
+        torch.cuda.synchronize()
+        self.step_word.zero_()
+        self._counts.zero_()
+        self.regrets.zero_()
+        self.sample_counter.zero_()
+        if capture is True:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph, stream=side):
+                    self._enqueue()
+            torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+
+    def _enqueue(self, train: bool = True):
+        """The six launches of one group update, on the current stream."""
+        ops.bandit_rows_group(self.g_act)
+        ops.bbb_group_fwd(self.g_fwd)
+        ops.bandit_act_group(self.g_act)
+        ops.bandit_replay_group(self.g_replay)
+        if train:
+            ops.bbb_group_train(self.g_train)
+
+    def _step(self):
+        if state.shard_samples:
+            raise BnnHipError("BNNBanditGroup: sample sharding is not supported")
+        for opt in self.optimisers:
+            opt.sync_lr()                        # what StepLR changed, into the device words (a fill, no host read)
+        if self.graph is not None:
+            self.graph.replay()
+        elif self.calls is not None:
+            BNNBandit._run_calls(self.calls)
+        else:
+            self._enqueue()
+        for s in self.schedulers:
+            s.step()
+        self.t += 1
+
+    def update(self, mushroom: Optional[int] = None):
+        """One bandit step of every agent (base_bandit.py:75-88 + main.py:103's scheduler.step()) on context `mushroom`,
+        the same for all agents, or, when None, on a context each agent draws from its own stream.  Does not synchronise."""
+        if self.t >= self.max_steps:
+            raise BnnHipError(f"BNNBanditGroup: max_steps={self.max_steps} reached")
+        if mushroom is not None:
+            i = int(mushroom)
+            if not 0 <= i < self.N:
+                raise BnnHipError(f"BNNBanditGroup: context index {i} outside [0, {self.N})")
+            self.indices[self.t].fill_(i)
+        self._step()
+
+    def run(self, indices: Sequence[int]):
+        """update(i) for every i of `indices`, the sequence uploaded once."""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if self.t + idx.size > self.max_steps:
+            raise BnnHipError(f"BNNBanditGroup: {idx.size} steps from step {self.t} pass max_steps={self.max_steps}")
+        if idx.size and (idx.min() < 0 or idx.max() >= self.N):
+            raise BnnHipError(f"BNNBanditGroup: context indices must lie in [0, {self.N})")
+        if idx.size:
+            self._staged = torch.from_numpy(idx).pin_memory()    # kept until the next run(): the copy does not wait for the host
+            self.indices[self.t:self.t + idx.size].copy_(self._staged, non_blocking=True)
+        for _ in range(idx.size):
+            self._step()
+
+    def __len__(self):
+        return self.G
+
+    def __getitem__(self, g: int) -> "BNNAgentView":
+        if not -self.G <= g < self.G:
+            raise IndexError(g)
+        return BNNAgentView(self, g % self.G)
+
+
+class BNNAgentView(GreedyAgentView):
+    """Agent g of a BNNBanditGroup with BNNBandit's read surface.  Every read synchronises with the device once."""
+
+    def __init__(self, group: BNNBanditGroup, g: int):
+        super().__init__(group, g)
+        self.eps_seed, self.policy, self.n_samples = group.eps_seeds[g], group.policies[g], group.n_samples
+
+    @property
+    def loss_info(self):
+        """(loss, mean log_p, mean log_q, mean nll) of the last minibatch of the last update (sample_elbo's tuple, as
+        floats), or None before the first update."""
+        return tuple(self.group.loss[self.g].tolist()) if self.group.t else None
+
+    @property
+    def sample_counter(self) -> int:
+        """The next unused MC-sample index of the agent's epsilon stream."""
+        return int(self.group.sample_counter[self.g].item()) & 0xFFFFFFFF
+
+
 class GreedyBandit(GreedyAgentView):
     """Greedy_Bandit (bandits.py:59-85) on the device: a GreedyBanditGroup of one, with the reference's constructor arguments
     (epsilon from bandit_params) -- a drop-in where main.py:91-93 builds one.  update() / run() as the group's."""

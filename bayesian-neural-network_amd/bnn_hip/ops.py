@@ -1365,6 +1365,105 @@ def mlp_group_train(a: L.MlpGroupArgs):
     L.check(L.load().bnn_mlp_group_train(C.byref(a), _stream()), "bnn_mlp_group_train")
 
 
+# ---------------------------------------------------------------------------------------------------------------- F7 groups
+def bbb_group_workspace_bytes(in_features: int, hidden: int) -> int:
+    """bnn_bbb_group_workspace_bytes: bytes of one agent's workspace (0 outside the limits)."""
+    return int(L.load().bnn_bbb_group_workspace_bytes(int(in_features), int(hidden)))
+
+
+def bbb_group_agent(*, params: Sequence[torch.Tensor], workspace: torch.Tensor, eps_seed: int, exp_avg=None, exp_avg_sq=None,
+                    step=None, lr=None, slab=None, targets=None, n_batches=None, loss_info=None, rows=None, outputs=None,
+                    sample_counter=None, eps_mode: int = L.EPS_PHILOX) -> L.BbbGroupAgent:
+    """One agent's block of bnn_bbb_group_*: params = the twelve tensors of networks.BayesianNetwork.parameters()
+    ((weight_mu, weight_rho, bias_mu, bias_rho) of l1, l2, l3; fp32), Adam's moments in the same order, step (int32 word), lr
+    (fp32 word), slab [max_batches, batch, in], targets [max_batches * batch], n_batches (int32 word), loss_info (fp32 [4]),
+    sample_counter (int32 word) for training; rows [n_rows, in], outputs and eps_mode (L.EPS_PHILOX: a draw per sample,
+    L.EPS_ZERO: w = mu) for the decision forward; workspace (fp32, bbb_group_workspace_bytes) and eps_seed for both."""
+    a = L.BbbGroupAgent()
+    keep = []
+    a._named = dict(params=list(params), slab=slab, targets=targets, rows=rows, outputs=outputs, workspace=workspace)
+    if len(params) != 12:
+        raise BnnHipError("bbb_group_agent: twelve parameter tensors ((weight_mu, weight_rho, bias_mu, bias_rho) x 3 layers)")
+    for f, ts in (("param", params), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+        if ts is None:
+            continue
+        if len(ts) != 12:
+            raise BnnHipError(f"bbb_group_agent: twelve {f} tensors")
+        arr = getattr(a, f)
+        for i, t in enumerate(ts):
+            keep.append(_typed(t, torch.float32, f"{f}[{i}]", params[i].numel()))
+            arr[i] = t.data_ptr()
+    for f, t, dt in (("step", step, torch.int32), ("lr", lr, torch.float32), ("slab", slab, torch.float32),
+                     ("targets", targets, torch.float32), ("n_batches", n_batches, torch.int32),
+                     ("loss_info", loss_info, torch.float32), ("rows", rows, torch.float32), ("outputs", outputs, torch.float32),
+                     ("sample_counter", sample_counter, torch.int32), ("workspace", workspace, torch.float32)):
+        if t is not None:
+            keep.append(_typed(t, dt, f))
+            setattr(a, f, t.data_ptr())
+    if loss_info is not None and loss_info.numel() != 4:
+        raise BnnHipError("bbb_group_agent: loss_info must have 4 elements (loss, log_p, log_q, nll)")
+    if eps_mode not in (L.EPS_PHILOX, L.EPS_ZERO):
+        raise BnnHipError("bbb_group_agent: eps_mode must be EPS_PHILOX or EPS_ZERO")
+    a.eps_seed, a.eps_mode = int(eps_seed) & 0xFFFFFFFFFFFFFFFF, int(eps_mode)
+    a._keep = keep
+    return a
+
+
+def bbb_group_args(agents: Sequence, *, in_features: int, hidden: int, n_samples: int, device, prior: Optional[PriorSpec] = None,
+                   batch: int = 0, max_batches: int = 0, n_rows: int = 0, kl_weights: Sequence[float] = (),
+                   betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0) -> L.BbbGroupArgs:
+    """The argument block of bnn_bbb_group_fwd / _train over G agent blocks (bbb_group_agent), with the device copy of the
+    blocks made once here.  The training form (max_batches > 0) needs slab [max_batches, batch, in], the prior and
+    kl_weights[j], the KL weight of minibatch j < max_batches (rounded to fp32 here); the forward form (n_rows > 0) rows
+    [n_rows, in] and outputs of n_samples * n_rows elements (n_rows for an EPS_ZERO agent)."""
+    if not agents:
+        raise BnnHipError("bbb_group_args: at least one agent")
+    I, H, S = int(in_features), int(hidden), int(n_samples)
+    shapes = (H * I, H * I, H, H, H * H, H * H, H, H, H, H, 1, 1)
+    if int(max_batches) > L.MLP_GROUP_MAX_BATCHES or len(kl_weights) > L.MLP_GROUP_MAX_BATCHES:
+        raise BnnHipError(f"bbb_group_args: at most {L.MLP_GROUP_MAX_BATCHES} minibatches per update")
+    if int(max_batches) and len(kl_weights) < int(max_batches):
+        raise BnnHipError("bbb_group_args: one KL weight per minibatch of the slab")
+    need = bbb_group_workspace_bytes(I, H)
+    ws_bytes = min(ag._named["workspace"].numel() * 4 for ag in agents)
+    for ag in agents:
+        named = ag._named
+        if tuple(t.numel() for t in named["params"]) != shapes:
+            raise BnnHipError(f"bbb_group_args: the parameters must be an {I}-{H}-{H}-1 BayesianNetwork's")
+        if int(max_batches) and (named["slab"] is None or named["slab"].numel() != int(max_batches) * int(batch) * I or
+                                          named["targets"] is None or named["targets"].numel() != int(max_batches) * int(batch)):
+            raise BnnHipError("bbb_group_args: slab must be [max_batches, batch, in] and targets [max_batches, batch]")
+        if int(n_rows):
+            want = int(n_rows) * (1 if ag.eps_mode == L.EPS_ZERO else S)
+            if named["rows"] is None or named["rows"].numel() != int(n_rows) * I or named["outputs"] is None or \
+                    named["outputs"].numel() < want:
+                raise BnnHipError("bbb_group_args: rows must be [n_rows, in] and outputs [n_samples, n_rows]")
+    host = (L.BbbGroupAgent * len(agents))(*agents)
+    dev = _device_copy(host, device)
+    a = L.BbbGroupArgs()
+    a.struct_bytes = C.sizeof(L.BbbGroupArgs)
+    a.n_agents, a.in_features, a.hidden, a.out_features = len(agents), I, H, 1
+    a.batch, a.max_batches, a.n_rows, a.n_samples = int(batch), int(max_batches), int(n_rows), S
+    a.prior = (prior if prior is not None else PriorSpec()).c()
+    a.beta1, a.beta2, a.eps, a.weight_decay = float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
+    for j, b in enumerate(kl_weights):
+        a.beta[j] = float(b)
+    a.workspace_bytes = ws_bytes
+    a.agents_host, a.agents, a.agents_bytes = C.addressof(host), dev.data_ptr(), dev.numel()
+    a._keep = (host, dev, [ag._keep for ag in agents])
+    return a
+
+
+def bbb_group_fwd(a: L.BbbGroupArgs):
+    """bnn_bbb_group_fwd: every agent's forward of its rows under its posterior draws (or w = mu), one launch."""
+    L.check(L.load().bnn_bbb_group_fwd(C.byref(a), _stream()), "bnn_bbb_group_fwd")
+
+
+def bbb_group_train(a: L.BbbGroupArgs):
+    """bnn_bbb_group_train: every agent's nb minibatch steps (BBB forward, ELBO, backward through mu and rho, Adam), one launch."""
+    L.check(L.load().bnn_bbb_group_train(C.byref(a), _stream()), "bnn_bbb_group_train")
+
+
 def dropout_params(p: float) -> tuple:
     """(thr, scale) of the kind-3 dropout map (include/bnn_hip.h) for a drop probability p in [0, 1), in fp64 as the
     library forms them.  Raises BnnHipError outside that range."""

@@ -981,6 +981,88 @@ int bnn_mlp_group_fwd(const bnn_mlp_group_args* args, void* stream);
 int bnn_mlp_group_train(const bnn_mlp_group_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F7  groups of Thompson-sampling BNN bandits — BNN_Bandit (reinforcement_learning/bandits.py:17-54: a Bayes-by-Backprop
+ * network in-(hidden)-(hidden)-1 of BayesianLinear layers, networks.py:48-88, trained by torch.optim.Adam on sample_elbo,
+ * networks.py:192-209) for G independent agents, each update a fixed number of launches whatever G:
+ *     bnn_bandit_rows_group -> bnn_bbb_group_fwd -> bnn_bandit_act_group -> bnn_bandit_replay_group (2) -> bnn_bbb_group_train
+ * One workgroup per agent in both entries; agents never wait on each other (no grid-wide barrier, no polled counter).
+ *
+ * bnn_bbb_group_fwd — the decision forward.  For agent g and its n_rows rows [n_rows, in] (what bnn_bandit_rows wrote):
+ *   eps_mode == BNN_EPS_PHILOX: outputs[s * n_rows + r] = net_g(rows[r]) under posterior draw s, s < n_samples: one weight
+ *     draw w = mu + log1p(exp(rho)) * eps shared by all rows, eps from the map at the top with GLOBAL MC-sample index
+ *     *sample_counter + s and the agent's own eps_seed as key.  The counter is read, not advanced (bnn_bandit_act does that
+ *     through sample_counter_inc).
+ *   eps_mode == BNN_EPS_ZERO: the one deterministic forward w = mu, outputs[r] (bnn_bandit_act reads it with stride 0);
+ *     sample_counter is not read.
+ * bnn_bbb_group_train — the training half of one update (base_bandit.py:86-88 with bandits.py:39-51) for every agent in
+ *   ONE launch: nb = min(*n_batches, max_batches) (the word bnn_bandit_replay writes), c = *sample_counter; for
+ *   j = 0 .. nb - 1 on slab[j] [batch, in] / targets[j] [batch]:
+ *     for s < n_samples, GLOBAL MC-sample index c + j * n_samples + s: w = mu + log1p(exp(rho)) * eps for the weight
+ *       (kind 0) and bias (kind 1) of layers 0, 1, 2; forward Linear-ReLU-Linear-ReLU-Linear;
+ *       log_q = sum log N(w; mu, sigma), log_p = sum log prior(w) (BNN_PRIOR_GAUSS / BNN_PRIOR_MIXTURE, one prior for the
+ *       launch); nll_s = -sum_b log N(y_b; z_b, 1), element by element;
+ *     loss = beta[j] (mean_s log_q - mean_s log_p) + mean_s nll_s; beta[] is a host-made table in the argument block:
+ *       bandits.py:44's value formed in fp64 and rounded once to fp32 (what train.GraphedTrainStep.step hands its device
+ *       word), beta[j] for j < max_batches;
+ *     the gradient of loss with respect to the twelve tensors, with the log_q terms in closed form as F1 has them
+ *       (g_mu = sum_s t_s, g_rho = (sum_s t_s eps_s - beta / sigma) sigmoid(rho), t_s = (d nll_s / dw - beta d log_p / dw) / S);
+ *     Adam (F2's arithmetic): t = *step + j + 1, lr = *lr (device words), bias corrections in fp64; the next minibatch
+ *       reads the updated parameters.
+ *   At the end *step += nb, *sample_counter += nb * n_samples and loss_info[0..3] = (loss, mean log_p, mean log_q,
+ *   mean nll) of minibatch nb - 1 (sample_elbo's tuple: the reference's loss_info).  nb == 0 writes nothing.
+ * Math: exact fp32 (fp32 FMA) in every math mode, as F6.  Every sum (GEMM elements: one fma chain, k ascending; log_q, log_p,
+ *   nll, the bias gradients' column sums) runs in one fixed order, no float atomics: an agent's bits do not depend on G, on
+ *   its place in the group or on graph replay against eager launches.
+ * Workspace: per agent, bnn_bbb_group_workspace_bytes(in, hidden) bytes of global memory (16-byte aligned), shared by the
+ *   two entries: the current draw's weights (layers 0 and 1 transposed, layer 1 also as stored), its eps, and the two
+ *   gradient accumulators sum_s t_s, sum_s t_s eps_s.  Contents between launches are scratch.
+ * Limits: F6's (in, hidden, out == 1, batch and n_rows, max_batches, n_agents) and 1 <= n_samples <=
+ *   BNN_BBB_GROUP_MAX_SAMPLES; else BNN_ERR_SHAPE.  prior.kind outside bnn_prior_kind, or an agent's eps_mode other than
+ *   BNN_EPS_PHILOX / BNN_EPS_ZERO: BNN_ERR_ENUM.  workspace NULL or workspace_bytes below the query: BNN_ERR_WORKSPACE.
+ * Agent blocks are passed host + device as in F6.  param / exp_avg / exp_avg_sq in networks.BayesianNetwork.parameters()
+ *   order: (weight_mu [out, in], weight_rho, bias_mu [out], bias_rho) of l1, l2, l3.  fwd reads param, rows, outputs,
+ *   sample_counter (BNN_EPS_PHILOX), workspace, eps_seed, eps_mode; train everything but rows / outputs / eps_mode.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_BBB_GROUP_MAX_SAMPLES 8
+typedef struct bnn_bbb_group_agent {
+  float* param[12];               /* (weight_mu, weight_rho, bias_mu, bias_rho) x (l1, l2, l3) */
+  float* exp_avg[12];             /* train: Adam's moments, same shapes */
+  float* exp_avg_sq[12];
+  uint32_t* step;                 /* train: Adam's device step word */
+  const float* lr;                /* train: device learning rate */
+  const float* slab;              /* train: [max_batches, batch, in] */
+  const float* targets;           /* train: [max_batches, batch] */
+  const int32_t* n_batches;       /* train: device word nb */
+  float* loss_info;               /* train: [4] (loss, mean log_p, mean log_q, mean nll) */
+  const float* rows;              /* fwd: [n_rows, in] */
+  float* outputs;                 /* fwd: [n_samples, n_rows] (BNN_EPS_PHILOX) or [n_rows] (BNN_EPS_ZERO) */
+  uint32_t* sample_counter;       /* device word: next unused MC-sample index of this agent */
+  float* workspace;               /* bnn_bbb_group_workspace_bytes(in, hidden) bytes */
+  uint64_t eps_seed;              /* the agent's key of the epsilon map */
+  int32_t eps_mode;               /* fwd: BNN_EPS_PHILOX (a draw per sample) or BNN_EPS_ZERO (w = mu) */
+  int32_t reserved;
+} bnn_bbb_group_agent;
+typedef struct bnn_bbb_group_args {
+  uint32_t struct_bytes;
+  int32_t n_agents;               /* G, 1 .. BNN_MLP_GROUP_MAX_AGENTS */
+  int32_t in_features, hidden, out_features;
+  int32_t batch;                  /* train: minibatch rows */
+  int32_t max_batches;            /* train: slab capacity */
+  int32_t n_rows;                 /* fwd: rows per agent */
+  int32_t n_samples;              /* S, 1 .. BNN_BBB_GROUP_MAX_SAMPLES */
+  bnn_prior prior;                /* train */
+  double beta1, beta2, eps, weight_decay;   /* train: Adam */
+  float beta[BNN_MLP_GROUP_MAX_BATCHES];    /* train: KL weight of minibatch j */
+  int64_t workspace_bytes;                  /* bytes behind every agent's workspace */
+  const bnn_bbb_group_agent* agents_host;   /* HOST array of G blocks (validated) */
+  const bnn_bbb_group_agent* agents;        /* DEVICE copy (read by the kernel) */
+  int64_t agents_bytes;                     /* bytes of the device copy */
+} bnn_bbb_group_args;
+size_t bnn_bbb_group_workspace_bytes(int32_t in_features, int32_t hidden);   /* 0 outside the limits */
+int bnn_bbb_group_fwd(const bnn_bbb_group_args* args, void* stream);
+int bnn_bbb_group_train(const bnn_bbb_group_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_philox_normal — materialise the on-chip epsilon stream (map at the top) into
  * eps[n_samples, rows, cols]: used by the backward pass to regenerate eps instead of
  * storing it, and by tests to check the frozen counter->element map.
