@@ -32,6 +32,7 @@ EXPORTS = (
     "bnn_bbb_group_workspace_bytes", "bnn_bbb_group_fwd", "bnn_bbb_group_train",
     "bnn_dense_fwd", "bnn_dense_plan", "bnn_dropout_mask",
     "bnn_dense_loss", "bnn_dense_bwd", "bnn_sgd_step",
+    "bnn_epoch_permutation", "bnn_epoch_stage",
 )
 
 
@@ -332,6 +333,27 @@ class SgdArgs(C.Structure):
                 ("weight_decay", C.c_double), ("lr_device", C.c_void_p)]
 
 
+EPOCH_MAX_ROWS = 65536
+EPOCH_MAX_LOSS_COLS = 4
+EPOCH_X_F32, EPOCH_X_U8 = 0, 1
+
+
+class EpochPermArgs(C.Structure):
+    """bnn_epoch_perm_args (include/bnn_hip.h F8)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_rows", C.c_int32), ("seed", C.c_uint64), ("epoch", C.c_void_p),
+                ("order", C.c_void_p)]
+
+
+class EpochStageArgs(C.Structure):
+    """bnn_epoch_stage_args (include/bnn_hip.h F8)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_rows", C.c_int32), ("row_dim", C.c_int32), ("batch_size", C.c_int32),
+                ("num_batches", C.c_int32), ("x_dtype", C.c_int32), ("target_dim", C.c_int32), ("loss_cols", C.c_int32),
+                ("x", C.c_void_p), ("targets", C.c_void_p), ("order", C.c_void_p), ("beta_table", C.c_void_p),
+                ("batch_index", C.c_void_p), ("epoch", C.c_void_p), ("ticket", C.c_void_p), ("x_out", C.c_void_p),
+                ("x_bf16_out", C.c_void_p), ("targets_out", C.c_void_p), ("beta", C.c_void_p),
+                ("loss_src", C.c_void_p * EPOCH_MAX_LOSS_COLS), ("loss_history", C.c_void_p)]
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -489,6 +511,10 @@ def _load_real():
     lib.bnn_dense_bwd.argtypes = [C.POINTER(DenseBwdArgs), C.c_void_p]
     lib.bnn_sgd_step.restype = C.c_int
     lib.bnn_sgd_step.argtypes = [C.POINTER(SgdArgs), C.c_void_p]
+    lib.bnn_epoch_permutation.restype = C.c_int
+    lib.bnn_epoch_permutation.argtypes = [C.POINTER(EpochPermArgs), C.c_void_p]
+    lib.bnn_epoch_stage.restype = C.c_int
+    lib.bnn_epoch_stage.argtypes = [C.POINTER(EpochStageArgs), C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

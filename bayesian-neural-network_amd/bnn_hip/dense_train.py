@@ -202,6 +202,11 @@ class GraphedDenseTrainStep:
         else:
             self.x.copy_(xf.reshape(self.x.shape), non_blocking=True)
             self.y.copy_(y.reshape(self.y.shape), non_blocking=True)
+        return self.replay()
+
+    def replay(self) -> torch.Tensor:
+        """The step on whatever the static buffers (x, y) hold -- step() after its staging; a caller that stages them on
+        the device itself (epoch.EpochRunner) calls this.  Same bookkeeping, same return value."""
         self.opt.sync_lr()
         self._sync_counter()
         if self.graph is not None:

@@ -1621,3 +1621,76 @@ def sgd_step(params, grads, *, lr: float, weight_decay: float = 0.0, lr_device=N
             a.param[j - lo], a.grad[j - lo], a.numel[j - lo] = p.data_ptr(), g.data_ptr(), p.numel()
         a.lr, a.weight_decay, a.lr_device = float(lr), float(weight_decay), _ptr(lr_device)
         L.check(lib.bnn_sgd_step(C.byref(a), _stream()), "bnn_sgd_step")
+
+
+# ---------------------------------------------------------------------------------------------------------------- F8 epochs
+def epoch_perm_args(*, n_rows: int, seed: int, epoch, order) -> L.EpochPermArgs:
+    """The argument block of bnn_epoch_permutation: `epoch` one int32 device word, `order` int32 [n_rows]."""
+    a = L.EpochPermArgs()
+    a.struct_bytes = C.sizeof(L.EpochPermArgs)
+    a.n_rows, a.seed = int(n_rows), int(seed) & 0xFFFFFFFFFFFFFFFF
+    keep = [_typed(epoch, torch.int32, "epoch", 1), _typed(order, torch.int32, "order", int(n_rows))]
+    a.epoch, a.order = (t.data_ptr() for t in keep)
+    a._keep = keep
+    return a
+
+
+def epoch_permutation(a: L.EpochPermArgs):
+    """bnn_epoch_permutation: the positions sorted by (Philox key, position) into `order`, one launch."""
+    L.check(L.load().bnn_epoch_permutation(C.byref(a), _stream()), "bnn_epoch_permutation")
+
+
+def epoch_stage_args(*, x, targets, batch_size: int, num_batches: int, batch_index, epoch, ticket, x_out, targets_out,
+                     order=None, x_bf16_out=None, beta_table=None, beta=None, loss_src=(), loss_history=None) -> L.EpochStageArgs:
+    """The argument block of bnn_epoch_stage (include/bnn_hip.h F8), built once per destination: the launch reads the
+    minibatch number from `batch_index`, so the same block serves every minibatch of every epoch.  x [N, d] float32 or
+    uint8, targets [N] int64 or [N, k] float32; x_out float32 and x_bf16_out bfloat16 of B * d elements, targets_out of B
+    (* k); batch_index / epoch / ticket one int32 word each; loss_src up to 4 float32 device words (views are fine) filed
+    into loss_history [num_batches, len(loss_src)] by the NEXT minibatch's launch."""
+    require_device(x, targets)
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.uint8) or not x.is_contiguous():
+        raise BnnHipError("epoch_stage: x must be a contiguous [N, d] float32 or uint8 tensor")
+    N, d = x.shape
+    B, M = int(batch_size), int(num_batches)
+    if targets.dtype == torch.int64:
+        k = 0
+        _typed(targets, torch.int64, "targets", N)
+    else:
+        if targets.dim() != 2:
+            raise BnnHipError("epoch_stage: float32 targets must be [N, k]")
+        k = int(targets.shape[1])
+        _typed(targets, torch.float32, "targets", N * k)
+    a = L.EpochStageArgs()
+    a.struct_bytes = C.sizeof(L.EpochStageArgs)
+    a.n_rows, a.row_dim, a.batch_size, a.num_batches = N, d, B, M
+    a.x_dtype, a.target_dim = (L.EPOCH_X_U8 if x.dtype == torch.uint8 else L.EPOCH_X_F32), k
+    keep = [x, targets, _typed(batch_index, torch.int32, "batch_index", 1), _typed(epoch, torch.int32, "epoch", 1),
+            _typed(ticket, torch.int32, "ticket", 1), _typed(x_out, torch.float32, "x_out", B * d),
+            _typed(targets_out, targets.dtype, "targets_out", B * max(k, 1))]
+    a.x, a.targets, a.batch_index, a.epoch, a.ticket, a.x_out, a.targets_out = (t.data_ptr() for t in keep)
+    if order is not None:
+        keep.append(_typed(order, torch.int32, "order", N))
+        a.order = order.data_ptr()
+    if x_bf16_out is not None:
+        keep.append(_typed(x_bf16_out, torch.bfloat16, "x_bf16_out", B * d))
+        a.x_bf16_out = x_bf16_out.data_ptr()
+    if beta_table is not None:
+        keep += [_typed(beta_table, torch.float32, "beta_table", M), _typed(beta, torch.float32, "beta", 1)]
+        a.beta_table, a.beta = beta_table.data_ptr(), beta.data_ptr()
+    if loss_history is not None:
+        if not 1 <= len(loss_src) <= L.EPOCH_MAX_LOSS_COLS:
+            raise BnnHipError(f"epoch_stage: 1 to {L.EPOCH_MAX_LOSS_COLS} loss words")
+        a.loss_cols = len(loss_src)
+        for c, w in enumerate(loss_src):
+            keep.append(_typed(w, torch.float32, "loss_src", 1))
+            a.loss_src[c] = w.data_ptr()
+        keep.append(_typed(loss_history, torch.float32, "loss_history", M * len(loss_src)))
+        a.loss_history = loss_history.data_ptr()
+    a._keep = keep
+    return a
+
+
+def epoch_stage(a: L.EpochStageArgs):
+    """bnn_epoch_stage: gather, cast and target copy of minibatch *batch_index, beta lookup, loss filing; advances the
+    minibatch word (and the epoch word after the last minibatch)."""
+    L.check(L.load().bnn_epoch_stage(C.byref(a), _stream()), "bnn_epoch_stage")

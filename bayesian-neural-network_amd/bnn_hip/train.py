@@ -427,6 +427,11 @@ class GraphedTrainStep:
                 self.x16.copy_(x, non_blocking=True)
             self.y.copy_(y, non_blocking=True)
             self.beta.fill_(float(beta))
+        return self.replay()
+
+    def replay(self):
+        """The step on whatever the static buffers (x, x16, y, beta) hold -- step() after its staging; a caller that stages
+        them on the device itself (epoch.EpochRunner) calls this.  Same bookkeeping, same return value."""
         self.opt.sync_lr()
         self._sync_counter()
         self.graph.replay()

@@ -1190,6 +1190,72 @@ typedef struct bnn_sgd_args {
 int bnn_sgd_step(const bnn_sgd_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F8  device-resident training epochs — the data-loader half of the reference's epoch loop (classification/class_task.py:67-79,
+ * regression/reg_task.py:60-74 over DataLoader(shuffle=True, drop_last=True)): the data set stays on the device, the epoch's
+ * permutation is drawn there, and ONE launch per minibatch gathers its rows into a captured training step's static buffers.
+ * The minibatch number j and the epoch number e are device words: the same argument blocks serve every launch.
+ *
+ * bnn_epoch_permutation   order[0 .. N-1] (int32) = the positions p sorted by (key_p, p), with
+ *     key_p = word (p & 3) of Philox4x32-R((p >> 2, e, 2, 1), key = (seed_lo, seed_hi)), R = bnn_philox_rounds(), e = *epoch.
+ *   Counter words 2 and 3 are (2, 1): every eps counter's word 3 is 0, and among the word-3 = 1 streams the bandit's coins use
+ *   (.., 0, 1) and its replay permutation (.., 1, 1), so this stream shares a counter with none.  The result is fixed by this
+ *   definition, not by the algorithm (rank by counting over LDS-staged key tiles; one launch, N <= BNN_EPOCH_MAX_ROWS).
+ *
+ * bnn_epoch_stage   minibatch j = *batch_index of an epoch of M = num_batches minibatches of B = batch_size rows:
+ *     i_r = order[j B + r] (order == NULL: j B + r, the unshuffled loader), r < B;
+ *     x_out[r, :] = x[i_r, :] in fp32: an fp32 source is copied, a uint8 source converted as (float)u / 255.0f (IEEE division:
+ *       torchvision's ToTensor);  x_bf16_out[r, :] (optional) = bf16 of that, round to nearest even, as bnn_stage_inputs_cast;
+ *     targets_out[r] = targets[i_r]: int64 labels (target_dim == 0) or target_dim fp32 values per row;
+ *     *beta = beta_table[j] when beta_table != NULL;
+ *     loss_history[(j - 1) loss_cols + c] = *loss_src[c], c < loss_cols, when loss_history != NULL and j > 0: the loss words the
+ *       training step of minibatch j - 1 left (the caller files row M - 1 after the last step);
+ *     then *batch_index = j + 1, or at j + 1 == M: *batch_index = 0 and *epoch += 1.
+ *   An order entry outside [0, N) reads row j B + r instead.  *ticket must be 0 before the first launch; the launch leaves it 0.
+ *   *batch_index >= M: nothing is written.  Rows are gathered with 16-byte stores when row_dim % 4 == 0 and x, x_out,
+ *   x_bf16_out are aligned to 16 / 16 / 8 bytes (uint8 x: 4), element by element otherwise: the same values either way.
+ * Errors: N outside [1, BNN_EPOCH_MAX_ROWS], B M > N, a non-positive dimension, loss_cols outside [0, BNN_EPOCH_MAX_LOSS_COLS]
+ * (0 with loss_history): BNN_ERR_SHAPE; x_dtype outside bnn_epoch_x_dtype: BNN_ERR_ENUM; x, targets, batch_index, epoch,
+ * ticket, x_out, targets_out (stage) or epoch, order (permutation) NULL, beta NULL with beta_table, a NULL loss_src[c < loss_cols]
+ * with loss_history: BNN_ERR_NULL.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_EPOCH_MAX_ROWS 65536       /* rows of a data set (MNIST: 60 000) */
+#define BNN_EPOCH_MAX_LOSS_COLS 4
+typedef enum bnn_epoch_x_dtype { BNN_EPOCH_X_F32 = 0, BNN_EPOCH_X_U8 = 1 } bnn_epoch_x_dtype;
+typedef struct bnn_epoch_perm_args {
+  uint32_t struct_bytes;
+  int32_t n_rows;                 /* N */
+  uint64_t seed;
+  const uint32_t* epoch;          /* device word e */
+  int32_t* order;                 /* [N] */
+} bnn_epoch_perm_args;
+int bnn_epoch_permutation(const bnn_epoch_perm_args* args, void* stream);
+
+typedef struct bnn_epoch_stage_args {
+  uint32_t struct_bytes;
+  int32_t n_rows;                 /* N */
+  int32_t row_dim;                /* d */
+  int32_t batch_size;             /* B */
+  int32_t num_batches;            /* M, B M <= N */
+  int32_t x_dtype;                /* bnn_epoch_x_dtype */
+  int32_t target_dim;             /* 0: int64 labels; k >= 1: fp32 [N, k] */
+  int32_t loss_cols;              /* 0 .. BNN_EPOCH_MAX_LOSS_COLS */
+  const void* x;                  /* [N, d] fp32 or uint8 */
+  const void* targets;            /* [N] int64 or [N, k] fp32 */
+  const int32_t* order;           /* optional [N] */
+  const float* beta_table;        /* optional [M] */
+  uint32_t* batch_index;          /* device word j */
+  uint32_t* epoch;                /* device word e */
+  uint32_t* ticket;               /* device word, 0 between launches */
+  float* x_out;                   /* [B, d] */
+  void* x_bf16_out;               /* optional bf16 [B, d] */
+  void* targets_out;              /* [B] int64 or [B, k] fp32 */
+  float* beta;                    /* device word (with beta_table) */
+  const float* loss_src[BNN_EPOCH_MAX_LOSS_COLS];   /* device words of the training step (with loss_history) */
+  float* loss_history;            /* optional [M, loss_cols] */
+} bnn_epoch_stage_args;
+int bnn_epoch_stage(const bnn_epoch_stage_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
