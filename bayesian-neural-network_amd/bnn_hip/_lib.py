@@ -33,6 +33,7 @@ EXPORTS = (
     "bnn_dense_fwd", "bnn_dense_plan", "bnn_dropout_mask",
     "bnn_dense_loss", "bnn_dense_bwd", "bnn_sgd_step",
     "bnn_epoch_permutation", "bnn_epoch_stage",
+    "bnn_snr_select_workspace_bytes", "bnn_snr_select", "bnn_prune_codes", "bnn_pruned_fwd", "bnn_prune_sweep_tail",
 )
 
 
@@ -354,6 +355,44 @@ class EpochStageArgs(C.Structure):
                 ("loss_src", C.c_void_p * EPOCH_MAX_LOSS_COLS), ("loss_history", C.c_void_p)]
 
 
+PRUNE_MAX_LEVELS = 16
+PRUNE_MAX_SEGMENTS = 16
+PRUNE_LEVELS_PER_LAUNCH = 8
+
+
+class SnrSelectArgs(C.Structure):
+    """bnn_snr_select_args (include/bnn_hip.h F9)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_segments", C.c_int32), ("n_levels", C.c_int32), ("reserved", C.c_int32),
+                ("snr", C.c_void_p * PRUNE_MAX_SEGMENTS), ("n", C.c_int64 * PRUNE_MAX_SEGMENTS),
+                ("fraction", C.c_double * PRUNE_MAX_LEVELS), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("thresholds", C.c_void_p)]
+
+
+class PruneCodesArgs(C.Structure):
+    """bnn_prune_codes_args (include/bnn_hip.h F9)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("out_features", C.c_int32), ("in_features", C.c_int32), ("ld", C.c_int32),
+                ("transposed", C.c_int32), ("n_levels", C.c_int32), ("mu_dtype", C.c_int32), ("reserved", C.c_int32),
+                ("mu", C.c_void_p), ("rho", C.c_void_p), ("thresholds", C.c_void_p), ("code", C.c_void_p),
+                ("mu_out", C.c_void_p), ("kept", C.c_void_p)]
+
+
+class PrunedFwdArgs(C.Structure):
+    """bnn_pruned_fwd_args (include/bnn_hip.h F9)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_levels", C.c_int32), ("rows", C.c_int32), ("in_features", C.c_int32),
+                ("out_features", C.c_int32), ("math", C.c_int32), ("relu", C.c_int32), ("x_shared", C.c_int32),
+                ("x_dtype", C.c_int32), ("y_dtype", C.c_int32), ("ldx", C.c_int32), ("ldy", C.c_int32), ("ld", C.c_int32),
+                ("reserved", C.c_int32), ("x", C.c_void_p), ("mu", C.c_void_p), ("code", C.c_void_p), ("b", C.c_void_p),
+                ("bcode", C.c_void_p), ("y", C.c_void_p)]
+
+
+class PruneTailArgs(C.Structure):
+    """bnn_prune_tail_args (include/bnn_hip.h F9)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("mode", C.c_int32), ("n_levels", C.c_int32), ("rows", C.c_int32),
+                ("classes", C.c_int32), ("reserved", C.c_int32), ("n_total", C.c_int64), ("row0", C.c_int64),
+                ("logits", C.c_void_p), ("target", C.c_void_p), ("probs", C.c_void_p), ("correct", C.c_void_p),
+                ("loss", C.c_void_p)]
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -515,6 +554,12 @@ def _load_real():
     lib.bnn_epoch_permutation.argtypes = [C.POINTER(EpochPermArgs), C.c_void_p]
     lib.bnn_epoch_stage.restype = C.c_int
     lib.bnn_epoch_stage.argtypes = [C.POINTER(EpochStageArgs), C.c_void_p]
+    lib.bnn_snr_select_workspace_bytes.restype = C.c_size_t
+    lib.bnn_snr_select_workspace_bytes.argtypes = []
+    for name, cls in (("bnn_snr_select", SnrSelectArgs), ("bnn_prune_codes", PruneCodesArgs), ("bnn_pruned_fwd", PrunedFwdArgs),
+                      ("bnn_prune_sweep_tail", PruneTailArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

@@ -1694,3 +1694,101 @@ def epoch_stage(a: L.EpochStageArgs):
     """bnn_epoch_stage: gather, cast and target copy of minibatch *batch_index, beta lookup, loss filing; advances the
     minibatch word (and the epoch word after the last minibatch)."""
     L.check(L.load().bnn_epoch_stage(C.byref(a), _stream()), "bnn_epoch_stage")
+
+
+# ---------------------------------------------------------------------------------------------------------------- F9 pruning sweep
+def snr_select(segments, fractions, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bnn_snr_select: the np.percentile thresholds (float64 [P], on the device, no host read) of the fp32 SNR values held
+    in `segments` (a list of device tensors, never concatenated) at the drop `fractions` (host floats in [0, 1], any order)."""
+    lib = L.load()
+    segs = [_f32c(s, "snr").reshape(-1) for s in segments]
+    require_device(*segs)
+    fr = [float(f) for f in fractions]
+    if not 1 <= len(segs) <= L.PRUNE_MAX_SEGMENTS or not 1 <= len(fr) <= L.PRUNE_MAX_LEVELS:
+        raise BnnHipError(f"snr_select: 1 to {L.PRUNE_MAX_SEGMENTS} segments and 1 to {L.PRUNE_MAX_LEVELS} levels")
+    dev = segs[0].device
+    if out is None:
+        out = torch.empty(len(fr), dtype=torch.float64, device=dev)
+    if workspace is None:
+        workspace = torch.empty(lib.bnn_snr_select_workspace_bytes() // 8 + 1, dtype=torch.int64, device=dev)
+    a = L.SnrSelectArgs()
+    a.struct_bytes = C.sizeof(L.SnrSelectArgs)
+    a.n_segments, a.n_levels = len(segs), len(fr)
+    for i, s in enumerate(segs):
+        a.snr[i], a.n[i] = s.data_ptr(), s.numel()
+    for i, f in enumerate(fr):
+        a.fraction[i] = f
+    a.workspace, a.workspace_bytes, a.thresholds = workspace.data_ptr(), workspace.numel() * 8, out.data_ptr()
+    L.check(lib.bnn_snr_select(C.byref(a), _stream()), "bnn_snr_select")
+    return out
+
+
+def prune_codes(mu: torch.Tensor, rho: torch.Tensor, thresholds: torch.Tensor, code: torch.Tensor, mu_out: torch.Tensor,
+                kept: torch.Tensor, *, out_features: int, in_features: int, transposed: bool):
+    """bnn_prune_codes: the level codes and the matmul-ready mu of one parameter tensor into the canonical [out, ld] images
+    `code` (uint8) and `mu_out` (float32 or bfloat16); kept (int64 [P]) += the survivors of each level."""
+    require_device(mu, rho, thresholds, code, mu_out, kept)
+    mu, rho = _f32c(mu, "mu"), _f32c(rho, "rho")
+    if mu.numel() != out_features * in_features or rho.numel() != mu.numel():
+        raise BnnHipError("prune_codes: mu and rho must hold out_features * in_features elements")
+    if code.dtype != torch.uint8 or code.dim() != 2 or code.shape != mu_out.shape or not code.is_contiguous() or \
+            not mu_out.is_contiguous() or code.shape[0] < out_features:
+        raise BnnHipError("prune_codes: code (uint8) and mu_out must be contiguous [>= out_features, ld] images of one shape")
+    if thresholds.dtype != torch.float64 or kept.dtype != torch.int64 or kept.numel() != thresholds.numel():
+        raise BnnHipError("prune_codes: thresholds float64 [P], kept int64 [P]")
+    a = L.PruneCodesArgs()
+    a.struct_bytes = C.sizeof(L.PruneCodesArgs)
+    a.out_features, a.in_features, a.ld, a.transposed = int(out_features), int(in_features), code.shape[1], int(bool(transposed))
+    a.n_levels, a.mu_dtype = thresholds.numel(), _dt(mu_out)
+    a.mu, a.rho, a.thresholds = mu.data_ptr(), rho.data_ptr(), thresholds.data_ptr()
+    a.code, a.mu_out, a.kept = code.data_ptr(), mu_out.data_ptr(), kept.data_ptr()
+    L.check(L.load().bnn_prune_codes(C.byref(a), _stream()), "bnn_prune_codes")
+
+
+def pruned_fwd_args(*, x: torch.Tensor, mu: torch.Tensor, code: torch.Tensor, b: Optional[torch.Tensor],
+                    bcode: Optional[torch.Tensor], y: torch.Tensor, n_levels: int, rows: int, in_features: int,
+                    out_features: int, math_mode: int, relu: bool, x_shared: bool) -> L.PrunedFwdArgs:
+    """The argument block of bnn_pruned_fwd for one layer: x [rows, ldx] (shared) or [P, rows, ldx], y [P, rows, ldy], the
+    canonical mu / code images [round_up(out, 64), ld]."""
+    require_device(x, mu, code, y, b, bcode)
+    if not (x.is_contiguous() and y.is_contiguous() and mu.is_contiguous() and code.is_contiguous()):
+        raise BnnHipError("pruned_fwd: contiguous tensors")
+    if mu.shape != code.shape or mu.shape[0] < -(-out_features // 64) * 64 or code.dtype != torch.uint8:
+        raise BnnHipError("pruned_fwd: mu and code must be [round_up(out_features, 64), ld] images of one shape")
+    if x.numel() != (1 if x_shared else n_levels) * rows * x.shape[-1] or y.numel() != n_levels * rows * y.shape[-1]:
+        raise BnnHipError("pruned_fwd: x must be [rows, ldx] or [P, rows, ldx] and y [P, rows, ldy]")
+    a = L.PrunedFwdArgs()
+    a.struct_bytes = C.sizeof(L.PrunedFwdArgs)
+    a.n_levels, a.rows, a.in_features, a.out_features = int(n_levels), int(rows), int(in_features), int(out_features)
+    a.math, a.relu, a.x_shared = int(math_mode), int(bool(relu)), int(bool(x_shared))
+    a.x_dtype, a.y_dtype, a.ldx, a.ldy, a.ld = _dt(x), _dt(y), x.shape[-1], y.shape[-1], mu.shape[1]
+    a.x, a.mu, a.code, a.b, a.bcode, a.y = x.data_ptr(), mu.data_ptr(), code.data_ptr(), _ptr(b), _ptr(bcode), y.data_ptr()
+    return a
+
+
+def pruned_fwd(a: L.PrunedFwdArgs):
+    L.check(L.load().bnn_pruned_fwd(C.byref(a), _stream()), "bnn_pruned_fwd")
+
+
+def prune_sweep_tail(logits: torch.Tensor, target: torch.Tensor, *, mode: int, probs: Optional[torch.Tensor],
+                     correct: Optional[torch.Tensor], loss: torch.Tensor, row0: int, n_total: int):
+    """bnn_prune_sweep_tail over the logits [P, rows, classes] of one minibatch (rows row0 .. of a data set of n_total)."""
+    require_device(logits, target, probs, correct, loss)
+    P, rows, classes = logits.shape
+    if logits.dtype != torch.float32 or not logits.is_contiguous() or not target.is_contiguous():
+        raise BnnHipError("prune_sweep_tail: contiguous float32 logits [P, rows, classes] and a contiguous target")
+    if mode == L.NLL_CLASSIFICATION:
+        if target.dtype != torch.int64 or target.numel() != rows:
+            raise BnnHipError("prune_sweep_tail: int64 labels [rows]")
+        if probs is None or probs.dtype != torch.float32 or not probs.is_contiguous() or probs.numel() != P * n_total * classes or \
+                correct is None or correct.dtype != torch.int64 or correct.numel() != P:
+            raise BnnHipError("prune_sweep_tail: probs float32 [P, n_total, classes] and correct int64 [P]")
+    elif target.dtype != torch.float32 or target.numel() != rows * classes:
+        raise BnnHipError("prune_sweep_tail: float32 targets [rows, classes]")
+    if loss.dtype != torch.float64 or loss.numel() != P:
+        raise BnnHipError("prune_sweep_tail: loss float64 [P]")
+    a = L.PruneTailArgs()
+    a.struct_bytes = C.sizeof(L.PruneTailArgs)
+    a.mode, a.n_levels, a.rows, a.classes, a.n_total, a.row0 = int(mode), P, rows, classes, int(n_total), int(row0)
+    a.logits, a.target, a.probs, a.correct, a.loss = logits.data_ptr(), target.data_ptr(), _ptr(probs), _ptr(correct), loss.data_ptr()
+    L.check(L.load().bnn_prune_sweep_tail(C.byref(a), _stream()), "bnn_prune_sweep_tail")

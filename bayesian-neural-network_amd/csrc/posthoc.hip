@@ -4,6 +4,7 @@
 //   bnn_snr_db       weight_pruning.py:85-87 (compute_snr), :100, :109
 //   bnn_snr_prune    weight_pruning.py:89-115 (prune_weights: mu, rho *= (snr > threshold))
 #include "bnn_device.h"
+#include "bnn_snr.h"
 #include "../../include/bnn_hip.h"
 
 namespace bnn {
@@ -103,11 +104,6 @@ __global__ void ece_final_kernel(const double* __restrict__ part, int nblocks, i
       if (cnt[b] > 0) ece += fabs(conf[b] / cnt[b] - cor[b] / cnt[b]) * cnt[b] / total;
     out[0] = (float)ece;
   }
-}
-
-// 10 * log10(|mu| / softplus(rho)) in fp32, as torch evaluates weight_pruning.py:100 / :109 (softplus = log1p(exp(rho)))
-__device__ __forceinline__ float snr_db(float mu, float rho) {
-  return 10.0f * (__builtin_amdgcn_logf(fabsf(mu) / softplus(rho)) * 0.30102999566398120f);   // log2 -> log10
 }
 
 __global__ __launch_bounds__(256) void snr_db_kernel(const float* __restrict__ mu, const float* __restrict__ rho, long n,

@@ -1256,6 +1256,135 @@ typedef struct bnn_epoch_stage_args {
 int bnn_epoch_stage(const bnn_epoch_stage_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F9  SNR pruning sweep — weight_pruning.py:89-115 for P drop levels at once, without touching or copying the model:
+ * thresholds by selection, a one-byte level code per parameter, a masked mean-weight forward for all levels, and the
+ * evaluation tail.  Nothing here reads anything back to the host.
+ *
+ * bnn_snr_select   thresholds[p] (fp64, device) = np.percentile(snr, 100 fraction[p]) over the n = sum_s n[s] fp32 values of
+ *     the segments snr[s][0 .. n[s]-1] (one segment per parameter tensor: the vector is never concatenated):
+ *       pos = (n - 1) fraction[p] (fp64, on the host), lo = floor(pos), hi = min(lo + 1, n - 1), a = v_(lo), b = v_(hi) the
+ *       order statistics, thresholds[p] = a when a == b, else a + (b - a) (pos - lo) -- two roundings, never fused.
+ *     NaNs order last (torch.sort).  A 4-pass radix selection over order-preserving 32-bit keys for all 2 P ranks together,
+ *     integer atomics only: bitwise reproducible.  fraction[] is a HOST array, in any order.  n < 2^31.
+ *     Workspace: bnn_snr_select_workspace_bytes() bytes, 8-byte aligned, any contents.
+ *   Errors: args, a segment, thresholds NULL: BNN_ERR_NULL; n_segments outside [1, BNN_PRUNE_MAX_SEGMENTS], n_levels outside
+ *   [1, BNN_PRUNE_MAX_LEVELS], n[s] < 1, n >= 2^31, a fraction outside [0, 1] (or NaN): BNN_ERR_SHAPE; workspace NULL or short:
+ *   BNN_ERR_WORKSPACE; a segment not 4-byte, thresholds / workspace not 8-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_prune_codes   one parameter tensor: code[o, i] = #{p < n_levels : snr_db(mu, rho) > (float)thresholds[p]} (thresholds
+ *     ascending: the parameter survives level p exactly when code > p -- the comparison bnn_snr_prune makes with the same
+ *     snr_db and the same fp32-rounded threshold), mu_out[o, i] = mu (fp32, or bf16 round to nearest even), both in the
+ *     canonical [out_features, in_features] layout with row stride ld; kept[p] += #{code > p} (int64, integer atomics).
+ *     The source is [out, in] (transposed = 0: BayesianLinear) or [in, out] (transposed = 1: BayesianLinearLR); a bias vector
+ *     is out_features = 1, in_features = its length.  Elements of a row past in_features are not written.
+ *   Errors: NULL mu, rho, thresholds, code, mu_out, kept: BNN_ERR_NULL; a dimension < 1, ld < in_features, n_levels outside
+ *   [1, BNN_PRUNE_MAX_LEVELS]: BNN_ERR_SHAPE; mu_dtype outside bnn_dtype: BNN_ERR_ENUM; mu / rho not 4-byte, thresholds / kept not
+ *   8-byte, mu_out not element aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_pruned_fwd   y[p] = act(x[p] . (mu (.) [code > p])^T + b (.) [bcode > p]) for the levels p < n_levels of one layer.
+ *     x: [rows, ldx] shared by all levels (x_shared != 0) or [n_levels, rows, ldx]; y: [n_levels, rows, ldy].  mu / code: the
+ *     canonical images bnn_prune_codes writes, here with round_up(out_features, 64) rows of ld elements, ld % 32 == 0, both
+ *     16-byte aligned, padding rows and columns zero (code 0 masks them at every level).  A block stages a 64 x 32 tile of mu
+ *     and its codes once per k step and forms each level's masked fragment in registers: parameter bytes are read once per
+ *     launch, whatever n_levels.  math BNN_MATH_BF16: x, mu bf16, v_mfma_f32_16x16x32_bf16, y bf16 or fp32; BNN_MATH_F32 and
+ *     BNN_MATH_BF16X3: x, mu, y fp32, the exact v_mfma_f32_16x16x4_f32.  More than BNN_PRUNE_LEVELS_PER_LAUNCH levels run as
+ *     several launches.  b / bcode: fp32 [out] and its codes, both or neither.
+ *   Errors: NULL x, mu, code, y, or one of b / bcode without the other: BNN_ERR_NULL; a dimension < 1, n_levels outside
+ *   [1, BNN_PRUNE_MAX_LEVELS], ld % 32, ld < in_features, ldx < in_features, ldy < out_features: BNN_ERR_SHAPE; math outside
+ *   bnn_math, a dtype outside bnn_dtype or not the math mode's: BNN_ERR_ENUM; mu / code not 16-byte, x / y not element,
+ *   b not 4-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_prune_sweep_tail   per level p and row r of a minibatch of `rows` rows starting at row `row0` of a data set of n_total:
+ *     classification (BNN_NLL_CLASSIFICATION): probs[p, row0 + r, :] = softmax(logits[p, r, :]), correct[p] += (first-maximum
+ *       argmax == target[r]), loss[p] += sum_r (logsumexp(logits[p, r, :]) - logits[p, r, target[r]])  (cross_entropy, sum);
+ *     regression (BNN_NLL_REGRESSION): loss[p] += sum_{r, c} (logits[p, r, c] - target[r, c])^2; probs, correct unused.
+ *     One block per level sums its rows in fp64 in a fixed order and is the only writer of its level's words: no float
+ *     atomics, bitwise reproducible.  target: int64 [rows] or fp32 [rows, classes].  probs: [n_levels, n_total, classes].
+ *   Errors: NULL logits, target, loss (and probs, correct in classification): BNN_ERR_NULL; a dimension < 1, n_levels outside
+ *   [1, BNN_PRUNE_MAX_LEVELS], row0 < 0, row0 + rows > n_total: BNN_ERR_SHAPE; mode outside bnn_nll_mode: BNN_ERR_ENUM; logits /
+ *   probs not 4-byte, target (labels) / correct / loss not 8-byte aligned: BNN_ERR_ALIGN.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_PRUNE_MAX_LEVELS 16
+#define BNN_PRUNE_MAX_SEGMENTS 16
+#define BNN_PRUNE_LEVELS_PER_LAUNCH 8
+/* layout: 4 x 4-byte words, 16 pointers, 16 int64, 16 doubles, pointer, size_t, pointer */
+typedef struct bnn_snr_select_args {
+  uint32_t struct_bytes;
+  int32_t n_segments;                          /* 1 .. BNN_PRUNE_MAX_SEGMENTS */
+  int32_t n_levels;                            /* P, 1 .. BNN_PRUNE_MAX_LEVELS */
+  int32_t reserved;
+  const float* snr[BNN_PRUNE_MAX_SEGMENTS];    /* device fp32 */
+  int64_t n[BNN_PRUNE_MAX_SEGMENTS];
+  double fraction[BNN_PRUNE_MAX_LEVELS];       /* host values in [0, 1] */
+  void* workspace;
+  size_t workspace_bytes;
+  double* thresholds;                          /* device [P] */
+} bnn_snr_select_args;
+size_t bnn_snr_select_workspace_bytes(void);
+int bnn_snr_select(const bnn_snr_select_args* args, void* stream);
+
+/* layout: 8 x 4-byte words, then 6 pointers */
+typedef struct bnn_prune_codes_args {
+  uint32_t struct_bytes;
+  int32_t out_features;
+  int32_t in_features;
+  int32_t ld;                                  /* row stride of code and mu_out, elements */
+  int32_t transposed;                          /* 0: source [out, in]; 1: source [in, out] */
+  int32_t n_levels;
+  int32_t mu_dtype;                            /* bnn_dtype of mu_out */
+  int32_t reserved;
+  const float* mu;
+  const float* rho;
+  const double* thresholds;                    /* device [P], ascending */
+  uint8_t* code;                               /* [out, ld] */
+  void* mu_out;                                /* [out, ld] fp32 or bf16 */
+  int64_t* kept;                               /* device [P], added to */
+} bnn_prune_codes_args;
+int bnn_prune_codes(const bnn_prune_codes_args* args, void* stream);
+
+/* layout: 14 x 4-byte words, then 6 pointers */
+typedef struct bnn_pruned_fwd_args {
+  uint32_t struct_bytes;
+  int32_t n_levels;
+  int32_t rows;
+  int32_t in_features;
+  int32_t out_features;
+  int32_t math;                                /* bnn_math */
+  int32_t relu;
+  int32_t x_shared;                            /* != 0: one x for all levels */
+  int32_t x_dtype;                             /* bnn_dtype */
+  int32_t y_dtype;                             /* bnn_dtype */
+  int32_t ldx, ldy;                            /* row strides of x and y, elements */
+  int32_t ld;                                  /* row stride of mu and code, elements, % 32 == 0 */
+  int32_t reserved;
+  const void* x;
+  const void* mu;                              /* canonical [round_up(out, 64), ld] fp32 or bf16 */
+  const uint8_t* code;                         /* same shape */
+  const float* b;                              /* optional [out] */
+  const uint8_t* bcode;                        /* with b */
+  void* y;
+} bnn_pruned_fwd_args;
+int bnn_pruned_fwd(const bnn_pruned_fwd_args* args, void* stream);
+
+/* layout: 6 x 4-byte words, 2 int64, then 5 pointers */
+typedef struct bnn_prune_tail_args {
+  uint32_t struct_bytes;
+  int32_t mode;                                /* bnn_nll_mode */
+  int32_t n_levels;
+  int32_t rows;
+  int32_t classes;
+  int32_t reserved;
+  int64_t n_total;
+  int64_t row0;
+  const float* logits;                         /* [P, rows, classes] */
+  const void* target;                          /* int64 [rows] or fp32 [rows, classes] */
+  float* probs;                                /* [P, n_total, classes] (classification) */
+  int64_t* correct;                            /* [P] (classification), added to */
+  double* loss;                                /* [P], added to */
+} bnn_prune_tail_args;
+int bnn_prune_sweep_tail(const bnn_prune_tail_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
