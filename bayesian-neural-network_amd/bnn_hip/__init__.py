@@ -9,8 +9,10 @@
 `train`      GraphedTrainStep: zero_grad -> sample_elbo -> backward -> Adam as one hipGraph
 `dense_train` GraphedDenseTrainStep: the same for MLP / MLP_Dropout (forward, loss, backward, SGD / Adam) (K6)
 `synth`      synthetic inputs with the reference's distributions (numpy only)
+`active`     ActivePool / ActiveLearner: pool scoring, top-k acquisition and training on the labelled subset (F10)
 """
 from .runtime import get_math, manual_seed, set_host_eps, set_math, shard_samples  # noqa: F401
 from ._lib import BnnHipError  # noqa: F401
+from .active import ActiveLearner, ActivePool  # noqa: F401
 
-__all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError"]
+__all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError", "ActiveLearner", "ActivePool"]

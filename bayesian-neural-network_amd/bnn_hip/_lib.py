@@ -34,6 +34,7 @@ EXPORTS = (
     "bnn_dense_loss", "bnn_dense_bwd", "bnn_sgd_step",
     "bnn_epoch_permutation", "bnn_epoch_stage",
     "bnn_snr_select_workspace_bytes", "bnn_snr_select", "bnn_prune_codes", "bnn_pruned_fwd", "bnn_prune_sweep_tail",
+    "bnn_acquire_topk_workspace_bytes", "bnn_acquire_topk", "bnn_acquire_compose", "bnn_acquire_random",
 )
 
 
@@ -393,6 +394,16 @@ class PruneTailArgs(C.Structure):
                 ("loss", C.c_void_p)]
 
 
+ACQUIRE_MAX_K = 4096
+
+
+class AcquireTopkArgs(C.Structure):
+    """bnn_acquire_topk_args (include/bnn_hip.h F10)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_rows", C.c_int32), ("k", C.c_int32), ("reserved", C.c_int32),
+                ("scores", C.c_void_p), ("candidate", C.c_void_p), ("selected", C.c_void_p), ("labelled", C.c_void_p),
+                ("n_labelled", C.c_void_p), ("n_selected", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -560,6 +571,14 @@ def _load_real():
                       ("bnn_prune_sweep_tail", PruneTailArgs)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    lib.bnn_acquire_topk_workspace_bytes.restype = C.c_size_t
+    lib.bnn_acquire_topk_workspace_bytes.argtypes = []
+    lib.bnn_acquire_topk.restype = C.c_int
+    lib.bnn_acquire_topk.argtypes = [C.POINTER(AcquireTopkArgs), C.c_void_p]
+    lib.bnn_acquire_compose.restype = C.c_int
+    lib.bnn_acquire_compose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.bnn_acquire_random.restype = C.c_int
+    lib.bnn_acquire_random.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

@@ -1792,3 +1792,57 @@ def prune_sweep_tail(logits: torch.Tensor, target: torch.Tensor, *, mode: int, p
     a.mode, a.n_levels, a.rows, a.classes, a.n_total, a.row0 = int(mode), P, rows, classes, int(n_total), int(row0)
     a.logits, a.target, a.probs, a.correct, a.loss = logits.data_ptr(), target.data_ptr(), _ptr(probs), _ptr(correct), loss.data_ptr()
     L.check(L.load().bnn_prune_sweep_tail(C.byref(a), _stream()), "bnn_prune_sweep_tail")
+
+
+# ---------------------------------------------------------------------------------------------------------------- F10 active learning
+def acquire_topk_workspace(device) -> torch.Tensor:
+    """bnn_acquire_topk's workspace (any contents; 8-byte aligned)."""
+    return torch.empty(L.load().bnn_acquire_topk_workspace_bytes() // 8 + 1, dtype=torch.int64, device=device)
+
+
+def acquire_topk_args(*, scores, candidate, k: int, selected, labelled, n_labelled, n_selected=None,
+                      workspace=None) -> L.AcquireTopkArgs:
+    """The argument block of bnn_acquire_topk (include/bnn_hip.h F10): scores float32 [N], candidate uint8 [N], selected
+    int32 [k], labelled int32 [N], n_labelled / n_selected one int32 device word each."""
+    N = scores.numel()
+    keep = [_typed(scores, torch.float32, "scores"), _typed(candidate, torch.uint8, "candidate", N),
+            _typed(selected, torch.int32, "selected", int(k)), _typed(labelled, torch.int32, "labelled", N),
+            _typed(n_labelled, torch.int32, "n_labelled", 1)]
+    a = L.AcquireTopkArgs()
+    a.struct_bytes = C.sizeof(L.AcquireTopkArgs)
+    a.n_rows, a.k = N, int(k)
+    a.scores, a.candidate, a.selected, a.labelled, a.n_labelled = (t.data_ptr() for t in keep)
+    if n_selected is not None:
+        keep.append(_typed(n_selected, torch.int32, "n_selected", 1))
+        a.n_selected = n_selected.data_ptr()
+    if workspace is None:
+        workspace = acquire_topk_workspace(scores.device)
+    require_device(workspace)
+    keep.append(workspace)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a._keep = keep
+    return a
+
+
+def acquire_topk(a: L.AcquireTopkArgs):
+    """bnn_acquire_topk: the first k candidates by (score descending, row ascending, NaN last) into `selected`; the mask,
+    the labelled list and its count word follow on the device."""
+    L.check(L.load().bnn_acquire_topk(C.byref(a), _stream()), "bnn_acquire_topk")
+
+
+def acquire_compose(labelled: torch.Tensor, perm: torch.Tensor, order: torch.Tensor, n: int):
+    """bnn_acquire_compose: order[i] = labelled[perm[i]], i < n."""
+    for t, name in ((labelled, "labelled"), (perm, "perm"), (order, "order")):
+        _typed(t, torch.int32, name)
+        if t.numel() < int(n):
+            raise BnnHipError(f"acquire_compose: {name} must hold at least {int(n)} entries")
+    L.check(L.load().bnn_acquire_compose(labelled.data_ptr(), perm.data_ptr(), order.data_ptr(), int(n), _stream()),
+            "bnn_acquire_compose")
+
+
+def acquire_random(scores: torch.Tensor, seed: int, round: int) -> torch.Tensor:
+    """bnn_acquire_random: one Philox uniform in [0, 1) per row, counter (row >> 2, round, 3, 1), word row & 3."""
+    _typed(scores, torch.float32, "scores")
+    L.check(L.load().bnn_acquire_random(scores.data_ptr(), scores.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        int(round) & 0xFFFFFFFF, _stream()), "bnn_acquire_random")
+    return scores

@@ -1198,7 +1198,7 @@ int bnn_sgd_step(const bnn_sgd_args* args, void* stream);
  * bnn_epoch_permutation   order[0 .. N-1] (int32) = the positions p sorted by (key_p, p), with
  *     key_p = word (p & 3) of Philox4x32-R((p >> 2, e, 2, 1), key = (seed_lo, seed_hi)), R = bnn_philox_rounds(), e = *epoch.
  *   Counter words 2 and 3 are (2, 1): every eps counter's word 3 is 0, and among the word-3 = 1 streams the bandit's coins use
- *   (.., 0, 1) and its replay permutation (.., 1, 1), so this stream shares a counter with none.  The result is fixed by this
+ *   (.., 0, 1) and its replay permutation (.., 1, 1), so this stream shares a counter with none (F10's random scores: (.., 3, 1)).  The result is fixed by this
  *   definition, not by the algorithm (rank by counting over LDS-staged key tiles; one launch, N <= BNN_EPOCH_MAX_ROWS).
  *
  * bnn_epoch_stage   minibatch j = *batch_index of an epoch of M = num_batches minibatches of B = batch_size rows:
@@ -1383,6 +1383,58 @@ typedef struct bnn_prune_tail_args {
   double* loss;                                /* [P], added to */
 } bnn_prune_tail_args;
 int bnn_prune_sweep_tail(const bnn_prune_tail_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * F10  pool-based active learning — score an unlabelled pool, take the k rows the model is least sure about, add them to the
+ * labelled subset, train on the subset: the selection and the subset's epoch order, without the host reading or writing data.
+ *
+ * bnn_acquire_topk   the candidates (rows i < N with candidate[i] != 0) in the TOTAL order
+ *       score descending, then row index ascending; a NaN score after every other score; -0.0 equal to +0.0
+ *     -- np.lexsort((index, key)) of key = the order-preserving integer image of -score, NaN last.  With C candidates and
+ *     m = min(k, C):  selected[0 .. m) = the first m candidates in that order, selected[m .. k) = -1;
+ *       candidate[selected[i]] = 0 and labelled[*n_labelled + i] = selected[i], i < m (entries past labelled[N - 1] are not
+ *       written);  *n_labelled += m;  *n_selected = m (optional).
+ *     Method: every candidate has the distinct 48-bit key (32 score bits, 16 index bits); a radix selection of the m-th
+ *     smallest key in four 12-bit passes (LDS histograms, integer atomics; every block re-derives the earlier passes' digits
+ *     from their histograms, so no block waits for another), a compaction of the keys up to it and a one-block bitonic sort
+ *     in LDS: separate launches on the stream behind this one entry.  Integer atomics only: bitwise reproducible.
+ *     Workspace: bnn_acquire_topk_workspace_bytes() bytes, 8-byte aligned, any contents.
+ *   Errors: args, scores, candidate, selected, labelled, n_labelled NULL: BNN_ERR_NULL; N outside [1, BNN_EPOCH_MAX_ROWS], k
+ *   outside [1, BNN_ACQUIRE_MAX_K]: BNN_ERR_SHAPE; workspace NULL or short: BNN_ERR_WORKSPACE; scores, selected, labelled,
+ *   n_labelled, n_selected not 4-byte, workspace not 8-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_acquire_compose   order[i] = labelled[perm[i]], i < n (a perm entry outside [0, n) reads labelled[i]): the epoch order
+ *     of the labelled subset from bnn_epoch_permutation's permutation of its n positions -- what bnn_epoch_stage gathers
+ *     through, over the whole data set's rows.  No row is copied.
+ *   Errors: a NULL pointer: BNN_ERR_NULL; n outside [1, BNN_EPOCH_MAX_ROWS]: BNN_ERR_SHAPE; a pointer not 4-byte aligned:
+ *   BNN_ERR_ALIGN.
+ *
+ * bnn_acquire_random   scores[i] = (w_i >> 8) 2^-24 in [0, 1), i < N, with
+ *     w_i = word (i & 3) of Philox4x32-R((i >> 2, round, 3, 1), key = (seed_lo, seed_hi)), R = bnn_philox_rounds():
+ *   the "random" acquisition.  Counter words 2 and 3 are (3, 1): off the eps counters (word 3 = 0), the bandit's streams
+ *   ((.., 0, 1), (.., 1, 1)) and F8's epoch permutation ((.., 2, 1)).
+ *   Errors: scores NULL: BNN_ERR_NULL; N outside [1, BNN_EPOCH_MAX_ROWS]: BNN_ERR_SHAPE; scores not 4-byte aligned: BNN_ERR_ALIGN.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_ACQUIRE_MAX_K 4096         /* winners of one launch: 4096 8-byte keys sort in 32 KiB of one block's LDS */
+/* layout: 4 x 4-byte words, 7 pointers, size_t */
+typedef struct bnn_acquire_topk_args {
+  uint32_t struct_bytes;
+  int32_t n_rows;                 /* N, 1 .. BNN_EPOCH_MAX_ROWS */
+  int32_t k;                      /* 1 .. BNN_ACQUIRE_MAX_K */
+  int32_t reserved;
+  const float* scores;            /* device [N] */
+  uint8_t* candidate;             /* device [N], 1 = still in the pool */
+  int32_t* selected;              /* device [k] */
+  int32_t* labelled;              /* device [N] */
+  int32_t* n_labelled;            /* device word */
+  int32_t* n_selected;            /* optional device word */
+  void* workspace;
+  size_t workspace_bytes;
+} bnn_acquire_topk_args;
+size_t bnn_acquire_topk_workspace_bytes(void);
+int bnn_acquire_topk(const bnn_acquire_topk_args* args, void* stream);
+int bnn_acquire_compose(const int32_t* labelled, const int32_t* perm, int32_t* order, int32_t n, void* stream);
+int bnn_acquire_random(float* scores, int32_t n_rows, uint64_t seed, uint32_t round, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
