@@ -35,6 +35,7 @@ EXPORTS = (
     "bnn_epoch_permutation", "bnn_epoch_stage",
     "bnn_snr_select_workspace_bytes", "bnn_snr_select", "bnn_prune_codes", "bnn_pruned_fwd", "bnn_prune_sweep_tail",
     "bnn_acquire_topk_workspace_bytes", "bnn_acquire_topk", "bnn_acquire_compose", "bnn_acquire_random",
+    "bnn_param_hist_workspace_bytes", "bnn_param_hist",
 )
 
 
@@ -404,6 +405,37 @@ class AcquireTopkArgs(C.Structure):
                 ("n_labelled", C.c_void_p), ("n_selected", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+HIST_MAX_JOBS = 16
+HIST_MAX_EDGES = 2048
+HIST_CHUNK = 8192
+HIST_VALUE, HIST_SIGMA, HIST_SNR_DB, HIST_SAMPLE = 0, 1, 2, 3
+
+
+class HistSummary(C.Structure):
+    """bnn_hist_summary (include/bnn_hip.h F11): what follows the counts in a job's record"""
+    _fields_ = [("n_in", C.c_uint64), ("n_below", C.c_uint64), ("n_above", C.c_uint64), ("n_nan", C.c_uint64),
+                ("min", C.c_float), ("max", C.c_float), ("sum", C.c_double), ("sum_sq", C.c_double)]
+
+
+class ParamHistJob(C.Structure):
+    """bnn_param_hist_job (include/bnn_hip.h F11)"""
+    _fields_ = [("kind", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("tensor_id", C.c_uint32),
+                ("sample", C.c_uint32), ("reserved", C.c_uint32), ("n", C.c_int64), ("seed", C.c_uint64),
+                ("src0", C.c_void_p), ("src1", C.c_void_p), ("values_out", C.c_void_p), ("record", C.c_void_p)]
+
+
+class ParamHistArgs(C.Structure):
+    """bnn_param_hist_args (include/bnn_hip.h F11)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_jobs", C.c_int32), ("n_edges", C.c_int32), ("reserved", C.c_int32),
+                ("edges", C.c_void_p), ("edges_host", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("jobs", ParamHistJob * HIST_MAX_JOBS)]
+
+
+def hist_record_bytes(n_edges: int) -> int:
+    """BNN_HIST_RECORD_BYTES(n_edges)"""
+    return 8 * (int(n_edges) - 1) + C.sizeof(HistSummary)
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -579,6 +611,10 @@ def _load_real():
     lib.bnn_acquire_compose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.bnn_acquire_random.restype = C.c_int
     lib.bnn_acquire_random.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint32, C.c_void_p]
+    lib.bnn_param_hist_workspace_bytes.restype = C.c_size_t
+    lib.bnn_param_hist_workspace_bytes.argtypes = [C.POINTER(ParamHistArgs)]
+    lib.bnn_param_hist.restype = C.c_int
+    lib.bnn_param_hist.argtypes = [C.POINTER(ParamHistArgs), C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

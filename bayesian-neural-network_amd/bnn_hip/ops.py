@@ -1846,3 +1846,87 @@ def acquire_random(scores: torch.Tensor, seed: int, round: int) -> torch.Tensor:
     L.check(L.load().bnn_acquire_random(scores.data_ptr(), scores.numel(), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                         int(round) & 0xFFFFFFFF, _stream()), "bnn_acquire_random")
     return scores
+
+
+# ---------------------------------------------------------------------------------------------------------------- F11 posterior statistics
+def hist_edges(edges):
+    """The bin-edge table of bnn_param_hist as a float64 numpy array: 2 .. HIST_MAX_EDGES finite, strictly increasing edges."""
+    import numpy as np
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+    if not 2 <= e.size <= L.HIST_MAX_EDGES:
+        raise BnnHipError(f"param_hist: 2 to {L.HIST_MAX_EDGES} bin edges, got {e.size}")
+    if not (np.all(np.isfinite(e)) and np.all(e[1:] > e[:-1])):
+        raise BnnHipError("param_hist: the bin edges must be finite and strictly increasing")
+    return e
+
+
+def _hist_f32(t, name: str) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous():
+        raise BnnHipError(f"param_hist: {name} must be a contiguous float32 tensor (tensors are neither copied nor padded)")
+    return t
+
+
+def param_hist_args(jobs: Sequence[dict], edges, *, records: Optional[torch.Tensor] = None,
+                    workspace: Optional[torch.Tensor] = None) -> L.ParamHistArgs:
+    """The argument block of bnn_param_hist (include/bnn_hip.h F11).  `jobs`: dicts with kind (L.HIST_*), src0, and by kind
+    src1 (SNR_DB, SAMPLE), seed / tensor_id / sample (SAMPLE; rows x cols is src0's shape, a vector a single row), values_out
+    (optional float32 [n]).  `edges`: the host table.  `records` (int64 [n_jobs, hist_record_bytes / 8]) and `workspace` are
+    allocated when not given; the block keeps them as .records / .workspace and the device table as .edges_device."""
+    e = hist_edges(edges)
+    if not 1 <= len(jobs) <= L.HIST_MAX_JOBS:
+        raise BnnHipError(f"param_hist: 1 to {L.HIST_MAX_JOBS} jobs per call, got {len(jobs)}")
+    a = L.ParamHistArgs()
+    a.struct_bytes = C.sizeof(L.ParamHistArgs)
+    a.n_jobs, a.n_edges = len(jobs), int(e.size)
+    keep = [e]
+    for i, job in enumerate(jobs):
+        kind = int(job["kind"])
+        if kind not in (L.HIST_VALUE, L.HIST_SIGMA, L.HIST_SNR_DB, L.HIST_SAMPLE):
+            raise BnnHipError(f"param_hist: unknown kind {kind}")
+        src0 = _hist_f32(job["src0"], "src0")
+        j = a.jobs[i]
+        j.kind, j.n, j.src0 = kind, src0.numel(), src0.data_ptr()
+        keep.append(src0)
+        if kind in (L.HIST_SNR_DB, L.HIST_SAMPLE):
+            src1 = _hist_f32(job.get("src1"), "src1")
+            if src1.numel() != src0.numel():
+                raise BnnHipError("param_hist: src0 and src1 must have the same number of elements")
+            j.src1 = src1.data_ptr()
+            keep.append(src1)
+        if kind == L.HIST_SAMPLE:
+            j.rows, j.cols = (1, src0.numel()) if src0.dim() < 2 else (src0.numel() // src0.shape[-1], src0.shape[-1])
+            j.seed = int(job.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF
+            j.tensor_id, j.sample = int(job.get("tensor_id", 0)) & 0xFFFFFFFF, int(job.get("sample", 0)) & 0xFFFFFFFF
+        out = job.get("values_out")
+        if out is not None:
+            if _hist_f32(out, "values_out").numel() != src0.numel():
+                raise BnnHipError("param_hist: values_out must have src0's number of elements")
+            j.values_out = out.data_ptr()
+            keep.append(out)
+    require_device(*keep[1:])
+    dev = keep[1].device
+    words = L.hist_record_bytes(e.size) // 8
+    if records is None:
+        records = torch.zeros((len(jobs), words), dtype=torch.int64, device=dev)
+    if records.dtype != torch.int64 or not records.is_contiguous() or tuple(records.shape) != (len(jobs), words):
+        raise BnnHipError(f"param_hist: records must be a contiguous int64 [{len(jobs)}, {words}] tensor")
+    require_device(records)
+    for i in range(len(jobs)):
+        a.jobs[i].record = records.data_ptr() + 8 * words * i
+    edges_device = torch.from_numpy(e).to(dev)
+    a.edges, a.edges_host = edges_device.data_ptr(), e.ctypes.data
+    need = int(L.load().bnn_param_hist_workspace_bytes(C.byref(a)))
+    if need == 0:
+        raise BnnHipError("param_hist: the job list is outside the library's limits")
+    if workspace is None:
+        workspace = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    require_device(workspace)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    keep += [records, edges_device, workspace]
+    a._keep, a.records, a.workspace_t, a.edges_device, a.edges_np = keep, records, workspace, edges_device, e
+    return a
+
+
+def param_hist(a: L.ParamHistArgs):
+    """bnn_param_hist: clear, bin and fold into a.records on the current stream; nothing is read back."""
+    L.check(L.load().bnn_param_hist(C.byref(a), _stream()), "bnn_param_hist")

@@ -50,6 +50,38 @@ def _bayesian_layers(model):
     return [l for l in model.children() if hasattr(l, "weight_mu") and hasattr(l, "weight_rho")]
 
 
+def collect_weights(model, bnn=False, sample=None):
+    """weight_pruning.py:16-38 on the device: the parameters whose names hold neither 'mu' nor 'rho', flattened and
+    concatenated in named_parameters() order; with bnn=True `[mus, sigmas]` (sigma = log1p(exp(rho)), rho_to_sigma :40-41);
+    with `sample` set (a global MC sample index) ONE draw per posterior instead, mu + sigma * eps on the network's seed and
+    epsilon tensor ids -- the vector sample_bnn_weights (:43-44) makes.  Flat fp32 device tensors; the sigmas and the draws
+    come out of bnn_param_hist's values_out, nothing goes through Python lists."""
+    from . import _lib as L
+    mus, rhos, weights = [], [], []
+    for name, p in model.named_parameters():
+        (mus if "mu" in name else rhos if "rho" in name else weights).append(p.detach())
+    if not bnn:
+        return torch.cat([w.flatten() for w in weights]) if weights else torch.empty(0)
+    if not mus or len(mus) != len(rhos):
+        raise ops.BnnHipError("collect_weights: bnn=True needs (mu, rho) parameter pairs")
+    ops.require_device(*mus, *rhos)
+    sizes = [r.numel() for r in rhos]
+    out = torch.empty(sum(sizes), dtype=torch.float32, device=rhos[0].device)
+    outs = list(torch.split(out, sizes))
+    if sample is None:
+        jobs = [dict(kind=L.HIST_SIGMA, src0=r, values_out=o) for r, o in zip(rhos, outs)]
+    else:
+        from .runtime import state
+        ids = [4 * int(getattr(l, "_layer_id", i)) + k for i, l in enumerate(_bayesian_layers(model)) for k in (0, 1)]
+        if len(ids) != len(mus):
+            raise ops.BnnHipError("collect_weights: sample needs Bayesian layers of one weight and one bias posterior each")
+        jobs = [dict(kind=L.HIST_SAMPLE, src0=m, src1=r, values_out=o, seed=state.seed, tensor_id=t, sample=int(sample))
+                for m, r, o, t in zip(mus, rhos, outs, ids)]
+    for i in range(0, len(jobs), L.HIST_MAX_JOBS):
+        ops.param_hist(ops.param_hist_args(jobs[i:i + L.HIST_MAX_JOBS], (-1.0, 1.0)))
+    return out if sample is not None else [torch.cat([m.flatten() for m in mus]), out]
+
+
 def compute_snr(model_or_mu, sigma=None):
     """weight_pruning.py:85-87.  compute_snr(mu, sigma) with numpy / python inputs keeps the reference's numpy
     arithmetic; compute_snr(model) returns the SNR (dB, fp32 device tensor) of every stochastic parameter of the

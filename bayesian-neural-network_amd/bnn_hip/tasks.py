@@ -3,7 +3,8 @@
 `best_acc` / `best_loss`) and methods (`train_step`, `predict`, `evaluate`, `log_progress`), thin over the graphed training
 steps: `train_step(train_data)` builds the step on first use and runs an epoch.EpochRunner when `train_data` is a
 DeviceLoader, the reference's loop through `step.step` over any other iterable of (x, y).  The optimisers are FusedAdam /
-FusedSGD (capturable) with the reference's StepLR on top; `log_progress` writes nothing unless a `writer` was given."""
+FusedSGD (capturable) with the reference's StepLR on top; `log_progress` writes nothing unless a `writer` was given.  With
+`histograms=True` the Bayesian tasks also write the reference's twelve weight histograms and its loss breakdown (F11)."""
 from __future__ import annotations
 
 import os
@@ -24,8 +25,9 @@ class _Task:
     _keys = ()
     bayesian = True
 
-    def __init__(self, label, parameters, writer=None):
+    def __init__(self, label, parameters, writer=None, histograms=False):
         self.writer = writer
+        self._histograms, self._stats = bool(histograms), None
         self.label = label
         for attr, key in self._keys:
             setattr(self, attr, parameters[key])
@@ -83,6 +85,27 @@ class _Task:
         self.writer.add_scalar("loss", float(loss), step)
         if hasattr(self, "acc"):
             self.writer.add_scalar("accuracy", self.acc, step)
+        if self._histograms and self.bayesian:
+            self._log_posterior(step)
+
+    def _log_posterior(self, step):
+        """The reference's Bayesian logging (utils/logger_utils.py:13-39): write_weight_histograms from one device pass and
+        one copy (diagnostics.PosteriorStats), write_loss_scalars from loss_info."""
+        from . import diagnostics
+        if self._stats is None:
+            self._stats = diagnostics.PosteriorStats(self.net)
+        for tag, fields in self._stats.update().read().items():
+            self.writer.add_histogram_raw(tag, **fields, global_step=step)
+        loss = [float(v) for v in self.loss_info]
+        self.writer.add_scalar("logs/loss", loss[0], step)
+        if len(loss) == 4:
+            self.writer.add_scalar("logs/complexity_cost", loss[2] - loss[1], step)
+            self.writer.add_scalar("logs/log_prior", loss[1], step)
+            self.writer.add_scalar("logs/log_variational_posterior", loss[2], step)
+            self.writer.add_scalar("logs/negative_log_likelihood", loss[3], step)
+        else:
+            self.writer.add_scalar("logs/complexity_cost", loss[1], step)
+            self.writer.add_scalar("logs/negative_log_likelihood", loss[2], step)
 
 
 def _makedirs(parameters):

@@ -1437,6 +1437,77 @@ int bnn_acquire_compose(const int32_t* labelled, const int32_t* perm, int32_t* o
 int bnn_acquire_random(float* scores, int32_t n_rows, uint64_t seed, uint32_t round, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F11  posterior statistics — the histograms of utils/logger_utils.py:13-26 (write_weight_histograms: twelve add_histogram
+ * calls per epoch, each a device-to-host copy of a parameter tensor and a numpy binning) and of weight_pruning.py's figures
+ * (collect_weights + sample_bnn_weights :16-44, the SNR density and CDF :59-79), for up to BNN_HIST_MAX_JOBS tensors in one
+ * pass: every parameter is read once, the transform is fused in, a few KB are written, nothing is read back.
+ *
+ * Job j bins v_i, i < n, with
+ *     BNN_HIST_VALUE    v = src0[i]                                     any fp32 tensor
+ *     BNN_HIST_SIGMA    v = log1p(exp(src0[i]))                         src0 = rho; bit for bit bnn_softplus
+ *     BNN_HIST_SNR_DB   v = 10 log10(|src0[i]| / log1p(exp(src1[i])))   src0 = mu, src1 = rho; bit for bit bnn_snr_db
+ *     BNN_HIST_SAMPLE   v = fmaf(log1p(exp(src1[i])), eps_i, src0[i])   one fused multiply-add; eps_i = element i of what
+ *                                                                       bnn_philox_normal(seed, tensor_id, sample, 1, rows, cols)
+ *                                                                       writes (rows * cols = n)
+ * against ONE table of n_edges strictly increasing finite fp64 edges, as np.histogram(v.astype(float64), bins=edges): bin b
+ * is [e_b, e_b+1), the last bin is closed on the right, every comparison is made in fp64.  values_out (optional) receives
+ * the n transformed fp32 values.
+ *
+ * Record of a job (device, 8-byte aligned, BNN_HIST_RECORD_BYTES(n_edges) bytes, overwritten by every call):
+ *     uint64 counts[n_edges - 1], then a bnn_hist_summary:
+ *     n_in (values inside [e_0, e_last]), n_below (< e_0, -inf included), n_above (> e_last, +inf included), n_nan;
+ *     min, max over the non-NaN values (+inf, -inf when there are none); sum, sum_sq in fp64 over the finite values.
+ * Counts are integer sums: exact.  The fp64 sums take a fixed order -- a block owns BNN_HIST_CHUNK consecutive elements of
+ * one job, a thread adds its elements in index order, the block reduces by a fixed lane and wave tree, and a second launch
+ * folds a job's block partials by a fixed tree -- so two calls over the same data return the same bits.  No floating-point
+ * atomics.  Tensors are neither padded nor copied; no alignment beyond 4 bytes is asked of src0 / src1 / values_out; n = 0
+ * is valid.  Workspace: bnn_param_hist_workspace_bytes(args) bytes, 8-byte aligned, any contents.  Three launches on the
+ * stream (clear, bin, fold); hipGraph-capturable like every entry point.
+ *   Errors: args, edges, a record, src0 (n > 0), src1 (SNR_DB / SAMPLE, n > 0) NULL: BNN_ERR_NULL; n_jobs outside
+ *   [1, BNN_HIST_MAX_JOBS], n_edges outside [2, BNN_HIST_MAX_EDGES], n outside [0, 2^31), SAMPLE (n > 0) with rows or cols < 1
+ *   or rows * cols != n, edges_host (optional HOST copy of the table, checked when given) not finite and strictly increasing:
+ *   BNN_ERR_SHAPE; kind outside bnn_hist_kind: BNN_ERR_ENUM; workspace NULL or short: BNN_ERR_WORKSPACE; src0 / src1 /
+ *   values_out not 4-byte, edges / record / workspace not 8-byte aligned: BNN_ERR_ALIGN.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_HIST_MAX_JOBS 16           /* the twelve tensors of a network in one call */
+#define BNN_HIST_MAX_EDGES 2048        /* 16 KiB of fp64 edges + four per-wave sub-histograms fit one block's LDS */
+#define BNN_HIST_CHUNK 8192            /* consecutive elements of a job per block */
+enum bnn_hist_kind { BNN_HIST_VALUE = 0, BNN_HIST_SIGMA = 1, BNN_HIST_SNR_DB = 2, BNN_HIST_SAMPLE = 3 };
+typedef struct bnn_hist_summary {
+  uint64_t n_in, n_below, n_above, n_nan;
+  float min, max;
+  double sum, sum_sq;
+} bnn_hist_summary;
+#define BNN_HIST_RECORD_BYTES(n_edges) (8u * ((size_t)(n_edges) - 1u) + sizeof(bnn_hist_summary))
+/* layout: 6 x 4-byte words, int64, uint64, 4 pointers */
+typedef struct bnn_param_hist_job {
+  int32_t kind;                   /* bnn_hist_kind */
+  int32_t rows, cols;             /* SAMPLE: the logical shape of the epsilon tensor */
+  uint32_t tensor_id;             /* SAMPLE: 4 * layer_id + kind of the epsilon map */
+  uint32_t sample;                /* SAMPLE: global MC sample index */
+  uint32_t reserved;
+  int64_t n;                      /* elements, 0 .. 2^31 - 1 */
+  uint64_t seed;                  /* SAMPLE */
+  const float* src0;              /* device [n] */
+  const float* src1;              /* device [n]: SNR_DB, SAMPLE */
+  float* values_out;              /* optional device [n] */
+  void* record;                   /* device, BNN_HIST_RECORD_BYTES(n_edges) bytes */
+} bnn_param_hist_job;
+typedef struct bnn_param_hist_args {
+  uint32_t struct_bytes;
+  int32_t n_jobs;                 /* 1 .. BNN_HIST_MAX_JOBS */
+  int32_t n_edges;                /* 2 .. BNN_HIST_MAX_EDGES */
+  int32_t reserved;
+  const double* edges;            /* device [n_edges] */
+  const double* edges_host;       /* optional HOST copy (validated) */
+  void* workspace;
+  size_t workspace_bytes;
+  bnn_param_hist_job jobs[BNN_HIST_MAX_JOBS];
+} bnn_param_hist_args;
+size_t bnn_param_hist_workspace_bytes(const bnn_param_hist_args* args);   /* 0 outside the limits */
+int bnn_param_hist(const bnn_param_hist_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
