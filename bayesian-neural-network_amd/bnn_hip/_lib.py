@@ -36,6 +36,7 @@ EXPORTS = (
     "bnn_snr_select_workspace_bytes", "bnn_snr_select", "bnn_prune_codes", "bnn_pruned_fwd", "bnn_prune_sweep_tail",
     "bnn_acquire_topk_workspace_bytes", "bnn_acquire_topk", "bnn_acquire_compose", "bnn_acquire_random",
     "bnn_param_hist_workspace_bytes", "bnn_param_hist",
+    "bnn_mc_score_workspace_bytes", "bnn_mc_score",
 )
 
 
@@ -436,6 +437,24 @@ def hist_record_bytes(n_edges: int) -> int:
     return 8 * (int(n_edges) - 1) + C.sizeof(HistSummary)
 
 
+SCORE_MAX_BINS = 64
+
+
+class McScoreArgs(C.Structure):
+    """bnn_mc_score_args (include/bnn_hip.h F12)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("mode", C.c_int32),
+                ("groups", C.c_int32), ("n_samples", C.c_int32), ("batch", C.c_int32), ("classes", C.c_int32),
+                ("logits", C.c_void_p), ("targets", C.c_void_p), ("n_valid", C.c_int64),
+                ("sigma", C.c_float), ("n_bins", C.c_int32), ("accumulate", C.c_int32), ("reserved", C.c_int32),
+                ("row_lpd", C.c_void_p), ("row_nll", C.c_void_p), ("record", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+def score_record_bytes(n_bins: int) -> int:
+    """BNN_SCORE_RECORD_BYTES(n_bins)"""
+    return 8 * (8 + 3 * int(n_bins))
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -615,6 +634,10 @@ def _load_real():
     lib.bnn_param_hist_workspace_bytes.argtypes = [C.POINTER(ParamHistArgs)]
     lib.bnn_param_hist.restype = C.c_int
     lib.bnn_param_hist.argtypes = [C.POINTER(ParamHistArgs), C.c_void_p]
+    lib.bnn_mc_score_workspace_bytes.restype = C.c_size_t
+    lib.bnn_mc_score_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.bnn_mc_score.restype = C.c_int
+    lib.bnn_mc_score.argtypes = [C.POINTER(McScoreArgs), C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

@@ -18,7 +18,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .epoch import DeviceDataset, DeviceLoader, EpochRunner
+from .epoch import DeviceDataset, DeviceLoader, EpochRunner, fill_rows
 from .ops import BnnHipError
 from .runtime import state
 
@@ -123,7 +123,7 @@ class ActivePool:
         self._words = torch.tensor([idx.size, 0], dtype=torch.int32, device=self.device)   # n_labelled, the last launch's winners
         self.n_labelled = int(idx.size)
         self.round = 0                  # acquisitions so far: word 1 of the random scores' counter
-        self._workspace = self._d255 = self._xb = None
+        self._workspace = self._xb = None
         self._evals = {}
 
     def __len__(self):
@@ -146,16 +146,8 @@ class ActivePool:
 
     # ---- scoring
     def _fill(self, dst: torch.Tensor, a: int, b: int):
-        """Rows a .. b-1 of the data set as fp32 into dst [rows >= b - a, d] (uint8 as u / 255, IEEE division: the staging
-        kernel's conversion), zero rows behind them."""
-        x = self.dataset.x
-        dst[:b - a].copy_(x[a:b])
-        if x.dtype == torch.uint8:
-            if self._d255 is None:
-                self._d255 = torch.full((1,), 255.0, dtype=torch.float32, device=self.device)
-            dst[:b - a].div_(self._d255)            # a device divisor: torch divides (a host scalar would multiply by 1 / 255)
-        if dst.shape[0] > b - a:
-            dst[b - a:].zero_()
+        """Rows a .. b-1 of the data set as fp32 into dst (epoch.fill_rows)."""
+        fill_rows(self.dataset, dst, a, b)
 
     def _evaluator(self, net, G: int, B: int, samples: int):
         from .engine import GraphedPredictive

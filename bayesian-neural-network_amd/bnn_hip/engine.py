@@ -898,6 +898,58 @@ class GraphedPredictive(GraphedElbo):
         return self.result
 
 
+def _score_unsharded(what: str):
+    if dist_info()[1] > 1:
+        raise ops.BnnHipError(f"{what}: the log predictive density needs every MC sample on one rank (sample sharding is on)")
+
+
+def mc_score(layers: Sequence[LayerSpec], x: torch.Tensor, y: torch.Tensor, samples: int, mode: str, sigma: float = 1.0,
+             bins: int = 10) -> "ops.Scores":
+    """F12: the held-out scores of `samples` stochastic passes of one minibatch against its targets (bnn_mc_score over
+    mc_forward's outputs; injected epsilon is honoured as there)."""
+    if mode not in ("classification", "regression"):
+        raise Exception("Training mode must be either 'regression' or 'classification'")
+    _score_unsharded("score")
+    return ops.mc_score(mc_forward(layers, x, samples), y, mode, sigma=sigma, bins=bins)
+
+
+class GraphedScore(GraphedElbo):
+    """F12 as a replayable evaluation: GraphedElbo's launch chain on static `.x` and `.y` with the score launch
+    (bnn_mc_score) behind it, FRESH epsilon on every replay; every replay ADDS its rows to one ops.Scores (`.scores`;
+    construction leaves it as it found it), so a loop `g.x.copy_(..); g.y.copy_(..); g.replay()` over a data set ends in
+    `g.scores.read()`.  `n_valid` (an attribute, read when a launch is enqueued: eager evaluations only) marks the rows
+    g * B + b >= n_valid of a stacked evaluation as padding.  `stacked`, `capture` as for GraphedPredictive.  A sample-sharded
+    job raises: merging log-sum-exps across ranks is not supported."""
+
+    def __init__(self, net, x: torch.Tensor, y: torch.Tensor, samples: int, sigma: float = 1.0, bins: int = 10, capture=True,
+                 stream: Optional[torch.cuda.Stream] = None, stacked: bool = False, scores=None, rows: bool = False):
+        if net.mode not in ("classification", "regression"):
+            raise Exception("Training mode must be either 'regression' or 'classification'")
+        _score_unsharded("GraphedScore")
+        self.scores = scores if scores is not None else ops.Scores(net.mode, bins, x.device)
+        if self.scores.mode != net.mode:
+            raise ops.BnnHipError(f"GraphedScore: the record holds {self.scores.mode} scores, the network's mode is {net.mode}")
+        self.score_sigma, self.n_valid, self.want_rows = float(sigma), None, bool(rows)
+        Cc = net._specs()[-1].in_out[1]
+        target = y.clone() if net.mode == "classification" else y.reshape(tuple(y.shape[:2 if stacked else 1]) + (Cc,)).clone()
+        saved = self.scores.record.clone()
+        super().__init__(net, x, target, samples, sigma=sigma, capture=capture, stream=stream, stacked=stacked)
+        self.scores.record.copy_(saved)                     # the warm-up / recorded passes of the construction do not count
+
+    @property
+    def y(self) -> torch.Tensor:
+        return self.target
+
+    def _enqueue(self):
+        super()._enqueue()
+        self.scores.accumulate(self.logits, self.target, groups=self.G, sigma=self.score_sigma, n_valid=self.n_valid,
+                               rows=self.want_rows)
+
+    def replay(self):
+        super().replay()
+        return self.scores
+
+
 def elbo_many(net, x: torch.Tensor, target: torch.Tensor, samples: int, sigma: float = 1.0) -> torch.Tensor:
     """Forward-only ELBO terms of G independent minibatches in ONE launch per layer: x [G, B, ...], target [G, B]
     (or [G, B, out] for regression).  Returns float32 [G, 4] = per minibatch {sum_s log p | sum_s KL, sum_s log q | 0,

@@ -149,6 +149,37 @@ class DeviceLoader:
         self.end_epoch()
 
 
+class EvalLoader:
+    """An evaluation pass over a DeviceDataset in identity order, for epoch.score: no step object is built on its
+    minibatches, so with drop_last=False a short last minibatch is allowed (it is padded to batch_size and the padding
+    rows are excluded from the scores)."""
+    shuffle = False
+
+    def __init__(self, dataset: DeviceDataset, batch_size: int, drop_last: bool = False):
+        self.dataset, self.batch_size, self.drop_last = dataset, int(batch_size), bool(drop_last)
+        N = len(dataset)
+        if not 1 <= self.batch_size <= N:
+            raise BnnHipError(f"EvalLoader: batch_size must lie in [1, {N}]")
+        self.num_batches = N // self.batch_size if self.drop_last else (N + self.batch_size - 1) // self.batch_size
+
+    def __len__(self):
+        return self.num_batches
+
+
+def fill_rows(dataset: DeviceDataset, dst: torch.Tensor, a: int, b: int):
+    """Rows a .. b-1 of the data set as fp32 into dst [rows >= b - a, d] (uint8 as u / 255, IEEE division: the staging
+    kernel's conversion), zero rows behind them."""
+    x = dataset.x
+    dst[:b - a].copy_(x[a:b])
+    if x.dtype == torch.uint8:
+        d255 = getattr(dataset, "_d255", None)
+        if d255 is None:
+            d255 = dataset._d255 = torch.full((1,), 255.0, dtype=torch.float32, device=dataset.device)
+        dst[:b - a].div_(d255)                  # a device divisor: torch divides (a host scalar would multiply by 1 / 255)
+    if dst.shape[0] > b - a:
+        dst[b - a:].zero_()
+
+
 class EpochRunner:
     """One epoch of the reference's train_step on a train.GraphedTrainStep or a dense_train.GraphedDenseTrainStep:
     run_epoch() = one bnn_epoch_permutation, then M x (bnn_epoch_stage into the step's own x, x16, y and beta, the step's
@@ -231,3 +262,61 @@ def evaluate(net, loader: DeviceLoader, samples: int, chunk: int = 16) -> int:
                 correct.add_((torch.argmax(net(x), dim=1) == y).sum())
         flush()
     return int(correct.item())
+
+
+def score(net, loader, samples: int, *, sigma: float = 1.0, bins: int = 10, chunk: int = 16):
+    """F12 over a whole data set: the held-out scores (an ops.Scores; `.read()` is the one copy) of every row the loader
+    covers -- a DeviceLoader or an EvalLoader, walked in identity order (the scores do not depend on the order).  With
+    drop_last=False a short last minibatch is padded with zero rows that bnn_mc_score's n_valid excludes; with
+    drop_last=True the rows behind the last full minibatch are left out, as `evaluate` leaves them out.
+    Bayesian networks run the stacked evaluation ActivePool.score runs: `chunk` minibatches per launch group, minibatch g
+    drawing the MC-sample indices the g-th call of a per-minibatch loop would.  MLP_Dropout: mc_forward per minibatch; MLP:
+    the plain forward as one sample.  No host synchronisation before read()."""
+    import networks
+    from . import mcdropout
+    ds, B, samples = loader.dataset, int(loader.batch_size), int(samples)
+    ops.require_device(ds.x)
+    N, d = ds.x.shape
+    rows = (N // B) * B if loader.drop_last else N
+    nb = (rows + B - 1) // B
+    scores = ops.Scores(net.mode, bins, ds.device)
+    cls = net.mode == "classification"
+    k = 1 if cls else ds.y.shape[1]
+    with torch.no_grad():
+        if isinstance(net, networks.BayesianNetwork):
+            if samples < 1:
+                raise BnnHipError("score: samples must be >= 1")
+            from .engine import GraphedScore
+            cache = loader.__dict__.setdefault("_score_evals", {})
+            for g0 in range(0, nb, int(chunk)):
+                G = min(int(chunk), nb - g0)
+                a, b = g0 * B, min(rows, (g0 + G) * B)
+                key = (id(net), G, B, samples, state.math, state.form)
+                ev = cache.get(key)
+                if ev is None:
+                    x0 = torch.zeros((G, B, d), dtype=torch.float32, device=ds.device)
+                    y0 = torch.zeros((G, B) if cls else (G, B, k), dtype=ds.y.dtype, device=ds.device)
+                    ev = cache[key] = GraphedScore(net, x0, y0, samples, sigma=sigma, capture=False, stacked=True, scores=scores)
+                ev.scores, ev.score_sigma, ev.n_valid = scores, float(sigma), b - a
+                fill_rows(ds, ev.x.view(G * B, d), a, b)
+                yv = ev.y.view(G * B) if cls else ev.y.view(G * B, k)
+                yv[:b - a].copy_(ds.y[a:b])
+                if G * B > b - a:
+                    yv[b - a:].zero_()                  # padding: a valid label for the chain's own NLL; never scored
+                c = state.counter                      # where a per-minibatch loop started now would draw
+                ev.counter.fill_(c - (1 << 32) if c >= (1 << 31) else c)
+                ev.replay()
+        else:
+            dropout = isinstance(net, networks.MLP_Dropout) and samples > 0
+            xb = torch.empty((B, d), dtype=torch.float32, device=ds.device)
+            yb = torch.zeros((B,) if cls else (B, k), dtype=ds.y.dtype, device=ds.device)
+            xin = xb.view(B, 1, 1, d) if cls else xb
+            for g in range(nb):
+                a, b = g * B, min(rows, (g + 1) * B)
+                fill_rows(ds, xb, a, b)
+                yb[:b - a].copy_(ds.y[a:b])
+                if dropout:
+                    mcdropout.score(net, xin, yb, samples, sigma=sigma, record=scores, n_valid=b - a)
+                else:
+                    mcdropout.score_plain(net, xin, yb, sigma=sigma, record=scores, n_valid=b - a)
+    return scores

@@ -134,6 +134,26 @@ def predictive(mlp, x: torch.Tensor, samples: int, quantiles=None, sigma: float 
     return _first_minibatch(ops.mc_predictive(logits, mlp.mode, sigma=float(sigma), quantiles=q))
 
 
+def score(mlp, x: torch.Tensor, y: torch.Tensor, samples: int, sigma: float = 1.0, bins: int = 10, record=None,
+          n_valid: Optional[int] = None) -> "ops.Scores":
+    """F12: bnn_mc_score over mc_forward's outputs against the targets: the same scores as BayesianNetwork.score."""
+    if mlp.mode not in ("classification", "regression"):
+        raise Exception("Training mode must be either 'regression' or 'classification'")
+    return ops.mc_score(mc_forward(mlp, x, samples), y, mlp.mode, sigma=float(sigma), bins=int(bins), record=record,
+                        n_valid=n_valid)
+
+
+def score_plain(mlp, x: torch.Tensor, y: torch.Tensor, sigma: float = 1.0, bins: int = 10, record=None,
+                n_valid: Optional[int] = None) -> "ops.Scores":
+    """F12 for a deterministic network: its forward as the single sample of bnn_mc_score."""
+    if mlp.mode not in ("classification", "regression"):
+        raise Exception("Training mode must be either 'regression' or 'classification'")
+    ops.require_device(x)
+    with torch.no_grad():
+        out = mlp(x).float().contiguous()
+    return ops.mc_score(out.unsqueeze(0), y, mlp.mode, sigma=float(sigma), bins=int(bins), record=record, n_valid=n_valid)
+
+
 class GraphedDropoutPredictive:
     """predictive() for one input shape as a replayable evaluation: static input `.x` ([B, in], the flattened input),
     static outputs, one launch per layer plus the summary launch, all on one stream, captured once as a hipGraph

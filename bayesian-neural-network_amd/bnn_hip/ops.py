@@ -1930,3 +1930,169 @@ def param_hist_args(jobs: Sequence[dict], edges, *, records: Optional[torch.Tens
 def param_hist(a: L.ParamHistArgs):
     """bnn_param_hist: clear, bin and fold into a.records on the current stream; nothing is read back."""
     L.check(L.load().bnn_param_hist(C.byref(a), _stream()), "bnn_param_hist")
+
+
+# ---------------------------------------------------------------------------------------------------------------- F12 held-out scores
+@dataclass(frozen=True)
+class ClassificationScore:
+    """Scores.read() of a classification record: per-row means, and the top-label reliability bins ((i / M, (i + 1) / M])
+    of the MC-mean prediction.  ece = sum_b |sum conf_b - correct_b| / n, mce = the largest |confidence - accuracy| over the
+    non-empty bins; bin_accuracy / bin_confidence are NaN for an empty bin."""
+    n: int
+    accuracy: float
+    lpd: float
+    nll: float
+    brier: float
+    ece: float
+    mce: float
+    bin_count: "object"
+    bin_accuracy: "object"
+    bin_confidence: "object"
+
+
+@dataclass(frozen=True)
+class RegressionScore:
+    """Scores.read() of a regression record: n counts output elements (rows * outputs); lpd / nll are per element; `pit` are
+    the counts of the probability integral transform's M equal bins over [0, 1]."""
+    n: int
+    rows: int
+    rmse: float
+    mae: float
+    lpd: float
+    nll: float
+    pit: "object"
+
+    def coverage(self, level: float) -> float:
+        """The share of elements whose PIT lies in [1/2 - level/2, 1/2 + level/2): the empirical coverage of the central
+        `level` predictive interval, read off the histogram.  Raises unless M is even and level * M / 2 is an integer in
+        [1, M / 2] -- the histogram cannot answer otherwise."""
+        M = len(self.pit)
+        half = float(level) * M / 2.0
+        k = int(round(half))
+        if M < 2 or M % 2 or abs(half - k) > 1e-9 or not 1 <= k <= M // 2:
+            raise BnnHipError(f"coverage({level}): {M} PIT bins cannot answer (M must be even and level * M / 2 an integer in [1, M / 2])")
+        return float(self.pit[M // 2 - k:M // 2 + k].sum()) / self.n if self.n else float("nan")
+
+
+def parse_score_record(words, mode: str, bins: int):
+    """A host copy of a bnn_mc_score record (int64 [8 + 3 * bins]) as a ClassificationScore / RegressionScore."""
+    import numpy as np
+    w = np.ascontiguousarray(np.asarray(words, dtype=np.int64).reshape(-1))
+    M = int(bins)
+    if w.size != 8 + 3 * M:
+        raise BnnHipError(f"score record: {8 + 3 * M} words for {M} bins, got {w.size}")
+    f = w.view(np.float64)
+    b = w[8:].reshape(M, 3)
+    count = b[:, 0].copy()
+    n = int(w[0])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if mode == "classification":
+            ok, conf = b[:, 1].astype(np.float64), b[:, 2].copy().view(np.float64)
+            gap = np.abs(conf - ok)
+            live = count > 0
+            mce = float((gap[live] / count[live]).max()) if live.any() else 0.0
+            d = float(n) if n else float("nan")
+            return ClassificationScore(n=n, accuracy=int(w[1]) / d, lpd=float(f[2]) / d, nll=float(f[3]) / d,
+                                       brier=float(f[4]) / d, ece=float(gap.sum()) / d, mce=mce, bin_count=count,
+                                       bin_accuracy=np.where(live, ok / count, np.nan),
+                                       bin_confidence=np.where(live, conf / count, np.nan))
+        if mode == "regression":
+            ne = int(w[1])
+            d = float(ne) if ne else float("nan")
+            return RegressionScore(n=ne, rows=n, rmse=math.sqrt(float(f[4]) / d) if ne else float("nan"), mae=float(f[5]) / d,
+                                   lpd=float(f[2]) / d, nll=float(f[3]) / d, pit=count)
+    raise Exception("Training mode must be either 'regression' or 'classification'")
+
+
+class Scores:
+    """The device record of bnn_mc_score (include/bnn_hip.h F12) for one mode and bin count.  `accumulate(logits, targets)`
+    adds a launch's rows to it and `reset()` zeroes it: both are capturable and read nothing.  `read()` is one
+    device-to-host copy and returns a ClassificationScore / RegressionScore of plain Python floats and numpy arrays.
+    With rows=True, `.row_lpd` / `.row_nll` hold the last launch's per-row values ([G, B] fp32; padding rows unwritten)."""
+
+    def __init__(self, mode: str, bins: int = 10, device=None, record: Optional[torch.Tensor] = None):
+        if mode not in ("classification", "regression"):
+            raise Exception("Training mode must be either 'regression' or 'classification'")
+        self.mode, self.bins = mode, int(bins)
+        if not 0 <= self.bins <= L.SCORE_MAX_BINS:
+            raise BnnHipError(f"Scores: bins must lie in [0, {L.SCORE_MAX_BINS}] (BNN_SCORE_MAX_BINS)")
+        words = L.score_record_bytes(self.bins) // 8
+        if record is None:
+            if device is None:
+                raise BnnHipError("Scores: a device (or a record tensor) is needed")
+            record = torch.zeros(words, dtype=torch.int64, device=device)
+        if record.dtype != torch.int64 or not record.is_contiguous() or record.numel() != words:
+            raise BnnHipError(f"Scores: the record must be a contiguous int64 tensor of {words} words")
+        self.record = record
+        self.row_lpd = self.row_nll = None
+        self._ws = {}
+
+    def reset(self):
+        self.record.zero_()
+        return self
+
+    def accumulate(self, logits: torch.Tensor, targets: torch.Tensor, *, groups: Optional[int] = None, sigma: float = 1.0,
+                   n_valid: Optional[int] = None, rows: bool = False, overwrite: bool = False):
+        """One bnn_mc_score call on the current stream.  logits: float32 [G, S, B, C], or [G * S, B, C] with `groups` (the
+        stacked evaluation's output; groups = 1 by default); targets: int64 [G, B] labels or float32 [G, B, C]."""
+        lib = L.load()
+        require_device(logits, targets, self.record)
+        lg = _f32c(logits, "logits")
+        if lg.dim() == 4 and groups is None:
+            G, S, B, Cc = lg.shape
+        elif lg.dim() == 3 and lg.shape[0] % int(groups or 1) == 0:
+            G = int(groups or 1)
+            S, B, Cc = lg.shape[0] // G, lg.shape[1], lg.shape[2]
+        else:
+            raise BnnHipError("mc_score: logits must be [groups, samples, batch, outputs] or [groups * samples, batch, outputs]")
+        cls = self.mode == "classification"
+        want, dt = (G * B, torch.int64) if cls else (G * B * Cc, torch.float32)
+        if targets.dtype != dt or targets.numel() != want:
+            raise BnnHipError(f"mc_score: targets must be {dt} with {want} entries, got {targets.dtype} {tuple(targets.shape)}")
+        tg = targets if targets.is_contiguous() else targets.contiguous()
+        nv = G * B if n_valid is None else int(n_valid)
+        if not 1 <= nv <= G * B:
+            raise BnnHipError(f"mc_score: n_valid must lie in [1, {G * B}], got {nv}")
+        if not cls and not float(sigma) > 0.0:
+            raise BnnHipError("mc_score: sigma must be > 0")
+        need = int(lib.bnn_mc_score_workspace_bytes(G, B, Cc))
+        if need == 0:
+            raise BnnHipError("mc_score: the shape is outside the library's limits")
+        ws = self._ws.get(need)
+        if ws is None:
+            ws = self._ws[need] = torch.empty(need // 8 + 1, dtype=torch.int64, device=lg.device)
+        a = L.McScoreArgs()
+        a.struct_bytes = C.sizeof(L.McScoreArgs)
+        a.mode = L.NLL_CLASSIFICATION if cls else L.NLL_REGRESSION
+        a.groups, a.n_samples, a.batch, a.classes = G, S, B, Cc
+        a.logits, a.targets, a.n_valid = lg.data_ptr(), tg.data_ptr(), nv
+        a.sigma, a.n_bins, a.accumulate = float(sigma), self.bins, 0 if overwrite else 1
+        if rows:
+            if self.row_lpd is None or tuple(self.row_lpd.shape) != (G, B):
+                self.row_lpd = torch.empty((G, B), dtype=torch.float32, device=lg.device)
+                self.row_nll = torch.empty((G, B), dtype=torch.float32, device=lg.device)
+            a.row_lpd, a.row_nll = self.row_lpd.data_ptr(), self.row_nll.data_ptr()
+        a.record = self.record.data_ptr()
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+        a._keep = (lg, tg, ws, self.record, self.row_lpd, self.row_nll)
+        L.check(lib.bnn_mc_score(C.byref(a), _stream()), "bnn_mc_score")
+        return self
+
+    def read(self):
+        """One device-to-host copy of the record."""
+        return parse_score_record(self.record.cpu().numpy(), self.mode, self.bins)
+
+
+def mc_score(logits: torch.Tensor, targets: torch.Tensor, mode: str, *, sigma: float = 1.0, bins: int = 10,
+             n_valid: Optional[int] = None, record: Optional[Scores] = None, rows: bool = False, groups: Optional[int] = None) -> Scores:
+    """F12: bnn_mc_score over the MC outputs `logits` ([G, S, B, C], or [S, B, C] for one minibatch) and their targets.
+    Without `record` a fresh Scores holds this call alone; with one (of the same mode) the call's rows are added to it.
+    Rows with flat index g * B + b >= n_valid are padding: never loaded, never counted.  Nothing is read back before
+    `.read()`."""
+    if record is None:
+        require_device(logits)
+        return Scores(mode, bins, logits.device).accumulate(logits, targets, groups=groups, sigma=sigma, n_valid=n_valid,
+                                                             rows=rows, overwrite=True)
+    if record.mode != mode:
+        raise BnnHipError(f"mc_score: the record holds {record.mode} scores, not {mode}")
+    return record.accumulate(logits, targets, groups=groups, sigma=sigma, n_valid=n_valid, rows=rows)

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from .epoch import DeviceLoader, EpochRunner, evaluate as _evaluate
+from .epoch import DeviceLoader, EpochRunner, EvalLoader, evaluate as _evaluate, score as _score
 from .optim import FusedAdam, FusedSGD
 
 
@@ -141,6 +141,14 @@ class _ClassTask(_Task):
             correct = int(correct.item())
         self.acc = correct / total
 
+    def score(self, test_loader, bins=10):
+        """The held-out scores of the test set (epoch.score: log predictive density, expected NLL, Brier, accuracy, ECE /
+        MCE and the reliability bins) at the task's test_samples -- the read() result, one copy."""
+        self.net.eval()
+        if not isinstance(test_loader, (DeviceLoader, EvalLoader)):
+            raise TypeError("score: a bnn_hip.epoch.DeviceLoader or EvalLoader over the test set is needed")
+        return _score(self.net, test_loader, self._eval_samples(), bins=bins).read()
+
     def _eval_samples(self):
         return 0
 
@@ -212,6 +220,15 @@ class _RegTask(_Task):
     def _after_epoch(self):
         self.epoch_loss = float(self.loss_info[0] if self.bayesian else self.loss_info)      # one read per epoch
 
+    def _score(self, x_test, y_test, bins):
+        """net.score on the whole test set as one minibatch, sigma = the NLL's noise_tolerance: the read() result."""
+        self.net.eval()
+        dev = _device()
+        x = torch.as_tensor(x_test, dtype=torch.float32).to(dev)
+        y = torch.as_tensor(y_test, dtype=torch.float32).to(dev).reshape(x.shape[0], -1)
+        with torch.no_grad():
+            return self.net.score(x, y, self.test_samples, sigma=self.noise_tol, bins=bins).read()
+
 
 class BNN_Regression(_RegTask):
     _keys = (("batch_size", "batch_size"), ("num_batches", "num_batches"), ("n_samples", "train_samples"),
@@ -240,6 +257,12 @@ class BNN_Regression(_RegTask):
         with torch.no_grad():
             y = self.predict(x_test.to(_device()))
             return y.reshape(self.test_samples, -1).double().cpu().numpy()
+
+    def score(self, x_test, y_test, bins=10):
+        """The held-out scores of (x_test, y_test) under the N(f_s, noise_tolerance^2) mixture of test_samples passes: log
+        predictive density and expected NLL per element, RMSE / MAE of the predictive mean, the PIT histogram with
+        coverage(level)."""
+        return self._score(x_test, y_test, bins)
 
 
 class MLP_Regression(_RegTask):
@@ -276,6 +299,10 @@ class MCDropout_Regression(MLP_Regression):
     _sched_step = 500
     _dropout = True
 
+    def init_net(self, parameters):
+        super().init_net(parameters)
+        self.noise_tol = float(parameters.get("noise_tolerance", 1.0))     # score()'s sigma; the reference's wrapper has none
+
     def predict(self, X):
         """[test_samples, n, out]: the MC-dropout passes evaluate() collects."""
         return self.net.mc_forward(X, self.test_samples)
@@ -285,3 +312,8 @@ class MCDropout_Regression(MLP_Regression):
         with torch.no_grad():
             y = self.predict(x_test.to(_device()))
             return y.reshape(self.test_samples, -1).double().cpu().numpy()
+
+    def score(self, x_test, y_test, bins=10):
+        """As BNN_Regression.score, over test_samples MC-dropout passes.  The reference gives this wrapper no
+        noise_tolerance: `noise_tol` (1.0 unless the parameters carry "noise_tolerance") is the mixture's sigma."""
+        return self._score(x_test, y_test, bins)

@@ -291,6 +291,27 @@ class BayesianNetwork(nn.Module):
         return _engine.GraphedPredictive(self, x, int(samples), quantiles=quantiles, sigma=float(sigma), capture=capture,
                                          stacked=stacked)
 
+    def score(self, x, y, samples, *, sigma=1., bins=10, stacked=False):
+        """Extension (not in the reference): the held-out scores of `samples` stochastic passes against the targets `y`,
+        computed on the device in fp64 -- a bnn_hip.ops.Scores whose read() gives, for classification, the log posterior
+        predictive density, the expected NLL of the ELBO, the Brier score, accuracy and the top-label reliability bins (ECE,
+        MCE) of the MC-mean prediction; for regression the two likelihood scores under the N(f_s, sigma^2) mixture, RMSE /
+        MAE of the predictive mean and the PIT histogram with coverage(level).  `stacked`: x [G, batch, ...], y [G, batch
+        (, out)], G minibatches in one launch per layer (eps is drawn on the device then, never injected)."""
+        if stacked:
+            with torch.no_grad():
+                return _engine.GraphedScore(self, x, y, int(samples), sigma=float(sigma), bins=int(bins), capture=False,
+                                            stacked=True).replay()
+        return _engine.mc_score(self._specs(), self._flat(x), y, int(samples), self.mode, sigma=float(sigma), bins=int(bins))
+
+    def score_graph(self, x, y, samples, *, sigma=1., bins=10, stacked=False, capture=True, scores=None):
+        """Extension (not in the reference): score for this input shape as a replayable evaluation -- `g =
+        net.score_graph(x, y, samples)`, then `g.x.copy_(..); g.y.copy_(..); g.replay()` per minibatch and `g.scores.read()`
+        at the end (static buffers, fresh epsilon each replay, every replay adds to one record:
+        bnn_hip.engine.GraphedScore).  `capture`: True (hipGraph), "calls" or False."""
+        return _engine.GraphedScore(self, x, y, int(samples), sigma=float(sigma), bins=int(bins), capture=capture,
+                                    stacked=stacked, scores=scores)
+
     def elbo_many(self, inputs, targets, samples, sigma=1.):
         """Extension (not in the reference): the forward-only ELBO terms of G independent minibatches -- inputs
         [G, batch, ...], targets [G, batch] -- in one launch per layer instead of G sample_elbo calls under
@@ -379,7 +400,10 @@ class _PlainMLP(nn.Module):
 
 
 class MLP(_PlainMLP):
-    pass
+    def score(self, x, y, samples=1, *, sigma=1., bins=10):
+        """Extension (not in the reference): the held-out scores (bnn_hip.ops.Scores, as BayesianNetwork.score) of the
+        deterministic forward taken as one sample -- lpd = -nll then."""
+        return _mcdropout.score_plain(self, x, y, sigma=float(sigma), bins=int(bins))
 
 
 class MLP_Dropout(_PlainMLP):
@@ -407,6 +431,11 @@ class MLP_Dropout(_PlainMLP):
         bnn_hip.ops.Predictive as BayesianNetwork.predictive (entropy decomposition for classification; mean, variance,
         predictive_variance and np.percentile quantiles for regression)."""
         return _mcdropout.predictive(self, x, int(samples), quantiles=quantiles, sigma=float(sigma))
+
+    def score(self, x, y, samples, *, sigma=1., bins=10):
+        """Extension (not in the reference): the held-out scores of `samples` MC-dropout passes against the targets -- the
+        same bnn_hip.ops.Scores as BayesianNetwork.score."""
+        return _mcdropout.score(self, x, y, int(samples), sigma=float(sigma), bins=int(bins))
 
     def predictive_graph(self, x, samples, *, quantiles=None, sigma=1., capture=True):
         """Extension (not in the reference): predictive for this input shape as a replayable evaluation -- `p =

@@ -1508,6 +1508,81 @@ size_t bnn_param_hist_workspace_bytes(const bnn_param_hist_args* args);   /* 0 o
 int bnn_param_hist(const bnn_param_hist_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F12  held-out predictive scores — how good the predictive distribution of S MC outputs is on labelled data: what a
+ * caller otherwise composes per minibatch from forward_mc's [S, B, C] tensor with torch ops in fp32 (where a softmax that
+ * underflows turns the log density into -inf).  One entry reads every sample once, evaluates in the log domain in fp64 and
+ * accumulates a data-set-level record on the device; nothing is read back.
+ *
+ * bnn_mc_score   logits [G, S, B, C] (the layout of a stacked evaluation's output); rows with flat index g * B + b <
+ * n_valid are scored, the others are padding: their logits and targets are never loaded and they add nothing.
+ *
+ *   BNN_NLL_CLASSIFICATION, per valid row, p_s = softmax(z_s), pbar = mean_s p_s, y the int64 label:
+ *     lpd     = logsumexp_s(log p_{s,y}) - log S,   log p_{s,y} = z_{s,y} - logsumexp_c z_s      (log posterior predictive
+ *               density; log domain throughout: finite when every p_{s,y} underflows)
+ *     nll     = -(1/S) sum_s log p_{s,y}            (summed over rows: the mean over s of get_nll(output_s, target),
+ *               networks.py:183-190 -- the expected NLL of the ELBO)
+ *     brier   = sum_c (pbar_c - [c == y])^2
+ *     correct = (argmax_c pbar == y), lowest index on ties (as preds of bnn_mc_predictive);  conf = max_c pbar_c
+ *     bin i   = min(M - 1, ceil(conf M) - 1), the interval (i / M, (i + 1) / M]:  TOP-LABEL reliability bins of the
+ *               MC-mean prediction -- not bnn_ece's bins, which are the reference's all-classes binning over a
+ *               materialised probability table (every (row, class) probability is binned there).
+ *     The label is compared against c and never used as an index: a label outside [0, C) reads nothing out of bounds and
+ *     gives lpd = -inf (nll = +inf).
+ *   BNN_NLL_REGRESSION, per valid (row, output), f_s the samples, y the fp32 target, under the N(f_s, sigma^2) mixture:
+ *     lpd     = logsumexp_s(-(y - f_s)^2 / (2 sigma^2)) - log S - log sigma - log(2 pi) / 2
+ *     nll     = (1/S) sum_s (y - f_s)^2 / (2 sigma^2) + log sigma + log(2 pi) / 2
+ *     sq_err  = (y - mean_s f_s)^2,   abs_err = |y - mean_s f_s|
+ *     PIT u   = (1/S) sum_s Phi((y - f_s) / sigma),  Phi(t) = erfc(-t / sqrt 2) / 2;   bin i = min(M - 1, floor(u M))
+ *   All per-row arithmetic is fp64 (exp, log, erfc); the inputs are fp32.  A NaN logit in a valid row makes that row's
+ *   terms NaN and the NaN goes into the sums; such a row (element) goes to no bin, is not counted correct, and still
+ *   counts in rows (elements).
+ *
+ * Record (device, 8-byte aligned, BNN_SCORE_RECORD_BYTES(n_bins) bytes), in 8-byte words:
+ *     word   classification                                regression
+ *     0      int64 rows                                    int64 rows
+ *     1      int64 correct                                 int64 elements (rows * C)
+ *     2      f64 sum lpd                                   f64 sum lpd
+ *     3      f64 sum nll                                   f64 sum nll
+ *     4      f64 sum brier                                 f64 sum sq_err
+ *     5      0                                             f64 sum abs_err
+ *     6, 7   reserved (0)                                  reserved (0)
+ *     then per bin, 3 words:  {int64 count, int64 correct, f64 sum conf}    {int64 count, 0, 0}
+ *   accumulate = 0 overwrites the record, 1 adds the call's totals to it (in stream order).
+ * row_lpd / row_nll (optional, fp32 [G, B]): the per-row values, for regression summed over the C outputs of the row;
+ * padding rows are left unwritten.
+ * Determinism: a block writes one partial record to the workspace (its rows in order; lanes and waves by a fixed tree), a
+ * second one-block launch adds the partials in block-index order and writes / adds to the record.  No floating-point
+ * atomics: the same call repeated gives a bit-identical record.  Workspace: bnn_mc_score_workspace_bytes(G, B, C) bytes,
+ * 8-byte aligned, any contents.  Two launches (three for regression with row outputs); hipGraph-capturable.
+ *   Errors, checked in this order before any launch: struct_bytes: BNN_ERR_ABI; mode outside bnn_nll_mode: BNN_ERR_ENUM; a
+ *   dimension < 1, n_valid outside [1, G B], n_bins outside [0, BNN_SCORE_MAX_BINS], regression sigma not > 0:
+ *   BNN_ERR_SHAPE; args, logits, targets, record NULL, workspace NULL or short: BNN_ERR_NULL; record / workspace / int64
+ *   targets not 8-byte, logits / fp32 targets / row outputs not 4-byte aligned: BNN_ERR_ALIGN.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_SCORE_MAX_BINS 64
+#define BNN_SCORE_RECORD_BYTES(n_bins) (8 * (8 + 3 * (n_bins)))   /* 8-byte words */
+/* layout: 6 x 4-byte words, 2 pointers, int64, 4 x 4-byte words, 4 pointers, size_t */
+typedef struct bnn_mc_score_args {
+  uint32_t struct_bytes;
+  int32_t mode;                   /* bnn_nll_mode */
+  int32_t groups, n_samples, batch, classes;
+  const float* logits;            /* device [G, S, B, C] */
+  const void* targets;            /* classification int64 [G, B]; regression fp32 [G, B, C] */
+  int64_t n_valid;                /* 1 .. G * B */
+  float sigma;                    /* regression, > 0 */
+  int32_t n_bins;                 /* 0 .. BNN_SCORE_MAX_BINS */
+  int32_t accumulate;             /* 0 overwrites the record, 1 adds to it */
+  int32_t reserved;
+  float* row_lpd;                 /* optional device [G, B] */
+  float* row_nll;                 /* optional device [G, B] */
+  void* record;                   /* device, BNN_SCORE_RECORD_BYTES(n_bins) bytes */
+  void* workspace;
+  size_t workspace_bytes;
+} bnn_mc_score_args;
+size_t bnn_mc_score_workspace_bytes(int32_t groups, int32_t batch, int32_t classes);   /* 0 outside the limits */
+int bnn_mc_score(const bnn_mc_score_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
