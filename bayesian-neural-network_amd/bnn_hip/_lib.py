@@ -37,6 +37,7 @@ EXPORTS = (
     "bnn_acquire_topk_workspace_bytes", "bnn_acquire_topk", "bnn_acquire_compose", "bnn_acquire_random",
     "bnn_param_hist_workspace_bytes", "bnn_param_hist",
     "bnn_mc_score_workspace_bytes", "bnn_mc_score",
+    "bnn_sparse_count", "bnn_sparse_fill", "bnn_sparse_fwd",
 )
 
 
@@ -455,6 +456,32 @@ def score_record_bytes(n_bins: int) -> int:
     return 8 * (8 + 3 * int(n_bins))
 
 
+class SparseCountArgs(C.Structure):
+    """bnn_sparse_count_args (include/bnn_hip.h F13)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("out_features", C.c_int32), ("in_features", C.c_int32), ("ld", C.c_int32),
+                ("level", C.c_int32), ("reserved", C.c_int32), ("code", C.c_void_p), ("row_ptr", C.c_void_p)]
+
+
+class SparseFillArgs(C.Structure):
+    """bnn_sparse_fill_args (include/bnn_hip.h F13)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("out_features", C.c_int32), ("in_features", C.c_int32), ("ld", C.c_int32),
+                ("level", C.c_int32), ("transposed", C.c_int32), ("code", C.c_void_p), ("row_ptr", C.c_void_p),
+                ("mu", C.c_void_p), ("rho", C.c_void_p), ("col", C.c_void_p), ("mu_val", C.c_void_p), ("rho_val", C.c_void_p)]
+
+
+class SparseFwdArgs(C.Structure):
+    """bnn_sparse_fwd_args (include/bnn_hip.h F13)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("rows", C.c_int32), ("in_features", C.c_int32),
+                ("out_features", C.c_int32), ("eps_mode", C.c_int32), ("relu", C.c_int32), ("x_per_sample", C.c_int32),
+                ("x_feature_major", C.c_int32), ("y_feature_major", C.c_int32), ("layer_id", C.c_uint32),
+                ("sample_offset", C.c_uint32), ("seed", C.c_uint64), ("sample_group", C.c_uint32),
+                ("sample_group_stride", C.c_uint32), ("reserved0", C.c_int32), ("reserved1", C.c_int32),
+                ("sample_counter", C.c_void_p), ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("mu_val", C.c_void_p),
+                ("sigma_val", C.c_void_p), ("b_mu", C.c_void_p), ("b_sigma", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
+                ("eps", C.c_void_p), ("eps_b", C.c_void_p), ("eps_dump", C.c_void_p), ("eps_b_dump", C.c_void_p),
+                ("x_scratch", C.c_void_p)]
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -638,6 +665,9 @@ def _load_real():
     lib.bnn_mc_score_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.bnn_mc_score.restype = C.c_int
     lib.bnn_mc_score.argtypes = [C.POINTER(McScoreArgs), C.c_void_p]
+    for name, cls in (("bnn_sparse_count", SparseCountArgs), ("bnn_sparse_fill", SparseFillArgs), ("bnn_sparse_fwd", SparseFwdArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

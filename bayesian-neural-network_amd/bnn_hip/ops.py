@@ -2096,3 +2096,87 @@ def mc_score(logits: torch.Tensor, targets: torch.Tensor, mode: str, *, sigma: f
     if record.mode != mode:
         raise BnnHipError(f"mc_score: the record holds {record.mode} scores, not {mode}")
     return record.accumulate(logits, targets, groups=groups, sigma=sigma, n_valid=n_valid, rows=rows)
+
+
+# ---------------------------------------------------------------------------------------------------------------- F13 compressed network
+def sparse_count(code: torch.Tensor, level: int, row_ptr: torch.Tensor, *, out_features: int, in_features: int):
+    """bnn_sparse_count: row_ptr (int32 [out + 1]) = the exclusive scan of the per-row survivor counts (code > level) of the
+    canonical [>= out, ld] uint8 code image; row_ptr[out] is nnz."""
+    require_device(code, row_ptr)
+    if code.dtype != torch.uint8 or code.dim() != 2 or not code.is_contiguous() or code.shape[0] < out_features:
+        raise BnnHipError("sparse_count: code must be a contiguous uint8 [>= out_features, ld] image")
+    if row_ptr.dtype != torch.int32 or not row_ptr.is_contiguous() or row_ptr.numel() != out_features + 1:
+        raise BnnHipError("sparse_count: row_ptr must be int32 [out_features + 1]")
+    a = L.SparseCountArgs()
+    a.struct_bytes = C.sizeof(L.SparseCountArgs)
+    a.out_features, a.in_features, a.ld, a.level = int(out_features), int(in_features), code.shape[1], int(level)
+    a.code, a.row_ptr = code.data_ptr(), row_ptr.data_ptr()
+    L.check(L.load().bnn_sparse_count(C.byref(a), _stream()), "bnn_sparse_count")
+    return row_ptr
+
+
+def sparse_fill(code: torch.Tensor, level: int, row_ptr: torch.Tensor, mu: torch.Tensor, rho: torch.Tensor, col: torch.Tensor,
+                mu_val: torch.Tensor, rho_val: torch.Tensor, *, out_features: int, in_features: int, transposed: bool):
+    """bnn_sparse_fill: the survivors' columns (uint16, viewed as int16 storage) and their fp32 mu / rho, ascending within
+    a row, at the places row_ptr (from sparse_count, same code and level) gives them."""
+    require_device(code, row_ptr, mu, rho, col, mu_val, rho_val)
+    mu, rho = _f32c(mu, "mu"), _f32c(rho, "rho")
+    if mu.numel() != out_features * in_features or rho.numel() != mu.numel():
+        raise BnnHipError("sparse_fill: mu and rho must hold out_features * in_features elements")
+    if code.dtype != torch.uint8 or code.dim() != 2 or not code.is_contiguous() or code.shape[0] < out_features:
+        raise BnnHipError("sparse_fill: code must be a contiguous uint8 [>= out_features, ld] image")
+    if col.dtype != torch.int16 or mu_val.dtype != torch.float32 or rho_val.dtype != torch.float32 or \
+            not (col.numel() == mu_val.numel() == rho_val.numel()) or row_ptr.dtype != torch.int32 or row_ptr.numel() != out_features + 1:
+        raise BnnHipError("sparse_fill: col int16 (uint16 bits), mu_val / rho_val float32, all [nnz]; row_ptr int32 [out + 1]")
+    a = L.SparseFillArgs()
+    a.struct_bytes = C.sizeof(L.SparseFillArgs)
+    a.out_features, a.in_features, a.ld, a.level = int(out_features), int(in_features), code.shape[1], int(level)
+    a.transposed = int(bool(transposed))
+    a.code, a.row_ptr, a.mu, a.rho = code.data_ptr(), row_ptr.data_ptr(), mu.data_ptr(), rho.data_ptr()
+    a.col, a.mu_val, a.rho_val = col.data_ptr(), mu_val.data_ptr(), rho_val.data_ptr()
+    L.check(L.load().bnn_sparse_fill(C.byref(a), _stream()), "bnn_sparse_fill")
+
+
+def sparse_fwd_args(*, row_ptr: torch.Tensor, col: torch.Tensor, mu_val: torch.Tensor, sigma_val: Optional[torch.Tensor],
+                    b_mu: torch.Tensor, b_sigma: Optional[torch.Tensor], x: torch.Tensor, y: torch.Tensor, n_samples: int,
+                    rows: int, in_features: int, out_features: int, eps_mode: int, relu: bool, x_per_sample: int = 0,
+                    x_feature_major: bool = False, y_feature_major: bool = False, layer_id: int = 0, seed: int = 0,
+                    sample_offset: int = 0, sample_counter: Optional[torch.Tensor] = None, sample_group: int = 0,
+                    sample_group_stride: int = 0, eps: Optional[torch.Tensor] = None, eps_b: Optional[torch.Tensor] = None,
+                    eps_dump: Optional[torch.Tensor] = None, eps_b_dump: Optional[torch.Tensor] = None,
+                    x_scratch: Optional[torch.Tensor] = None) -> L.SparseFwdArgs:
+    """The argument block of bnn_sparse_fwd for one layer (include/bnn_hip.h F13).  x [x_rows, rows, in] or, feature-major,
+    [x_rows, in, rows]; y [S, rows, out] or [S, out, rows]; eps / eps_dump [S, nnz], eps_b / eps_b_dump [S, out]."""
+    tensors = (row_ptr, col, mu_val, sigma_val, b_mu, b_sigma, x, y, sample_counter, eps, eps_b, eps_dump, eps_b_dump, x_scratch)
+    require_device(*tensors)
+    if any(t is not None and not t.is_contiguous() for t in tensors):
+        raise BnnHipError("sparse_fwd: contiguous tensors")
+    if row_ptr.dtype != torch.int32 or row_ptr.numel() != out_features + 1 or col.dtype != torch.int16:
+        raise BnnHipError("sparse_fwd: row_ptr int32 [out + 1], col int16 (uint16 bits)")
+    for name, t in (("mu_val", mu_val), ("sigma_val", sigma_val), ("b_mu", b_mu), ("b_sigma", b_sigma), ("x", x), ("y", y),
+                    ("eps", eps), ("eps_b", eps_b), ("eps_dump", eps_dump), ("eps_b_dump", eps_b_dump), ("x_scratch", x_scratch)):
+        if t is not None and t.dtype != torch.float32:
+            raise BnnHipError(f"sparse_fwd: {name} must be float32")
+    x_rows = 1 if x_per_sample == 0 else -(-int(n_samples) // int(x_per_sample))
+    if x.numel() != x_rows * rows * in_features or y.numel() != n_samples * rows * out_features or b_mu.numel() != out_features:
+        raise BnnHipError("sparse_fwd: x must hold x_rows * rows * in, y n_samples * rows * out and b_mu out elements")
+    if x_scratch is not None and x_scratch.numel() < x.numel():
+        raise BnnHipError("sparse_fwd: x_scratch must hold as many elements as x")
+    if sample_counter is not None and sample_counter.dtype not in (torch.int32, torch.uint32):
+        raise BnnHipError("sparse_fwd: sample_counter must be a 32-bit device word")
+    a = L.SparseFwdArgs()
+    a.struct_bytes = C.sizeof(L.SparseFwdArgs)
+    a.n_samples, a.rows, a.in_features, a.out_features = int(n_samples), int(rows), int(in_features), int(out_features)
+    a.eps_mode, a.relu, a.x_per_sample = int(eps_mode), int(bool(relu)), int(x_per_sample)
+    a.x_feature_major, a.y_feature_major = int(bool(x_feature_major)), int(bool(y_feature_major))
+    a.layer_id, a.sample_offset, a.seed = int(layer_id), int(sample_offset) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.sample_group, a.sample_group_stride = int(sample_group), int(sample_group_stride)
+    a.sample_counter, a.row_ptr, a.col, a.mu_val, a.sigma_val = _ptr(sample_counter), row_ptr.data_ptr(), col.data_ptr(), mu_val.data_ptr(), _ptr(sigma_val)
+    a.b_mu, a.b_sigma, a.x, a.y = b_mu.data_ptr(), _ptr(b_sigma), x.data_ptr(), y.data_ptr()
+    a.eps, a.eps_b, a.eps_dump, a.eps_b_dump, a.x_scratch = _ptr(eps), _ptr(eps_b), _ptr(eps_dump), _ptr(eps_b_dump), _ptr(x_scratch)
+    a._keep = tensors                 # (the structure owns what its pointers refer to)
+    return a
+
+
+def sparse_fwd(a: L.SparseFwdArgs):
+    L.check(L.load().bnn_sparse_fwd(C.byref(a), _stream()), "bnn_sparse_fwd")

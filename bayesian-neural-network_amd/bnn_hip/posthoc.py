@@ -270,6 +270,17 @@ class PruneSweep:
         survives the caller's level i exactly when its code > level_rank[i]."""
         return [(code[:fout, :fin], bcode[0, :fout]) for fin, fout, _, code, _, bcode in self._layers]
 
+    def compress(self, level_index, zero_signs=True):
+        """The network pruned at the caller's level `level_index` of this sweep as a CompressedNetwork (CSR, run over the
+        survivors only).  Reads the fp32 parameters of the sweep's network, which must not have changed since the sweep was
+        built, and the three nnz words (the one host read)."""
+        i = int(level_index)
+        if not 0 <= i < self.levels:
+            raise ops.BnnHipError(f"PruneSweep.compress: level_index must lie in [0, {self.levels})")
+        images = [(fin, fout, code, bcode) for fin, fout, _, code, _, bcode in self._layers]
+        return CompressedNetwork._build(_bayesian_layers(self.net), images, self.level_rank[i], bool(self.net.local_reparam),
+                                        self.mode, zero_signs, self.drop_percentages[i], self.thresholds[i:i + 1])
+
     def _plan(self, rows, dev):
         """The static buffers and argument blocks of a forward over `rows` rows (hidden activations padded to a multiple
         of 32 columns, zero there for good: the next layer's vector loads need no tail)."""
@@ -361,3 +372,304 @@ class PruneSweep:
                 ece_out, probs, correct = self._caller_order(ece_out), self._caller_order(probs), self._caller_order(correct)
             loss = self._caller_order(loss)
         return PruneSweepResult(self.mode, N, correct, loss, ece_out, probs, labels, self.thresholds, self.kept, bin_step)
+
+
+# ---------------------------------------------------------------------------------------------------- F13 compressed network
+_BIT_WEIGHTS = (1, 2, 4, 8, 16, 32, 64, 128)
+
+
+def _pack_bits(flags):
+    """bool [n] -> uint8 [ceil(n / 8)], bit i % 8 of byte i // 8."""
+    f = flags.flatten().to(torch.uint8)
+    f = torch.nn.functional.pad(f, (0, (-f.numel()) % 8)).view(-1, 8)
+    w = torch.tensor(_BIT_WEIGHTS, dtype=torch.uint8, device=f.device)
+    return (f * w).sum(1, dtype=torch.uint8)
+
+
+def _unpack_bits(packed, n):
+    w = torch.tensor(_BIT_WEIGHTS, dtype=torch.uint8, device=packed.device)
+    return ((packed[:, None] & w) != 0).flatten()[:n]
+
+
+def compressed_state_bytes(shapes, nnzs, zero_signs=True):
+    """The bytes CompressedNetwork.state_dict holds for layers of `shapes` [(in, out)] with `nnzs` surviving weights:
+    per layer 4 (out + 1) of row_ptr + nnz (2 + 4 + 4) of col, mu_val, rho_val + 2 * 4 out of the masked bias vectors
+    + (zero_signs) 2 ceil(in out / 8) of the sign bits of mu and rho."""
+    total = 0
+    for (fin, fout), nnz in zip(shapes, nnzs):
+        total += 4 * (fout + 1) + 10 * int(nnz) + 8 * fout
+        if zero_signs:
+            total += 2 * (-(-(fin * fout) // 8))
+    return total
+
+
+class _CsrLayer:
+    __slots__ = ("fin", "fout", "nnz", "layer_id", "row_ptr", "col", "mu_val", "rho_val", "sigma_val", "b_mu", "b_rho", "b_sigma",
+                 "mu_sign", "rho_sign")
+
+
+class CompressedNetwork:
+    """A BayesianNetwork pruned at one SNR level, kept as CSR and run over the surviving weights only (bnn_sparse_count,
+    bnn_sparse_fill, bnn_sparse_fwd): per layer row_ptr (int32 [out + 1]), col (uint16 bits in an int16 tensor), mu_val,
+    rho_val and the derived sigma_val = bnn_softplus(rho_val), the bias vectors multiplied by their mask, the mode and the
+    layer ids.  Build one with PruneSweep.compress(level_index) or posthoc.compress(net, drop_percentage).
+
+    The posterior this object samples: a surviving weight is N(mu, softplus(rho)^2) and draws the epsilon the dense
+    network draws for it (the weight-space Philox map on the canonical [out, in] indices, also for a local-reparameterisation
+    network: a draw from the same factorised posterior, not its activation-space draw); a pruned weight is EXACTLY zero in
+    every sample.  That is not what sampling a prune_weights copy gives: there a pruned weight has mu = rho = 0, i.e.
+    sigma = softplus(0) = ln 2.
+
+    Arithmetic: exact fp32, one ascending fmaf chain per output element, whatever the math mode set -- the result depends on
+    no tiling, on no cut of a batch into calls and not on the number of samples.
+
+    Host reads: construction reads the three nnz words back ONCE, to size the arrays; that is the only one.  forward /
+    forward_mc allocate their buffers at the first call for a (rows, samples) shape and then neither allocate nor read
+    anything back, so they can be captured; they return their OWN static buffer, overwritten by the next call of that shape
+    (clone it to keep it).  A captured forward_mc bakes x's address, the seed and sample_offset: pass a device
+    `sample_counter` to draw fresh epsilon on every replay.
+
+    `zero_signs` (default True) also keeps one bit per dense weight for each of mu and rho: the sign of the zero that
+    prune_weights' `mu * 0` leaves, so that to_dense() equals prune_weights on a copy bit for bit; without them to_dense()
+    writes +0 there (equal in value) and state_bytes shrinks by in * out / 4 bytes per layer."""
+
+    def __init__(self, layers, mode, local_reparam, drop_percentage=None, threshold=None):
+        self._layers, self.mode, self.local_reparam = list(layers), mode, bool(local_reparam)
+        self.drop_percentage, self.threshold = drop_percentage, threshold
+        self._plans = {}
+
+    # ------------------------------------------------------------------------------------------------ construction
+    @classmethod
+    def _build(cls, net_layers, images, rank, lr, mode, zero_signs, drop_percentage=None, threshold=None):
+        """images: per layer (fin, fout, code [>= out, ld], bcode [1, >= out]) of a sweep; rank: the level's threshold rank."""
+        with torch.no_grad():
+            rps = []
+            for (fin, fout, code, _bcode) in images:
+                rp = torch.empty(fout + 1, dtype=torch.int32, device=code.device)
+                rps.append(ops.sparse_count(code, rank, rp, out_features=fout, in_features=fin))
+            nnzs = [int(v) for v in torch.stack([rp[-1] for rp in rps]).cpu().tolist()]      # the one host read
+            out = []
+            for l, (fin, fout, code, bcode), rp, nnz in zip(net_layers, images, rps, nnzs):
+                dev = code.device
+                c = _CsrLayer()
+                c.fin, c.fout, c.nnz, c.layer_id, c.row_ptr = fin, fout, nnz, int(getattr(l, "_layer_id", len(out))), rp
+                c.col = torch.zeros(max(nnz, 1), dtype=torch.int16, device=dev)              # (never an empty tensor: its address is NULL)
+                c.mu_val = torch.zeros(max(nnz, 1), dtype=torch.float32, device=dev)
+                c.rho_val = torch.zeros(max(nnz, 1), dtype=torch.float32, device=dev)
+                wmu, wrho = l.weight_mu.detach(), l.weight_rho.detach()
+                ops.sparse_fill(code, rank, rp, wmu, wrho, c.col, c.mu_val, c.rho_val, out_features=fout, in_features=fin,
+                                transposed=lr)
+                keep = bcode[0, :fout] > rank
+                bmu, brho = l.bias_mu.detach(), l.bias_rho.detach()
+                c.b_mu = torch.where(keep, bmu, bmu * 0.0).contiguous()                      # prune_weights' mu * 0: a signed zero
+                c.b_rho = torch.where(keep, brho, brho * 0.0).contiguous()
+                c.mu_sign = _pack_bits(torch.signbit(wmu)) if zero_signs else None           # (source layout, flattened)
+                c.rho_sign = _pack_bits(torch.signbit(wrho)) if zero_signs else None
+                cls._derive(c)
+                out.append(c)
+        return cls(out, mode, lr, drop_percentage, threshold)
+
+    @staticmethod
+    def _derive(c):
+        """What is not state: sigma_val and the masked bias sigma, from the bits bnn_softplus gives."""
+        c.sigma_val = ops.softplus(c.rho_val)
+        keep = (c.b_mu != 0) | (c.b_rho != 0)                          # a kept bias has rho != 0 or mu != 0 (SNR > threshold needs mu != 0)
+        c.b_sigma = torch.where(keep, ops.softplus(c.b_rho), torch.zeros_like(c.b_rho)).contiguous()
+
+    # ------------------------------------------------------------------------------------------------ size
+    @property
+    def nnz(self):
+        """Surviving weights per layer (biases not counted)."""
+        return tuple(c.nnz for c in self._layers)
+
+    @property
+    def density(self):
+        return sum(self.nnz) / float(sum(c.fin * c.fout for c in self._layers))
+
+    @property
+    def zero_signs(self):
+        return self._layers[0].mu_sign is not None
+
+    @property
+    def state_bytes(self):
+        """Bytes of state_dict(): compressed_state_bytes of the shapes and nnz."""
+        return compressed_state_bytes([(c.fin, c.fout) for c in self._layers], self.nnz, self.zero_signs)
+
+    # ------------------------------------------------------------------------------------------------ state
+    def state_dict(self):
+        sd = {}
+        for i, c in enumerate(self._layers):
+            p = f"l{i + 1}."
+            sd[p + "row_ptr"], sd[p + "col"] = c.row_ptr, c.col[:c.nnz]
+            sd[p + "mu_val"], sd[p + "rho_val"] = c.mu_val[:c.nnz], c.rho_val[:c.nnz]
+            sd[p + "bias_mu"], sd[p + "bias_rho"] = c.b_mu, c.b_rho
+            if c.mu_sign is not None:
+                sd[p + "mu_sign"], sd[p + "rho_sign"] = c.mu_sign, c.rho_sign
+        return sd
+
+    def load_state_dict(self, sd):
+        """Replace the CSR tensors by those of `sd` (a state_dict() of a network of the same shapes; device tensors);
+        sigma_val is derived again.  Reads the nnz words of `sd` (their lengths: no device read)."""
+        with torch.no_grad():
+            for i, c in enumerate(self._layers):
+                p = f"l{i + 1}."
+                rp = sd[p + "row_ptr"]
+                ops.require_device(rp)
+                if rp.numel() != c.fout + 1 or sd[p + "bias_mu"].numel() != c.fout:
+                    raise ops.BnnHipError("CompressedNetwork.load_state_dict: a layer of another shape")
+                nnz = int(sd[p + "col"].numel())
+                c.nnz, c.row_ptr = nnz, rp.to(torch.int32).contiguous().clone()
+                for name, dt, dst in (("col", torch.int16, "col"), ("mu_val", torch.float32, "mu_val"), ("rho_val", torch.float32, "rho_val")):
+                    buf = torch.zeros(max(nnz, 1), dtype=dt, device=rp.device)
+                    buf[:nnz].copy_(sd[p + name])
+                    setattr(c, dst, buf)
+                c.b_mu, c.b_rho = sd[p + "bias_mu"].clone().contiguous(), sd[p + "bias_rho"].clone().contiguous()
+                c.mu_sign = sd[p + "mu_sign"].clone() if p + "mu_sign" in sd else None
+                c.rho_sign = sd[p + "rho_sign"].clone() if p + "rho_sign" in sd else None
+                self._derive(c)
+        self._plans = {}
+        return self
+
+    def to_dense(self):
+        """The 12-key state dict of the pruned BayesianNetwork: what prune_weights(copy, None, drop_percentage) leaves --
+        bit for bit with zero_signs, equal in value (+0 for every pruned entry) without."""
+        sd = {}
+        for i, c in enumerate(self._layers):
+            dev = c.row_ptr.device
+            counts = (c.row_ptr[1:] - c.row_ptr[:-1]).to(torch.int64)
+            r = torch.repeat_interleave(torch.arange(c.fout, device=dev), counts, output_size=c.nnz)
+            k = c.col[:c.nnz].to(torch.int64) & 0xFFFF
+            flat = (k * c.fout + r) if self.local_reparam else (r * c.fin + k)         # index in the source layout
+            shape = (c.fin, c.fout) if self.local_reparam else (c.fout, c.fin)
+            for name, val, sign in (("weight_mu", c.mu_val, c.mu_sign), ("weight_rho", c.rho_val, c.rho_sign)):
+                d = torch.zeros(c.fin * c.fout, dtype=torch.float32, device=dev)
+                if sign is not None:
+                    d = torch.where(_unpack_bits(sign, d.numel()), -d, d)               # the signed zeros of mu * 0
+                d[flat] = val[:c.nnz]
+                sd[f"l{i + 1}.{name}"] = d.view(shape)
+            sd[f"l{i + 1}.bias_mu"], sd[f"l{i + 1}.bias_rho"] = c.b_mu.clone(), c.b_rho.clone()
+        return sd
+
+    # ------------------------------------------------------------------------------------------------ forward
+    def _plan(self, rows, S, dev):
+        from . import _lib as L
+        key = (rows, S)
+        pl = self._plans.get(key)
+        if pl is None:
+            c1, c2, c3 = self._layers
+            f = dict(dtype=torch.float32, device=dev)
+            xt = torch.empty((c1.fin, rows), **f)
+            h1, h2 = torch.empty((S, c1.fout, rows), **f), torch.empty((S, c2.fout, rows), **f)
+            logits = torch.empty((S, rows, c3.fout), **f)
+            x0 = xt.view(rows, c1.fin)                                                  # stands in for x until a call sets it
+            args = {}
+            for mode in (L.EPS_ZERO, L.EPS_PHILOX):
+                if mode == L.EPS_ZERO and S != 1:
+                    continue
+                args[mode] = [
+                    ops.sparse_fwd_args(row_ptr=c.row_ptr, col=c.col, mu_val=c.mu_val, sigma_val=c.sigma_val, b_mu=c.b_mu,
+                                        b_sigma=c.b_sigma, x=xin, y=yout, n_samples=S, rows=rows, in_features=c.fin,
+                                        out_features=c.fout, eps_mode=mode, relu=relu, x_per_sample=xps, x_feature_major=xfm,
+                                        y_feature_major=yfm, layer_id=c.layer_id, x_scratch=scr)
+                    for c, xin, yout, relu, xps, xfm, yfm, scr in ((c1, x0, h1, True, 0, False, True, xt),
+                                                                   (c2, h1, h2, True, 1, True, True, None),
+                                                                   (c3, h2, logits, False, 1, True, False, None))]
+            pl = self._plans[key] = (args, logits)
+        return pl
+
+    def _x(self, x):
+        ops.require_device(x)
+        fin = self._layers[0].fin
+        x = x.reshape(-1, fin) if self.mode == "classification" else x
+        if x.dim() != 2 or x.shape[1] != fin or x.dtype != torch.float32:
+            raise ops.BnnHipError(f"CompressedNetwork: x must be float32 [rows, {fin}]")
+        return x if x.is_contiguous() else x.contiguous()
+
+    def forward(self, x):
+        """The mean-weight forward (eps = 0): float32 [rows, classes], in the plan's own buffer."""
+        from . import _lib as L
+        x = self._x(x)
+        args, logits = self._plan(x.shape[0], 1, x.device)
+        a = args[L.EPS_ZERO]
+        a[0].x = x.data_ptr()
+        for al in a:
+            ops.sparse_fwd(al)
+        return logits[0]
+
+    __call__ = forward
+
+    def forward_mc(self, x, samples, seed=None, sample_offset=None, sample_counter=None):
+        """[samples, rows, classes]: `samples` draws of the surviving weights, global MC sample indices sample_offset ..
+        (the next unused ones by default, as BayesianNetwork.forward_mc), Philox key `seed` (the process seed by default);
+        `sample_counter`: an optional device int32 word added to sample_offset when the kernels run."""
+        from . import _lib as L
+        from .runtime import state, take_samples
+        x, S = self._x(x), int(samples)
+        args, logits = self._plan(x.shape[0], S, x.device)
+        a = args[L.EPS_PHILOX]
+        first = take_samples(S) if sample_offset is None else int(sample_offset)
+        sd = state.seed if seed is None else int(seed)
+        a[0].x = x.data_ptr()
+        for al in a:
+            al.seed, al.sample_offset = sd & 0xFFFFFFFFFFFFFFFF, first & 0xFFFFFFFF
+            al.sample_counter = None if sample_counter is None else sample_counter.data_ptr()
+            ops.sparse_fwd(al)
+        return logits
+
+    def predict_mc(self, x, samples, **kw):
+        """(preds [rows], probs [rows, classes]): the mean softmax over forward_mc's samples (ops.mc_predictive)."""
+        p = ops.mc_predictive(self.forward_mc(x, samples, **kw), "classification")
+        return p.preds[0], p.probs[0]
+
+    def predictive(self, x, samples, *, quantiles=None, sigma=1., **kw):
+        """BayesianNetwork.predictive over forward_mc's samples: ops.mc_predictive, one minibatch."""
+        from .engine import _first_minibatch
+        q = ops.quantile_levels(quantiles) if self.mode == "regression" else ()
+        return _first_minibatch(ops.mc_predictive(self.forward_mc(x, samples, **kw), self.mode, sigma=float(sigma), quantiles=q))
+
+    def score(self, x, y, samples, *, sigma=1., bins=10, **kw):
+        """BayesianNetwork.score over forward_mc's samples: ops.mc_score (an ops.Scores)."""
+        return ops.mc_score(self.forward_mc(x, samples, **kw), y, self.mode, sigma=float(sigma), bins=int(bins))
+
+    def evaluate(self, data, bin_step=0.1, batch_size=128):
+        """PruneSweep.evaluate for this one level with the mean-weight forward: a PruneSweepResult of one level (accuracy,
+        nll, ece, bins ... or sse); `data` a DeviceLoader or a pair of device tensors."""
+        from . import _lib as L
+        from .epoch import DeviceLoader
+        cls = self.mode == "classification"
+        C_ = self._layers[2].fout
+        if isinstance(data, DeviceLoader):
+            N, batches, dev = len(data) * data.batch_size, iter(data), data.dataset.device
+        else:
+            X, Y = data
+            ops.require_device(X, Y)
+            N, dev, bs = int(X.shape[0]), X.device, int(batch_size)
+            batches = ((X[i:i + bs], Y[i:i + bs]) for i in range(0, N, bs))
+        loss = torch.zeros(1, dtype=torch.float64, device=dev)
+        probs = correct = labels = ece_out = None
+        if cls:
+            probs = torch.empty((1, N, C_), dtype=torch.float32, device=dev)
+            correct = torch.zeros(1, dtype=torch.int64, device=dev)
+            labels = torch.empty(N, dtype=torch.int64, device=dev)
+        mode = L.NLL_CLASSIFICATION if cls else L.NLL_REGRESSION
+        row0 = 0
+        with torch.no_grad():
+            for x, y in batches:
+                logits = self.forward(x).unsqueeze(0)
+                rows = logits.shape[1]
+                y = (y if cls else y.reshape(rows, C_)).contiguous()
+                if cls:
+                    labels[row0:row0 + rows].copy_(y)
+                ops.prune_sweep_tail(logits, y, mode=mode, probs=probs, correct=correct, loss=loss, row0=row0, n_total=N)
+                row0 += rows
+            if row0 != N:
+                raise ops.BnnHipError(f"CompressedNetwork.evaluate: the data handed out {row0} rows, not {N}")
+            if cls:
+                ece_out = ops.ece_bins(probs[0], labels, np.arange(0, 1.1, bin_step)).unsqueeze(0)
+        kept = torch.tensor([sum(self.nnz)], dtype=torch.int64)
+        return PruneSweepResult(self.mode, N, correct, loss, ece_out, probs, labels, self.threshold, kept, bin_step)
+
+
+def compress(net, drop_percentage=0.5, zero_signs=True):
+    """prune_weights(net, None, drop_percentage) without touching net: a one-level PruneSweep, compressed."""
+    return PruneSweep(net, (float(drop_percentage),)).compress(0, zero_signs=zero_signs)

@@ -1583,6 +1583,117 @@ size_t bnn_mc_score_workspace_bytes(int32_t groups, int32_t batch, int32_t class
 int bnn_mc_score(const bnn_mc_score_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F13  compressed pruned network — the network F9 prunes at ONE level, kept as CSR (one row per output feature, the surviving
+ * columns ascending) and run over the survivors only: a pruned weight is neither stored, read nor drawn.  The posterior this
+ * samples: a survivor is N(mu, softplus(rho)^2), a pruned weight is a point mass at exactly zero -- not the sigma = ln 2 that
+ * sampling a prune_weights copy (mu = rho = 0) gives.
+ *
+ * bnn_sparse_count   one parameter tensor at level `level` of the canonical [out, ld] code image bnn_prune_codes writes:
+ *     row_ptr[0 .. out] (int32) = the exclusive scan of the per-row survivor counts #{i < in : code[o, i] > level};
+ *     row_ptr[out] is nnz.  Two launches (counts, then a one-block scan in place); integers only: bitwise reproducible.
+ *   Errors: NULL code, row_ptr: BNN_ERR_NULL; a dimension < 1, ld < in_features, out * in >= 2^31, level outside
+ *   [0, BNN_PRUNE_MAX_LEVELS): BNN_ERR_SHAPE; row_ptr not 4-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_sparse_fill   the second pass: for row o and its j-th survivor (columns ascending), at e = row_ptr[o] + j,
+ *     col[e] (uint16) = the column, mu_val[e] / rho_val[e] = the ORIGINAL fp32 parameters mu / rho (source [out, in], or
+ *     [in, out] with transposed = 1, as in bnn_prune_codes) -- not the sweep's mu_out, which is bf16 under bf16 math.
+ *     A wave owns a row and places its survivors by ballot and prefix count: the order depends on no scheduling.
+ *     sigma_val is not written here: the caller forms it with bnn_softplus over rho_val, so it holds the bits every
+ *     other kernel uses for that weight.  row_ptr must be what bnn_sparse_count wrote for the same code and level.
+ *   Errors: NULL code, row_ptr, mu, rho, col, mu_val, rho_val: BNN_ERR_NULL; a dimension < 1, ld < in_features,
+ *   in_features > 65536 (uint16 columns), level outside [0, BNN_PRUNE_MAX_LEVELS): BNN_ERR_SHAPE; row_ptr / mu / rho / mu_val /
+ *   rho_val not 4-byte, col not 2-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_sparse_fwd   one layer, n_samples MC samples, `rows` batch rows, exact fp32, one fixed chain per output element:
+ *       acc = 0;  for e = row_ptr[o] .. row_ptr[o+1]-1 (ascending):  acc = fmaf(x[xs, r, col[e]], w_e, acc)
+ *       y[s, r, o] = act(acc + b_o)
+ *     w_e = fmaf(sigma_val[e], eps_e, mu_val[e]) (mu_val[e] under BNN_EPS_ZERO); b_o = fmaf(b_sigma[o], eps_b, b_mu[o])
+ *     (b_mu[o] under BNN_EPS_ZERO) on dense [out] bias vectors the caller has multiplied by the bias mask (pruned bias:
+ *     b_mu = 0, b_sigma = 0).  The result depends on no tiling, on no cut of a batch into calls, and not on n_samples.
+ *     Epsilon: eps_e is element (row o, col col[e]) of the Philox map at the head of this file for tensor id 4 * layer_id + 0
+ *     and the global sample g, computed as for the DENSE [out, in] tensor -- group = o * ceil(in / 4) + (col >> 2), slot
+ *     col & 3 -- so a kept weight draws exactly the epsilon the dense network draws for it; the survivors that share a
+ *     group share one Philox call.  eps_b is kind 1, as in K1.  For a BayesianLinearLR network the SAME weight-space map is
+ *     used on the canonical [out, in] indices: a draw from the same factorised posterior over the weights, not the
+ *     activation-space draw (kind 2) the local-reparameterisation layers make.  sample_offset, sample_counter,
+ *     sample_group and sample_group_stride behave as in K1's argument block.  BNN_EPS_MEMORY reads eps [n_samples, nnz] and
+ *     eps_b [n_samples, out]; eps_dump / eps_b_dump (optional, same shapes) return what was used.
+ *     Layout: x is [x_rows, rows, in] (x_feature_major = 0) or [x_rows, in, rows] (1); x_rows = 1 when x_per_sample == 0,
+ *     else sample s reads x[s / x_per_sample].  y is [n_samples, rows, out] (y_feature_major = 0) or [n_samples, out, rows]
+ *     (1).  The lanes of a wave are batch rows and a row's CSR entries are wave-uniform, so a feature-major x makes a
+ *     column's gather one coalesced read: keep activations feature-major between layers.  With a row-major x and
+ *     x_scratch (fp32 [x_rows, in, rows]) a transpose launch ahead of the layer writes x there and the layer reads that.
+ *   Errors: NULL row_ptr, col, mu_val, x, y, b_mu (sigma_val, b_sigma unless BNN_EPS_ZERO; eps, eps_b under
+ *   BNN_EPS_MEMORY): BNN_ERR_NULL; a dimension < 1, n_samples > 65535, in_features > 65536, x_per_sample < 0:
+ *   BNN_ERR_SHAPE; eps_mode outside bnn_eps_mode: BNN_ERR_ENUM; a pointer not aligned to its element: BNN_ERR_ALIGN.
+ * ---------------------------------------------------------------------------------- */
+/* layout: 6 x 4-byte words, then 2 pointers */
+typedef struct bnn_sparse_count_args {
+  uint32_t struct_bytes;
+  int32_t out_features;
+  int32_t in_features;
+  int32_t ld;                                  /* row stride of code, elements */
+  int32_t level;                               /* the survivors have code > level */
+  int32_t reserved;
+  const uint8_t* code;                         /* [out, ld] */
+  int32_t* row_ptr;                            /* [out + 1] */
+} bnn_sparse_count_args;
+int bnn_sparse_count(const bnn_sparse_count_args* args, void* stream);
+
+/* layout: 6 x 4-byte words, then 7 pointers */
+typedef struct bnn_sparse_fill_args {
+  uint32_t struct_bytes;
+  int32_t out_features;
+  int32_t in_features;
+  int32_t ld;
+  int32_t level;
+  int32_t transposed;                          /* 0: mu / rho are [out, in]; 1: [in, out] */
+  const uint8_t* code;                         /* [out, ld] */
+  const int32_t* row_ptr;                      /* [out + 1], from bnn_sparse_count */
+  const float* mu;
+  const float* rho;
+  uint16_t* col;                               /* [nnz] */
+  float* mu_val;                               /* [nnz] */
+  float* rho_val;                              /* [nnz] */
+} bnn_sparse_fill_args;
+int bnn_sparse_fill(const bnn_sparse_fill_args* args, void* stream);
+
+/* layout: 12 x 4-byte words, the 8-byte seed, 4 x 4-byte words, then 14 pointers */
+typedef struct bnn_sparse_fwd_args {
+  uint32_t struct_bytes;
+  int32_t n_samples;
+  int32_t rows;                                /* batch rows */
+  int32_t in_features;
+  int32_t out_features;
+  int32_t eps_mode;                            /* bnn_eps_mode */
+  int32_t relu;
+  int32_t x_per_sample;                        /* 0: one x for all samples; g >= 1: sample s reads x[s / g] */
+  int32_t x_feature_major;                     /* x is [x_rows, in, rows] */
+  int32_t y_feature_major;                     /* y is [n_samples, out, rows] */
+  uint32_t layer_id;
+  uint32_t sample_offset;
+  uint64_t seed;
+  uint32_t sample_group;                       /* as in K1 */
+  uint32_t sample_group_stride;
+  int32_t reserved0, reserved1;
+  const uint32_t* sample_counter;              /* optional device word added to sample_offset at run time */
+  const int32_t* row_ptr;                      /* [out + 1] */
+  const uint16_t* col;                         /* [nnz] */
+  const float* mu_val;                         /* [nnz] */
+  const float* sigma_val;                      /* [nnz], bnn_softplus over rho_val */
+  const float* b_mu;                           /* [out], masked */
+  const float* b_sigma;                        /* [out], masked */
+  const float* x;
+  float* y;
+  const float* eps;                            /* BNN_EPS_MEMORY: [n_samples, nnz] */
+  const float* eps_b;                          /* BNN_EPS_MEMORY: [n_samples, out] */
+  float* eps_dump;                             /* optional [n_samples, nnz] */
+  float* eps_b_dump;                           /* optional [n_samples, out] */
+  float* x_scratch;                            /* optional [x_rows, in, rows]: the transposed copy of a row-major x */
+} bnn_sparse_fwd_args;
+int bnn_sparse_fwd(const bnn_sparse_fwd_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
