@@ -1469,7 +1469,14 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
     else stage_slow(t, pbuf, xbuf, wp_, wx_);                      // the K tail inside a k-step: clamped per-lane addresses
   };
   auto stage = [&](int t, int buf) __attribute__((always_inline)) { stage_sel(t, buf, buf, std::true_type{}, std::true_type{}); };
+  // A PHANTOM wave: its tile lies past the last one (N = 1200 is 75 tiles, the blocks hold 4: in the last feature group the
+  // wave fw == 3 owns tile 75).  It has x pieces of its pair to bring -- the pair's real waves read them -- and nothing else
+  // to do: no parameter pieces, no generator, no statistics, no MFMAs.  (wave-uniform: `tile` is scalar)
+  const bool phantom = tile >= T;
 
+  // the first step's pieces go out ahead of the bias draw (a Philox call and two loads they need not wait behind)
+  if (phantom) stage_sel(0, 0, 0, std::false_type{}, std::true_type{});
+  else stage(0, 0);
   // bias of this wave's tile: eps now, applied in the epilogue
   float bmu_pre = 0.f, brho_pre = 0.f, beps_pre = 0.f;
   if (q == 0 && n_ok) {
@@ -1477,7 +1484,6 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
     brho_pre = p.b_rho[n];
     beps_pre = bias_eps(p, n, s, gs, do_dump);
   }
-  stage(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -1486,9 +1492,10 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
   for (int m = 0; m < 8; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
   float s_e2 = 0.f, s_a = 0.f, s_ls = 0.f;
 
-  // One k-step.  FULL (block-uniform, compile-time in the body): every lane of the block holds real weights in this step --
-  // all four feature tiles inside N and the step's 32 k inside K -- so the edge masks (11 v_cndmask per step) are
-  // compiled out; the statistics and w run two lanes-worth per instruction (v_pk_fma_f32).  The kernel is bound by its
+  // One k-step.  FULL (wave-uniform, compile-time in the body): every lane of the WAVE holds real weights in this step --
+  // its feature tile inside N and the step's 32 k inside K -- so the edge masks (11 v_cndmask per step) are
+  // compiled out (the waves of a block may run different bodies: what they share is the step count and the barriers); the
+  // statistics and w run two lanes-worth per instruction (v_pk_fma_f32).  The kernel is bound by its
   // vector instruction stream once the parameters come through LDS (tools/k1b_ablate.py), so every one of them counts.
   typedef __attribute__((ext_vector_type(2))) float f32x2;
 #ifdef BNN_STAMPS
@@ -1563,6 +1570,7 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
     constexpr bool FULL = decltype(full_)::value;
     const int k = t * 32 + q * 8;
     const bool lane_ok = FULL || (n_ok && k < K);
+    const bool real = FULL || !phantom;                          // wave-uniform
     K2_T(st0);
     // the buffer staged here was last read in step t - 1 (barrier since)
     const bool staged = t + 1 < ksteps;                          // block-uniform
@@ -1573,115 +1581,129 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
 #else
     if (staged) {
 #endif
-      if (X3) stage_sel(t + 1, 0, cur ^ 1, std::false_type{}, std::true_type{});      // x of step t + 1 now, its parameters below
+      if (X3 || !real) stage_sel(t + 1, 0, cur ^ 1, std::false_type{}, std::true_type{});   // x of step t + 1 now (X3: its parameters below)
       else stage(t + 1, cur ^ 1);
     }
     // LDS reads by hand (ds_read_b128 in asm): a compiler-visible read of `sm` would be ordered behind EVERY LDS-DMA in
     // flight that may alias it -- s_waitcnt vmcnt(0) right behind the prefetch this step has just issued -- although
     // buffer t & 1 was complete at the last barrier.  The "+v" operands of the wait tie the consumers to it; the outputs
     // are early-clobber: a result register must not be the address register of a later read of the same statement.
+    // BARRIER INVARIANT: every wave of the block, phantom or real, masked or FULL body, passes each barrier of a step exactly
+    // once per step -- the one that closes the step and, X3, the one behind the parameter reads -- and all waves run the same
+    // `ksteps` steps.  A phantom wave therefore skips the COMPUTE only: the barriers and the waits in front of them stand
+    // outside the `real` branches.  (A wave that missed one would leave the block's other waves waiting forever.)
     const uint32_t pa = lds0 + (uint32_t)((p_idx(cur) + fw * 256 + lane) * 16);
     f32x4 m_lo, m_hi, g_lo, g_hi;
-    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
-                 : "=&v"(m_lo), "=&v"(m_hi), "=&v"(g_lo), "=&v"(g_hi) : "v"(pa));
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(m_lo), "+v"(m_hi), "+v"(g_lo), "+v"(g_hi));
     if (X3) {
+      // (read by a phantom wave too -- stale bytes it never uses: the reads precede a barrier all waves must reach)
+      asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
+                   : "=&v"(m_lo), "=&v"(m_hi), "=&v"(g_lo), "=&v"(g_hi) : "v"(pa));
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(m_lo), "+v"(m_hi), "+v"(g_lo), "+v"(g_hi));
       // every wave of the block holds its (mu, sigma) fragments in registers: the one parameter buffer is free for step t + 1
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
 #ifdef BNN_TUNE
-      if (t + 1 < ksteps && !(p.tune & 8)) stage_sel(t + 1, 0, 0, std::true_type{}, std::false_type{});
+      if (t + 1 < ksteps && real && !(p.tune & 8)) stage_sel(t + 1, 0, 0, std::true_type{}, std::false_type{});
 #else
-      if (t + 1 < ksteps) stage_sel(t + 1, 0, 0, std::true_type{}, std::false_type{});
+      if (t + 1 < ksteps && real) stage_sel(t + 1, 0, 0, std::true_type{}, std::false_type{});
 #endif
     }
-    K2_T(st1);
-    const f32x2 mu2[4] = {{m_lo[0], m_lo[1]}, {m_lo[2], m_lo[3]}, {m_hi[0], m_hi[1]}, {m_hi[2], m_hi[3]}};
-    const f32x2 sg2[4] = {{g_lo[0], g_lo[1]}, {g_lo[2], g_lo[3]}, {g_hi[0], g_hi[1]}, {g_hi[2], g_hi[3]}};
-    float e[8];
-    if (EPS == BNN_EPS_PHILOX) {
-      const uint32_t g = (uint32_t)n * (uint32_t)gpr + (uint32_t)(k >> 2);
-      uint4 pa_, pb_;
-      philox_pair<>(g, gs, wid, p.k0, p.k1, pa_, pb_);
-      box_muller8(pa_, pb_, e);
-    } else if (EPS == BNN_EPS_MEMORY) {
-      load8<true>(p.eps_w + ((size_t)s * N + n) * K + k, lane_ok ? 8 : 0, e);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) e[j] = 0.f;
-    }
-    if (p.eps_w_dump && do_dump) store8<true>(p.eps_w_dump + ((size_t)s * N + n) * K + k, lane_ok ? 8 : 0, e);
-    f32x2 w2[4], e2v = {0.f, 0.f}, av = {0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x2 ev = {e[2 * j], e[2 * j + 1]};
-      w2[j] = __builtin_elementwise_fma(sg2[j], ev, mu2[j]);
-      e2v = __builtin_elementwise_fma(ev, ev, e2v);
-    }
-    if (do_stats) {
-      float a, ls = 0.f;
-      if (p.prior_kind == BNN_PRIOR_GAUSS) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) av = __builtin_elementwise_fma(w2[j], w2[j], av);
-        a = av[0] + av[1];
+    if (real) {
+      if (!X3) {
+        asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
+                     : "=&v"(m_lo), "=&v"(m_hi), "=&v"(g_lo), "=&v"(g_hi) : "v"(pa));
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(m_lo), "+v"(m_hi), "+v"(g_lo), "+v"(g_hi));
+      }
+      K2_T(st1);
+      const f32x2 mu2[4] = {{m_lo[0], m_lo[1]}, {m_lo[2], m_lo[3]}, {m_hi[0], m_hi[1]}, {m_hi[2], m_hi[3]}};
+      const f32x2 sg2[4] = {{g_lo[0], g_lo[1]}, {g_lo[2], g_lo[3]}, {g_hi[0], g_hi[1]}, {g_hi[2], g_hi[3]}};
+      float e[8];
+      if (EPS == BNN_EPS_PHILOX) {
+        const uint32_t g = (uint32_t)n * (uint32_t)gpr + (uint32_t)(k >> 2);
+        uint4 pa_, pb_;
+        philox_pair<>(g, gs, wid, p.k0, p.k1, pa_, pb_);
+        box_muller8(pa_, pb_, e);
+      } else if (EPS == BNN_EPS_MEMORY) {
+        load8<true>(p.eps_w + ((size_t)s * N + n) * K + k, lane_ok ? 8 : 0, e);
       } else {
-        a = 0.f;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          a = add_log(a, mix_p(p, w2[j][0]));
-          a = add_log(a, mix_p(p, w2[j][1]));
-        }
+        for (int j = 0; j < 8; ++j) e[j] = 0.f;
       }
-      if (do_ls) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          ls = add_log(ls, sg2[j][0]);
-          ls = add_log(ls, sg2[j][1]);
-        }
-      }
-      const float e2 = e2v[0] + e2v[1];
-      s_e2 += lane_ok ? e2 : 0.f;
-      s_a += lane_ok ? a : 0.f;
-      s_ls += lane_ok ? ls : 0.f;
-    }
-    bf16x8 wa, wl = {};
-    if (X3) {
-      // the split pair, two weights per instruction where the ISA has one: hi = cvt_pk(w0, w1); its two floats by a shift and
-      // a mask of the packed word; the exact differences; lo = cvt_pk(d0, d1): 6 vector instructions per two weights
-      typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-      uint32_t hw[4], lw[4];
+      if (p.eps_w_dump && do_dump) store8<true>(p.eps_w_dump + ((size_t)s * N + n) * K + k, lane_ok ? 8 : 0, e);
+      f32x2 w2[4], e2v = {0.f, 0.f}, av = {0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const f32x2 wv = lane_ok ? w2[j] : f32x2{0.f, 0.f};
-        const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(wv, bf16x2));
-        const f32x2 hf = {__uint_as_float(hb << 16), __uint_as_float(hb & 0xffff0000u)};
-        hw[j] = hb;
-        lw[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(wv - hf, bf16x2));
+        const f32x2 ev = {e[2 * j], e[2 * j + 1]};
+        w2[j] = __builtin_elementwise_fma(sg2[j], ev, mu2[j]);
+        e2v = __builtin_elementwise_fma(ev, ev, e2v);
       }
-      wa = __builtin_bit_cast(bf16x8, make_uint4(hw[0], hw[1], hw[2], hw[3]));
-      wl = __builtin_bit_cast(bf16x8, make_uint4(lw[0], lw[1], lw[2], lw[3]));
-    } else {
+      if (do_stats) {
+        float a, ls = 0.f;
+        if (p.prior_kind == BNN_PRIOR_GAUSS) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        wa[2 * j] = lane_ok ? (__bf16)w2[j][0] : (__bf16)0.f;
-        wa[2 * j + 1] = lane_ok ? (__bf16)w2[j][1] : (__bf16)0.f;
+          for (int j = 0; j < 4; ++j) av = __builtin_elementwise_fma(w2[j], w2[j], av);
+          a = av[0] + av[1];
+        } else {
+          a = 0.f;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            a = add_log(a, mix_p(p, w2[j][0]));
+            a = add_log(a, mix_p(p, w2[j][1]));
+          }
+        }
+        if (do_ls) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            ls = add_log(ls, sg2[j][0]);
+            ls = add_log(ls, sg2[j][1]);
+          }
+        }
+        const float e2 = e2v[0] + e2v[1];
+        s_e2 += lane_ok ? e2 : 0.f;
+        s_a += lane_ok ? a : 0.f;
+        s_ls += lane_ok ? ls : 0.f;
       }
-    }
+      bf16x8 wa, wl = {};
+      if (X3) {
+        // the split pair, two weights per instruction where the ISA has one: hi = cvt_pk(w0, w1); its two floats by a shift and
+        // a mask of the packed word; the exact differences; lo = cvt_pk(d0, d1): 6 vector instructions per two weights
+        typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+        uint32_t hw[4], lw[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const f32x2 wv = lane_ok ? w2[j] : f32x2{0.f, 0.f};
+          const uint32_t hb = __builtin_bit_cast(uint32_t, __builtin_convertvector(wv, bf16x2));
+          const f32x2 hf = {__uint_as_float(hb << 16), __uint_as_float(hb & 0xffff0000u)};
+          hw[j] = hb;
+          lw[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(wv - hf, bf16x2));
+        }
+        wa = __builtin_bit_cast(bf16x8, make_uint4(hw[0], hw[1], hw[2], hw[3]));
+        wl = __builtin_bit_cast(bf16x8, make_uint4(lw[0], lw[1], lw[2], lw[3]));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          wa[2 * j] = lane_ok ? (__bf16)w2[j][0] : (__bf16)0.f;
+          wa[2 * j + 1] = lane_ok ? (__bf16)w2[j][1] : (__bf16)0.f;
+        }
+      }
 #ifdef BNN_STAMPS
-    asm volatile("" :: "v"(wa));
+      asm volatile("" :: "v"(wa));
 #endif
-    K2_T(st2);
-    mfma_phase(wa, wl, x_idx(cur) + sb * XT, m_lo);
+      K2_T(st2);
+      mfma_phase(wa, wl, x_idx(cur) + sb * XT, m_lo);
+#ifdef BNN_STAMPS
+      asm volatile("" :: "v"(acc[0]), "v"(acc[7]));
+      K2_T(st3);
+      ph[0] += st1 - st0; ph[1] += st2 - st1; ph[2] += st3 - st2;
+#endif
+    }
     // this wave's DMA pieces of step t + 1 have landed and its LDS reads of buffer `cur` are back; then the block meets
     // (a bare s_barrier: __syncthreads()'s fence would add the same vmcnt(0))
 #ifdef BNN_TUNE
     if (!(p.tune & 2)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if (!(p.tune & 1)) __builtin_amdgcn_s_barrier();
 #else
-#ifdef BNN_STAMPS
-    asm volatile("" :: "v"(acc[0]), "v"(acc[7]));
-    K2_T(st3);
-#endif
+    K2_T(st3w);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     K2_T(st4);
     __builtin_amdgcn_s_barrier();
@@ -1689,12 +1711,12 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
     asm volatile("" ::: "memory");
 #ifdef BNN_STAMPS
     K2_T(st5);
-    ph[0] += st1 - st0; ph[1] += st2 - st1; ph[2] += st3 - st2; ph[3] += st4 - st3; ph[4] += st5 - st4;
+    ph[3] += st4 - st3w; ph[4] += st5 - st4;
 #endif
   };
   {
-    const bool tiles_full = (tb * NF + NF) * 16 <= N;           // block-uniform
-    const int full_steps = tiles_full ? (K >> 5) : 0;           // steps whose 32 k are all inside K
+    const bool tile_full = (tile + 1) * 16 <= N;                // wave-uniform
+    const int full_steps = tile_full ? (K >> 5) : 0;            // steps whose 32 k are all inside K
     int t = 0, cur = 0;
 #pragma nounroll
     for (; t < full_steps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, std::true_type{});
@@ -1733,56 +1755,77 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
 #pragma unroll
     for (int i = 0; i < 4; ++i) bq[i] = bias_s[wave][q * 4 + i];
   }
-  if (nb < N) {
+  if (nb >= N) return;
+  // The eight 16-row output tiles.  FAST (block-uniform): N % 4 == 0 and all 128 rows of the block inside B -- one vector
+  // store per tile with nothing to test, and the output type and the ReLU compile-time too (YBF, RELU); otherwise those are
+  // the launch's run-time flags and every row and column is checked.  The row base is formed once and stepped by 16 rows.
+  auto store_tiles = [&](auto fast_, auto ybf_, auto relu_) __attribute__((always_inline)) {
+    constexpr bool FAST = decltype(fast_)::value;
+    const bool ybf = FAST ? decltype(ybf_)::value : p.y_bf16 != 0;
+    const bool relu = FAST ? decltype(relu_)::value : p.relu != 0;
+    const size_t esz = ybf ? 2 : 4;
+    const size_t y0 = (((size_t)s * B + m0 + r) * N + nb) * esz, ystep = (size_t)16 * N * esz;
+    char* yrow = reinterpret_cast<char*>(p.y) + y0;
+    char* lrow = X3 ? reinterpret_cast<char*>(p.y_lo) + y0 : nullptr;
 #pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const int brow = m0 + m * 16 + r;
-      if (brow < B) {
-        f32x4 v = acc[m];
+    for (int m = 0; m < 8; ++m, yrow += ystep, lrow += X3 ? ystep : 0) {
+      if (!FAST && m0 + m * 16 + r >= B) continue;
+      f32x4 v = acc[m];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float o = v[i] + bq[i];
-          if (p.relu) o = fmaxf(o, 0.f);
-          v[i] = o;
-        }
-        const size_t yoff = ((size_t)s * B + brow) * N + nb;
-        if (p.y_bf16) {
-          __bf16* yp = reinterpret_cast<__bf16*>(p.y) + yoff;
-          bf16x4 o;
+      for (int i = 0; i < 4; ++i) {
+        float o = v[i] + bq[i];
+        if (relu) o = fmaxf(o, 0.f);
+        v[i] = o;
+      }
+      if (ybf) {
+        __bf16* yp = reinterpret_cast<__bf16*>(yrow);
+        bf16x4 o;
 #pragma unroll
-          for (int i = 0; i < 4; ++i) o[i] = (__bf16)v[i];
-          if (vec_ok) {
-            *reinterpret_cast<bf16x4*>(yp) = o;
-          } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-              if (nb + i < N) yp[i] = o[i];
-          }
-          if (X3) {                                  // the low plane of the split pair
-            __bf16* lp = reinterpret_cast<__bf16*>(p.y_lo) + yoff;
-            bf16x4 l;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) l[i] = (__bf16)(v[i] - (float)o[i]);
-            if (vec_ok) {
-              *reinterpret_cast<bf16x4*>(lp) = l;
-            } else {
-#pragma unroll
-              for (int i = 0; i < 4; ++i)
-                if (nb + i < N) lp[i] = l[i];
-            }
-          }
+        for (int i = 0; i < 4; ++i) o[i] = (__bf16)v[i];
+        if (FAST || vec_ok) {
+          *reinterpret_cast<bf16x4*>(yp) = o;
         } else {
-          float* yp = reinterpret_cast<float*>(p.y) + yoff;
-          if (vec_ok) {
-            *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (nb + i < N) yp[i] = o[i];
+        }
+        if (X3) {                                  // the low plane of the split pair
+          __bf16* lp = reinterpret_cast<__bf16*>(lrow);
+          bf16x4 l;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) l[i] = (__bf16)(v[i] - (float)o[i]);
+          if (FAST || vec_ok) {
+            *reinterpret_cast<bf16x4*>(lp) = l;
           } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-              if (nb + i < N) yp[i] = v[i];
+              if (nb + i < N) lp[i] = l[i];
           }
+        }
+      } else {
+        float* yp = reinterpret_cast<float*>(yrow);
+        if (FAST || vec_ok) {
+          *reinterpret_cast<float4*>(yp) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (nb + i < N) yp[i] = v[i];
         }
       }
     }
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (vec_ok && m0 + 128 <= B) {                               // block-uniform, like the flags below
+    if (p.y_bf16) {
+      if (p.relu) store_tiles(yes, yes, yes);
+      else store_tiles(yes, yes, no);
+    } else {
+      if (p.relu) store_tiles(yes, no, yes);
+      else store_tiles(yes, no, no);
+    }
+  } else {
+    store_tiles(no, no, no);
   }
 }
 

@@ -19,7 +19,16 @@ constexpr float kLog2e = 1.442695040888963407f;
 
 // ---------------------------------------------------------------------------- Philox
 // One round = two 32x32->64 multiplies (v_mad_u64_u32 / v_mul_hi_u32 + v_mul_lo_u32) and
-// four xors; the key schedule is wave-uniform and lives on the scalar unit.
+// two three-input xors; the key schedule is wave-uniform and lives on the scalar unit.
+// a ^ b ^ c as ONE instruction: gfx950's v_bitop3_b32 with truth table 0x96 (the round key rides as its scalar operand).
+// The compiler does not form it from the two-xor expression; integer logic, so the same bits either way.
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+#else
+  return a ^ b ^ c;
+#endif
+}
 template <int ROUNDS = BNN_PHILOX_ROUNDS>
 __device__ __forceinline__ uint4 philox4x32(uint4 c, uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -28,7 +37,7 @@ __device__ __forceinline__ uint4 philox4x32(uint4 c, uint32_t k0, uint32_t k1) {
     const uint64_t p1 = (uint64_t)c.z * 0xCD9E8D57u;
     const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
     const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+    c = make_uint4(xor3(hi1, c.y, k0), lo1, xor3(hi0, c.w, k1), lo0);
     k0 += 0x9E3779B9u;
     k1 += 0xBB67AE85u;
   }
@@ -72,18 +81,35 @@ __device__ __forceinline__ void philox_pair(uint32_t group, uint32_t gsample, ui
   for (int i = 0; i < ROUNDS; ++i) {
     const uint64_t pa0 = (uint64_t)a.x * 0xD2511F53u, pb0 = (uint64_t)b.x * 0xD2511F53u;
     const uint64_t pa1 = (uint64_t)a.z * 0xCD9E8D57u, pb1 = (uint64_t)b.z * 0xCD9E8D57u;
-    a = make_uint4((uint32_t)(pa1 >> 32) ^ a.y ^ k0, (uint32_t)pa1, (uint32_t)(pa0 >> 32) ^ a.w ^ k1, (uint32_t)pa0);
-    b = make_uint4((uint32_t)(pb1 >> 32) ^ b.y ^ k0, (uint32_t)pb1, (uint32_t)(pb0 >> 32) ^ b.w ^ k1, (uint32_t)pb0);
+    a = make_uint4(xor3((uint32_t)(pa1 >> 32), a.y, k0), (uint32_t)pa1, xor3((uint32_t)(pa0 >> 32), a.w, k1), (uint32_t)pa0);
+    b = make_uint4(xor3((uint32_t)(pb1 >> 32), b.y, k0), (uint32_t)pb1, xor3((uint32_t)(pb0 >> 32), b.w, k1), (uint32_t)pb0);
     k0 += 0x9E3779B9u;
     k1 += 0xBB67AE85u;
   }
 }
 // four Box-Muller pairs, level by level: the uniforms, the four logarithms, the four square roots, the sines / cosines
 __device__ __forceinline__ void box_muller8(const uint4& a, const uint4& b, float out[8]) {
-  const float u[8] = {u01(a.x), u01(a.y), u01(a.z), u01(a.w), u01(b.x), u01(b.y), u01(b.z), u01(b.w)};
+  // the uniforms (u01's fma) and the radius scale two values per instruction (v_pk_fma_f32 / v_pk_mul_f32): per element
+  // the same correctly rounded fma / product as the scalar form, so the same bits
+  typedef __attribute__((ext_vector_type(2))) float f32x2;
+  const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  const f32x2 us = {2.3283064365386963e-10f, 2.3283064365386963e-10f}, uo = {1.1641532182693481e-10f, 1.1641532182693481e-10f};
+  float u[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const f32x2 c = {(float)w[2 * j], (float)w[2 * j + 1]};
+    const f32x2 v = __builtin_elementwise_fma(c, us, uo);
+    u[2 * j] = v[0];
+    u[2 * j + 1] = v[1];
+  }
   float rad[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) rad[j] = -2.0f * kLn2 * __builtin_amdgcn_logf(u[2 * j]);
+  for (int j = 0; j < 2; ++j) {
+    const f32x2 l = {__builtin_amdgcn_logf(u[4 * j]), __builtin_amdgcn_logf(u[4 * j + 2])};
+    const f32x2 v = l * f32x2{-2.0f * kLn2, -2.0f * kLn2};
+    rad[2 * j] = v[0];
+    rad[2 * j + 1] = v[1];
+  }
 #pragma unroll
   for (int j = 0; j < 4; ++j) rad[j] = __builtin_amdgcn_sqrtf(rad[j]);
 #pragma unroll

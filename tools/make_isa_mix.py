@@ -70,7 +70,14 @@ def main():
                                stderr=subprocess.DEVNULL)
             cand = [c for c in loops(asm[src], kname) if c[0]["mfma"] > 0]
             if key.startswith("bbb"):      # the Philox k-step loop: the shortest loop holding both the multiplies and the MFMAs
-                cls, ops, length = min((c for c in cand if c[0]["imul"] > 0), key=lambda c: c[2])
+                # -- of a WHOLE maskless step where the kernel has one: the compiler lays the wave-uniform branches of the masked
+                # step (edge masks = v_cndmask; K1b2's phantom-wave branch) out of line, and a backward branch inside it closes
+                # a range that is only part of an iteration.  So: the loops with a whole generator call, of those the ones with
+                # the fewest v_cndmask (the steady-state body), of those the shortest.
+                gen = [c for c in cand if c[0]["imul"] > 0]
+                calls = min(gen, key=lambda c: c[2])[0]["imul"]
+                masks = lambda c: sum(v for k, v in c[1].items() if k.startswith("v_cndmask"))
+                cls, ops, length = min((c for c in gen if c[0]["imul"] >= calls), key=lambda c: (masks(c), c[2]))
             else:                          # K3b: the unrolled steady-state body (six k-steps)
                 cls, ops, length = max(cand, key=lambda c: c[0]["mfma"])
             # the static body holds branches the benchmark configuration does not take: the scale-mixture prior (2 v_exp + 1

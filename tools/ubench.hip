@@ -162,6 +162,29 @@ __global__ void k(unsigned long long* out, float* sink, int iters) {
       acc += k1b_body24<0>(x, i, f); x += 6;
     } else if (WHAT == 14) { // 24 weights, map v3 candidate: 4 philox-7 calls, 24-bit radius / 16-bit angle
       acc += k1b_body24<1>(x, i, f); x += 4;
+    } else if (WHAT == 15 || WHAT == 16) {
+      // 16 three-input xors a ^ b ^ k with a wave-uniform k (the Philox round's shape), each feeding the next iteration's:
+      // 15 = two dependent v_xor_b32 each (32 in all), 16 = one v_bitop3_b32 (truth table 0x96) each
+      unsigned v[16], n[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] = x + j * 0x9E3779B9u;
+#pragma unroll 1
+      for (int u = 0; u < 8; ++u) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          if (WHAT == 15) {
+            unsigned t = v[j] ^ v[(j + 1) & 15];
+            asm volatile("" : "+v"(t));          // keeps the pair two plain xors, as the generator's were
+            n[j] = t ^ (unsigned)(i + u);
+          } else {
+            n[j] = __builtin_amdgcn_bitop3_b32(v[j], v[(j + 1) & 15], (unsigned)(i + u), 0x96);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = n[j] + 1u;   // (one v_add per value in both cases: no algebraic collapse across rounds)
+      }
+#pragma unroll
+      for (int j = 0; j < 16; ++j) x ^= v[j];
     }
   }
   unsigned long long t1 = __builtin_amdgcn_s_memtime();
@@ -173,10 +196,11 @@ int main() {
   const char* names[] = {"philox4x32_10 (4 u32)", "philox_normal4 (4 normals)", "softplus x8", "16 mad_u64_u32 (+32 xor)", "16 fma (+16 add)", "box_muller x2 (4 normals)",
                          "normal4, philox-10 mul_hi+mul_lo", "normal4, philox-7", "normal8, 1 philox-10, 16-bit u", "K1b body/8w: 2 philox-10",
                          "K1b body/8w: 2 philox-7", "K1b body/8w: 1 philox-10 16b", "K1b body/8w: 1 philox-7 16b",
-                         "body/24w: 6 philox-7 (map v2)", "body/24w: 4 philox-7 (v3: 24b/16b)"};
+                         "body/24w: 6 philox-7 (map v2)", "body/24w: 4 philox-7 (v3: 24b/16b)",
+                         "8 x (32 v_xor + 16 add)", "8 x (16 v_bitop3 + 16 add)"};
   unsigned long long* d; float* s; hipMalloc(&d, 1 << 20); hipMalloc(&s, 64 << 20);
   const int iters = 2000;
-  for (int what = (getenv("UBENCH_FROM") ? atoi(getenv("UBENCH_FROM")) : 0); what < 15; ++what) {
+  for (int what = (getenv("UBENCH_FROM") ? atoi(getenv("UBENCH_FROM")) : 0); what < 17; ++what) {
     for (int wps = 1; wps <= 4; ++wps) {   // waves per SIMD: block = wps*4 waves, one block per CU
       dim3 grid(256), block(wps * 256);
       for (int rep = 0; rep < 3; ++rep) {
@@ -196,6 +220,8 @@ int main() {
           case 12: hipLaunchKernelGGL(k<12>, grid, block, 0, 0, d, s, iters); break;
           case 13: hipLaunchKernelGGL(k<13>, grid, block, 0, 0, d, s, iters); break;
           case 14: hipLaunchKernelGGL(k<14>, grid, block, 0, 0, d, s, iters); break;
+          case 15: hipLaunchKernelGGL(k<15>, grid, block, 0, 0, d, s, iters); break;
+          case 16: hipLaunchKernelGGL(k<16>, grid, block, 0, 0, d, s, iters); break;
         }
       }
       hipDeviceSynchronize();
