@@ -16,6 +16,7 @@ EPS_PHILOX, EPS_MEMORY, EPS_ZERO = 0, 1, 2
 PRIOR_GAUSS, PRIOR_MIXTURE = 0, 1
 NLL_REGRESSION, NLL_CLASSIFICATION = 0, 1
 FORM_AUTO, FORM_TILE, FORM_GEMM, FORM_GEMM_KSLICE, FORM_BLOCK256 = 0, 1, 2, 3, 4
+LAYOUT_ROWS, LAYOUT_PIECES = 0, 1
 
 EXPORTS = (
     "bnn_version", "bnn_philox_rounds", "bnn_status_string",
@@ -65,6 +66,7 @@ class BbbFwdArgs(C.Structure):
         ("split_scratch", C.c_void_p), ("split_scratch_bytes", C.c_size_t), ("w_sigma", C.c_void_p),
         ("w_sampled", C.c_void_p), ("b_sampled", C.c_void_p), ("rider", C.c_void_p), ("y_bf16_copy", C.c_void_p),
         ("w_sampled_t_out", C.c_void_p), ("x_lo", C.c_void_p), ("y_lo", C.c_void_p),
+        ("x_layout", C.c_int32), ("y_layout", C.c_int32), ("w_pieces", C.c_void_p),
     ]
 
 
@@ -208,7 +210,9 @@ class PrepareArgs(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("n_softplus", C.c_int32),
                 ("rho", C.c_void_p * PREPARE_MAX), ("sigma", C.c_void_p * PREPARE_MAX), ("n", C.c_int64 * PREPARE_MAX),
                 ("cast_src", C.c_void_p), ("cast_dst", C.c_void_p), ("cast_dst_sq", C.c_void_p), ("cast_n", C.c_int64),
-                ("cast_dst_lo", C.c_void_p)]
+                ("cast_dst_lo", C.c_void_p), ("cast_layout", C.c_int32), ("cast_batch", C.c_int32), ("cast_features", C.c_int32),
+                ("mu", C.c_void_p * PREPARE_MAX), ("pieces", C.c_void_p * PREPARE_MAX),
+                ("rows", C.c_int32 * PREPARE_MAX), ("cols", C.c_int32 * PREPARE_MAX)]
 
 
 PREDICTIVE_MAX_QUANTILES = 8

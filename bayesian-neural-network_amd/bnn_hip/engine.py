@@ -677,6 +677,24 @@ class GraphedElbo:
                 self.w_pre[i] = torch.empty((S, n_i, k_i), dtype=torch.bfloat16, device=dev)
                 self.b_pre[i] = torch.empty((S, n_i), dtype=torch.float32, device=dev)
                 self.ws[i] = ops.sample_workspace(S, k_i, n_i, dev)
+        # Piece-order activations (ops.pieces_activation): layer i's input is in piece order exactly when layer i
+        # launches the pair block GEMM (K1b2) in bf16 math and its producer can write the layout -- the prepare launch's cast for
+        # the first layer, a K1b2 launch for a later one.  The last layer's input stays row-major (K1c / K1r read it).  The
+        # buffers keep their places (x16, bufs[i]) and carry the layout themselves, so whoever hands them to ops.bbb_plan /
+        # ops.bbb_linear_fwd launches the form the evaluation runs.
+        self.k1b2 = self._k1b2_layers() if state.pieces else [False] * nl
+        for i in range(nl - 1):
+            if self.k1b2[i] and i == 0 and self.x16 is not None:
+                self.x16 = ops.pieces_activation(self.x.shape, dev)
+            elif self.k1b2[i] and i > 0 and self.k1b2[i - 1]:
+                self.bufs[i - 1] = ops.pieces_activation(self.bufs[i - 1].shape, dev)
+        # ... and the (mu, sigma) of those layers once more in piece order, written by the prepare launch of every evaluation (mu
+        # changes between evaluations); the buffer rides on the layer's sigma tensor (ops.param_pieces)
+        self.wpieces = [ops.param_pieces(sp.in_out[1], sp.in_out[0], dev) if (k and state.param_pieces) else None
+                        for sp, k in zip(self.specs, self.k1b2)]
+        for w, pc in zip(self.wsigma, self.wpieces):
+            if pc is not None:
+                w.bnn_param_pieces = pc
         self.graph = None
         self.calls = None
         if capture == "calls":
@@ -722,7 +740,8 @@ class GraphedElbo:
         if self.x16 is not None or hoist:
             ops.eval_prepare([self.specs[i].m.weight_rho.detach() for i in hoist], [self.wsigma[i] for i in hoist],
                              cast=self.x if self.x16 is not None else None, cast_out=self.x16,
-                             cast_out_sq=self.x16_sq, cast_out_lo=self.x16_lo)
+                             cast_out_sq=self.x16_sq, cast_out_lo=self.x16_lo,
+                             mus=[self.specs[i].m.weight_mu.detach() for i in hoist], pieces=[self.wpieces[i] for i in hoist])
             if self.x16 is not None:
                 h, h_sq, h_lo = self.x16, self.x16_sq, self.x16_lo
         last = len(self.specs) - 1
@@ -740,9 +759,7 @@ class GraphedElbo:
                       ticket=self.ticket, scratch=self.scratch, group_samples=self.group)
         for i, sp in enumerate(self.specs):
             p = tuple(t.detach() for t in (sp.m.weight_mu, sp.m.weight_rho, sp.m.bias_mu, sp.m.bias_rho))
-            common = dict(n_samples=self.n_local, math_mode=math_mode, relu=sp.relu, y_dtype=self.bufs[i].dtype,
-                          eps_mode=L.EPS_PHILOX, seed=state.seed, layer_id=sp.layer_id, sample_offset=self.lo,
-                          sample_counter=self.counter, workspace=self.ws[i], out=self.bufs[i], form=state.form, **grp)
+            common = self._common_kw(i)
             if self.lr:
                 if self.lr_x3 and i == last:
                     common["math_mode"] = L.MATH_F32          # the narrow output layer: exact fp32 on the fp32 activations
@@ -764,9 +781,7 @@ class GraphedElbo:
                 if i == last:
                     ops.elbo_finalize(workspaces=self.ws, logits=self.bufs[i], **fin_kw)
             else:
-                kw = dict(prior=sp.m._prior_spec, want_stats=True, split_scratch=self.split[i], w_sigma=self.wsigma[i], **common)
-                if self.x3:
-                    kw.update(x_lo=h_lo if h.dtype == torch.bfloat16 else None, out_lo=self.bufs_lo[i])
+                kw = self._bbb_kw(i, h, h_lo, common)
                 if i == last and self.rows:
                     ops.bbb_final_fwd((h, None, None, None, None),
                                       dict(n_samples=self.n_local, prior=sp.m._prior_spec, math_mode=math_mode, relu=sp.relu,
@@ -776,17 +791,49 @@ class GraphedElbo:
                 elif i == last:
                     ops.bbb_final_fwd((h,) + p, kw, dict(workspaces=self.ws[:last], **fin_kw))
                 else:
-                    if i == self.pre_from:                   # the output layer's weights are drawn beside this layer
-                        kw["rider"] = ops.build_sample_job(
-                            [dict(w_mu=q.m.weight_mu.detach(), w_rho=q.m.weight_rho.detach(), b_mu=q.m.bias_mu.detach(),
-                                  b_rho=q.m.bias_rho.detach(), prior=q.m._prior_spec, layer_id=q.layer_id,
-                                  workspace=self.ws[j], w_out=self.w_pre[j], b_out=self.b_pre[j])
-                             for j, q in enumerate(self.specs) if j > i],
-                            n_samples=self.n_local, seed=state.seed, sample_offset=self.lo, sample_counter=self.counter, **grp)
                     ops.bbb_linear_fwd(h, *p, **kw)
             h, h_lo = self.bufs[i], self.bufs_lo[i]
         if self.lr:
             ops.elbo_finalize(workspaces=self.ws, logits=h, **fin_kw)
+
+    def _common_kw(self, i):
+        """The arguments every launch form of layer i shares."""
+        sp = self.specs[i]
+        grp = dict(sample_group=self.group, sample_group_stride=self.samples) if self.G > 1 else {}
+        return dict(n_samples=self.n_local, math_mode=self.math, relu=sp.relu, y_dtype=self.bufs[i].dtype,
+                    eps_mode=L.EPS_PHILOX, seed=state.seed, layer_id=sp.layer_id, sample_offset=self.lo,
+                    sample_counter=self.counter, workspace=self.ws[i], out=self.bufs[i], form=state.form, **grp)
+
+    def _bbb_kw(self, i, h, h_lo, common):
+        """The K1 arguments of Bayes-by-backprop layer i over the input h (beside the parameters)."""
+        sp = self.specs[i]
+        kw = dict(prior=sp.m._prior_spec, want_stats=True, split_scratch=self.split[i], w_sigma=self.wsigma[i], **common)
+        if self.x3:
+            kw.update(x_lo=h_lo if h.dtype == torch.bfloat16 else None, out_lo=self.bufs_lo[i])
+        if i == self.pre_from and i < len(self.specs) - 1:      # the output layer's weights are drawn beside this layer
+            grp = dict(sample_group=self.group, sample_group_stride=self.samples) if self.G > 1 else {}
+            kw["rider"] = ops.build_sample_job(
+                [dict(w_mu=q.m.weight_mu.detach(), w_rho=q.m.weight_rho.detach(), b_mu=q.m.bias_mu.detach(),
+                      b_rho=q.m.bias_rho.detach(), prior=q.m._prior_spec, layer_id=q.layer_id,
+                      workspace=self.ws[j], w_out=self.w_pre[j], b_out=self.b_pre[j])
+                 for j, q in enumerate(self.specs) if j > i],
+                n_samples=self.n_local, seed=state.seed, sample_offset=self.lo, sample_counter=self.counter, **grp)
+        return kw
+
+    def _k1b2_layers(self):
+        """Per layer: does its launch take the pair block GEMM (K1b2) in bf16 math?  Asked of the library's plan with the
+        arguments _enqueue hands the launch, over the row-major buffers (the plan does not depend on the layouts)."""
+        res = [False] * len(self.specs)
+        if self.lr or self.math != L.MATH_BF16:
+            return res
+        h = self.x16 if self.x16 is not None else self.x
+        for i, sp in enumerate(self.specs[:-1]):
+            if not self.lib[i] and self.wsigma[i] is not None and h.dtype == torch.bfloat16:
+                p = tuple(t.detach() for t in (sp.m.weight_mu, sp.m.weight_rho, sp.m.bias_mu, sp.m.bias_rho))
+                plan = ops.bbb_plan(h, *p, **self._bbb_kw(i, h, None, self._common_kw(i)))
+                res[i] = plan["form"] == L.FORM_GEMM and plan["waves"] == 8
+            h = self.bufs[i]
+        return res
 
     def _sample_layer(self, i, grp):
         """K1s of layer i into its static buffers (on the current stream)."""

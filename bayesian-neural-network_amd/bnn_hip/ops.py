@@ -73,10 +73,55 @@ def _exact_unless_bf16(math_mode: int) -> int:
     return L.MATH_F32 if math_mode == L.MATH_BF16X3 else math_mode
 
 
-def _x3(x: torch.Tensor, n_samples: int):
+def pieces_activation(shape, device) -> torch.Tensor:
+    """A zeroed bf16 activation buffer in PIECE ORDER (include/bnn_hip.h, bnn_layout) for the logical tensor `shape` =
+    [batch, features] or [rows, batch, features]: [rows * ceil(batch / 128)][ceil(features / 32)][8 batch tiles][64 lanes][8].
+    The layout travels with the tensor OBJECT (its `bnn_pieces` attribute holds the logical shape): bbb_linear_fwd / bbb_plan /
+    eval_prepare read it from the `x`, `out` and `cast_out` they are handed, every other entry point refuses such a tensor.
+    Pad positions are never written by a launch, so the buffer is zeroed once, here."""
+    shape = tuple(int(d) for d in shape)
+    if len(shape) not in (2, 3) or min(shape) < 1:
+        raise BnnHipError(f"pieces_activation: shape must be [batch,features] or [rows,batch,features], got {shape}")
+    rows = shape[0] if len(shape) == 3 else 1
+    t = torch.zeros((rows * ((shape[-2] + 127) // 128), (shape[-1] + 31) // 32, 8, 64, 8), dtype=torch.bfloat16, device=device)
+    t.bnn_pieces = shape
+    return t
+
+
+def param_pieces(out_features: int, in_features: int, device) -> torch.Tensor:
+    """A zeroed buffer for the (mu, sigma) of one [out, in] layer in the piece order of the pair block GEMM (include/bnn_hip.h,
+    bnn_bbb_fwd_args.w_pieces): fp32 [feature tiles][k-steps][mu lo | mu hi | sigma lo | sigma hi][64 lanes][4].  eval_prepare
+    (`mus`, `pieces`) fills it from the current parameters; bbb_linear_fwd / bbb_plan take it as `w_pieces`, or find it as the
+    `bnn_param_pieces` attribute of the `w_sigma` tensor they are handed."""
+    return torch.zeros(((out_features + 15) // 16, (in_features + 31) // 32, 4, 64, 4), dtype=torch.float32, device=device)
+
+
+def pieces_shape(t: Optional[torch.Tensor]):
+    """The logical shape of a piece-order activation buffer, None for a row-major tensor."""
+    return getattr(t, "bnn_pieces", None) if t is not None else None
+
+
+def unpiece(t: torch.Tensor) -> torch.Tensor:
+    """The row-major copy of a piece-order activation buffer (its logical shape)."""
+    shape = pieces_shape(t)
+    rows, B, K = (shape if len(shape) == 3 else (1,) + shape)
+    mbs, ks = (B + 127) // 128, (K + 31) // 32
+    # [row, mb, t, m, q, r, 8] -> [row, mb, m, r, t, q, 8]
+    v = t.view(rows, mbs, ks, 8, 4, 16, 8).permute(0, 1, 3, 5, 2, 4, 6).reshape(rows, mbs * 128, ks * 32)
+    return v[:, :B, :K].reshape(shape).contiguous()
+
+
+def _x3(x: torch.Tensor, n_samples: int, pieces_ok: bool = False):
     """Returns (contiguous x, batch, in_features, x_per_sample): 0 = one x for all samples, g >= 1 = sample s reads
     x[s // g] (x [rows, batch, in] with rows * g == n_samples: g = 1 is one x per sample, g = S is one x per minibatch
-    of S MC samples)."""
+    of S MC samples).  A piece-order x (pieces_activation) counts by its logical shape, where the caller can pass the layout on."""
+    shape = pieces_shape(x)
+    if shape is not None:
+        if not pieces_ok:
+            raise BnnHipError("a piece-order activation buffer (ops.pieces_activation) is read by bbb_linear_fwd only")
+        if len(shape) == 3 and n_samples % shape[0]:
+            raise BnnHipError(f"x has {shape[0]} row blocks, which does not divide {n_samples} samples")
+        return x, shape[-2], shape[-1], (n_samples // shape[0] if len(shape) == 3 else 0)
     if x.dim() == 2:
         xs = x if x.is_contiguous() else x.contiguous()
         return xs, x.shape[0], x.shape[1], 0
@@ -166,13 +211,22 @@ def _y16(a, y: torch.Tensor) -> torch.Tensor:
     return y16
 
 
+def _layouts(x, y, n_samples: int, B: int, N: int):
+    """(x_layout, y_layout) of a K1 call from the tensors themselves (ops.pieces_activation marks a buffer)."""
+    ys = pieces_shape(y)
+    if ys is not None and tuple(ys) != (n_samples, B, N):
+        raise BnnHipError(f"out: a piece-order buffer for {tuple(ys)}, the launch writes {(n_samples, B, N)}")
+    return (L.LAYOUT_PIECES if pieces_shape(x) is not None else L.LAYOUT_ROWS,
+            L.LAYOUT_PIECES if ys is not None else L.LAYOUT_ROWS)
+
+
 def _bbb_build(x, w_mu, w_rho, b_mu, b_rho, *, n_samples: int, prior: PriorSpec, math_mode: int,
                relu: bool, y_dtype: torch.dtype, eps_mode: int, eps_w=None, eps_b=None, seed: int = 0,
                layer_id: int = 0, sample_offset: int = 0, want_stats: bool = True,
                want_scalars: bool = False, dump_eps: bool = False, workspace=None, sample_counter=None,
                out=None, split_scratch=None, w_sigma=None, form: int = 0, sample_group: int = 0,
                sample_group_stride: int = 0, w_sampled=None, b_sampled=None, rider=None, want_y16: bool = False, wt_out=None,
-               x_lo=None, out_lo=None):
+               x_lo=None, out_lo=None, w_pieces=None):
     """Argument block of K1 + the tensors it points at (kept alive by the caller).  `w_sampled` / `b_sampled` (bf16
     [S,out,in] / fp32 [S,out] from bbb_sample_weights): the matmul-only form, the parameter tensors may then be None.
     `rider` = the (args, results, keep) of build_sample_job: an independent sampling job carried by the launch."""
@@ -184,7 +238,7 @@ def _bbb_build(x, w_mu, w_rho, b_mu, b_rho, *, n_samples: int, prior: PriorSpec,
         if w_sampled.shape[0] != n_samples or b_sampled.numel() != n_samples * w_sampled.shape[1]:
             raise BnnHipError("w_sampled / b_sampled do not match n_samples")
         N, K = w_sampled.shape[1], w_sampled.shape[2]
-        xs, B, Kx, per_sample = _x3(x, n_samples)
+        xs, B, Kx, per_sample = _x3(x, n_samples, pieces_ok=True)
         if Kx != K:
             raise BnnHipError(f"shape mismatch: x[...,{Kx}] sampled weight {tuple(w_sampled.shape)}")
         y = out if out is not None else torch.empty((n_samples, B, N), dtype=y_dtype, device=xs.device)
@@ -192,6 +246,7 @@ def _bbb_build(x, w_mu, w_rho, b_mu, b_rho, *, n_samples: int, prior: PriorSpec,
         a.struct_bytes = C.sizeof(L.BbbFwdArgs)
         a.n_samples, a.batch, a.in_features, a.out_features = n_samples, B, K, N
         a.x, a.x_dtype, a.x_per_sample = xs.data_ptr(), _dt(xs), per_sample
+        a.x_layout, a.y_layout = _layouts(xs, y, n_samples, B, N)      # (the library refuses them for this form)
         a.eps_mode, a.math = L.EPS_ZERO, L.MATH_BF16
         a.want_stats, a.relu = 0, int(relu)
         a.y, a.y_dtype = y.data_ptr(), _dt(y)
@@ -207,7 +262,7 @@ def _bbb_build(x, w_mu, w_rho, b_mu, b_rho, *, n_samples: int, prior: PriorSpec,
     w_mu, w_rho = _f32c(w_mu, "weight_mu"), _f32c(w_rho, "weight_rho")
     b_mu, b_rho = _f32c(b_mu, "bias_mu"), _f32c(b_rho, "bias_rho")
     N, K = w_mu.shape
-    xs, B, Kx, per_sample = _x3(x, n_samples)
+    xs, B, Kx, per_sample = _x3(x, n_samples, pieces_ok=True)
     if Kx != K or tuple(w_rho.shape) != (N, K) or tuple(b_mu.shape) != (N,) or tuple(b_rho.shape) != (N,):
         raise BnnHipError(f"shape mismatch: x[...,{Kx}] weight {tuple(w_mu.shape)} bias {tuple(b_mu.shape)}")
     dev = xs.device
@@ -240,6 +295,7 @@ def _bbb_build(x, w_mu, w_rho, b_mu, b_rho, *, n_samples: int, prior: PriorSpec,
     a.workspace_bytes = workspace.numel() * 4 if (want_stats and workspace is not None) else 0
     a.log_prior, a.log_q = _ptr(lp), _ptr(lq)
     a.y, a.y_dtype = y.data_ptr(), _dt(y)
+    a.x_layout, a.y_layout = _layouts(xs, y, n_samples, B, N)
     y_lo = None
     if math_mode == L.MATH_BF16X3:
         # split-bf16 math: a bf16 activation is a PAIR of planes (hi = x / y, lo = x_lo / out_lo), fp32 ones are split on chip
@@ -255,13 +311,21 @@ def _bbb_build(x, w_mu, w_rho, b_mu, b_rho, *, n_samples: int, prior: PriorSpec,
             a.y_lo = y_lo.data_ptr()
     if w_sigma is not None:
         a.w_sigma = w_sigma.data_ptr()
+        if w_pieces is None:
+            w_pieces = getattr(w_sigma, "bnn_param_pieces", None)
+    if w_pieces is not None:
+        require_device(w_pieces)
+        if w_sigma is None or w_pieces.dtype != torch.float32 or not w_pieces.is_contiguous() or \
+                w_pieces.numel() != ((N + 15) // 16) * ((K + 31) // 32) * 1024:
+            raise BnnHipError("w_pieces: ops.param_pieces(out, in) filled by eval_prepare, beside w_sigma")
+        a.w_pieces = w_pieces.data_ptr()
     if split_scratch is not None:
         a.split_scratch = split_scratch.data_ptr()
         a.split_scratch_bytes = split_scratch.numel() * split_scratch.element_size()
     if rider is not None:
         a.rider = C.addressof(rider[0])
     res = dict(y=y, y16=_y16(a, y) if want_y16 else None, workspace=workspace, log_prior=lp, log_q=lq, eps_w=dw, eps_b=db, y_lo=y_lo)
-    keep = (xs, w_mu, w_rho, b_mu, b_rho, eps_w, eps_b, sample_counter, split_scratch, w_sigma, rider, x_lo, y_lo)
+    keep = (xs, w_mu, w_rho, b_mu, b_rho, eps_w, eps_b, sample_counter, split_scratch, w_sigma, rider, x_lo, y_lo, w_pieces)
     a._keep = keep                    # (the structure owns what its pointers refer to: engine.GraphedElbo(capture="calls") replays it)
     return a, res, keep
 
@@ -1092,10 +1156,13 @@ def softplus(rho: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Ten
 
 
 def eval_prepare(rhos=(), sigmas=None, cast: Optional[torch.Tensor] = None, cast_out: Optional[torch.Tensor] = None,
-                 cast_out_sq: Optional[torch.Tensor] = None, want_sq: bool = False, cast_out_lo: Optional[torch.Tensor] = None):
+                 cast_out_sq: Optional[torch.Tensor] = None, want_sq: bool = False, cast_out_lo: Optional[torch.Tensor] = None,
+                 mus=None, pieces=None):
     """bnn_eval_prepare: sigma = softplus(rho) for every tensor of `rhos` and (optionally) the bf16 cast of `cast`
     (+ its squares; + `cast_out_lo`, the low plane bf16(x - bf16(x)) of the split-bf16 math mode) in ONE launch --
-    everything of an evaluation that depends on no activation.
+    everything of an evaluation that depends on no activation.  `cast_out` may be a piece-order buffer (pieces_activation).
+    `mus` / `pieces` (lists beside `rhos`, entries may be None): the 2-D tensor's (mu, sigma) once more in piece order
+    (param_pieces), by the same launch.
     Returns (list of sigma tensors, cast_out, cast_out_sq)."""
     lib = L.load()
     rhos = [_f32c(r, "rho") for r in rhos]
@@ -1111,6 +1178,15 @@ def eval_prepare(rhos=(), sigmas=None, cast: Optional[torch.Tensor] = None, cast
         if sg.shape != r.shape or sg.dtype != torch.float32 or not sg.is_contiguous():
             raise BnnHipError("eval_prepare: sigma must be a contiguous fp32 tensor of rho's shape")
         a.rho[i], a.sigma[i], a.n[i] = r.data_ptr(), sg.data_ptr(), r.numel()
+        pc = pieces[i] if pieces is not None else None
+        if pc is not None:
+            mu = _f32c(mus[i], "mu")
+            require_device(mu, pc)
+            if r.dim() != 2 or mu.shape != r.shape or pc.dtype != torch.float32 or not pc.is_contiguous() or \
+                    pc.numel() != ((r.shape[0] + 15) // 16) * ((r.shape[1] + 31) // 32) * 1024:
+                raise BnnHipError("eval_prepare: pieces[i] must be ops.param_pieces(out, in) of the [out, in] tensors mus[i] / rhos[i]")
+            a.mu[i], a.pieces[i], a.rows[i], a.cols[i] = mu.data_ptr(), pc.data_ptr(), r.shape[0], r.shape[1]
+            a._keep_mu = getattr(a, "_keep_mu", ()) + (mu,)
     if cast is not None:
         cast = _f32c(cast, "x")
         if cast_out is None:
@@ -1118,6 +1194,11 @@ def eval_prepare(rhos=(), sigmas=None, cast: Optional[torch.Tensor] = None, cast
         if want_sq and cast_out_sq is None:
             cast_out_sq = torch.empty(cast.shape, dtype=torch.bfloat16, device=cast.device)
         a.cast_src, a.cast_dst, a.cast_dst_sq, a.cast_n = cast.data_ptr(), cast_out.data_ptr(), _ptr(cast_out_sq), cast.numel()
+        ps = pieces_shape(cast_out)
+        if ps is not None:                  # the cast in piece order (ops.pieces_activation of the input's shape)
+            if tuple(ps) != tuple(cast.shape):
+                raise BnnHipError(f"eval_prepare: cast_out is a piece-order buffer for {tuple(ps)}, the input is {tuple(cast.shape)}")
+            a.cast_layout, a.cast_batch, a.cast_features = L.LAYOUT_PIECES, ps[-2], ps[-1]
         if cast_out_lo is not None:
             if cast_out_lo.dtype != torch.bfloat16 or cast_out_lo.numel() != cast.numel() or not cast_out_lo.is_contiguous():
                 raise BnnHipError("eval_prepare: cast_out_lo must be a contiguous bf16 tensor of the input's size")

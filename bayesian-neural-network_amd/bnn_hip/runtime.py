@@ -11,6 +11,9 @@ arguments (networks.py:50, :92, :142), so build-side settings live here and in e
   BNN_HIP_SEED   64-bit Philox key (default 2026)
   BNN_HIP_EPS    device (default; on-chip Philox)  |  host (draw eps with torch's CPU
                  generator in the reference's order, networks.py:42, then copy H2D)
+  BNN_HIP_PIECES 1 (default) | 0: keep the operands of the pair-block-GEMM layers of a captured evaluation row-major
+                 (engine.GraphedElbo; the same bits either way -- the switch is there to compare the two);
+  BNN_HIP_PARAM_PIECES 1 (default) | 0: the same for the (mu, sigma) copy alone
 """
 from __future__ import annotations
 
@@ -32,6 +35,8 @@ class _State:
         self.shard_samples = False  # split MC samples over torch.distributed ranks
         self.form = L.FORM_AUTO     # kernel-form preference handed to every layer launch (bnn_form; the tests compare
                                     # the forms with each other through it)
+        self.pieces = os.environ.get("BNN_HIP_PIECES", "1") != "0"   # piece-order activations between K1b2 layers (engine.GraphedElbo)
+        self.param_pieces = self.pieces and os.environ.get("BNN_HIP_PARAM_PIECES", "1") != "0"   # ... and their (mu, sigma)
         self.device_counter = None  # device int32[1] added to every layer's sample index at run time
                                     # (set while a training step is captured as a hipGraph: train.py)
 

@@ -76,6 +76,7 @@ struct BbbK {
   float inv2var1, c1, inv2var2, c2, pi;   // mixture: log N(w;0,s_i) = c_i - w^2 * inv2var_i
   const void* x_lo;                       // BNN_MATH_BF16X3, bf16 x: the low plane of x (strided like x)
   void* y_lo;                             // BNN_MATH_BF16X3, bf16 y: the low plane of y
+  const char* w_pieces;                   // K1b2, optional: (mu, sigma) in piece order (bnn_bbb_fwd_args.w_pieces)
 #ifdef BNN_STAMPS
   unsigned long long* dbg;   // diagnostic build only: [block][16] shader-clock stamps of wave 0
 #endif
@@ -1339,9 +1340,19 @@ __global__ __launch_bounds__(NW * 64, 4) void bbb_fwd_gemm_kernel(const BbbK p) 
 // only then are the next step's parameter pieces requested into the same 16 KiB; x stays double-buffered, the bias goes
 // through lane shuffles instead of LDS: 16 + 2 x 32 KiB = 80 KiB, two blocks per CU, four waves per SIMD like the bf16 form.
 // The bf16 form double-buffers everything: two staging buffers (one k-step of DMA run-ahead) of 32 KiB + the bias table.
-template <int NF, int SB, int EPS, int NB = 2, bool X3 = false>
+// LAY (bf16 form only): bit 0 = x in PIECE ORDER (include/bnn_hip.h, bnn_layout), bit 1 = y written in the piece order of the
+// next layer's x, bit 2 = the parameters staged from their piece-order copy (bnn_bbb_fwd_args.w_pieces: a tile's four pieces of a
+// k-step 4 KiB contiguous, where the row-major pieces take every other 16 bytes of sixteen rows 4 K bytes apart -- 24 lines touched
+// for 8 of payload, shared with the twin piece).  From a row-major x a piece is sixteen 64-byte row segments at a 2 K byte stride -- 20 lines of 128 B touched
+// for 8 lines of payload, half of each needed one k-step later, long after the CU's L1 has dropped it; in piece order it is 1 KiB
+// contiguous: a scalar base per piece and the loop-invariant lane offset lane * 16, the k tail and the batch edge zero-padded in
+// memory (no clamped addresses, so no stage_slow for x).  The LDS image, the reads, the step structure and the arithmetic are
+// those of LAY = 0; so are the bits.
+template <int NF, int SB, int EPS, int NB = 2, bool X3 = false, int LAY = 0>
 __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const BbbK p) {
   constexpr int NW = NF * SB;
+  constexpr bool XTL = (LAY & 1) != 0, YTL = (LAY & 2) != 0, WTL = (LAY & 4) != 0;
+  static_assert(!X3 || LAY == 0, "piece order: bf16 form only");
   static_assert(NB == 2, "two staging buffers");
   constexpr int WPW = 4 / SB;                 // parameter pieces (of a tile's four) each of the SB waves of a tile brings
   constexpr int XPW = 8 / NF;                 // x pieces (batch tiles of its pair) each of the NF waves of a pair brings
@@ -1404,11 +1415,35 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
   const uint32_t lds0 = (uint32_t)(size_t)(__attribute__((address_space(3))) void*)&sm_all[0];
   // float4 index of this wave's pair's x tile in staging buffer `slot`
   auto x_slot = [&](int slot) { return x_idx(slot) + sb * XT; };
+  // XTL: the pair's first piece (scalar; x_sstride counts the padded elements of an x row block) and the lane's chunk in a piece
+  const char* xt_unit = reinterpret_cast<const char*>(xs) + (size_t)mb * (size_t)ksteps * 8192;
+  const uint32_t voff_xt = (uint32_t)lane * 16u;
+  // WTL: the tile's first parameter piece (scalar: `tile` is; a phantom wave stages none)
+  const char* wt_tile = p.w_pieces + (size_t)tile * (size_t)ksteps * 4096;
+  auto stage_w_pieces = [&](int t, int pbuf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < WPW; ++i) {
+      const int j = sb * WPW + i;                               // wave-uniform
+      const char* base = wt_tile + (size_t)t * 4096 + j * 1024;
+      const uint32_t m0v = lds0 + (uint32_t)((p_idx(pbuf) + (fw * 4 + j) * 64) * 16);
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_xt), "s"(base), "s"(m0v) : "memory", "m0");
+    }
+  };
+  auto stage_x_pieces = [&](int t, int xbuf) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < XPW; ++i) {
+      const char* base = xt_unit + (size_t)t * 8192 + (fw + i * NF) * 1024;
+      const uint32_t m0v = lds0 + (uint32_t)((x_slot(xbuf) + (fw + i * NF) * 64) * 16);
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_xt), "s"(base), "s"(m0v) : "memory", "m0");
+    }
+  };
   // (the plan takes this form only where the tensors' byte spans fit 32 bits)
   // WP / WX (compile-time): stage the parameter pieces / the x pieces of step t (the X3 form requests them at different points
   // of a step, into different buffer indices)
   auto stage_fast = [&](int t, int pbuf, int xbuf, auto wp_, auto wx_) __attribute__((always_inline)) {
-    if (decltype(wp_)::value) {
+    if (WTL && decltype(wp_)::value) {
+      stage_w_pieces(t, pbuf);
+    } else if (decltype(wp_)::value) {
 #pragma unroll
       for (int i = 0; i < WPW; ++i) {
         const int j = sb * WPW + i;                               // wave-uniform
@@ -1417,7 +1452,9 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_w), "s"(base), "s"(m0v) : "memory", "m0");
       }
     }
-    if (decltype(wx_)::value) {
+    if (XTL && decltype(wx_)::value) {
+      stage_x_pieces(t, xbuf);
+    } else if (decltype(wx_)::value) {
 #pragma unroll
       for (int i = 0; i < XPW; ++i) {
         const char* base = reinterpret_cast<const char*>(xs) + (size_t)t * 64;
@@ -1436,7 +1473,9 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
   };
   auto stage_slow = [&](int t, int pbuf, int xbuf, auto wp_, auto wx_) __attribute__((always_inline)) {
     const int kk = min(t * 32 + q * 8, K - 8);
-    if (decltype(wp_)::value) {
+    if (WTL && decltype(wp_)::value) {
+      stage_w_pieces(t, pbuf);                                     // (zero-padded in memory, like the x pieces)
+    } else if (decltype(wp_)::value) {
 #pragma unroll
       for (int i = 0; i < WPW; ++i) {
 #ifdef BNN_TUNE
@@ -1449,7 +1488,9 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
                                          (__attribute__((address_space(3))) void*)&sm_all[p_idx(pbuf) + (fw * 4 + j) * 64], 16, 0, 0);
       }
     }
-    if (decltype(wx_)::value) {
+    if (XTL && decltype(wx_)::value) {
+      stage_x_pieces(t, xbuf);                                     // (zero-padded in memory: the tail step's pieces are whole too)
+    } else if (decltype(wx_)::value) {
 #pragma unroll
       for (int i = 0; i < XPW; ++i) {
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xs + xrow[i] + kk),
@@ -1764,7 +1805,12 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
     const bool ybf = FAST ? decltype(ybf_)::value : p.y_bf16 != 0;
     const bool relu = FAST ? decltype(relu_)::value : p.relu != 0;
     const size_t esz = ybf ? 2 : 4;
-    const size_t y0 = (((size_t)s * B + m0 + r) * N + nb) * esz, ystep = (size_t)16 * N * esz;
+    // YTL (bf16 y): this wave's feature tile is half `tile & 1` of the consumer's k-step `tile >> 1`; the lane's four features are
+    // half (q & 1) of the chunk of consumer lane (r, 2 * (tile & 1) + (q >> 1)) in the piece of each batch tile -- two 256-byte
+    // runs per wave and batch tile instead of sixteen 32-byte segments at a 2 N byte stride
+    const size_t y0 = YTL ? (((size_t)unit * ((N + 31) >> 5) + (tile >> 1)) * 8192 + ((2 * (tile & 1) + (q >> 1)) * 16 + r) * 16 + (q & 1) * 8)
+                          : (((size_t)s * B + m0 + r) * N + nb) * esz;
+    const size_t ystep = YTL ? (size_t)1024 : (size_t)16 * N * esz;
     char* yrow = reinterpret_cast<char*>(p.y) + y0;
     char* lrow = X3 ? reinterpret_cast<char*>(p.y_lo) + y0 : nullptr;
 #pragma unroll
@@ -2117,6 +2163,10 @@ static int prepare(const bnn_bbb_fwd_args* a, BbbK& k, bool& al) {
   if ((unsigned)a->x_dtype > 1u || (unsigned)a->y_dtype > 1u || (unsigned)a->math > 2u || (unsigned)a->eps_mode > 2u ||
       (unsigned)a->prior.kind > 1u || (unsigned)a->form > 4u)
     return BNN_ERR_ENUM;
+  if ((unsigned)a->x_layout > 1u || (unsigned)a->y_layout > 1u) return BNN_ERR_ENUM;
+  if ((a->x_layout && a->x_dtype != BNN_BF16) || (a->y_layout && a->y_dtype != BNN_BF16)) return BNN_ERR_ENUM;
+  if ((a->x_layout && !aligned16(a->x)) || (a->y_layout && !aligned16(a->y)) || !aligned16(a->w_pieces)) return BNN_ERR_ALIGN;
+  k.w_pieces = reinterpret_cast<const char*>(a->w_pieces);
   if (!pre && a->eps_mode == BNN_EPS_MEMORY && (!a->eps_w || !a->eps_b)) return BNN_ERR_NULL;
   if (a->want_stats) {
     if (!a->workspace || a->workspace_bytes < bnn_bbb_linear_fwd_workspace_bytes(a->n_samples, a->out_features))
@@ -2224,6 +2274,10 @@ static int bbb_linear_fwd_impl(const bnn_bbb_fwd_args* a, void* stream_, bool no
   BbbPlan pl{};
   rc = bbb_plan(a, al, pl, grad_mask == nullptr);    // the masked input-gradient epilogue belongs to the tile form
   if (rc != BNN_OK) return rc;
+  // piece-order operands: the pair block GEMM in bf16 math reads and writes them and nothing else does -- any other plan would
+  // misread the buffer
+  if ((a->x_layout || a->y_layout || a->w_pieces) && !(pl.form == BNN_FORM_GEMM && pl.pairs > 1 && a->math == BNN_MATH_BF16))
+    return BNN_ERR_ENUM;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   const int K = a->in_features;
   const int xdt = a->x_dtype, math = a->math;
@@ -2300,9 +2354,31 @@ static int bbb_linear_fwd_impl(const bnn_bbb_fwd_args* a, void* stream_, bool no
         if (k.eps_mode == BNN_EPS_PHILOX) hipLaunchKernelGGL((bbb_fwd_gemm2_kernel<4, kGemmPairsX3, BNN_EPS_PHILOX, 2, true>), grid2, block2, 0, stream, k);
         else if (k.eps_mode == BNN_EPS_MEMORY) hipLaunchKernelGGL((bbb_fwd_gemm2_kernel<4, kGemmPairsX3, BNN_EPS_MEMORY, 2, true>), grid2, block2, 0, stream, k);
         else hipLaunchKernelGGL((bbb_fwd_gemm2_kernel<4, kGemmPairsX3, BNN_EPS_ZERO, 2, true>), grid2, block2, 0, stream, k);
-      } else if (k.eps_mode == BNN_EPS_PHILOX) hipLaunchKernelGGL((bbb_fwd_gemm2_kernel<4, kGemmPairs, BNN_EPS_PHILOX, kGemmRing>), grid2, block2, 0, stream, k);
-      else if (k.eps_mode == BNN_EPS_MEMORY) hipLaunchKernelGGL((bbb_fwd_gemm2_kernel<4, kGemmPairs, BNN_EPS_MEMORY, kGemmRing>), grid2, block2, 0, stream, k);
-      else hipLaunchKernelGGL((bbb_fwd_gemm2_kernel<4, kGemmPairs, BNN_EPS_ZERO, kGemmRing>), grid2, block2, 0, stream, k);
+      } else {
+        // piece-order operands (bnn_layout): an x row block is then mbs * ksteps pieces-of-8 of 8 KiB
+        const int lay = (a->x_layout == BNN_LAYOUT_PIECES ? 1 : 0) | (a->y_layout == BNN_LAYOUT_PIECES ? 2 : 0) | (a->w_pieces ? 4 : 0);
+        if (lay & 1) k.x_sstride = a->x_per_sample ? (long)((a->batch + 127) / 128) * ((K + 31) / 32) * 4096 : 0;
+#define BNN_GEMM2(LAYV)                                                                                                               \
+  do {                                                                                                                                \
+    if (k.eps_mode == BNN_EPS_PHILOX)                                                                                                 \
+      hipLaunchKernelGGL((bbb_fwd_gemm2_kernel<4, kGemmPairs, BNN_EPS_PHILOX, kGemmRing, false, LAYV>), grid2, block2, 0, stream, k); \
+    else if (k.eps_mode == BNN_EPS_MEMORY)                                                                                            \
+      hipLaunchKernelGGL((bbb_fwd_gemm2_kernel<4, kGemmPairs, BNN_EPS_MEMORY, kGemmRing, false, LAYV>), grid2, block2, 0, stream, k); \
+    else                                                                                                                              \
+      hipLaunchKernelGGL((bbb_fwd_gemm2_kernel<4, kGemmPairs, BNN_EPS_ZERO, kGemmRing, false, LAYV>), grid2, block2, 0, stream, k);   \
+  } while (0)
+        switch (lay) {
+          case 0: BNN_GEMM2(0); break;
+          case 1: BNN_GEMM2(1); break;
+          case 2: BNN_GEMM2(2); break;
+          case 3: BNN_GEMM2(3); break;
+          case 4: BNN_GEMM2(4); break;
+          case 5: BNN_GEMM2(5); break;
+          case 6: BNN_GEMM2(6); break;
+          default: BNN_GEMM2(7); break;
+        }
+#undef BNN_GEMM2
+      }
     } else if (ride) {
       const unsigned n_main = grid.x;
       const dim3 grid_r(n_main + (unsigned)rider_blocks);
@@ -2413,6 +2489,7 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
   bool al = false;
   int rc = prepare(a, k, al);
   if (rc != BNN_OK) return rc;
+  if (a->x_layout || a->y_layout || a->w_pieces) return BNN_ERR_ENUM;     // the output-layer forms read row-major operands
   FinPack fp;
   rc = make_fin(f, fp.k, fp.c);
   if (rc != BNN_OK) return rc;

@@ -299,4 +299,39 @@ __device__ __forceinline__ void cast_bf16_span(const float* __restrict__ src, __
   }
 }
 
+// The same cast into PIECE ORDER (include/bnn_hip.h, bnn_layout), one block of 256 threads per (x row block, batch block, FOUR
+// k-steps from t0): `src` = the batch block's first row ([rows][K] fp32, `rows` of its 128 inside the batch), `dst` = the batch
+// block's pieces ([ksteps][8][64][8] bf16).  Wave w takes k-step t0 + w, lane -> chunk with q fastest: four lanes read 128 contiguous
+// bytes of a row, the block's four waves the 512 bytes next to each other (a row's lines are fetched once per CU although the rows
+// start at 64 mod 128 bytes), and a wave writes one whole 1 KiB piece per batch tile; the eight batch tiles' loads go out together.
+// Chunks past the batch or past K are pad: never written (the buffer is zeroed once by its owner).  K % 8 == 0.
+__device__ __forceinline__ void cast_bf16_pieces(const float* __restrict__ src, __bf16* __restrict__ dst, int rows, int K, int t0,
+                                                 int vec_ok, int tid) {
+  const int q = tid & 3, r = (tid >> 2) & 15, t = t0 + (tid >> 6);
+  const int col = t * 32 + q * 8;
+  if (col >= K) return;                                    // (no barrier below)
+  float f[8][8];
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    const int row = m * 16 + r;
+    if (row >= rows) continue;
+    const float* sp = src + (size_t)row * K + col;
+    if (vec_ok) {
+      const float4 a = reinterpret_cast<const float4*>(sp)[0], b = reinterpret_cast<const float4*>(sp)[1];
+      f[m][0] = a.x; f[m][1] = a.y; f[m][2] = a.z; f[m][3] = a.w; f[m][4] = b.x; f[m][5] = b.y; f[m][6] = b.z; f[m][7] = b.w;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) f[m][i] = sp[i];
+    }
+  }
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    if (m * 16 + r >= rows) continue;
+    bf16x8 v;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = (__bf16)f[m][i];
+    reinterpret_cast<bf16x8*>(dst)[((size_t)t * 8 + m) * 64 + q * 16 + r] = v;
+  }
+}
+
 }  // namespace bnn

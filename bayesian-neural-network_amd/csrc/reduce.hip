@@ -250,11 +250,56 @@ struct PrepK {
   __bf16* cast_dlo;
   long cast_n;
   int cast_vec;
+  int cast_pieces;        // cast_dst in piece order (bnn_layout): a cast block then owns four k-steps of a 128-row batch block
+  int cast_b, cast_k;     // ... of src [cast_n / (cast_b * cast_k)][cast_b][cast_k]
+  // (mu, sigma) in piece order (bnn_bbb_fwd_args.w_pieces), behind the cast's blocks: a block owns four k-steps of a 16-feature tile
+  const float* pp_mu[BNN_PREPARE_MAX];
+  const float* pp_rho[BNN_PREPARE_MAX];
+  float4* pp_dst[BNN_PREPARE_MAX];
+  int pp_n[BNN_PREPARE_MAX], pp_k[BNN_PREPARE_MAX];
+  int pp_first[BNN_PREPARE_MAX + 1];      // first block of each job; [n_pp] = the grid
+  int n_pp;
 };
 constexpr int kPrepPerBlock = 4096;
 
 __global__ __launch_bounds__(256) void eval_prepare_kernel(const PrepK p) {
   const int b = blockIdx.x;
+  if (p.n_pp > 0 && b >= p.pp_first[0]) {                  // block-uniform
+    int j = 0;
+#pragma unroll 1
+    while (j + 1 < p.n_pp && b >= p.pp_first[j + 1]) ++j;
+    const int N = p.pp_n[j], K = p.pp_k[j], ksteps = (K + 31) >> 5, tq = (ksteps + 3) >> 2;
+    const int blk = b - p.pp_first[j], tile = blk / tq, t0 = (blk - tile * tq) * 4;
+    // threads 0 .. 127 take mu, 128 .. 255 rho -> sigma; eight threads read the 128 bytes of a row's k-step (whole lines where the
+    // row starts on one), 16-byte chunk c = 2 q + half; a wave's chunks of a piece are 128-byte runs: lanes q * 16 + (8 rows)
+    const int which = threadIdx.x >> 7, c = threadIdx.x & 7, r = (threadIdx.x >> 3) & 15;
+    const int n = tile * 16 + r;
+    if (n >= N) return;                                    // pad rows of an edge tile: never written (no barrier below)
+    const float* src = (which ? p.pp_rho[j] : p.pp_mu[j]) + (size_t)n * K + c * 4;
+    float4 v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if ((t0 + i) * 32 + c * 4 < K) v[i] = *reinterpret_cast<const float4*>(src + (t0 + i) * 32);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if ((t0 + i) * 32 + c * 4 >= K) continue;            // the K tail's pad (K % 8 == 0: whole chunks)
+      if (which) v[i] = make_float4(softplus(v[i].x), softplus(v[i].y), softplus(v[i].z), softplus(v[i].w));
+      p.pp_dst[j][(((size_t)tile * ksteps + t0 + i) * 4 + which * 2 + (c & 1)) * 64 + (c >> 1) * 16 + r] = v[i];
+    }
+    return;
+  }
+  if (b >= p.first_block[p.n_softplus] && p.cast_pieces) {  // block-uniform
+    // four k-steps (from t0) of batch block mb of x row block `slot`: per batch tile 4 KiB written as whole pieces, read as 16 rows x 512 B
+    const int ksteps = (p.cast_k + 31) >> 5, mbs = (p.cast_b + 127) >> 7, tq = (ksteps + 3) >> 2;
+    const long blk = b - p.first_block[p.n_softplus];
+    const int t0 = (int)(blk % tq) * 4;
+    const long um = blk / tq;                              // slot * mbs + mb
+    const int mb = (int)(um % mbs);
+    const long slot = um / mbs;
+    cast_bf16_pieces(p.cast_src + (slot * p.cast_b + (long)mb * 128) * p.cast_k, p.cast_dst + um * ksteps * 4096, p.cast_b - mb * 128,
+                     p.cast_k, t0, p.cast_vec, threadIdx.x);
+    return;
+  }
   if (b >= p.first_block[p.n_softplus]) {                  // block-uniform
     const long lo = (long)(b - p.first_block[p.n_softplus]) * kPrepPerBlock;
     const long cnt = min((long)kPrepPerBlock, p.cast_n - lo);
@@ -701,9 +746,34 @@ extern "C" int bnn_eval_prepare(const bnn_prepare_args* a, void* stream_) {
     k.cast_dlo = reinterpret_cast<__bf16*>(a->cast_dst_lo);
     k.cast_vec = !((reinterpret_cast<uintptr_t>(a->cast_src) | reinterpret_cast<uintptr_t>(a->cast_dst) |
                     reinterpret_cast<uintptr_t>(a->cast_dst_sq) | reinterpret_cast<uintptr_t>(a->cast_dst_lo)) & 15);
-    blocks += (a->cast_n + kPrepPerBlock - 1) / kPrepPerBlock;
+    if ((unsigned)a->cast_layout > 1u) return BNN_ERR_ENUM;
+    if (a->cast_layout == BNN_LAYOUT_PIECES) {
+      if (a->cast_dst_sq || a->cast_dst_lo) return BNN_ERR_ENUM;
+      if (a->cast_batch <= 0 || a->cast_features <= 0 || (a->cast_features & 7) ||
+          a->cast_n % ((int64_t)a->cast_batch * a->cast_features))
+        return BNN_ERR_SHAPE;
+      if (reinterpret_cast<uintptr_t>(a->cast_dst) & 15) return BNN_ERR_ALIGN;
+      k.cast_pieces = 1; k.cast_b = a->cast_batch; k.cast_k = a->cast_features;
+      blocks += a->cast_n / ((int64_t)a->cast_batch * a->cast_features) * ((a->cast_batch + 127) / 128) * ((a->cast_features + 127) / 128);
+    } else {
+      blocks += (a->cast_n + kPrepPerBlock - 1) / kPrepPerBlock;
+    }
     if (blocks > 0x3fffffff) return BNN_ERR_SHAPE;
   }
+  for (int i = 0; i < a->n_softplus; ++i) {
+    if (!a->pieces[i]) continue;
+    if (!a->mu[i]) return BNN_ERR_NULL;
+    if (a->rows[i] <= 0 || a->cols[i] <= 0 || (a->cols[i] & 7) || (int64_t)a->rows[i] * a->cols[i] != a->n[i]) return BNN_ERR_SHAPE;
+    if ((reinterpret_cast<uintptr_t>(a->mu[i]) | reinterpret_cast<uintptr_t>(a->rho[i]) | reinterpret_cast<uintptr_t>(a->pieces[i])) & 15)
+      return BNN_ERR_ALIGN;
+    const int j = k.n_pp++;
+    k.pp_mu[j] = a->mu[i]; k.pp_rho[j] = a->rho[i]; k.pp_dst[j] = reinterpret_cast<float4*>(a->pieces[i]);
+    k.pp_n[j] = a->rows[i]; k.pp_k[j] = a->cols[i];
+    k.pp_first[j] = (int)blocks;
+    blocks += (long)((a->rows[i] + 15) / 16) * ((a->cols[i] + 127) / 128);
+    if (blocks > 0x3fffffff) return BNN_ERR_SHAPE;
+  }
+  for (int j = k.n_pp; j <= BNN_PREPARE_MAX; ++j) k.pp_first[j] = (int)blocks;
   if (blocks == 0) return BNN_ERR_SHAPE;
   hipLaunchKernelGGL(eval_prepare_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_), k);
   hipError_t err = hipGetLastError();

@@ -173,6 +173,18 @@ typedef struct bnn_plan {
  * ---------------------------------------------------------------------------------- */
 struct bnn_bbb_sample_args;
 
+/* Piece order of a bf16 activation tensor [rows, batch, features] (bnn_bbb_fwd_args.x_layout / y_layout, bnn_prepare_args.cast_layout):
+ * the order in which the pair block GEMM (the BNN_FORM_GEMM plan of 8 waves, bf16 math) stages x, so that each of its LDS-DMA pieces
+ * -- 16 batch rows x 32 features, one 16-byte chunk per lane -- is 1 KiB of whole, 128-byte aligned lines instead of sixteen 64-byte
+ * row segments at a 2 * features byte stride:
+ *     [row][batch block of 128][k-step t = feature / 32][batch tile m (8)][lane (64)][8 bf16]
+ * lane (r = lane & 15, q = lane >> 4) of piece (t, m) holds x[128 * block + 16 * m + r][32 * t + 8 * q .. + 7].  Features are padded to
+ * a multiple of 32 and batch rows to a multiple of 128 with ZEROS -- rows * ceil(batch / 128) * ceil(features / 32) * 8192 bytes in
+ * all, 16-byte aligned: the caller allocates the buffer zeroed and no launch writes a pad position.  Only that plan reads or writes the layout: every other
+ * launch handed a BNN_LAYOUT_PIECES operand returns BNN_ERR_ENUM (the plan itself, bnn_bbb_plan, does not depend on the layouts);
+ * the split-bf16 form of the plan refuses it too (its operands are plane pairs). */
+typedef enum bnn_layout { BNN_LAYOUT_ROWS = 0, BNN_LAYOUT_PIECES = 1 } bnn_layout;
+
 typedef struct bnn_bbb_fwd_args {
   uint32_t struct_bytes;
   int32_t n_samples, batch, in_features, out_features;
@@ -237,6 +249,15 @@ typedef struct bnn_bbb_fwd_args {
   const void* x_lo;         /* BNN_MATH_BF16X3 with x_dtype == BNN_BF16: the low plane of x (shaped and strided like x), i.e.
                                bf16(x_fp32 - x) as bnn_eval_prepare (cast_dst_lo) or a previous layer's y_lo left it */
   void* y_lo;               /* BNN_MATH_BF16X3 with y_dtype == BNN_BF16: the low plane of y, bf16(y_fp32 - y) after bias / ReLU */
+  int32_t x_layout;         /* bnn_layout of a bf16 x: BNN_LAYOUT_PIECES = piece order (below) */
+  int32_t y_layout;         /* bnn_layout of a bf16 y: BNN_LAYOUT_PIECES = the piece order of the NEXT layer's x; the pad positions of the
+                               buffer are never written (the caller zeroes it once) */
+  const void* w_pieces;     /* optional, with w_sigma: (w_mu, w_sigma) once more in the piece order of the same plan, as bnn_eval_prepare
+                               (pieces) wrote it from the CURRENT parameters: fp32 [ceil(out / 16) feature tiles][ceil(in / 32) k-steps]
+                               [mu lo | mu hi | sigma lo | sigma hi][64 lanes][4] -- lane (r, q) of tile T, k-step t holds
+                               mu | sigma [16 T + r][32 t + 8 q + 0..3] in the lo piece and + 4..7 in the hi piece, zero-padded; 16-byte
+                               aligned.  The launch then stages its parameters from here (4 KiB contiguous per tile and k-step) and reads
+                               w_mu / w_sigma for nothing; same refusals as the piece-order activations */
 } bnn_bbb_fwd_args;
 
 size_t bnn_bbb_linear_fwd_workspace_bytes(int32_t n_samples, int32_t out_features);
@@ -1722,6 +1743,16 @@ typedef struct bnn_prepare_args {
   void* cast_dst_sq;                      /* optional bf16 squares: bf16(bf16(src)^2); with cast_dst_lo (BNN_MATH_BF16X3) bf16(src^2) */
   int64_t cast_n;
   void* cast_dst_lo;                      /* optional bf16: the low plane bf16(src - cast_dst) of BNN_MATH_BF16X3 */
+  int32_t cast_layout;                    /* bnn_layout of cast_dst: BNN_LAYOUT_PIECES = the same values in piece order (see
+                                             bnn_bbb_fwd_args), src being [cast_n / (cast_batch * cast_features)][cast_batch]
+                                             [cast_features], cast_features % 8 == 0, cast_dst 16-byte aligned and zeroed by the
+                                             caller; no cast_dst_sq / cast_dst_lo then */
+  int32_t cast_batch, cast_features;      /* BNN_LAYOUT_PIECES only */
+  const float* mu[BNN_PREPARE_MAX];       /* with pieces[i]: the [rows[i], cols[i]] mean tensor beside rho[i] (n[i] = rows[i] * cols[i]) */
+  void* pieces[BNN_PREPARE_MAX];          /* optional per tensor: (mu, sigma) in piece order (bnn_bbb_fwd_args.w_pieces), written by the
+                                             same launch; zeroed by the caller once (pads are never written); cols[i] % 8 == 0,
+                                             mu / rho / pieces 16-byte aligned */
+  int32_t rows[BNN_PREPARE_MAX], cols[BNN_PREPARE_MAX];
 } bnn_prepare_args;
 int bnn_eval_prepare(const bnn_prepare_args* args, void* stream);
 
