@@ -300,11 +300,7 @@ __device__ __forceinline__ void epilogue_store(const BbbK& p, const f32x4* __res
 // ALIGNED = true : K % 8 == 0 and 16-byte aligned bases; every load is an unconditional
 //                  16-byte access at a clamped address, issued in batches.
 // ALIGNED = false: any K / alignment (guarded scalar loads); R must be 1.
-struct FinPack {
-  FinK k;
-  FinC c;
-  float* sums;          // float[4] or nullptr
-  uint32_t* ticket;     // zero-initialised word: arrival counter of the sample blocks
+struct FinPack : FinTail {   // the tail's block + K1c's K-slice stage
   int ks;               // K-range slices per sample (blocks per sample); 1: no cross-block stage
   uint32_t* ks_ticket;  // [S] zero-initialised arrival counters of a sample's slice blocks
   float4* ks_stats;     // [S*ks] per-slice {sum eps^2, sum w^2|log p_mix, sum log sigma, 0}
@@ -750,18 +746,7 @@ __device__ __forceinline__ bool bbb_fwd_body(const BbbK& p, const FinPack* fp) {
         }
         if (fk.sample_counter) *fk.sample_counter += fk.sample_counter_inc;
       } else if (fp->ticket) {
-        // last-arriving sample block folds the per-sample scalars (sample order) and advances
-        // the Philox sample counter: every block has read it by the time it takes a ticket.
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t tk = __hip_atomic_fetch_add(fp->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tk == (uint32_t)fk.S - 1u) {
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          if (fp->sums) fin_fold_sums(fk, fp->sums);
-          *fp->ticket = 0u;
-          if (fk.sample_counter) *fk.sample_counter += fk.sample_counter_inc;
-        }
+        fin_samples_meet(fk, fp->sums, fp->ticket);
       }
     }
   }
@@ -795,9 +780,7 @@ __global__ __launch_bounds__(768) void bbb_fwd_rider_kernel(const BbbK p, const 
 //   row block : logits of its 16 batch rows = bf16 x . w^T (4 waves split the k-steps, every load of a wave issued
 //               before its MFMAs; one LDS round to add the waves up), + bias, stored; the rows' NLL (networks.py:183-190).
 //   stats     : the layers' log p / log q partial sums (networks.py:174-178), as K4 forms them.
-// Hand-off (placement-independent, nobody waits): each block's thread 0 stores its scalar(s) write-through (agent-scope
-// relaxed atomic store = sc1), drains (vmcnt(0)) and takes a ticket; the block whose ticket is last reads the RB + 2
-// scalars back with agent-scope loads, in a fixed order, and writes the sample's outputs.  Samples meet the same way.
+// Hand-off: fin_rows_meet<2> (bnn_fin.h) -- the block whose ticket is last writes the sample's outputs, samples meet the same way.
 struct FinRows {
   const void* x;        // [S | shared, B, K], bf16 or (XF32: the training step's saved activations) fp32 rounded here
   long x_sstride;
@@ -901,73 +884,18 @@ __global__ __launch_bounds__(256) void bbb_final_rows_kernel(const FinRows p, co
     }
     __syncthreads();
     if (wave == 0) {
-      // ---- NLL of the block's rows: lane r < 16 takes row r (the arithmetic of fin_sample's thread-per-row forms)
+      // ---- NLL of the block's rows: lane r < 16 takes row r
       float acc_n = 0.f;
       const int brow = rb * 16 + lane;
       if (lane < 16 && brow < B && fk.nll) {
-        const int C = fk.C;
-        if (fk.nll_mode == BNN_NLL_CLASSIFICATION) {
-          const long long* tgt = reinterpret_cast<const long long*>(fk.target) + (fk.group > 0 ? (s / fk.group) * fk.tgt_stride : 0);
-          const long long tc = tgt[brow];
-          float mx = -3.0e38f, se = 0.f;
-          for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[lane][c]);
-          for (int c = 0; c < C; ++c) se += __expf(lg[lane][c] - mx);
-          const float picked = (tc >= 0 && tc < C) ? lg[lane][(int)tc] : __builtin_nanf("");
-          acc_n = (mx + __logf(se)) - picked;
-        } else {
-          const float* tgt = reinterpret_cast<const float*>(fk.target) + (fk.group > 0 ? (s / fk.group) * fk.tgt_stride : 0);
-          for (int c = 0; c < C; ++c) {
-            const float d = tgt[(size_t)brow * C + c] - lg[lane][c];
-            acc_n += (float)((double)(d * d) * fp.c.reg_inv2var + fp.c.reg_const);
-          }
-        }
+        acc_n = fin_row_nll(fk, fp.c, s, brow, lg[lane]);
         if (tr.out4) fin_loss_row_grad(fk, tr, s, p.B, brow, lg[lane]);
       }
       pub0 = wave_sum(acc_n);
     }
   }
   if (threadIdx.x != 0) return;
-  float* mine = p.parts + (size_t)s * 16;
-  __hip_atomic_store(mine + slot, pub0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (rb == RB) __hip_atomic_store(mine + 9, pub1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const uint32_t tk = __hip_atomic_fetch_add(p.tickets + s, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (tk != (uint32_t)RB) return;                           // RB + 1 blocks per sample
-  // ---- last block of the sample: fold (row-block order), store the sample's scalars
-  // (all ten loads in flight before the first is consumed -- one round trip, not RB + 1: a loop over `tn += load` waits per
-  // element; slots past RB hold no block's value and are not added)
-  float pv[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) pv[i] = __hip_atomic_load(mine + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const float a = __hip_atomic_load(mine + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const float b = __hip_atomic_load(mine + 9, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  double tn = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if (i < RB) tn += pv[i];
-  const float nll = (float)tn;
-  __hip_atomic_store(p.tickets + s, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
-  if (fk.log_prior) __hip_atomic_store(fk.log_prior + s, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (fk.log_q) __hip_atomic_store(fk.log_q + s, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (fk.nll) __hip_atomic_store(fk.nll + s, nll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (fk.S == 1) {
-    if (fp.sums) {
-      fp.sums[0] = a; fp.sums[1] = b; fp.sums[2] = nll; fp.sums[3] = 1.f;
-    }
-    if (tr.out4) fin_loss_assemble(fk, tr);
-    if (fk.sample_counter) *fk.sample_counter += fk.sample_counter_inc;
-    return;
-  }
-  // ---- samples meet: the sample whose ticket is last folds the 4-vector(s) and advances the Philox counter (no ticket: a
-  // follow-up launch does both)
-  if (!fp.ticket) return;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const uint32_t t2 = __hip_atomic_fetch_add(fp.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (t2 != (uint32_t)fk.S - 1u) return;
-  if (fp.sums) fin_fold_sums(fk, fp.sums);
-  if (tr.out4) fin_loss_assemble(fk, tr);
-  __hip_atomic_store(fp.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (fk.sample_counter) *fk.sample_counter += fk.sample_counter_inc;
+  fin_rows_meet<2>(fk, tr, fp.sums, fp.ticket, p.tickets, p.parts, s, slot, pub0, pub1, RB, RB);   // RB + 1 blocks per sample
 }
 
 // matmul half over pre-sampled bf16 weights (bnn_bbb_sample_weights): no generator work in the launch
@@ -2460,30 +2388,20 @@ extern "C" int bnn_bbb_linear_fwd(const bnn_bbb_fwd_args* a, void* stream_) {
   return bbb_linear_fwd_impl(a, stream_, false, nullptr, 0);
 }
 
-static constexpr int kFinalMaxSlices = 8;
 // above this many samples a one-block follow-up launch folds the sums: per-block fences cost more (re-measured this
 // round at 20 / 32 / 64 pairs: 16 -> 32 loses 6 % / 4 % / 1 %)
 static constexpr int kFinalTicketMaxSamples = 16;
 static constexpr int kRowsTicketMaxSamples = 64;     // K1r: up to here the last sample's last block folds the sums (<= 4 round trips)
 
-// reduce.hip: sums over the per-sample outputs + sample-counter advance (one block)
-extern "C" int bnn_elbo_sums_(const bnn_finalize_args* f, void* stream);
-
-// Scratch of the fused last layer: per-sample tickets, per-slice stats and partial logits tiles.
-// Zero-initialised ONCE by the caller (the kernel leaves the tickets at zero again).
+// Scratch of the fused last layer (fin_scratch, bnn_fin.h)
 extern "C" size_t bnn_bbb_final_scratch_bytes(int32_t n_samples) {
-  if (n_samples <= 0) return 0;
-  const size_t S = (size_t)n_samples;
-  return ((S * 4 + 255) / 256) * 256 + S * kFinalMaxSlices * 16 + S * kFinalMaxSlices * (128 * 16 * 4);
+  return n_samples <= 0 ? 0 : fin_scratch(nullptr, (size_t)n_samples).bytes;
 }
 
 // Last layer + ELBO finalize.  Fused into ONE launch when the layer is a single 16-feature
 // tile over a single 128-row batch block (MNIST: 10 classes; regression: 1 output); otherwise
 // the two launches of bnn_bbb_linear_fwd + bnn_elbo_finalize.
-// reduce.hip: the training step's tail as its own launch (f->loss set, and the launch that finalized did not carry it)
-extern "C" int bnn_loss_tail_(const bnn_finalize_args* f, void* stream_);
-static int loss_tail(const bnn_finalize_args* f, void* stream_) { return bnn_loss_tail_(f, stream_); }
-
+// (bnn_loss_tail_: f->loss set, and the launch that finalized did not carry it)
 extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_args* f, void* stream_) {
   BbbK k;
   bool al = false;
@@ -2512,7 +2430,7 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
     if (!rows) {
       rc = bnn_bbb_linear_fwd(a, stream_);
       if (rc == BNN_OK) rc = bnn_elbo_finalize(f, stream_);
-      return rc != BNN_OK ? rc : loss_tail(f, stream_);
+      return rc != BNN_OK ? rc : bnn_loss_tail_(f, stream_);
     }
     const FinLoss tr = make_fin_loss(f);
     FinRows fr;
@@ -2521,9 +2439,9 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
     fr.w = k.w_pre; fr.b = k.b_pre;
     fr.y = reinterpret_cast<float*>(a->y);
     fr.S = S; fr.B = B; fr.K = K; fr.N = N; fr.relu = a->relu ? 1 : 0;
-    char* base = reinterpret_cast<char*>(f->scratch);
-    fr.tickets = reinterpret_cast<uint32_t*>(base);
-    fr.parts = reinterpret_cast<float*>(base + (((size_t)S * 4 + 255) / 256) * 256);      // the K-slice statistics' region
+    const FinScratch sc = fin_scratch(f->scratch, (size_t)S);
+    fr.tickets = sc.tickets;
+    fr.parts = sc.stats;
     // (many samples: the sums of the per-sample scalars and the counter advance by a one-block follow-up kernel, as for K1c below --
     // one thread folding hundreds of samples behind the last block's ticket would be the longest thing in the launch)
     const bool rows_tail = S > kRowsTicketMaxSamples && !tr.out4;
@@ -2550,7 +2468,7 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
     rc = bnn_bbb_linear_fwd(a, stream_);
     if (rc != BNN_OK) return rc;
     rc = bnn_elbo_finalize(f, stream_);
-    return rc != BNN_OK ? rc : loss_tail(f, stream_);
+    return rc != BNN_OK ? rc : bnn_loss_tail_(f, stream_);
   }
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   fp.sums = f->sums;
@@ -2582,13 +2500,10 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
   int nw = (spb + spw - 1) / spw;
   nw = nw < 1 ? 1 : nw;
   fp.ks = KS;
-  {
-    char* base = reinterpret_cast<char*>(f->scratch);
-    const size_t S = (size_t)a->n_samples;
-    fp.ks_ticket = reinterpret_cast<uint32_t*>(base);
-    fp.ks_stats = reinterpret_cast<float4*>(base + ((S * 4 + 255) / 256) * 256);
-    fp.ks_tiles = reinterpret_cast<float*>(base + ((S * 4 + 255) / 256) * 256 + S * kFinalMaxSlices * 16);
-  }
+  const FinScratch sc = fin_scratch(f->scratch, (size_t)a->n_samples);     // (KS == 1: never dereferenced)
+  fp.ks_ticket = sc.tickets;
+  fp.ks_stats = reinterpret_cast<float4*>(sc.stats);
+  fp.ks_tiles = sc.tiles;
   const long total = (long)a->n_samples * KS;           // one tile, one batch block, KS slices
   hipError_t err = hipSuccess;
   const dim3 grid((unsigned)(((total + 7) / 8) * 8)), block(nw * 64);
@@ -2611,7 +2526,7 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
   err = hipGetLastError();
   if (err != hipSuccess) return (int)err;
   rc = tail_kernel ? bnn_elbo_sums_(f, stream_) : (int)BNN_OK;
-  return rc != BNN_OK ? rc : loss_tail(f, stream_);
+  return rc != BNN_OK ? rc : bnn_loss_tail_(f, stream_);
 }
 
 // gx[S,B,K] = gz[S,B,N] . w_s with w regenerated (TRANS form of the K-split kernel).  Called by

@@ -1,10 +1,18 @@
-// ELBO finalize pieces shared by the standalone K4 kernel (reduce.hip) and the fused tail of
-// the last layer's kernel (bbb_linear.hip): per-sample log p / log q (or KL) from the layers'
-// stats partials plus the NLL of the sample's logits (reference networks.py:174-190).
+// The whole finalize tail of an ELBO evaluation, shared by the standalone K4 kernel (reduce.hip) and the kernels that
+// finish an evaluation with their last layer (K1c / K1r in bbb_linear.hip, K3r in lr_linear.hip): per-sample
+// log p / log q (or KL) from the layers' stats partials plus the NLL of the sample's logits (reference
+// networks.py:174-190), the hand-offs in which a sample's blocks and then the samples meet (fin_rows_meet,
+// fin_samples_meet), the training step's loss tail, the kernels' tail parameter block (FinTail) and the layout of
+// bnn_finalize_args.scratch (fin_scratch).
 #pragma once
 #include "bnn_device.h"
 #include "../../include/bnn_hip.h"
 #include <math.h>
+
+// reduce.hip, for the launch functions whose finalizing launch left them over: the sums over the per-sample outputs + the
+// sample-counter advance (one block), and the training step's tail (bnn_finalize_args.loss) as its own launch
+extern "C" int bnn_elbo_sums_(const bnn_finalize_args* f, void* stream);
+extern "C" int bnn_loss_tail_(const bnn_finalize_args* f, void* stream);
 
 namespace bnn {
 
@@ -36,8 +44,35 @@ struct FinC {
   double reg_inv2var;    // 1 / (2 nll_sigma^2)
 };
 
+// What every kernel that finishes an evaluation takes (K1c, with its K-slice fields behind it; K1r; K3r).
+struct FinTail {
+  FinK k;
+  FinC c;
+  float* sums;          // float[4] per minibatch, or nullptr
+  uint32_t* ticket;     // zero-initialised word: arrival counter of the samples (nullptr: a follow-up launch folds the sums)
+};
+
 constexpr int kFinNV = 25;            // 3 sums x 8 layers + nll
 constexpr int kFinMaxWaves = 16;
+constexpr int kFinalMaxSlices = 8;    // K-range slices of K1c per sample at most
+
+// bnn_finalize_args.scratch of S samples: [tickets, padded to 256 B | S x 8 x 16 B | S x 8 x 8 KiB].  Zero-initialised ONCE
+// by the caller (the kernels leave the tickets at zero again).
+//   tickets : a word per sample -- the arrival counter of K1c's K slices, or of K1r / K3r's row + statistics blocks;
+//   stats   : per sample 8 float4 (K1c: the slices' statistics) or 16 floats (K1r / K3r: `parts`, see fin_rows_meet);
+//   tiles   : per sample 8 partial logits tiles [128][16] of K1c's slices, or K4's row-block NLL sums (16384 floats).
+struct FinScratch {
+  uint32_t* tickets;
+  float* stats;
+  float* tiles;
+  size_t bytes;
+};
+static inline FinScratch fin_scratch(void* base, size_t S) {
+  const size_t tickets = ((S * 4 + 255) / 256) * 256, stats = S * kFinalMaxSlices * 16, tiles = S * kFinalMaxSlices * (128 * 16 * 4);
+  const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+  return {reinterpret_cast<uint32_t*>(b), reinterpret_cast<float*>(b + tickets), reinterpret_cast<float*>(b + tickets + stats),
+          tickets + stats + tiles};
+}
 
 static inline int make_fin(const bnn_finalize_args* a, FinK& k, FinC& cst) {
   if (!a) return BNN_ERR_NULL;
@@ -187,6 +222,30 @@ __device__ __forceinline__ float fin_nll(const FinK& p, const FinC& cst, int s, 
     }
   }
   return acc;
+}
+
+// The NLL of batch row `brow` of sample s from the block's logits tile in LDS (`lgrow`: the row's C <= 16 logits): what the
+// row blocks of K1r / K3r call with lanes < 16 of wave 0, a lane per row.  The arithmetic of fin_nll's thread-per-row forms,
+// but its own operation order (its last bits differ from theirs).
+__device__ __forceinline__ float fin_row_nll(const FinK& fk, const FinC& cst, int s, int brow, const float* lgrow) {
+  const int C = fk.C;
+  float acc_n = 0.f;
+  if (fk.nll_mode == BNN_NLL_CLASSIFICATION) {
+    const long long* tgt = reinterpret_cast<const long long*>(fk.target) + (fk.group > 0 ? (s / fk.group) * fk.tgt_stride : 0);
+    const long long tc = tgt[brow];
+    float mx = -3.0e38f, se = 0.f;
+    for (int c = 0; c < C; ++c) mx = fmaxf(mx, lgrow[c]);
+    for (int c = 0; c < C; ++c) se += __expf(lgrow[c] - mx);
+    const float picked = (tc >= 0 && tc < C) ? lgrow[(int)tc] : __builtin_nanf("");   // bad label: NaN loss, loudly
+    acc_n = (mx + __logf(se)) - picked;
+  } else {
+    const float* tgt = reinterpret_cast<const float*>(fk.target) + (fk.group > 0 ? (s / fk.group) * fk.tgt_stride : 0);
+    for (int c = 0; c < C; ++c) {
+      const float d = tgt[(size_t)brow * C + c] - lgrow[c];
+      acc_n += (float)((double)(d * d) * cst.reg_inv2var + cst.reg_const);
+    }
+  }
+  return acc_n;
 }
 
 // ELBO scalars of sample s, valid in thread 0 on return.
@@ -425,6 +484,86 @@ __device__ __forceinline__ void fin_loss_row_grad(const FinK& fk, const FinLoss&
     const float* tg = reinterpret_cast<const float*>(fk.target) + (size_t)brow * C;
     for (int c = 0; c < C; ++c) go[c] = (lgrow[c] - tg[c]) * tr.inv_var * gs;
   }
+}
+
+// ---- The hand-offs that finish an evaluation.  Both are placement-independent and nobody waits: whoever has something to hand
+// over makes it visible at agent scope and takes a ticket; the one whose ticket is last is the only one to go on, and leaves the
+// ticket word at zero for the next launch.  The folds are in slot / sample order: no result depends on who arrived when.  Two
+// idioms make "visible" true, each where its cost is the smaller one -- they are not interchangeable:
+//   fin_rows_meet    : every word handed over is stored write-through (a relaxed agent-scope atomic store = sc1) and read back with
+//                      relaxed agent-scope atomic loads, which go to L2 past the CU's cache.  s_waitcnt vmcnt(0) between the
+//                      stores and the ticket orders the two at L2 (the stores are acknowledged before the ticket's atomic is
+//                      issued), and the last arriver's loads are issued behind its ticket's return.  No cache holds a stale or
+//                      an unwritten copy of these few words, so there is nothing for a fence to write back or invalidate -- and
+//                      a fence is an L2 write-back per block, paid by S x (RB + 1) small blocks of a launch a few us long.
+//   fin_samples_meet : the per-sample scalars were PLAIN stores (fin_store), so a release fence ahead of the ticket and an acquire
+//                      fence behind it are what makes them visible to the last arriver; one pair per sample block, which the
+//                      hosts take only up to a measured number of samples (kFinalTicketMaxSamples, K4: 64).
+// The sample counter is advanced by the last arriver: every block has read it by the time it takes a ticket.
+
+// K1r / K3r: thread 0 of each of a sample's `last + 1` blocks (row blocks + one statistics block) hands over its scalar(s) in
+// the sample's row of `parts` ([S][16]: slots 0..7 the NLL of the 16-row tiles, 8.. the statistics block's NSTAT scalars -- log p
+// and log q, or the KL); the last one folds the sample, and the samples then meet the same way on `ticket` (S == 1: nobody to
+// meet; no ticket: a follow-up launch folds the sums and advances the counter).  `slot`: where pub0 goes (8: the statistics
+// block, whose second scalar is pub1).  RB: the sample's 16-row tiles.
+template <int NSTAT>
+__device__ __forceinline__ void fin_rows_meet(const FinK& fk, const FinLoss& tr, float* sums, uint32_t* ticket, uint32_t* tickets, float* parts,
+                                              int s, int slot, float pub0, float pub1, int RB, int last) {
+  static_assert(NSTAT == 1 || NSTAT == 2, "KL | log p, log q");
+  float* mine = parts + (size_t)s * 16;
+  __hip_atomic_store(mine + slot, pub0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (NSTAT == 2 && slot == 8) __hip_atomic_store(mine + 9, pub1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const uint32_t tk = __hip_atomic_fetch_add(tickets + s, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tk != (uint32_t)last) return;
+  // ---- last block of the sample: fold (tile order), store the sample's scalars
+  // (all 8 + NSTAT loads in flight before the first is consumed -- one round trip, not RB + 1: a loop over `tn += load` waits per
+  // element; slots past RB hold no block's value and are not added)
+  float pv[8 + NSTAT];
+#pragma unroll
+  for (int i = 0; i < 8 + NSTAT; ++i) pv[i] = __hip_atomic_load(mine + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  double tn = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    if (i < RB) tn += pv[i];
+  const float a = pv[8], b = NSTAT == 2 ? pv[8 + NSTAT - 1] : 0.f;
+  const float nll = (float)tn;
+  __hip_atomic_store(tickets + s, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
+  float* const out_a = NSTAT == 2 ? fk.log_prior : fk.kl;
+  if (out_a) __hip_atomic_store(out_a + s, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (NSTAT == 2 && fk.log_q) __hip_atomic_store(fk.log_q + s, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (fk.nll) __hip_atomic_store(fk.nll + s, nll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (fk.S == 1) {
+    if (sums) {
+      sums[0] = a; sums[1] = b; sums[2] = nll; sums[3] = 1.f;
+    }
+    if (tr.out4) fin_loss_assemble(fk, tr);
+    if (fk.sample_counter) *fk.sample_counter += fk.sample_counter_inc;
+    return;
+  }
+  // ---- samples meet: the sample whose ticket is last folds the 4-vector(s), assembles the training loss and advances the counter
+  if (!ticket) return;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const uint32_t t2 = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (t2 != (uint32_t)fk.S - 1u) return;
+  if (sums) fin_fold_sums(fk, sums);
+  if (tr.out4) fin_loss_assemble(fk, tr);
+  __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (fk.sample_counter) *fk.sample_counter += fk.sample_counter_inc;
+}
+
+// K1c / K4: thread 0 of each sample's block, behind its fin_store; S > 1 and a ticket word (the callers keep their S == 1 and
+// no-ticket branches).
+__device__ __forceinline__ void fin_samples_meet(const FinK& fk, float* sums, uint32_t* ticket) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const uint32_t tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tk != (uint32_t)fk.S - 1u) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (sums) fin_fold_sums(fk, sums);
+  *ticket = 0u;
+  if (fk.sample_counter) *fk.sample_counter += fk.sample_counter_inc;
 }
 
 static inline FinLoss make_fin_loss(const bnn_finalize_args* f) {

@@ -1543,9 +1543,8 @@ __global__ __launch_bounds__(NW * 64, PREP ? 4 : 3) void lr_fwd_gemm_kernel(cons
 //               and bias in the D layout (networks.py:120-128), logits stored, the rows' NLL (networks.py:183-190);
 //   stats     : the KL of every layer (networks.py:109-114, :179-181): the layers below from their KL workspaces, this
 //               layer's closed-form sums from its own parameters.
-// Hand-off as in bbb_final_rows_kernel (nobody waits): each block publishes its scalar(s) write-through, drains, takes
-// the sample's ticket; the last one folds them in a fixed order and writes the sample's outputs; samples meet the
-// same way.  A separate K3a launch + bnn_elbo_finalize cost 9.4 + 7.3 us and two launch boundaries at one sample.
+// Hand-off: fin_rows_meet<1> (bnn_fin.h), as in bbb_final_rows_kernel.  A separate K3a launch + bnn_elbo_finalize cost
+// 9.4 + 7.3 us and two launch boundaries at one sample.
 struct LrRows {
   const __bf16* x;      // [S | shared, B, K]
   long x_sstride;
@@ -1569,17 +1568,11 @@ struct LrRows {
 constexpr int kRowsBatch = 12;   // 16-byte loads of each weight tensor a thread keeps in flight (12 x 256 x 4 = the 1200 x 10 layer)
 constexpr int kRowsX = 10;       // x fragments a wave requests up front (4 waves x 10 k-steps = K up to 1280)
 constexpr int kRowsMaxTiles = 4; // 16-row tiles a row block of the many-pairs form takes at most (LrRows.rt)
-struct LrFin {
-  FinK k;
-  FinC c;
-  float* sums;
-  uint32_t* ticket;
-};
 
 // MULTI: a row block takes p.rt 16-row tiles one after the other (a compile-time fact: written as a run-time loop, the one-tile
 // form -- the latency form of a few-pair evaluation -- compiled to 164 registers + 528 bytes of scratch instead of 188 and none)
 template <bool MULTI>
-__global__ __launch_bounds__(256) void lr_final_rows_kernel(const LrRows p, const LrFin fp, const FinLoss tr) {
+__global__ __launch_bounds__(256) void lr_final_rows_kernel(const LrRows p, const FinTail fp, const FinLoss tr) {
   __shared__ __attribute__((aligned(16))) f32x4 red_m[4][64], red_v[4][64];
   __shared__ float lg[16][17];
   __shared__ __attribute__((aligned(8))) float part[4 * kFinNV];
@@ -1843,22 +1836,7 @@ __global__ __launch_bounds__(256) void lr_final_rows_kernel(const LrRows p, cons
       float acc_n = 0.f;
       const int brow = rb * 16 + lane;
       if (lane < 16 && brow < B && fk.nll) {
-        const int C = fk.C;
-        if (fk.nll_mode == BNN_NLL_CLASSIFICATION) {
-          const long long* tgt = reinterpret_cast<const long long*>(fk.target) + (fk.group > 0 ? (s / fk.group) * fk.tgt_stride : 0);
-          const long long tc = tgt[brow];
-          float mx = -3.0e38f, se = 0.f;
-          for (int c = 0; c < C; ++c) mx = fmaxf(mx, lg[lane][c]);
-          for (int c = 0; c < C; ++c) se += __expf(lg[lane][c] - mx);
-          const float picked = (tc >= 0 && tc < C) ? lg[lane][(int)tc] : __builtin_nanf("");
-          acc_n = (mx + __logf(se)) - picked;
-        } else {
-          const float* tgt = reinterpret_cast<const float*>(fk.target) + (fk.group > 0 ? (s / fk.group) * fk.tgt_stride : 0);
-          for (int c = 0; c < C; ++c) {
-            const float d = tgt[(size_t)brow * C + c] - lg[lane][c];
-            acc_n += (float)((double)(d * d) * fp.c.reg_inv2var + fp.c.reg_const);
-          }
-        }
+        acc_n = fin_row_nll(fk, fp.c, s, brow, lg[lane]);
         if (tr.out4) fin_loss_row_grad(fk, tr, s, B, brow, lg[lane]);
       }
       pub0 = wave_sum(acc_n);
@@ -1874,38 +1852,7 @@ __global__ __launch_bounds__(256) void lr_final_rows_kernel(const LrRows p, cons
     }
   }
   if (threadIdx.x != 0) return;
-  __hip_atomic_store(mine + slot, pub0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const uint32_t tk = __hip_atomic_fetch_add(p.tickets + s, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (tk != (uint32_t)NBLK) return;                         // NBLK + 1 blocks per sample
-  float pv[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) pv[i] = __hip_atomic_load(mine + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // one round trip
-  double tn = 0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if (i < RB) tn += pv[i];
-  const float a = pv[8];
-  const float nll = (float)tn;
-  __hip_atomic_store(p.tickets + s, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next launch
-  if (fk.kl) __hip_atomic_store(fk.kl + s, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (fk.nll) __hip_atomic_store(fk.nll + s, nll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (fk.S == 1) {
-    if (fp.sums) {
-      fp.sums[0] = a; fp.sums[1] = 0.f; fp.sums[2] = nll; fp.sums[3] = 1.f;
-    }
-    if (tr.out4) fin_loss_assemble(fk, tr);
-    if (fk.sample_counter) *fk.sample_counter += fk.sample_counter_inc;
-    return;
-  }
-  if (!fp.ticket) return;                                   // (the samples meet in a follow-up launch)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const uint32_t t2 = __hip_atomic_fetch_add(fp.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (t2 != (uint32_t)fk.S - 1u) return;
-  if (fp.sums) fin_fold_sums(fk, fp.sums);
-  if (tr.out4) fin_loss_assemble(fk, tr);
-  __hip_atomic_store(fp.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (fk.sample_counter) *fk.sample_counter += fk.sample_counter_inc;
+  fin_rows_meet<1>(fk, tr, fp.sums, fp.ticket, p.tickets, p.parts, s, slot, pub0, 0.f, RB, NBLK);   // NBLK + 1 blocks per sample
 }
 
 // KL of one LR layer from its partials (networks.py:113, :134-136).  The partials fold
@@ -2409,9 +2356,6 @@ extern "C" int bnn_lr_linear_fwd(const bnn_lr_fwd_args* a, void* stream_) {
   return BNN_OK;
 }
 
-extern "C" size_t bnn_bbb_final_scratch_bytes(int32_t n_samples);   // bbb_linear.hip: the same scratch layout serves K3r
-extern "C" int bnn_loss_tail_(const bnn_finalize_args* f, void* stream_);   // reduce.hip
-
 // Last LR layer + ELBO finalize: ONE launch (K3r) for a few-sample evaluation with a narrow output layer, else
 // bnn_lr_linear_fwd followed by bnn_elbo_finalize.
 static constexpr int kLrRowsPreparedMax = 4096;   // K3r over prepared fragments: up to this many pairs (16 without them)
@@ -2419,12 +2363,11 @@ static constexpr int kLrRowsRtMax = 2;            // K3r: 16-row tiles per block
                                                   // one box, alternating: 573-576 us at 1, 552-557 at 2, 559-563 at 4 (profiles/r04_lr_rows_ab.log)
 static_assert(kLrRowsRtMax >= 1 && kLrRowsRtMax <= bnn::kRowsMaxTiles, "LrRows.rt is at most kRowsMaxTiles");
 static constexpr int kLrRowsTicketMaxSamples = 64;   // K3r: up to here the last sample's last block folds the sums
-extern "C" int bnn_elbo_sums_(const bnn_finalize_args* f, void* stream_);
 extern "C" int bnn_lr_final_fwd(const bnn_lr_fwd_args* a, const bnn_finalize_args* f, void* stream_) {
   LrK k;
   int rc = lr_fill(a, k);
   if (rc != BNN_OK) return rc;
-  LrFin fp;
+  FinTail fp;
   rc = make_fin(f, fp.k, fp.c);
   if (rc != BNN_OK) return rc;
   rc = check_fin_loss(f);
@@ -2460,9 +2403,9 @@ extern "C" int bnn_lr_final_fwd(const bnn_lr_fwd_args* a, const bnn_finalize_arg
   // prepared operands (bnn_lr_prepare, or the rider of the previous layer's launch) with the KL sums that came with them
   r.w_frag = (a->w_frag && a->want_kl && a->workspace && !(reinterpret_cast<uintptr_t>(a->w_frag) & 15)) ? reinterpret_cast<const float4*>(a->w_frag) : nullptr;
   r.ws_own = r.w_frag ? reinterpret_cast<const float4*>(a->workspace) : nullptr;
-  char* base = reinterpret_cast<char*>(f->scratch);
-  r.tickets = reinterpret_cast<uint32_t*>(base);
-  r.parts = reinterpret_cast<float*>(base + (((size_t)S * 4 + 255) / 256) * 256);
+  const FinScratch sc = fin_scratch(f->scratch, (size_t)S);         // (the scratch layout of bnn_bbb_final_fwd serves K3r)
+  r.tickets = sc.tickets;
+  r.parts = sc.stats;
   // (many samples: the sums of the per-sample scalars and the counter advance by a one-block follow-up kernel, as in bnn_bbb_final_fwd)
   const bool rows_tail = S > kLrRowsTicketMaxSamples && !tr.out4;
   fp.sums = f->sums;

@@ -104,8 +104,8 @@ __global__ void cast_bf16_kernel(const float* __restrict__ src, __bf16* __restri
 
 // grid = n_samples blocks (one sample each), or ONE block looping over all samples when `single`: then the
 // block also writes the 4-vector(s) of sums, in sample order.  With a `ticket` word the one-block-per-sample form
-// does that too: the last-arriving block folds the per-sample scalars (release / ticket / acquire, nobody
-// waits), so a handful of samples is finalized in parallel and still in one launch (8 samples: 31.7 us serially).
+// does that too: the last-arriving block folds the per-sample scalars (fin_samples_meet: release / ticket /
+// acquire, nobody waits), so a handful of samples is finalized in parallel and still in one launch (8 samples: 31.7 us serially).
 __global__ __launch_bounds__(256) void elbo_finalize_kernel(const FinK p, const FinC cst, int single, float* sums,
                                                             uint32_t* ticket) {
   __shared__ __attribute__((aligned(8))) float part[4 * kFinNV];
@@ -143,18 +143,7 @@ __global__ __launch_bounds__(256) void elbo_finalize_kernel(const FinK p, const 
     if (p.sample_counter && blockIdx.x == 0 && threadIdx.x == 0) *p.sample_counter += p.sample_counter_inc;
     return;
   }
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t tk = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tk == (uint32_t)p.S - 1u) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (sums) fin_fold_sums(p, sums);                      // sample order: the sums do not depend on who arrived when
-      *ticket = 0u;
-      if (p.sample_counter) *p.sample_counter += p.sample_counter_inc;
-    }
-  }
+  if (threadIdx.x == 0) fin_samples_meet(p, sums, ticket);
 }
 
 // NLL of wide outputs, split by rows: one block per (row block, sample) sums the NLL of its rows into
@@ -626,8 +615,6 @@ extern "C" int bnn_mc_softmax_mean(const float* logits, int32_t n_samples, int32
   return err == hipSuccess ? BNN_OK : (int)err;
 }
 
-extern "C" size_t bnn_bbb_final_scratch_bytes(int32_t n_samples);   // bbb_linear.hip
-
 extern "C" int bnn_elbo_finalize(const bnn_finalize_args* a, void* stream_) {
   FinK k;
   FinC cst;
@@ -643,8 +630,7 @@ extern "C" int bnn_elbo_finalize(const bnn_finalize_args* a, void* stream_) {
     const int rpb = 4;                                        // a wave per row
     const int nrb = (a->batch + rpb - 1) / rpb;
     if (nrb <= 8 * 2048) {                                    // the scratch's partial-tile region: 64 KiB per sample
-      float* partial = reinterpret_cast<float*>(reinterpret_cast<char*>(a->scratch) + (((size_t)a->n_samples * 4 + 255) / 256) * 256 +
-                                                (size_t)a->n_samples * 8 * 16);
+      float* partial = fin_scratch(a->scratch, (size_t)a->n_samples).tiles;
       // [sample][row block], 16384 floats of room per sample
       hipLaunchKernelGGL(nll_rows_kernel, dim3((unsigned)nrb, (unsigned)a->n_samples), dim3(256), 0, stream, k, cst, rpb, partial);
       const hipError_t e0 = hipGetLastError();

@@ -210,16 +210,18 @@ def layer_params(N, K, lr, seed):
             torch.from_numpy(rs.uniform(-5, -4, N).astype(np.float32)))
 
 
-def run_final(dev, form, S, B, N, K, mode, tg, ticketed, loss=None, counter=None, seed=0):
+def run_final(dev, form, S, B, N, K, mode, tg, ticketed, loss=None, counter=None, seed=0, scratch=None, ticket=None):
     """One bbb_final_fwd / lr_final_fwd call.  form: "k1c" (the layer samples its weights), "k1r" (over bbb_sample_weights'
-    draw), "k3r" (LR, the block parks the layer), "k3r_prep" (LR over lr_prepare's fragments).
-    Returns (layer result, finalize result, scratch, ticket)."""
+    draw), "k3r" (LR, the block parks the layer), "k3r_prep" (LR over lr_prepare's fragments).  `scratch` / `ticket`: the
+    ones an earlier call left, instead of fresh ones.
+    Returns (layer result, finalize result, sums, scratch, ticket)."""
     lr = form.startswith("k3r")
     p = [t.to(dev) for t in layer_params(N, K, lr, seed)]
     rs = np.random.RandomState(seed + 1)
     x = torch.from_numpy(rs.uniform(-1, 1, (B, K)).astype(np.float32)).to(dev)
-    sc = sentinel_scratch(S, dev)
-    ticket = torch.zeros(1, dtype=torch.int32, device=dev) if ticketed else None
+    sc = sentinel_scratch(S, dev) if scratch is None else scratch
+    if ticket is None and ticketed:
+        ticket = torch.zeros(1, dtype=torch.int32, device=dev)
     prior = ops.PriorSpec()
     fin = dict(layer_in=[K], layer_out=[N], prior=prior, n_samples=S, target=dev_target(tg, dev), mode=mode, nll_sigma=SIGMA,
                scratch=sc, ticket=ticket, sums=torch.full((1, 4), float("nan"), device=dev), sample_counter=counter,
@@ -292,6 +294,45 @@ def test_fused_final_forms_nll_against_fp64(dev, form, S, B, N, mode):
     check_sums(sums, out["nll"], S, form)
     assert int(counter.item()) == S and int(ticket.item()) == 0
     check_form(form, sc, S, B, N, True, False)
+
+
+RELAUNCH = [  # (form, S, B, N)
+    ("k1c", 4, 17, 10),           # K-slice tickets + the sample ticket
+    ("k1r", 3, 17, 5),
+    ("k3r", 2, 17, 16),           # parked
+    ("k3r_prep", 64, 128, 4),     # 64 x 9 = 576 > 512 blocks: two tiles per row block, still ticketed
+    ("k3r_prep", 65, 128, 4),     # no sample ticket: the follow-up sums launch
+    ("k4", 10, 17, 17),           # bnn_elbo_finalize, a block per sample folded by the ticket
+]
+
+
+@pytest.mark.parametrize("form,S,B,N", RELAUNCH, ids=[f"{c[0]}-S{c[1]}-B{c[2]}-N{c[3]}" for c in RELAUNCH])
+def test_second_launch_on_a_used_scratch_and_ticket(dev, form, S, B, N):
+    """The hand-offs (bnn_fin.h fin_rows_meet / fin_samples_meet, K1c's K-slice stage) leave every ticket word at zero: a
+    second call on the same scratch and ticket, same seed and no sample counter (so epsilon repeats), gives the same bits."""
+    mode = "classification"
+    tg = R.make_labels(B, N, 900 + N)
+    sc, ticket, first = None, None, None
+    if form == "k4":
+        lg, _ = inputs(mode, S, B, N, 900 + N)
+        lg_t, tgt = torch.from_numpy(lg).to(dev), dev_target(tg, dev)
+        ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+    for launch in (1, 2):
+        if form == "k4":
+            sums = torch.full((1, 4), float("nan"), device=dev)
+            out = k4_call(dev, lg_t, tgt, mode, S, sums=sums, ticket=ticket)
+            torch.cuda.synchronize()
+            got = [lg_t, out["nll"], sums]
+        else:
+            res, out, sums, sc, ticket = run_final(dev, form, S, B, N, 512 if form == "k1c" else 96, mode, tg, True, seed=N,
+                                                   scratch=sc, ticket=ticket)
+            got = [res["y"], out["nll"], sums] + ([out["kl"]] if form.startswith("k3r") else [out["log_prior"], out["log_q"]])
+            assert tickets_zero(sc, S), f"launch {launch}"
+        assert int(ticket.item()) == 0, f"launch {launch}"
+        if first is None:
+            first = [t.clone() for t in got]
+        else:
+            assert all(torch.equal(a, b) for a, b in zip(first, got))
 
 
 LOSS_SHAPES = [(1, True), (2, True), (16, True), (64, True), (65, True), (128, True), (65, False), (128, False)]
