@@ -239,7 +239,7 @@ struct PrepK {
   __bf16* cast_dlo;
   long cast_n;
   int cast_vec;
-  int cast_pieces;        // cast_dst in piece order (bnn_layout): a cast block then owns four k-steps of a 128-row batch block
+  int cast_pieces;        // cast_dst in piece order (bnn_layout): a cast block then owns a 16-row batch tile x up to 1024 features
   int cast_b, cast_k;     // ... of src [cast_n / (cast_b * cast_k)][cast_b][cast_k]
   // (mu, sigma) in piece order (bnn_bbb_fwd_args.w_pieces), behind the cast's blocks: a block owns four k-steps of a 16-feature tile
   const float* pp_mu[BNN_PREPARE_MAX];
@@ -250,6 +250,76 @@ struct PrepK {
   int n_pp;
 };
 constexpr int kPrepPerBlock = 4096;
+constexpr int kCastChunk = 1024;          // features of a piece-order cast block: 32 k-steps
+
+// Row pitch (bytes) of the cast block's LDS tile of `kc` bf16 per row: 32 mod 256, so that the sixteen rows one ds_read_b128 lane
+// group addresses (rows 0-3 and 12-15 at one 16-byte column, rows 4-11 at the next) fall in sixteen different 16-byte bank slots.
+__host__ __device__ constexpr int cast_pitch_bytes(int kc) { return ((kc * 2 - 32 + 255) & ~255) + 32; }
+
+extern __shared__ __attribute__((aligned(16))) unsigned char prep_lds[];
+
+// The cast into PIECE ORDER (include/bnn_hip.h, bnn_layout), one block of 256 threads per (x row block, 16-row batch tile, chunk of
+// at most 1024 features: all of K when K <= 1024).  The 16 rows of a tile are consecutive in the source, so with the whole K the
+// block streams one contiguous run (50 176 B at K = 784) with 16-byte loads, all issued before the first is used, rounds to bf16
+// and parks the tile in LDS; after one barrier each wave writes whole pieces: lane (r = lane & 15, q = lane >> 4) of piece (t, m)
+// takes x[16 m + r][32 t + 8 q .. + 7] from LDS and stores 16 bytes at lane, 1 KiB of whole lines per store instruction.
+// Rows past the batch are neither read nor written, chunks past K are not written (the buffer is zeroed once by its owner).
+// K % 8 == 0.  The same values as cast_bf16_span.  kVec: the source is 16-byte aligned; otherwise scalar loads, the same stores.
+template <bool kVec>
+__device__ __forceinline__ void cast_tile_pieces(const PrepK& p, long blk, int tid) {
+  const int K = p.cast_k, B = p.cast_b;
+  const int ksteps = (K + 31) >> 5, mbs = (B + 127) >> 7, tiles = (B + 15) >> 4, kchunks = (K + kCastChunk - 1) / kCastChunk;
+  const int c0 = (int)(blk % kchunks) * kCastChunk, kc = min(kCastChunk, K - c0);
+  const long u = blk / kchunks;
+  const int gt = (int)(u % tiles), mb = gt >> 3, m = gt & 7;  // batch tile of the whole batch, its batch block, its tile there
+  const long slot = u / tiles;
+  const int rows = min(16, B - gt * 16);
+  const float* src = p.cast_src + (slot * B + (long)gt * 16) * K + c0;
+  const int pitch = cast_pitch_bytes(kc);
+  // 16-byte load i of the tile = (row i / kc4, four features from 4 * (i % kc4)); i < 4096 and kc4 <= 256, where
+  // (i * (2^20 / kc4 + 1)) >> 20 is the exact quotient.  Source offset 4 i + row * (K - kc): linear when the chunk is all of K.
+  const unsigned kc4 = (unsigned)kc >> 2, total = (unsigned)rows * kc4, magic = (1u << 20) / kc4 + 1u;
+  // (a load past the tile's end is aimed at its last 16 bytes and dropped below: no branch between the sixteen loads)
+  float4 v[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const unsigned i = min((unsigned)tid + 256u * j, total - 1u);
+    const unsigned row = (i * magic) >> 20;
+    const float* sp = src + (i * 4u + row * (unsigned)(K - kc));   // (K < 2^27: 32 bits)
+    if (kVec) {
+      v[j] = *reinterpret_cast<const float4*>(sp);
+    } else {
+      asm volatile("" : "+v"(sp));                         // opaque: keeps the two forms' loads from being merged into scalar ones for both
+      v[j] = make_float4(sp[0], sp[1], sp[2], sp[3]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const unsigned i = (unsigned)tid + 256u * j;
+    if (i >= total) continue;
+    const unsigned row = (i * magic) >> 20, c4 = i - row * kc4;
+    bf16x4 o;
+    o[0] = (__bf16)v[j].x; o[1] = (__bf16)v[j].y; o[2] = (__bf16)v[j].z; o[3] = (__bf16)v[j].w;
+    *reinterpret_cast<bf16x4*>(prep_lds + row * (unsigned)pitch + c4 * 8u) = o;
+  }
+  __syncthreads();
+  const int lane = tid & 63, r = lane & 15, q = lane >> 4;
+  if (r >= rows) return;                                   // pad rows: never written (no barrier below)
+  const int nt = (kc + 31) >> 5;
+  bf16x8* dst = reinterpret_cast<bf16x8*>(p.cast_dst) + (((slot * mbs + mb) * ksteps + (c0 >> 5)) * 8 + m) * 64 + lane;
+  const unsigned char* from = prep_lds + r * pitch + q * 16;
+  bf16x8 o[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {                            // wave w: k-steps w, w + 4, ... of the chunk
+    const int t = (tid >> 6) + 4 * j;
+    if (t < nt && t * 32 + q * 8 < kc) o[j] = *reinterpret_cast<const bf16x8*>(from + t * 64);
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int t = (tid >> 6) + 4 * j;
+    if (t < nt && t * 32 + q * 8 < kc) dst[(size_t)t * 512] = o[j];
+  }
+}
 
 __global__ __launch_bounds__(256) void eval_prepare_kernel(const PrepK p) {
   const int b = blockIdx.x;
@@ -278,15 +348,8 @@ __global__ __launch_bounds__(256) void eval_prepare_kernel(const PrepK p) {
     return;
   }
   if (b >= p.first_block[p.n_softplus] && p.cast_pieces) {  // block-uniform
-    // four k-steps (from t0) of batch block mb of x row block `slot`: per batch tile 4 KiB written as whole pieces, read as 16 rows x 512 B
-    const int ksteps = (p.cast_k + 31) >> 5, mbs = (p.cast_b + 127) >> 7, tq = (ksteps + 3) >> 2;
-    const long blk = b - p.first_block[p.n_softplus];
-    const int t0 = (int)(blk % tq) * 4;
-    const long um = blk / tq;                              // slot * mbs + mb
-    const int mb = (int)(um % mbs);
-    const long slot = um / mbs;
-    cast_bf16_pieces(p.cast_src + (slot * p.cast_b + (long)mb * 128) * p.cast_k, p.cast_dst + um * ksteps * 4096, p.cast_b - mb * 128,
-                     p.cast_k, t0, p.cast_vec, threadIdx.x);
+    if (p.cast_vec) cast_tile_pieces<true>(p, b - p.first_block[p.n_softplus], threadIdx.x);
+    else cast_tile_pieces<false>(p, b - p.first_block[p.n_softplus], threadIdx.x);
     return;
   }
   if (b >= p.first_block[p.n_softplus]) {                  // block-uniform
@@ -711,6 +774,7 @@ extern "C" int bnn_eval_prepare(const bnn_prepare_args* a, void* stream_) {
   if (a->n_softplus < 0 || a->n_softplus > BNN_PREPARE_MAX || a->cast_n < 0) return BNN_ERR_SHAPE;
   PrepK k{};
   long blocks = 0;
+  size_t lds = 0;                         // of the piece-order cast's blocks: their 16-row tile
   for (int i = 0; i < a->n_softplus; ++i) {
     if (!a->rho[i] || !a->sigma[i]) return BNN_ERR_NULL;
     if (a->n[i] <= 0) return BNN_ERR_SHAPE;
@@ -735,12 +799,14 @@ extern "C" int bnn_eval_prepare(const bnn_prepare_args* a, void* stream_) {
     if ((unsigned)a->cast_layout > 1u) return BNN_ERR_ENUM;
     if (a->cast_layout == BNN_LAYOUT_PIECES) {
       if (a->cast_dst_sq || a->cast_dst_lo) return BNN_ERR_ENUM;
-      if (a->cast_batch <= 0 || a->cast_features <= 0 || (a->cast_features & 7) ||
+      if (a->cast_batch <= 0 || a->cast_features <= 0 || (a->cast_features & 7) || a->cast_features >= (1 << 27) ||
           a->cast_n % ((int64_t)a->cast_batch * a->cast_features))
         return BNN_ERR_SHAPE;
       if (reinterpret_cast<uintptr_t>(a->cast_dst) & 15) return BNN_ERR_ALIGN;
       k.cast_pieces = 1; k.cast_b = a->cast_batch; k.cast_k = a->cast_features;
-      blocks += a->cast_n / ((int64_t)a->cast_batch * a->cast_features) * ((a->cast_batch + 127) / 128) * ((a->cast_features + 127) / 128);
+      blocks += a->cast_n / ((int64_t)a->cast_batch * a->cast_features) * ((a->cast_batch + 15) / 16) *
+                ((a->cast_features + kCastChunk - 1) / kCastChunk);
+      lds = (size_t)16 * cast_pitch_bytes(a->cast_features < kCastChunk ? a->cast_features : kCastChunk);
     } else {
       blocks += (a->cast_n + kPrepPerBlock - 1) / kPrepPerBlock;
     }
@@ -761,7 +827,7 @@ extern "C" int bnn_eval_prepare(const bnn_prepare_args* a, void* stream_) {
   }
   for (int j = k.n_pp; j <= BNN_PREPARE_MAX; ++j) k.pp_first[j] = (int)blocks;
   if (blocks == 0) return BNN_ERR_SHAPE;
-  hipLaunchKernelGGL(eval_prepare_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_), k);
+  hipLaunchKernelGGL(eval_prepare_kernel, dim3((unsigned)blocks), dim3(256), lds, reinterpret_cast<hipStream_t>(stream_), k);
   hipError_t err = hipGetLastError();
   return err == hipSuccess ? BNN_OK : (int)err;
 }
