@@ -39,6 +39,8 @@ EXPORTS = (
     "bnn_param_hist_workspace_bytes", "bnn_param_hist",
     "bnn_mc_score_workspace_bytes", "bnn_mc_score",
     "bnn_sparse_count", "bnn_sparse_fill", "bnn_sparse_fwd",
+    "bnn_sparse_elbo_terms_workspace_bytes", "bnn_sparse_elbo_terms", "bnn_sparse_bwd_workspace_bytes", "bnn_sparse_bwd",
+    "bnn_sparse_sigma_refresh",
 )
 
 
@@ -486,6 +488,45 @@ class SparseFwdArgs(C.Structure):
                 ("x_scratch", C.c_void_p)]
 
 
+SPARSE_MAX_LAYERS = 8
+SPARSE_MAX_SEGMENTS = 8
+
+
+class SparseElboLayer(C.Structure):
+    """bnn_sparse_elbo_layer (include/bnn_hip.h F14)"""
+    _fields_ = [("in_features", C.c_int32), ("out_features", C.c_int32), ("nnz", C.c_int32), ("layer_id", C.c_uint32),
+                ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("mu_val", C.c_void_p), ("sigma_val", C.c_void_p),
+                ("b_mu", C.c_void_p), ("b_sigma", C.c_void_p), ("b_keep", C.c_void_p)]
+
+
+class SparseElboArgs(C.Structure):
+    """bnn_sparse_elbo_args (include/bnn_hip.h F14)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_layers", C.c_int32), ("n_samples", C.c_int32), ("sample_offset", C.c_uint32),
+                ("seed", C.c_uint64), ("prior", Prior), ("reserved", C.c_int32), ("sample_counter", C.c_void_p),
+                ("layer", SparseElboLayer * SPARSE_MAX_LAYERS), ("log_prior", C.c_void_p), ("log_q", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class SparseBwdArgs(C.Structure):
+    """bnn_sparse_bwd_args (include/bnn_hip.h F14)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("rows", C.c_int32), ("in_features", C.c_int32),
+                ("out_features", C.c_int32), ("nnz", C.c_int32), ("relu", C.c_int32), ("gy_row_major", C.c_int32),
+                ("x_per_sample", C.c_int32), ("gx_relu_mask", C.c_int32), ("layer_id", C.c_uint32), ("sample_offset", C.c_uint32),
+                ("seed", C.c_uint64), ("prior", Prior), ("reserved", C.c_int32), ("sample_counter", C.c_void_p),
+                ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("mu_val", C.c_void_p), ("rho_val", C.c_void_p),
+                ("col_ptr", C.c_void_p), ("row", C.c_void_p), ("perm", C.c_void_p), ("b_mu", C.c_void_p), ("b_rho", C.c_void_p),
+                ("b_keep", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p), ("gy", C.c_void_p), ("g_log_prior", C.c_void_p),
+                ("g_log_q", C.c_void_p), ("g_mu_val", C.c_void_p), ("g_rho_val", C.c_void_p), ("g_b_mu", C.c_void_p),
+                ("g_b_rho", C.c_void_p), ("g_x", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class SparseSigmaArgs(C.Structure):
+    """bnn_sparse_sigma_args (include/bnn_hip.h F14)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_segments", C.c_int32), ("rho", C.c_void_p * SPARSE_MAX_SEGMENTS),
+                ("sigma", C.c_void_p * SPARSE_MAX_SEGMENTS), ("keep", C.c_void_p * SPARSE_MAX_SEGMENTS),
+                ("n", C.c_int64 * SPARSE_MAX_SEGMENTS)]
+
+
 class BnnHipError(RuntimeError):
     pass
 
@@ -672,6 +713,14 @@ def _load_real():
     for name, cls in (("bnn_sparse_count", SparseCountArgs), ("bnn_sparse_fill", SparseFillArgs), ("bnn_sparse_fwd", SparseFwdArgs)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    for name, cls in (("bnn_sparse_elbo_terms", SparseElboArgs), ("bnn_sparse_bwd", SparseBwdArgs),
+                      ("bnn_sparse_sigma_refresh", SparseSigmaArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    lib.bnn_sparse_elbo_terms_workspace_bytes.restype = C.c_size_t
+    lib.bnn_sparse_elbo_terms_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.bnn_sparse_bwd_workspace_bytes.restype = C.c_size_t
+    lib.bnn_sparse_bwd_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

@@ -1043,8 +1043,9 @@ def _nll_target(target, mode: str, B: int, Cc: int):
 
 
 def elbo_loss_nll_bwd(a, b, nll, beta, total_samples: int, local_reparam: bool, logits, target, mode: str,
-                      sigma: float = 1.0, grad_scale: float = 1.0):
-    """bnn_elbo_loss_nll_bwd: elbo_loss + nll_bwd in one launch.  Returns (out4, g_a, g_b, g_kl3, g_logits)."""
+                      sigma: float = 1.0, grad_scale: float = 1.0, out=None):
+    """bnn_elbo_loss_nll_bwd: elbo_loss + nll_bwd in one launch.  Returns (out4, g_a, g_b, g_kl3, g_logits): fresh tensors, or
+    `out` -- the caller's own five float32 buffers of those shapes (a captured step that keeps static outputs)."""
     lib = L.load()
     require_device(a, b, nll, beta, logits, target)
     lg = _f32c(logits, "logits")
@@ -1053,11 +1054,18 @@ def elbo_loss_nll_bwd(a, b, nll, beta, total_samples: int, local_reparam: bool, 
         raise BnnHipError("nll must have one element per MC sample")
     tg, m = _nll_target(target, mode, B, Cc)
     dev = nll.device
-    out4 = torch.empty(4, dtype=torch.float32, device=dev)
-    g_a = torch.empty(S, dtype=torch.float32, device=dev)
-    g_b = torch.empty(S, dtype=torch.float32, device=dev)
-    g_kl3 = torch.empty(3, dtype=torch.float32, device=dev)
-    g_logits = torch.empty_like(lg)
+    if out is not None:
+        out4, g_a, g_b, g_kl3, g_logits = out
+        require_device(*out)
+        for t_, n_ in zip(out, (4, S, S, 3, lg.numel())):
+            if t_.dtype != torch.float32 or not t_.is_contiguous() or t_.numel() != n_:
+                raise BnnHipError("elbo_loss_nll_bwd: out = (out4 [4], g_a [S], g_b [S], g_kl3 [3], g_logits like logits), contiguous float32")
+    else:
+        out4 = torch.empty(4, dtype=torch.float32, device=dev)
+        g_a = torch.empty(S, dtype=torch.float32, device=dev)
+        g_b = torch.empty(S, dtype=torch.float32, device=dev)
+        g_kl3 = torch.empty(3, dtype=torch.float32, device=dev)
+        g_logits = torch.empty_like(lg)
     L.check(lib.bnn_elbo_loss_nll_bwd(a.data_ptr(), _ptr(b), nll.data_ptr(), beta.data_ptr(), S, float(total_samples),
                                       float(grad_scale), int(local_reparam), out4.data_ptr(), g_a.data_ptr(), g_b.data_ptr(),
                                       g_kl3.data_ptr(), lg.data_ptr(), tg.data_ptr(), g_logits.data_ptr(), B, Cc, m,
@@ -2261,3 +2269,158 @@ def sparse_fwd_args(*, row_ptr: torch.Tensor, col: torch.Tensor, mu_val: torch.T
 
 def sparse_fwd(a: L.SparseFwdArgs):
     L.check(L.load().bnn_sparse_fwd(C.byref(a), _stream()), "bnn_sparse_fwd")
+
+
+# ---------------------------------------------------------------------------------------------------------------- F14 sparse training
+def _u8c(t: torch.Tensor, name: str, numel: int) -> torch.Tensor:
+    if t.dtype != torch.uint8 or not t.is_contiguous() or t.numel() != numel:
+        raise BnnHipError(f"{name} must be a contiguous uint8 tensor of {numel} elements")
+    return t
+
+
+def sparse_elbo_terms_workspace(layers: Sequence[dict], n_samples: int, device) -> torch.Tensor:
+    """The partials of bnn_sparse_elbo_terms for `layers` (dicts with nnz and out_features) and n_samples."""
+    n = len(layers)
+    nnz = (C.c_int32 * n)(*[int(l["nnz"]) for l in layers])
+    outs = (C.c_int32 * n)(*[int(l["out_features"]) for l in layers])
+    nb = L.load().bnn_sparse_elbo_terms_workspace_bytes(n, int(n_samples), nnz, outs)
+    if nb == 0:
+        raise BnnHipError("sparse_elbo_terms: 1 to 8 layers, 1 to 65535 samples")
+    return torch.empty(nb // 4, dtype=torch.float32, device=device)
+
+
+def sparse_elbo_terms_args(layers: Sequence[dict], *, n_samples: int, prior: PriorSpec, log_prior: torch.Tensor, log_q: torch.Tensor,
+                           workspace: torch.Tensor, seed: int = 0, sample_offset: int = 0,
+                           sample_counter: Optional[torch.Tensor] = None) -> L.SparseElboArgs:
+    """The argument block of bnn_sparse_elbo_terms (include/bnn_hip.h F14).  A layer: dict(row_ptr, col, mu_val, sigma_val,
+    b_mu, b_sigma, b_keep (uint8 [out]), in_features, out_features, nnz, layer_id)."""
+    if not 1 <= len(layers) <= L.SPARSE_MAX_LAYERS:
+        raise BnnHipError(f"sparse_elbo_terms: 1 to {L.SPARSE_MAX_LAYERS} layers")
+    a = L.SparseElboArgs()
+    a.struct_bytes = C.sizeof(L.SparseElboArgs)
+    a.n_layers, a.n_samples = len(layers), int(n_samples)
+    a.sample_offset, a.seed = int(sample_offset) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.prior = prior.c()
+    keep = [log_prior, log_q, workspace, sample_counter]
+    require_device(*keep)
+    for i, l in enumerate(layers):
+        ts = [l[k] for k in ("row_ptr", "col", "mu_val", "sigma_val", "b_mu", "b_sigma", "b_keep")]
+        require_device(*ts)
+        if any(not t.is_contiguous() for t in ts):
+            raise BnnHipError("sparse_elbo_terms: contiguous tensors")
+        out = int(l["out_features"])
+        if l["row_ptr"].dtype != torch.int32 or l["row_ptr"].numel() != out + 1 or l["col"].dtype != torch.int16:
+            raise BnnHipError("sparse_elbo_terms: row_ptr int32 [out + 1], col int16 (uint16 bits)")
+        for k in ("mu_val", "sigma_val", "b_mu", "b_sigma"):
+            if l[k].dtype != torch.float32:
+                raise BnnHipError(f"sparse_elbo_terms: {k} must be float32")
+        if l["mu_val"].numel() < int(l["nnz"]) or l["sigma_val"].numel() < int(l["nnz"]) or l["b_mu"].numel() != out:
+            raise BnnHipError("sparse_elbo_terms: mu_val / sigma_val must hold nnz elements, the bias vectors out")
+        _u8c(l["b_keep"], "sparse_elbo_terms: b_keep", out)
+        y = a.layer[i]
+        y.in_features, y.out_features, y.nnz, y.layer_id = int(l["in_features"]), out, int(l["nnz"]), int(l["layer_id"])
+        y.row_ptr, y.col, y.mu_val, y.sigma_val = (l[k].data_ptr() for k in ("row_ptr", "col", "mu_val", "sigma_val"))
+        y.b_mu, y.b_sigma, y.b_keep = (l[k].data_ptr() for k in ("b_mu", "b_sigma", "b_keep"))
+        keep += ts
+    if log_prior.dtype != torch.float32 or log_q.dtype != torch.float32 or log_prior.numel() != n_samples or log_q.numel() != n_samples:
+        raise BnnHipError("sparse_elbo_terms: log_prior and log_q must be float32 [n_samples]")
+    a.sample_counter, a.log_prior, a.log_q = _ptr(sample_counter), log_prior.data_ptr(), log_q.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a._keep = keep
+    return a
+
+
+def sparse_elbo_terms(a: L.SparseElboArgs):
+    L.check(L.load().bnn_sparse_elbo_terms(C.byref(a), _stream()), "bnn_sparse_elbo_terms")
+
+
+def sparse_bwd_workspace(n_samples: int, rows: int, out_features: int, device) -> torch.Tensor:
+    nb = L.load().bnn_sparse_bwd_workspace_bytes(int(n_samples), int(rows), int(out_features))
+    if nb == 0:
+        raise BnnHipError("sparse_bwd: positive dimensions, at most 65535 samples")
+    return torch.empty(nb // 4, dtype=torch.float32, device=device)
+
+
+def sparse_bwd_args(*, row_ptr: torch.Tensor, col: torch.Tensor, mu_val: torch.Tensor, rho_val: torch.Tensor, b_mu: torch.Tensor,
+                    b_rho: torch.Tensor, b_keep: torch.Tensor, x: torch.Tensor, gy: torch.Tensor, y: Optional[torch.Tensor],
+                    g_mu_val: torch.Tensor, g_rho_val: torch.Tensor, g_b_mu: torch.Tensor, g_b_rho: torch.Tensor,
+                    workspace: Optional[torch.Tensor], n_samples: int, rows: int, in_features: int, out_features: int, nnz: int,
+                    prior: PriorSpec, relu: bool, gy_row_major: bool, x_per_sample: int = 0, gx_relu_mask: bool = False,
+                    layer_id: int = 0, seed: int = 0, sample_offset: int = 0, sample_counter: Optional[torch.Tensor] = None,
+                    g_log_prior: Optional[torch.Tensor] = None, g_log_q: Optional[torch.Tensor] = None,
+                    g_x: Optional[torch.Tensor] = None, col_ptr: Optional[torch.Tensor] = None, row: Optional[torch.Tensor] = None,
+                    perm: Optional[torch.Tensor] = None) -> L.SparseBwdArgs:
+    """The argument block of bnn_sparse_bwd for one layer (include/bnn_hip.h F14).  x [x_rows, in, rows] and y [S, out, rows]
+    feature-major; gy [S, rows, out] (gy_row_major) or [S, out, rows]; g_x [S, in, rows] with the CSC view (col_ptr, row, perm)."""
+    f32 = dict(mu_val=mu_val, rho_val=rho_val, b_mu=b_mu, b_rho=b_rho, x=x, gy=gy, y=y, g_mu_val=g_mu_val, g_rho_val=g_rho_val,
+               g_b_mu=g_b_mu, g_b_rho=g_b_rho, workspace=workspace, g_log_prior=g_log_prior, g_log_q=g_log_q, g_x=g_x)
+    tensors = list(f32.values()) + [row_ptr, col, b_keep, sample_counter, col_ptr, row, perm]
+    require_device(*tensors)
+    if any(t is not None and not t.is_contiguous() for t in tensors):
+        raise BnnHipError("sparse_bwd: contiguous tensors")
+    for name, t in f32.items():
+        if t is not None and t.dtype != torch.float32:
+            raise BnnHipError(f"sparse_bwd: {name} must be float32")
+    S, nnz = int(n_samples), int(nnz)
+    if row_ptr.dtype != torch.int32 or row_ptr.numel() != out_features + 1 or col.dtype != torch.int16:
+        raise BnnHipError("sparse_bwd: row_ptr int32 [out + 1], col int16 (uint16 bits)")
+    _u8c(b_keep, "sparse_bwd: b_keep", out_features)
+    x_rows = 1 if x_per_sample == 0 else -(-S // int(x_per_sample))
+    if x.numel() != x_rows * rows * in_features or gy.numel() != S * rows * out_features or \
+            (y is not None and y.numel() != gy.numel()) or (g_x is not None and g_x.numel() != S * rows * in_features):
+        raise BnnHipError("sparse_bwd: x must hold x_rows * rows * in, gy and y n_samples * rows * out, g_x n_samples * rows * in elements")
+    if min(t.numel() for t in (col, mu_val, rho_val, g_mu_val, g_rho_val)) < nnz or \
+            any(t.numel() != out_features for t in (b_mu, b_rho, g_b_mu, g_b_rho)):
+        raise BnnHipError("sparse_bwd: the value arrays must hold nnz elements, the bias vectors out_features")
+    if any(t is not None and t.numel() != S for t in (g_log_prior, g_log_q)):
+        raise BnnHipError("sparse_bwd: g_log_prior / g_log_q must hold n_samples elements")
+    if g_x is not None:
+        if col_ptr is None or row is None or perm is None or col_ptr.dtype != torch.int32 or col_ptr.numel() != in_features + 1 or \
+                row.dtype != torch.int16 or perm.dtype != torch.int32 or row.numel() < nnz or perm.numel() < nnz:
+            raise BnnHipError("sparse_bwd: g_x needs the CSC view: col_ptr int32 [in + 1], row int16 (uint16 bits) [nnz], perm int32 [nnz]")
+    a = L.SparseBwdArgs()
+    a.struct_bytes = C.sizeof(L.SparseBwdArgs)
+    a.n_samples, a.rows, a.in_features, a.out_features, a.nnz = S, int(rows), int(in_features), int(out_features), nnz
+    a.relu, a.gy_row_major, a.x_per_sample, a.gx_relu_mask = int(bool(relu)), int(bool(gy_row_major)), int(x_per_sample), int(bool(gx_relu_mask))
+    a.layer_id, a.sample_offset, a.seed = int(layer_id), int(sample_offset) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.prior = prior.c()
+    a.sample_counter, a.row_ptr, a.col, a.mu_val, a.rho_val = _ptr(sample_counter), row_ptr.data_ptr(), col.data_ptr(), mu_val.data_ptr(), rho_val.data_ptr()
+    a.col_ptr, a.row, a.perm = _ptr(col_ptr), _ptr(row), _ptr(perm)
+    a.b_mu, a.b_rho, a.b_keep, a.x, a.y, a.gy = b_mu.data_ptr(), b_rho.data_ptr(), b_keep.data_ptr(), x.data_ptr(), _ptr(y), gy.data_ptr()
+    a.g_log_prior, a.g_log_q = _ptr(g_log_prior), _ptr(g_log_q)
+    a.g_mu_val, a.g_rho_val, a.g_b_mu, a.g_b_rho, a.g_x = g_mu_val.data_ptr(), g_rho_val.data_ptr(), g_b_mu.data_ptr(), g_b_rho.data_ptr(), _ptr(g_x)
+    a.workspace = _ptr(workspace)                            # read only when the gz launch runs (relu or gy_row_major)
+    a.workspace_bytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    a._keep = tensors
+    return a
+
+
+def sparse_bwd(a: L.SparseBwdArgs):
+    L.check(L.load().bnn_sparse_bwd(C.byref(a), _stream()), "bnn_sparse_bwd")
+
+
+def sparse_sigma_args(segments: Sequence[tuple]) -> L.SparseSigmaArgs:
+    """The argument block of bnn_sparse_sigma_refresh: segments of (rho, sigma, keep uint8 or None, n): sigma[:n] =
+    keep ? softplus(rho[:n]) : 0."""
+    if not 1 <= len(segments) <= L.SPARSE_MAX_SEGMENTS:
+        raise BnnHipError(f"sparse_sigma_refresh: 1 to {L.SPARSE_MAX_SEGMENTS} segments")
+    a = L.SparseSigmaArgs()
+    a.struct_bytes = C.sizeof(L.SparseSigmaArgs)
+    a.n_segments = len(segments)
+    keep_alive = []
+    for i, (rho, sigma, keep, n) in enumerate(segments):
+        require_device(rho, sigma, keep)
+        n = int(n)
+        if rho.dtype != torch.float32 or sigma.dtype != torch.float32 or not rho.is_contiguous() or not sigma.is_contiguous() or \
+                rho.numel() < n or sigma.numel() < n:
+            raise BnnHipError("sparse_sigma_refresh: rho and sigma must be contiguous float32 of at least n elements")
+        if keep is not None:
+            _u8c(keep, "sparse_sigma_refresh: keep", n)
+        a.rho[i], a.sigma[i], a.keep[i], a.n[i] = rho.data_ptr(), sigma.data_ptr(), _ptr(keep), n
+        keep_alive += [rho, sigma, keep]
+    a._keep = keep_alive
+    return a
+
+
+def sparse_sigma_refresh(a: L.SparseSigmaArgs):
+    L.check(L.load().bnn_sparse_sigma_refresh(C.byref(a), _stream()), "bnn_sparse_sigma_refresh")

@@ -433,10 +433,12 @@ class CompressedNetwork:
     prune_weights' `mu * 0` leaves, so that to_dense() equals prune_weights on a copy bit for bit; without them to_dense()
     writes +0 there (equal in value) and state_bytes shrinks by in * out / 4 bytes per layer."""
 
-    def __init__(self, layers, mode, local_reparam, drop_percentage=None, threshold=None):
+    def __init__(self, layers, mode, local_reparam, drop_percentage=None, threshold=None, prior=None):
         self._layers, self.mode, self.local_reparam = list(layers), mode, bool(local_reparam)
         self.drop_percentage, self.threshold = drop_percentage, threshold
+        self.prior = prior                  # the source network's ops.PriorSpec (_build); None for an object built by hand
         self._plans = {}
+        self._params = None
 
     # ------------------------------------------------------------------------------------------------ construction
     @classmethod
@@ -467,7 +469,7 @@ class CompressedNetwork:
                 c.rho_sign = _pack_bits(torch.signbit(wrho)) if zero_signs else None
                 cls._derive(c)
                 out.append(c)
-        return cls(out, mode, lr, drop_percentage, threshold)
+        return cls(out, mode, lr, drop_percentage, threshold, prior=getattr(net_layers[0], "_prior_spec", None))
 
     @staticmethod
     def _derive(c):
@@ -528,7 +530,26 @@ class CompressedNetwork:
                 c.rho_sign = sd[p + "rho_sign"].clone() if p + "rho_sign" in sd else None
                 self._derive(c)
         self._plans = {}
+        self._params = None
         return self
+
+    # ------------------------------------------------------------------------------------------------ training (F14)
+    def parameters(self):
+        """The twelve nn.Parameters of the surviving posterior, in the order l1.weight_mu, l1.weight_rho, l1.bias_mu,
+        l1.bias_rho, l2...: flat fp32 tensors sharing storage with mu_val[:nnz], rho_val[:nnz], b_mu, b_rho, so an optimiser
+        step on them IS a step of this object (sigma_val / b_sigma are refreshed by the training step).  Created once and
+        cached; load_state_dict drops the cache."""
+        if self._params is None:
+            self._params = [torch.nn.Parameter(t, requires_grad=True) for c in self._layers
+                            for t in (c.mu_val[:c.nnz], c.rho_val[:c.nnz], c.b_mu, c.b_rho)]
+        return list(self._params)
+
+    def graphed_train_step(self, opt, x, y, samples, sigma=1.0, prior=None, warmup=2):
+        """One Bayes-by-backprop step over the surviving weights only, captured as one hipGraph: a
+        sparse_train.SparseTrainStep (train.GraphedTrainStep's contract).  `opt`: FusedAdam(self.parameters(),
+        capturable=True); `prior`: an ops.PriorSpec, by default the source network's (self.prior)."""
+        from .sparse_train import SparseTrainStep
+        return SparseTrainStep(self, opt, x, y, samples, sigma=sigma, prior=prior, warmup=warmup)
 
     def to_dense(self):
         """The 12-key state dict of the pruned BayesianNetwork: what prune_weights(copy, None, drop_percentage) leaves --

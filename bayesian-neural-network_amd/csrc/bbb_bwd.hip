@@ -22,6 +22,7 @@
 // regenerated in the epilogue and neither eps nor w ever exists in memory.  (G, H) = (sum t, sum t*eps) stay in registers across the
 // sample loop; one pass writes g_mu and g_rho.  No atomics.
 #include "bnn_device.h"
+#include "bnn_prior.h"
 #include "../../include/bnn_hip.h"
 
 namespace bnn {
@@ -67,16 +68,8 @@ struct BwdK {
 #define BWD_STAMP_RT(i)
 #endif
 
-// d log p(w) / dw
-__device__ __forceinline__ float dlogp(const BwdK& p, float w) {
-  if (p.prior_kind == BNN_PRIOR_GAUSS) return -w * p.inv_var_p;
-  const float w2 = w * w;
-  const float n1 = p.a1 * fast_exp(-w2 * p.inv2var1);
-  const float n2 = p.a2 * fast_exp(-w2 * p.inv2var2);
-  return -w * (n1 * p.invvar1 + n2 * p.invvar2) * __builtin_amdgcn_rcpf(n1 + n2);
-}
-
-__device__ __forceinline__ float sigmoidf(float r) { return __builtin_amdgcn_rcpf(1.0f + fast_exp(-r)); }
+// d log p(w) / dw (bnn_prior.h: shared with the sparse backward)
+__device__ __forceinline__ float dlogp(const BwdK& p, float w) { return prior_dlogp(p, w); }
 
 // VEC: K % 4 == 0 and 16-byte aligned rows.  No load sits under per-lane control flow (a load in a
 // divergent branch gets its own basic block and the waits between blocks serialise the batch):
@@ -595,20 +588,7 @@ extern "C" int bnn_bbb_linear_bwd(const bnn_bbb_bwd_args* a, void* stream_) {
     k.dbg = v ? reinterpret_cast<unsigned long long*>(strtoull(v, nullptr, 0)) : nullptr;
   }
 #endif
-  k.inv_var_p = 0.f; k.a1 = k.a2 = k.inv2var1 = k.inv2var2 = k.invvar1 = k.invvar2 = 0.f;
-  if (a->prior.kind == BNN_PRIOR_MIXTURE) {
-    if (!(a->prior.sigma1 > 0.f) || !(a->prior.sigma2 > 0.f)) return BNN_ERR_SHAPE;
-    const double s1 = a->prior.sigma1, s2 = a->prior.sigma2;
-    k.a1 = (float)(a->prior.pi / s1);
-    k.a2 = (float)((1.0 - a->prior.pi) / s2);
-    k.inv2var1 = (float)(1.0 / (2.0 * s1 * s1));
-    k.inv2var2 = (float)(1.0 / (2.0 * s2 * s2));
-    k.invvar1 = (float)(1.0 / (s1 * s1));
-    k.invvar2 = (float)(1.0 / (s2 * s2));
-  } else {
-    if (!(a->prior.sigma_p > 0.f)) return BNN_ERR_SHAPE;
-    k.inv_var_p = (float)(1.0 / ((double)a->prior.sigma_p * a->prior.sigma_p));
-  }
+  if (prior_dlogp_fill(a->prior, k) != BNN_OK) return BNN_ERR_SHAPE;      // bnn_prior.h: shared with the sparse backward
   if (a->g_x_bf16 && (!a->g_x || (reinterpret_cast<uintptr_t>(a->g_x_bf16) & 15))) return BNN_ERR_ALIGN;
   if (a->w_sampled && a->g_x && a->out_features <= 16 && a->batch <= 256 && (a->in_features & 7) == 0 &&
       a->eps_mode == BNN_EPS_PHILOX && a->math == BNN_MATH_BF16 &&

@@ -51,6 +51,19 @@ __device__ __forceinline__ float sample_mix_p(const SampleMix& L, float w) {
   return __builtin_fmaf(L.pi, p1, (1.0f - L.pi) * p2);
 }
 
+// host side: the mixture constants from a bnn_prior (sigma1, sigma2 > 0 checked by the caller); fill_sample below and
+// bnn_sparse_elbo_terms (sparse_train.hip) use it
+inline SampleMix sample_mix_make(const bnn_prior& pr) {
+  const double c0 = -0.91893853320467274178;
+  SampleMix m;
+  m.inv2var1 = (float)(1.0 / (2.0 * (double)pr.sigma1 * pr.sigma1));
+  m.inv2var2 = (float)(1.0 / (2.0 * (double)pr.sigma2 * pr.sigma2));
+  m.c1 = (float)(c0 - log((double)pr.sigma1));
+  m.c2 = (float)(c0 - log((double)pr.sigma2));
+  m.pi = pr.pi;
+  return m;
+}
+
 // One block of the sampling job: `block` = index within the job's own block range, `red` = LDS scratch of
 // >= kSampleRedFloats floats.  Every thread of the block must call it (one barrier inside); threads beyond
 // kSampleThreads take no octet.
@@ -257,10 +270,8 @@ static inline int fill_sample(const bnn_bbb_sample_args* a, bnn::SampleK& k, lon
     o.pi = l.prior.pi;
     if (l.prior.kind == BNN_PRIOR_MIXTURE) {
       if (!(l.prior.sigma1 > 0.f) || !(l.prior.sigma2 > 0.f)) return BNN_ERR_SHAPE;
-      o.inv2var1 = (float)(1.0 / (2.0 * (double)l.prior.sigma1 * l.prior.sigma1));
-      o.inv2var2 = (float)(1.0 / (2.0 * (double)l.prior.sigma2 * l.prior.sigma2));
-      o.c1 = (float)(c0 - log((double)l.prior.sigma1));
-      o.c2 = (float)(c0 - log((double)l.prior.sigma2));
+      const bnn::SampleMix m = bnn::sample_mix_make(l.prior);
+      o.inv2var1 = m.inv2var1; o.inv2var2 = m.inv2var2; o.c1 = m.c1; o.c2 = m.c2;
     } else {
       if (!(l.prior.sigma_p > 0.f)) return BNN_ERR_SHAPE;
       o.inv2var1 = o.inv2var2 = o.c1 = o.c2 = 0.f;

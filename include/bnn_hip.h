@@ -1715,6 +1715,160 @@ typedef struct bnn_sparse_fwd_args {
 int bnn_sparse_fwd(const bnn_sparse_fwd_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F14  training the compressed network — the Bayes-by-backprop step over the SURVIVORS of an F13 network only: the pattern
+ * (row_ptr, col) is fixed, a pruned weight or bias is a point mass at exactly zero in every sample, is in neither ELBO sum
+ * and receives no gradient.  The forward is bnn_sparse_fwd, the NLL / loss / seeds are bnn_elbo_finalize (n_layers = 0)
+ * and bnn_elbo_loss_nll_bwd, the update is bnn_adam_step over the value arrays; the entry points below add the rest.
+ * Per layer and global MC sample g (sample_offset + *sample_counter + s, as in bnn_sparse_fwd), with e = (o, c) a CSR entry:
+ *     w_e = fmaf(sigma_e, eps_e, mu_e),  sigma_e = softplus(rho_e);    b_o = fmaf(b_sigma_o, eps_b, b_mu_o) for a kept bias
+ *     eps_e: the dense weight-space map of F13 (tensor id 4 * layer_id + 0, group o * ceil(in / 4) + (c >> 2), slot c & 3);
+ *     eps_b: kind 1, group o >> 2, slot o & 3.
+ * No float atomics anywhere and one fixed summation order per shape: a step repeated from one state gives the same bits.
+ *
+ * bnn_sparse_elbo_terms   log_q[s] and log_prior[s] (float [n_samples]) of up to BNN_SPARSE_MAX_LAYERS layers:
+ *       log_q[s]     = sum over kept weights and kept biases of  -log sqrt(2 pi) - log sigma - eps^2 / 2
+ *       log_prior[s] = sum over kept weights and kept biases of  log prior(w)          (Gaussian or scale mixture)
+ *     per layer as K1 / K4 form them (sums of eps^2, of w^2 or log mixture density, of log sigma; the constants times the
+ *     count in fp64; one fp32 rounding per layer, then fp32 adds in layer order).  Two launches: blocks of 1024 entries
+ *     (or 256 biases) of one (layer, sample) write one partial each -- thread, wave (DPP), block in a fixed order -- then one
+ *     block per sample folds the partials of each layer in fp64 in a fixed tree.  b_keep (uint8 [out]): 1 = the bias is kept.
+ *     nnz must be the layer's row_ptr[out] (the host knows it from construction; the kernels never run past the smaller).
+ *   Errors, in this order: args NULL: BNN_ERR_NULL; struct_bytes: BNN_ERR_ABI; n_layers outside [1, BNN_SPARSE_MAX_LAYERS],
+ *   n_samples outside [1, 65535], a layer with a dimension < 1, in_features > 65536, nnz < 0 or nnz > out * in:
+ *   BNN_ERR_SHAPE; prior.kind outside bnn_prior_kind: BNN_ERR_ENUM; a prior scale <= 0: BNN_ERR_SHAPE; log_prior, log_q or a
+ *   layer's row_ptr, col, mu_val, sigma_val, b_mu, b_sigma, b_keep NULL: BNN_ERR_NULL; workspace NULL or below
+ *   bnn_sparse_elbo_terms_workspace_bytes: BNN_ERR_WORKSPACE; a pointer not aligned to its element, the workspace not
+ *   16-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_sparse_bwd   the backward of ONE layer: the closed forms of bnn_bbb_linear_bwd restricted to the survivors.
+ *       gz_s = gy_s * (y_s > 0) if relu
+ *       G_e,s = sum_r gz_s[o, r] x_s[c, r];   t_e,s = G_e,s + g_log_prior[s] * dlogp/dw(w_e,s)
+ *       g_mu_val[e]  = sum_s t_e,s
+ *       g_rho_val[e] = (sum_s t_e,s eps_e,s - (sum_s g_log_q[s]) / sigma_e) * sigmoid(rho_e)
+ *       g_b_mu / g_b_rho likewise with the row sums of gz in place of G; 0 for a pruned bias (b_keep[o] == 0)
+ *       g_x[s, c, r] = sum_o w_(o,c),s gz_s[o, r]   (ascending o; times (x > 0) with gx_relu_mask), optional
+ *     Layouts: x [x_rows, in, rows] and y [n_samples, out, rows] feature-major, as bnn_sparse_fwd leaves them (x_rows and
+ *     x_per_sample as there; y is read only with relu); gy [n_samples, rows, out] with gy_row_major (the output layer:
+ *     bnn_elbo_loss_nll_bwd's g_logits), else [n_samples, out, rows]; g_x [n_samples, in, rows].  Epsilon is REGENERATED:
+ *     nothing of size [n_samples, nnz] is kept from the forward.  Up to three launches:
+ *       gz      into the workspace, feature-major (skipped when gy is feature-major and relu == 0);
+ *       weights a wave owns 16 consecutive entries and walks them in runs of up to four survivors of one row and one Philox
+ *               group: per run ONE Philox call serves 64 samples (lane = sample), the samples run in ascending order
+ *               inside the kernel with sum_s t and sum_s t eps in registers, and an entry's G is the dot of two coalesced
+ *               rows (lane l takes batch rows l, l + 64, ... ascending, then the wave's fixed DPP sum).  The biases are
+ *               further blocks of the same launch, a wave per output feature;
+ *       g_x     bnn_sparse_fwd's structure over the CSC view: a block is (column group, sample, batch block), stage A
+ *               regenerates w from mu_val[perm], rho_val[perm] and the epsilon at (o, c) into LDS, stage B runs one
+ *               ascending-o fmaf chain per g_x element, lanes over batch rows.
+ *     The CSC view (only with g_x): col_ptr int32 [in + 1], row uint16 [nnz] (the output feature), perm int32 [nnz] (the
+ *     CSR position), rows ascending within a column -- a stable sort of col.
+ *   Errors, in this order: args NULL: BNN_ERR_NULL; struct_bytes: BNN_ERR_ABI; a dimension < 1, n_samples > 65535,
+ *   in_features > 65536, out_features > 65536 or rows > 65535 * 256 with g_x, nnz < 0 or nnz > out * in, x_per_sample < 0: BNN_ERR_SHAPE;
+ *   prior.kind outside bnn_prior_kind: BNN_ERR_ENUM; a prior scale <= 0: BNN_ERR_SHAPE; row_ptr, col, mu_val, rho_val, b_mu, b_rho, b_keep, x,
+ *   gy, g_mu_val, g_rho_val, g_b_mu, g_b_rho NULL, y NULL with relu, col_ptr / row / perm NULL with g_x: BNN_ERR_NULL;
+ *   workspace NULL or below bnn_sparse_bwd_workspace_bytes when the gz launch runs (relu or gy_row_major; it is not read
+ *   otherwise and may be NULL): BNN_ERR_WORKSPACE; a pointer not aligned to its element:
+ *   BNN_ERR_ALIGN.
+ *
+ * bnn_sparse_sigma_refresh   after the optimiser: sigma[i] = keep[i] ? softplus(rho[i]) : 0 over up to
+ *     BNN_SPARSE_MAX_SEGMENTS segments in one launch (keep NULL: every element kept) -- the bits bnn_softplus gives.
+ *   Errors: args NULL: BNN_ERR_NULL; struct_bytes: BNN_ERR_ABI; n_segments outside [1, BNN_SPARSE_MAX_SEGMENTS], n[i] < 0:
+ *   BNN_ERR_SHAPE; rho or sigma of a segment with n > 0 NULL: BNN_ERR_NULL; rho / sigma not 4-byte aligned: BNN_ERR_ALIGN.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_SPARSE_MAX_LAYERS 8
+#define BNN_SPARSE_MAX_SEGMENTS 8
+
+/* layout: 4 x 4-byte words, then 7 pointers */
+typedef struct bnn_sparse_elbo_layer {
+  int32_t in_features;
+  int32_t out_features;
+  int32_t nnz;
+  uint32_t layer_id;
+  const int32_t* row_ptr;                      /* [out + 1] */
+  const uint16_t* col;                         /* [nnz] */
+  const float* mu_val;                         /* [nnz] */
+  const float* sigma_val;                      /* [nnz] */
+  const float* b_mu;                           /* [out] */
+  const float* b_sigma;                        /* [out] */
+  const uint8_t* b_keep;                       /* [out] */
+} bnn_sparse_elbo_layer;
+
+/* layout: 4 x 4-byte words, the 8-byte seed, the prior (5 words), 1 word, a pointer, the layers, 3 pointers, a size */
+typedef struct bnn_sparse_elbo_args {
+  uint32_t struct_bytes;
+  int32_t n_layers;
+  int32_t n_samples;
+  uint32_t sample_offset;
+  uint64_t seed;
+  bnn_prior prior;
+  int32_t reserved;
+  const uint32_t* sample_counter;              /* optional device word added to sample_offset at run time */
+  bnn_sparse_elbo_layer layer[BNN_SPARSE_MAX_LAYERS];
+  float* log_prior;                            /* [n_samples] */
+  float* log_q;                                /* [n_samples] */
+  void* workspace;
+  size_t workspace_bytes;
+} bnn_sparse_elbo_args;
+/* nnz, out_features: [n_layers]; 0 outside the limits */
+size_t bnn_sparse_elbo_terms_workspace_bytes(int32_t n_layers, int32_t n_samples, const int32_t* nnz, const int32_t* out_features);
+int bnn_sparse_elbo_terms(const bnn_sparse_elbo_args* args, void* stream);
+
+/* layout: 12 x 4-byte words, the 8-byte seed, the prior (5 words), 1 word, 22 pointers, a size */
+typedef struct bnn_sparse_bwd_args {
+  uint32_t struct_bytes;
+  int32_t n_samples;
+  int32_t rows;                                /* batch rows */
+  int32_t in_features;
+  int32_t out_features;
+  int32_t nnz;
+  int32_t relu;
+  int32_t gy_row_major;                        /* gy is [n_samples, rows, out] */
+  int32_t x_per_sample;                        /* as in bnn_sparse_fwd */
+  int32_t gx_relu_mask;                        /* g_x is multiplied by (x > 0) */
+  uint32_t layer_id;
+  uint32_t sample_offset;
+  uint64_t seed;
+  bnn_prior prior;
+  int32_t reserved;
+  const uint32_t* sample_counter;              /* optional: the value the forward of the same step read */
+  const int32_t* row_ptr;                      /* [out + 1] */
+  const uint16_t* col;                         /* [nnz] */
+  const float* mu_val;                         /* [nnz] */
+  const float* rho_val;                        /* [nnz] */
+  const int32_t* col_ptr;                      /* [in + 1]   (with g_x) */
+  const uint16_t* row;                         /* [nnz]      (with g_x) */
+  const int32_t* perm;                         /* [nnz]      (with g_x) */
+  const float* b_mu;                           /* [out] */
+  const float* b_rho;                          /* [out] */
+  const uint8_t* b_keep;                       /* [out] */
+  const float* x;
+  const float* y;                              /* with relu */
+  const float* gy;
+  const float* g_log_prior;                    /* [n_samples] or NULL (zeros) */
+  const float* g_log_q;                        /* [n_samples] or NULL (zeros) */
+  float* g_mu_val;                             /* [nnz] */
+  float* g_rho_val;                            /* [nnz] */
+  float* g_b_mu;                               /* [out] */
+  float* g_b_rho;                              /* [out] */
+  float* g_x;                                  /* optional [n_samples, in, rows] */
+  void* workspace;
+  size_t workspace_bytes;
+} bnn_sparse_bwd_args;
+size_t bnn_sparse_bwd_workspace_bytes(int32_t n_samples, int32_t rows, int32_t out_features);   /* 0 outside the limits */
+int bnn_sparse_bwd(const bnn_sparse_bwd_args* args, void* stream);
+
+/* layout: 2 x 4-byte words, then 3 x 8 pointers and 8 x 8-byte counts */
+typedef struct bnn_sparse_sigma_args {
+  uint32_t struct_bytes;
+  int32_t n_segments;
+  const float* rho[BNN_SPARSE_MAX_SEGMENTS];
+  float* sigma[BNN_SPARSE_MAX_SEGMENTS];
+  const uint8_t* keep[BNN_SPARSE_MAX_SEGMENTS];   /* optional per segment */
+  int64_t n[BNN_SPARSE_MAX_SEGMENTS];
+} bnn_sparse_sigma_args;
+int bnn_sparse_sigma_refresh(const bnn_sparse_sigma_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
