@@ -41,6 +41,8 @@ EXPORTS = (
     "bnn_sparse_count", "bnn_sparse_fill", "bnn_sparse_fwd",
     "bnn_sparse_elbo_terms_workspace_bytes", "bnn_sparse_elbo_terms", "bnn_sparse_bwd_workspace_bytes", "bnn_sparse_bwd",
     "bnn_sparse_sigma_refresh",
+    "bnn_batchbald_configs", "bnn_batchbald_joint_workspace_bytes", "bnn_batchbald_probs", "bnn_batchbald_joint",
+    "bnn_batchbald_begin", "bnn_batchbald_extend",
 )
 
 
@@ -413,6 +415,39 @@ class AcquireTopkArgs(C.Structure):
                 ("n_labelled", C.c_void_p), ("n_selected", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+BATCHBALD_MAX_CLASSES = 32
+BATCHBALD_MAX_SAMPLES = 128
+BATCHBALD_MAX_K = 64
+BATCHBALD_MAX_CONFIGS = 65536
+
+
+class BatchBaldProbsArgs(C.Structure):
+    """bnn_batchbald_probs_args (include/bnn_hip.h F15)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("n_rows", C.c_int32), ("n_classes", C.c_int32),
+                ("row0", C.c_int32), ("chunk_rows", C.c_int32),
+                ("logits", C.c_void_p), ("probs", C.c_void_p), ("cond", C.c_void_p), ("marg", C.c_void_p)]
+
+
+class BatchBaldJointArgs(C.Structure):
+    """bnn_batchbald_joint_args (include/bnn_hip.h F15)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("n_rows", C.c_int32), ("n_classes", C.c_int32),
+                ("n_configs", C.c_int32), ("reserved", C.c_int32),
+                ("probs", C.c_void_p), ("phat", C.c_void_p), ("weight", C.c_void_p), ("offset", C.c_void_p), ("cond", C.c_void_p),
+                ("base", C.c_void_p), ("scores", C.c_void_p), ("scores64", C.c_void_p), ("joint64", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class BatchBaldStateArgs(C.Structure):
+    """bnn_batchbald_state_args (include/bnn_hip.h F15)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("n_rows", C.c_int32), ("n_classes", C.c_int32),
+                ("max_configs", C.c_int32), ("n_chosen", C.c_int32), ("round", C.c_uint32), ("last", C.c_uint32),
+                ("seed", C.c_uint64),
+                ("probs", C.c_void_p), ("cond", C.c_void_p), ("labelled", C.c_void_p), ("n_labelled", C.c_void_p),
+                ("scores64", C.c_void_p), ("phat_in", C.c_void_p), ("expo_in", C.c_void_p), ("phat_out", C.c_void_p),
+                ("expo_out", C.c_void_p), ("weight", C.c_void_p), ("offset", C.c_void_p), ("base", C.c_void_p),
+                ("batch_scores", C.c_void_p)]
+
+
 HIST_MAX_JOBS = 16
 HIST_MAX_EDGES = 2048
 HIST_CHUNK = 8192
@@ -721,6 +756,14 @@ def _load_real():
     lib.bnn_sparse_elbo_terms_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.bnn_sparse_bwd_workspace_bytes.restype = C.c_size_t
     lib.bnn_sparse_bwd_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.bnn_batchbald_configs.restype = C.c_int32
+    lib.bnn_batchbald_configs.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.bnn_batchbald_joint_workspace_bytes.restype = C.c_size_t
+    lib.bnn_batchbald_joint_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    for name, cls in (("bnn_batchbald_probs", BatchBaldProbsArgs), ("bnn_batchbald_joint", BatchBaldJointArgs),
+                      ("bnn_batchbald_begin", BatchBaldStateArgs), ("bnn_batchbald_extend", BatchBaldStateArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

@@ -2424,3 +2424,141 @@ def sparse_sigma_args(segments: Sequence[tuple]) -> L.SparseSigmaArgs:
 
 def sparse_sigma_refresh(a: L.SparseSigmaArgs):
     L.check(L.load().bnn_sparse_sigma_refresh(C.byref(a), _stream()), "bnn_sparse_sigma_refresh")
+
+
+# ---------------------------------------------------------------------------------------------------------------- F15 BatchBALD
+def batchbald_configs(n_classes: int, n_chosen: int, max_configs: int) -> int:
+    """bnn_batchbald_configs on the host: rows of Phat when n_chosen rows are in the batch -- C^n while that does not
+    exceed max_configs, else max_configs."""
+    m = 1
+    for _ in range(int(n_chosen)):
+        m *= int(n_classes)
+        if m > int(max_configs):
+            return int(max_configs)
+    return m
+
+
+def _batchbald_dims(what, S, N, Cc):
+    if not (2 <= Cc <= L.BATCHBALD_MAX_CLASSES and 1 <= S <= L.BATCHBALD_MAX_SAMPLES and 1 <= N <= L.EPOCH_MAX_ROWS):
+        raise BnnHipError(f"{what}: classes must lie in [2, {L.BATCHBALD_MAX_CLASSES}], samples in [1, {L.BATCHBALD_MAX_SAMPLES}], "
+                          f"rows in [1, {L.EPOCH_MAX_ROWS}]; got {Cc}, {S}, {N}")
+
+
+def batchbald_probs(logits: torch.Tensor, probs: torch.Tensor, cond: torch.Tensor, marg: torch.Tensor, row0: int):
+    """bnn_batchbald_probs: logits float32 [S, B, C] of pool rows row0 .. row0 + B - 1 into probs float32 [S, N, C] and the
+    float64 [N] entropies cond (expected) and marg (of the mean)."""
+    if logits.dim() != 3 or probs.dim() != 3:
+        raise BnnHipError("batchbald_probs: logits [S, B, C] and probs [S, N, C]")
+    S, B, Cc = logits.shape
+    N = probs.shape[1]
+    _batchbald_dims("batchbald_probs", S, N, Cc)
+    if probs.shape[0] != S or probs.shape[2] != Cc or not 0 <= int(row0) <= N - B:
+        raise BnnHipError("batchbald_probs: probs must be [S, N, C] with row0 + B <= N")
+    keep = [_typed(logits, torch.float32, "logits"), _typed(probs, torch.float32, "probs"), _typed(cond, torch.float64, "cond", N),
+            _typed(marg, torch.float64, "marg", N)]
+    a = L.BatchBaldProbsArgs()
+    a.struct_bytes = C.sizeof(L.BatchBaldProbsArgs)
+    a.n_samples, a.n_rows, a.n_classes, a.row0, a.chunk_rows = S, N, Cc, int(row0), B
+    a.logits, a.probs, a.cond, a.marg = (t.data_ptr() for t in keep)
+    L.check(L.load().bnn_batchbald_probs(C.byref(a), _stream()), "bnn_batchbald_probs")
+
+
+def batchbald_joint_workspace(n_rows: int, n_classes: int, n_configs: int, device) -> torch.Tensor:
+    """bnn_batchbald_joint's workspace for up to n_configs rows of Phat (any contents; 8-byte aligned)."""
+    nbytes = L.load().bnn_batchbald_joint_workspace_bytes(int(n_rows), int(n_classes), int(n_configs))
+    return torch.empty(nbytes // 8 + 1, dtype=torch.float64, device=device)
+
+
+def batchbald_joint_args(*, probs, phat, weight, offset, cond, base, scores, n_configs: int, scores64=None, joint64=None,
+                         workspace=None) -> L.BatchBaldJointArgs:
+    """The argument block of bnn_batchbald_joint (include/bnn_hip.h F15): probs float32 [S, N, C], phat float32 [>= M, S],
+    weight / offset float64 [>= M], cond float64 [N], base one float64 device word, scores float32 [N], scores64 / joint64
+    optional float64 [N]."""
+    if probs.dim() != 3:
+        raise BnnHipError("batchbald_joint: probs [S, N, C]")
+    S, N, Cc = probs.shape
+    M = int(n_configs)
+    _batchbald_dims("batchbald_joint", S, N, Cc)
+    if not 1 <= M <= L.BATCHBALD_MAX_CONFIGS:
+        raise BnnHipError(f"batchbald_joint: n_configs must lie in [1, {L.BATCHBALD_MAX_CONFIGS}]")
+    keep = [_typed(probs, torch.float32, "probs"), _typed(phat, torch.float32, "phat"), _typed(weight, torch.float64, "weight"),
+            _typed(offset, torch.float64, "offset"), _typed(cond, torch.float64, "cond", N), _typed(base, torch.float64, "base", 1),
+            _typed(scores, torch.float32, "scores", N)]
+    if phat.numel() < M * S or weight.numel() < M or offset.numel() < M:
+        raise BnnHipError("batchbald_joint: phat, weight and offset must hold n_configs rows")
+    a = L.BatchBaldJointArgs()
+    a.struct_bytes = C.sizeof(L.BatchBaldJointArgs)
+    a.n_samples, a.n_rows, a.n_classes, a.n_configs = S, N, Cc, M
+    a.probs, a.phat, a.weight, a.offset, a.cond, a.base, a.scores = (t.data_ptr() for t in keep)
+    for name, t in (("scores64", scores64), ("joint64", joint64)):
+        if t is not None:
+            keep.append(_typed(t, torch.float64, name, N))
+            setattr(a, name, t.data_ptr())
+    if workspace is None:
+        workspace = batchbald_joint_workspace(N, Cc, M, probs.device)
+    require_device(workspace)
+    keep.append(workspace)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a._keep = keep
+    return a
+
+
+def batchbald_joint(a: L.BatchBaldJointArgs):
+    """bnn_batchbald_joint: scores[i] = H(chosen rows, row i) - cond[i] - base for every row of the pool."""
+    L.check(L.load().bnn_batchbald_joint(C.byref(a), _stream()), "bnn_batchbald_joint")
+
+
+def batchbald_state_args(*, probs, cond, labelled, n_labelled, phat_in, expo_in, phat_out, expo_out, weight, offset, base,
+                         max_configs: int, n_chosen: int = 0, round: int = 0, seed: int = 0, scores64=None,
+                         batch_scores=None, last: bool = False) -> L.BatchBaldStateArgs:
+    """The argument block of bnn_batchbald_begin / bnn_batchbald_extend (include/bnn_hip.h F15).  The state tensors must
+    hold bnn_batchbald_configs rows for the step they serve: phat float32 [M, S], expo int32 [M], weight / offset float64
+    [M]; phat_in / expo_in and phat_out / expo_out are different tensors.  `last`: the extend of a batch's last row, which
+    writes base and batch_scores only (the state tensors are not sized for it)."""
+    if probs.dim() != 3:
+        raise BnnHipError("batchbald_state: probs [S, N, C]")
+    S, N, Cc = probs.shape
+    _batchbald_dims("batchbald_state", S, N, Cc)
+    mc, n = int(max_configs), int(n_chosen)
+    if not 1 <= mc <= L.BATCHBALD_MAX_CONFIGS or not 0 <= n <= L.BATCHBALD_MAX_K:
+        raise BnnHipError(f"batchbald_state: max_configs must lie in [1, {L.BATCHBALD_MAX_CONFIGS}], n_chosen in "
+                          f"[0, {L.BATCHBALD_MAX_K}] (BNN_BATCHBALD_MAX_K)")
+    m_out, m_in = batchbald_configs(Cc, n, mc), batchbald_configs(Cc, max(n - 1, 0), mc)
+    if last:
+        m_out = 0
+    keep = [_typed(probs, torch.float32, "probs"), _typed(cond, torch.float64, "cond", N),
+            _typed(labelled, torch.int32, "labelled", N), _typed(n_labelled, torch.int32, "n_labelled", 1),
+            _typed(phat_in, torch.float32, "phat_in"), _typed(expo_in, torch.int32, "expo_in"),
+            _typed(phat_out, torch.float32, "phat_out"), _typed(expo_out, torch.int32, "expo_out"),
+            _typed(weight, torch.float64, "weight"), _typed(offset, torch.float64, "offset"), _typed(base, torch.float64, "base", 1)]
+    if phat_in.numel() < m_in * S or expo_in.numel() < m_in or phat_out.numel() < m_out * S or expo_out.numel() < m_out or \
+            weight.numel() < m_out or offset.numel() < m_out:
+        raise BnnHipError(f"batchbald_state: the state tensors must hold {m_in} rows in and {m_out} rows out")
+    if phat_in.data_ptr() == phat_out.data_ptr() or expo_in.data_ptr() == expo_out.data_ptr():
+        raise BnnHipError("batchbald_state: the in and out state must be different tensors")
+    a = L.BatchBaldStateArgs()
+    a.struct_bytes = C.sizeof(L.BatchBaldStateArgs)
+    a.n_samples, a.n_rows, a.n_classes, a.max_configs, a.n_chosen = S, N, Cc, mc, n
+    a.round, a.seed, a.last = int(round) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF, int(bool(last))
+    (a.probs, a.cond, a.labelled, a.n_labelled, a.phat_in, a.expo_in, a.phat_out, a.expo_out, a.weight, a.offset,
+     a.base) = (t.data_ptr() for t in keep)
+    if scores64 is not None:
+        keep.append(_typed(scores64, torch.float64, "scores64", N))
+        a.scores64 = scores64.data_ptr()
+    if batch_scores is not None:
+        if scores64 is None or batch_scores.numel() < n:
+            raise BnnHipError("batchbald_state: batch_scores needs scores64 and n_chosen entries")
+        keep.append(_typed(batch_scores, torch.float64, "batch_scores"))
+        a.batch_scores = batch_scores.data_ptr()
+    a._keep = keep
+    return a
+
+
+def batchbald_begin(a: L.BatchBaldStateArgs):
+    """bnn_batchbald_begin: the empty batch into (phat_out, expo_out, weight, offset, base)."""
+    L.check(L.load().bnn_batchbald_begin(C.byref(a), _stream()), "bnn_batchbald_begin")
+
+
+def batchbald_extend(a: L.BatchBaldStateArgs):
+    """bnn_batchbald_extend: the winner bnn_acquire_topk just appended folded into the state of the next step."""
+    L.check(L.load().bnn_batchbald_extend(C.byref(a), _stream()), "bnn_batchbald_extend")

@@ -1433,7 +1433,7 @@ int bnn_prune_sweep_tail(const bnn_prune_tail_args* args, void* stream);
  * bnn_acquire_random   scores[i] = (w_i >> 8) 2^-24 in [0, 1), i < N, with
  *     w_i = word (i & 3) of Philox4x32-R((i >> 2, round, 3, 1), key = (seed_lo, seed_hi)), R = bnn_philox_rounds():
  *   the "random" acquisition.  Counter words 2 and 3 are (3, 1): off the eps counters (word 3 = 0), the bandit's streams
- *   ((.., 0, 1), (.., 1, 1)) and F8's epoch permutation ((.., 2, 1)).
+ *   ((.., 0, 1), (.., 1, 1)) and F8's epoch permutation ((.., 2, 1)).  F15's label stream takes (.., 4, 1).
  *   Errors: scores NULL: BNN_ERR_NULL; N outside [1, BNN_EPOCH_MAX_ROWS]: BNN_ERR_SHAPE; scores not 4-byte aligned: BNN_ERR_ALIGN.
  * ---------------------------------------------------------------------------------- */
 #define BNN_ACQUIRE_MAX_K 4096         /* winners of one launch: 4096 8-byte keys sort in 32 KiB of one block's LDS */
@@ -1867,6 +1867,139 @@ typedef struct bnn_sparse_sigma_args {
   int64_t n[BNN_SPARSE_MAX_SEGMENTS];
 } bnn_sparse_sigma_args;
 int bnn_sparse_sigma_refresh(const bnn_sparse_sigma_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * F15  BatchBALD — a batch of k pool rows chosen JOINTLY (Kirsch, van Amersfoort, Gal 2019): F10's top-k of per-row mutual
+ * information picks near-duplicates, because every row is scored as if it were acquired alone.  The batch score is
+ *     I(y_1 .. y_n ; w) = H(y_1 .. y_n) - sum_j E_w H(y_j | w),
+ * built greedily: step n scores every pool row i together with the n-1 rows already chosen, bnn_acquire_topk (k = 1) takes
+ * the winner, bnn_batchbald_extend folds it into the state.  S weight draws are shared by ALL rows (weight-space epsilon is
+ * keyed by the sample index and not by x), so P[s, i, :] of different rows are conditionally independent given s.
+ * State of a batch: Phat [M, S] fp32 (row m: one label configuration of the chosen rows, entry s: its probability under
+ * draw s, times 2^-E[m]), E int32 [M], weight w and offset o fp64 [M], base fp64 (sum of cond over the chosen rows).
+ *   M = bnn_batchbald_configs(C, n, max_configs) = C^n while C^n <= max_configs (every configuration: EXACT mode), else
+ *   max_configs (SAMPLED mode); 0 for arguments outside the limits below.  A host value: grids are sized without a read.
+ *
+ * bnn_batchbald_probs   one chunk of MC logits [S, B, C] (rows row0 .. row0 + B - 1 of the pool):
+ *     P[s, row0 + b, c] = e_c / sum_c' e_c', e_c = expf(logit_c - max_c' logit_c'), all fp32, into the pool-wide P [S, N, C];
+ *     cond[row] = -(1/S) sum_s sum_c P log P and marg[row] = - sum_c pbar_c log pbar_c, pbar_c = (1/S) sum_s P[s, row, c]:
+ *     fp64 sums in ascending (s, c) of the fp32 P, fp64 log, 0 log 0 = 0.
+ *   Errors: args, logits, probs, cond, marg NULL: BNN_ERR_NULL; C outside [2, BNN_BATCHBALD_MAX_CLASSES], S outside
+ *   [1, BNN_BATCHBALD_MAX_SAMPLES], N outside [1, BNN_EPOCH_MAX_ROWS], B < 1, row0 < 0 or row0 + B > N: BNN_ERR_SHAPE;
+ *   logits, probs not 4-byte, cond, marg not 8-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_batchbald_joint   for every row i < N, with pt[m, i, y] = (1/S) sum_s Phat[m, s] P[s, i, y]:
+ *     joint64[i]  = H[i] = - sum_m w[m] sum_y pt (log pt + o[m])        (pt = 0 contributes 0)
+ *     scores64[i] = H[i] - cond[i] - *base;   scores[i] = (float)scores64[i]        -- what bnn_acquire_topk ranks.
+ *   The M x (N C) product is never stored: v_mfma_f32_16x16x4_f32 tiles (exact fp32 operands; one fp32 fmaf chain over
+ *   the samples in the order s = 16 Q + 4 g + j for Q, then j, then g = 0 .. 3 ascending, samples past S skipped)
+ *   whose accumulators go straight into log (fp32 v_log_f32, widened) and an fp64 sum.  A block owns floor(64 / C) rows and
+ *   a contiguous range of M ("split"); every lane adds its terms in ascending m, the lanes of a row are folded in a fixed
+ *   order, the splits [splits, N] (fp64, in the workspace) by a second launch in ascending split: no float atomics, the same
+ *   inputs give the same bits.  The split count is a function of (N, C, M) alone.  An s-sum below FLT_MIN (1.2e-38)
+ *   contributes 0 like an exact zero (its term is below 1e-35).  Never NaN for finite inputs.
+ *   Workspace: bnn_batchbald_joint_workspace_bytes(N, C, M) bytes, 8-byte aligned, any contents: enough for every n_configs
+ *   up to M, so one buffer serves all steps of a batch (0 for arguments outside the limits).
+ *   Errors: args, probs, phat, weight, offset, cond, base, scores NULL: BNN_ERR_NULL; C, S, N as above, M outside
+ *   [1, BNN_BATCHBALD_MAX_CONFIGS]: BNN_ERR_SHAPE; workspace NULL or short: BNN_ERR_WORKSPACE; probs, phat, scores not
+ *   4-byte, weight, offset, cond, base, scores64, joint64, workspace not 8-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_batchbald_begin   the empty batch: phat_out[0, 0 .. S) = 1, expo_out[0] = 0, weight[0] = 1, offset[0] = 0, *base = 0
+ *     (M = 1).  The first bnn_batchbald_joint then gives marg - cond: plain BALD.
+ *   Errors: args, phat_out, expo_out, weight, offset, base NULL: BNN_ERR_NULL; S outside its limits: BNN_ERR_SHAPE; phat_out,
+ *   expo_out not 4-byte, weight, offset, base not 8-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_batchbald_extend   after bnn_acquire_topk appended the winner of step n = n_chosen: i* = labelled[*n_labelled - 1]
+ *     (the position and the row clamped into [0, N): a bad word never indexes outside P or labelled), chosen row j < n:
+ *     i_j = labelled[*n_labelled - n + j] likewise.  Writes the state of step n + 1 from (phat_in, expo_in) into (phat_out,
+ *     expo_out, weight, offset) -- in and out must not overlap --, *base += cond[i*] and, with batch_scores,
+ *     batch_scores[n - 1] = scores64[i*]: the BatchBALD value of the first n rows.
+ *     With `last` set nothing else is written: no further step reads a state (phat_out and its companions are untouched).
+ *     A FACTOR f[s] multiplies a row: v[s] = fl32(row[s] * f[s]); then the row is RESCALED by an exact power of two: with
+ *     x = max_s v[s] > 0 and frexp(x) = (f, e), f in [0.5, 1): row[s] = ldexpf(v[s], -e), E += e; an all-zero row keeps e = 0.
+ *     EXACT (C^n <= max_configs):  row m C + c of the M C new rows = row m times the factor P[s, i*, c], E from E[m];
+ *       weight = 2^E (ldexp(1.0, E)), offset = E ln 2 (fp64 product with 0x1.62e42fefa39efp-1).
+ *     SAMPLED (otherwise), M = max_configs rows, row m tied to weight draw s_m = m mod S: its label for chosen row j is
+ *       y = min(C - 1, #{c : cum_c <= t}), cum_c the fp32 running sums of P[s_m, i_j, :] in ascending c, t = fl32(u cum_{C-1}),
+ *       u = (word 0 >> 8) 2^-24 of Philox4x32-R((m, j | round << 8, 4, 1), key = (seed_lo, seed_hi)), R = bnn_philox_rounds():
+ *       counter words 2 and 3 are (4, 1), beside F10's (3, 1).  A pure function of (seed, round, m, j, that row of P).
+ *       At the first sampled step the rows are rebuilt from ones by the factors P[s, i_j, y_mj] of j = 0 .. n - 1 in
+ *       ascending j, rescaled after each; later steps multiply the rows of phat_in by the one factor j = n - 1.
+ *       weight = 1 / (M qt), qt = (sum_s row[s]) / S in fp64, ascending s (0 where qt = 0); offset = E ln 2: the paper's
+ *       importance-weighted estimator  H ~ -(1/M) sum_m sum_y (p(yhat_m, y) / p(yhat_m)) log p(yhat_m, y).
+ *   Errors: args, probs, cond, labelled, n_labelled, phat_in, expo_in, phat_out, expo_out, weight, offset, base NULL,
+ *   scores64 NULL with batch_scores: BNN_ERR_NULL; C, S, N as above, max_configs outside [1, BNN_BATCHBALD_MAX_CONFIGS],
+ *   n_chosen outside [1, BNN_BATCHBALD_MAX_K]: BNN_ERR_SHAPE; a 4-byte (probs, labelled, n_labelled, phat_*, expo_*) or
+ *   8-byte (cond, scores64, weight, offset, base, batch_scores) pointer misaligned: BNN_ERR_ALIGN.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_BATCHBALD_MAX_CLASSES 32
+#define BNN_BATCHBALD_MAX_SAMPLES 128     /* the K dimension of the joint product; a block's Phat tile is 64 x 132 fp32 = 33 KiB of LDS */
+#define BNN_BATCHBALD_MAX_K 64            /* rows of one batch (j takes 8 bits of the label stream's counter) */
+#define BNN_BATCHBALD_MAX_CONFIGS 65536
+/* layout: 6 x 4-byte words, 4 pointers */
+typedef struct bnn_batchbald_probs_args {
+  uint32_t struct_bytes;
+  int32_t n_samples;              /* S */
+  int32_t n_rows;                 /* N: rows of the pool */
+  int32_t n_classes;              /* C */
+  int32_t row0;                   /* first pool row of the chunk */
+  int32_t chunk_rows;             /* B */
+  const float* logits;            /* device [S, B, C] */
+  float* probs;                   /* device [S, N, C] */
+  double* cond;                   /* device [N] */
+  double* marg;                   /* device [N] */
+} bnn_batchbald_probs_args;
+/* layout: 6 x 4-byte words, 10 pointers, size_t */
+typedef struct bnn_batchbald_joint_args {
+  uint32_t struct_bytes;
+  int32_t n_samples;              /* S */
+  int32_t n_rows;                 /* N */
+  int32_t n_classes;              /* C */
+  int32_t n_configs;              /* M */
+  int32_t reserved;
+  const float* probs;             /* device [S, N, C] */
+  const float* phat;              /* device [M, S] */
+  const double* weight;           /* device [M] */
+  const double* offset;           /* device [M] */
+  const double* cond;             /* device [N] */
+  const double* base;             /* device word */
+  float* scores;                  /* device [N] */
+  double* scores64;               /* optional device [N] */
+  double* joint64;                /* optional device [N] */
+  void* workspace;
+  size_t workspace_bytes;
+} bnn_batchbald_joint_args;
+/* layout: 8 x 4-byte words, uint64, 13 pointers */
+typedef struct bnn_batchbald_state_args {
+  uint32_t struct_bytes;
+  int32_t n_samples;              /* S */
+  int32_t n_rows;                 /* N */
+  int32_t n_classes;              /* C */
+  int32_t max_configs;
+  int32_t n_chosen;               /* extend: n, the rows chosen so far, the winner included */
+  uint32_t round;                 /* extend: the acquisition round, word 1 of the label stream's counter (<< 8) */
+  uint32_t last;                  /* extend: nonzero = the last row of a batch: only *base and batch_scores are written */
+  uint64_t seed;
+  const float* probs;             /* device [S, N, C] */
+  const double* cond;             /* device [N] */
+  const int32_t* labelled;        /* device [N]: bnn_acquire_topk's list */
+  const int32_t* n_labelled;      /* device word */
+  const double* scores64;         /* optional device [N]: the step's bnn_batchbald_joint scores */
+  const float* phat_in;           /* device [M(n - 1), S] */
+  const int32_t* expo_in;         /* device [M(n - 1)] */
+  float* phat_out;                /* device [M(n), S] */
+  int32_t* expo_out;              /* device [M(n)] */
+  double* weight;                 /* device [M(n)] */
+  double* offset;                 /* device [M(n)] */
+  double* base;                   /* device word */
+  double* batch_scores;           /* optional device [>= n] */
+} bnn_batchbald_state_args;
+int32_t bnn_batchbald_configs(int32_t n_classes, int32_t n_chosen, int32_t max_configs);
+size_t bnn_batchbald_joint_workspace_bytes(int32_t n_rows, int32_t n_classes, int32_t n_configs);
+int bnn_batchbald_probs(const bnn_batchbald_probs_args* args, void* stream);
+int bnn_batchbald_joint(const bnn_batchbald_joint_args* args, void* stream);
+int bnn_batchbald_begin(const bnn_batchbald_state_args* args, void* stream);
+int bnn_batchbald_extend(const bnn_batchbald_state_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
