@@ -11,6 +11,7 @@
 `synth`      synthetic inputs with the reference's distributions (numpy only)
 `active`     ActivePool / ActiveLearner: pool scoring, top-k acquisition and training on the labelled subset (F10); BatchBALD batches
              chosen jointly (joint_probs / acquire_batchbald, F15)
+`flipout`    FlipoutLinear / FlipoutNetwork: the Flipout estimator on BayesianLinear's parameters, per-row weight noise (F16)
 `diagnostics` PosteriorStats: weight / sigma / SNR / posterior-sample histograms of a model in one device pass (F11)
 """
 from .runtime import get_math, manual_seed, set_host_eps, set_math, shard_samples  # noqa: F401

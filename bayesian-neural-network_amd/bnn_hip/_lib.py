@@ -43,6 +43,8 @@ EXPORTS = (
     "bnn_sparse_sigma_refresh",
     "bnn_batchbald_configs", "bnn_batchbald_joint_workspace_bytes", "bnn_batchbald_probs", "bnn_batchbald_joint",
     "bnn_batchbald_begin", "bnn_batchbald_extend",
+    "bnn_flipout_signs", "bnn_flipout_prepare", "bnn_flipout_fwd", "bnn_flipout_bwd",
+    "bnn_flipout_prepare_workspace_bytes", "bnn_flipout_bwd_workspace_bytes",
 )
 
 
@@ -448,6 +450,61 @@ class BatchBaldStateArgs(C.Structure):
                 ("batch_scores", C.c_void_p)]
 
 
+FLIPOUT_MAX_FEATURES = 16384
+
+
+class FlipoutSignsArgs(C.Structure):
+    """bnn_flipout_signs_args (include/bnn_hip.h F16)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("kind", C.c_int32), ("layer_id", C.c_uint32), ("sample_offset", C.c_uint32), ("row_offset", C.c_uint32),
+                ("seed", C.c_uint64), ("out", C.c_void_p)]
+
+
+class FlipoutPrepareArgs(C.Structure):
+    """bnn_flipout_prepare_args (include/bnn_hip.h F16)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("n_draws", C.c_int32),
+                ("in_features", C.c_int32), ("out_features", C.c_int32), ("eps_mode", C.c_int32), ("math", C.c_int32),
+                ("layer_id", C.c_uint32), ("sample_offset", C.c_uint32), ("sample_group", C.c_uint32),
+                ("sample_group_stride", C.c_uint32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("sample_counter", C.c_void_p),
+                ("w_mu", C.c_void_p), ("w_rho", C.c_void_p), ("b_mu", C.c_void_p), ("b_rho", C.c_void_p),
+                ("eps_w", C.c_void_p), ("eps_b", C.c_void_p),
+                ("prior", Prior), ("want_stats", C.c_int32),
+                ("delta", C.c_void_p), ("b_draw", C.c_void_p), ("delta_bf16", C.c_void_p), ("mu_bf16", C.c_void_p),
+                ("log_prior", C.c_void_p), ("log_q", C.c_void_p), ("eps_w_dump", C.c_void_p), ("eps_b_dump", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class FlipoutFwdArgs(C.Structure):
+    """bnn_flipout_fwd_args (include/bnn_hip.h F16)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("n_draws", C.c_int32),
+                ("batch", C.c_int32), ("in_features", C.c_int32), ("out_features", C.c_int32),
+                ("x_dtype", C.c_int32), ("x_per_sample", C.c_int32), ("math", C.c_int32), ("eps_mode", C.c_int32),
+                ("relu", C.c_int32), ("y_dtype", C.c_int32),
+                ("layer_id", C.c_uint32), ("sample_offset", C.c_uint32), ("sample_group", C.c_uint32),
+                ("sample_group_stride", C.c_uint32), ("row_offset", C.c_uint32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("sample_counter", C.c_void_p), ("x", C.c_void_p),
+                ("w_mu", C.c_void_p), ("delta", C.c_void_p), ("mu_bf16", C.c_void_p), ("delta_bf16", C.c_void_p),
+                ("b_draw", C.c_void_p), ("y", C.c_void_p)]
+
+
+class FlipoutBwdArgs(C.Structure):
+    """bnn_flipout_bwd_args (include/bnn_hip.h F16)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("n_draws", C.c_int32),
+                ("batch", C.c_int32), ("in_features", C.c_int32), ("out_features", C.c_int32),
+                ("x_per_sample", C.c_int32), ("relu", C.c_int32),
+                ("layer_id", C.c_uint32), ("sample_offset", C.c_uint32), ("sample_group", C.c_uint32),
+                ("sample_group_stride", C.c_uint32), ("row_offset", C.c_uint32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("sample_counter", C.c_void_p),
+                ("x", C.c_void_p), ("gy", C.c_void_p), ("y", C.c_void_p),
+                ("w_mu", C.c_void_p), ("w_rho", C.c_void_p), ("b_mu", C.c_void_p), ("b_rho", C.c_void_p),
+                ("eps_w", C.c_void_p), ("eps_b", C.c_void_p),
+                ("prior", Prior), ("reserved2", C.c_int32),
+                ("g_log_prior", C.c_void_p), ("g_log_q", C.c_void_p),
+                ("g_w_mu", C.c_void_p), ("g_w_rho", C.c_void_p), ("g_b_mu", C.c_void_p), ("g_b_rho", C.c_void_p),
+                ("g_x", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 HIST_MAX_JOBS = 16
 HIST_MAX_EDGES = 2048
 HIST_CHUNK = 8192
@@ -764,6 +821,14 @@ def _load_real():
                       ("bnn_batchbald_begin", BatchBaldStateArgs), ("bnn_batchbald_extend", BatchBaldStateArgs)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    for name, cls in (("bnn_flipout_signs", FlipoutSignsArgs), ("bnn_flipout_prepare", FlipoutPrepareArgs),
+                      ("bnn_flipout_fwd", FlipoutFwdArgs), ("bnn_flipout_bwd", FlipoutBwdArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    lib.bnn_flipout_prepare_workspace_bytes.restype = C.c_size_t
+    lib.bnn_flipout_prepare_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    lib.bnn_flipout_bwd_workspace_bytes.restype = C.c_size_t
+    lib.bnn_flipout_bwd_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

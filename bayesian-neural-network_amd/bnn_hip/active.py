@@ -53,6 +53,10 @@ def check_joint(net):
     """Host-side refusals of the joint (BatchBALD) acquisition: it needs the SAME weight draw s for every row of the pool,
     which only weight-space noise gives -- a BayesianNetwork with local_reparam=False, classification, all samples here."""
     import networks
+    from .flipout import FlipoutNetwork
+    if isinstance(net, FlipoutNetwork):
+        raise BnnHipError("batchbald: a Flipout network (FlipoutNetwork) draws its noise per row, not one weight draw shared "
+                          "across rows; use the BayesianNetwork it views (local_reparam=False) or 'bald'")
     if isinstance(net, networks.MLP_Dropout):
         raise BnnHipError("batchbald: MLP_Dropout draws its masks per row, not one weight draw shared across rows; use 'bald'")
     if not isinstance(net, networks.BayesianNetwork):

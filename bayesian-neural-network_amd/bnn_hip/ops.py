@@ -2562,3 +2562,136 @@ def batchbald_begin(a: L.BatchBaldStateArgs):
 def batchbald_extend(a: L.BatchBaldStateArgs):
     """bnn_batchbald_extend: the winner bnn_acquire_topk just appended folded into the state of the next step."""
     L.check(L.load().bnn_batchbald_extend(C.byref(a), _stream()), "bnn_batchbald_extend")
+
+
+# ---------------------------------------------------------------------------------------------- F16: Flipout
+def _flipout_math(math_mode: int) -> int:
+    if math_mode == L.MATH_BF16X3:
+        raise BnnHipError("Flipout has no split-bf16 (bf16x3) form: use bnn_hip.set_math('bf16') or set_math('f32')")
+    return math_mode
+
+
+def flipout_signs(seed: int, layer_id: int, kind: int, sample_offset: int, n_samples: int, rows: int, cols: int, device,
+                  row_offset: int = 0) -> torch.Tensor:
+    """The Flipout sign stream, materialised: int8[n_samples, rows, cols] of +1 / -1 (kind 0: input signs r, 1: output signs s)."""
+    lib = L.load()
+    if torch.device(device).type != "cuda":
+        raise BnnHipError("bnn_hip.flipout_signs needs a ROCm device")
+    out = torch.empty((n_samples, rows, cols), dtype=torch.int8, device=device)
+    a = L.FlipoutSignsArgs(C.sizeof(L.FlipoutSignsArgs), n_samples, rows, cols, kind, layer_id, sample_offset & 0xFFFFFFFF,
+                           row_offset & 0xFFFFFFFF, seed & 0xFFFFFFFFFFFFFFFF, out.data_ptr())
+    L.check(lib.bnn_flipout_signs(C.byref(a), _stream()), "bnn_flipout_signs")
+    return out
+
+
+def flipout_prepare(w_mu, w_rho, b_mu, b_rho, *, n_samples: int, n_draws: int, prior: PriorSpec, math_mode: int, eps_mode: int,
+                    eps_w=None, eps_b=None, seed: int = 0, layer_id: int = 0, sample_offset: int = 0, sample_counter=None,
+                    want_stats: bool = False, want_eps: bool = False) -> dict:
+    """Everything of a Flipout layer that depends on no activation (bnn_flipout_prepare): delta [D, out, in], b_draw [D, out],
+    in bf16 math their bf16 copies and mu's, with want_stats log_prior[D] / log_q[D], with want_eps the epsilon used."""
+    lib = L.load()
+    require_device(w_mu, w_rho, b_mu, b_rho, eps_w, eps_b)
+    math_mode = _flipout_math(math_mode)
+    N, K = w_mu.shape
+    D, dev = int(n_draws), w_mu.device
+    w_mu, w_rho, b_mu, b_rho = (_f32c(t, n) for t, n in ((w_mu, "w_mu"), (w_rho, "w_rho"), (b_mu, "b_mu"), (b_rho, "b_rho")))
+    if eps_mode == L.EPS_MEMORY:
+        eps_w, eps_b = _f32c(eps_w, "eps_w"), _f32c(eps_b, "eps_b")
+        if tuple(eps_w.shape) != (D, N, K) or tuple(eps_b.shape) != (D, N):
+            raise BnnHipError(f"flipout_prepare: injected eps must be [{D}, {N}, {K}] and [{D}, {N}] (one per base draw)")
+    bf16 = math_mode == L.MATH_BF16
+    out = dict(delta=torch.empty((D, N, K), dtype=torch.float32, device=dev), b_draw=torch.empty((D, N), dtype=torch.float32, device=dev),
+               delta_bf16=torch.empty((D, N, K), dtype=torch.bfloat16, device=dev) if bf16 else None,
+               mu_bf16=torch.empty((N, K), dtype=torch.bfloat16, device=dev) if bf16 else None,
+               log_prior=torch.empty(D, dtype=torch.float32, device=dev) if want_stats else None,
+               log_q=torch.empty(D, dtype=torch.float32, device=dev) if want_stats else None,
+               eps_w=torch.empty((D, N, K), dtype=torch.float32, device=dev) if want_eps else None,
+               eps_b=torch.empty((D, N), dtype=torch.float32, device=dev) if want_eps else None)
+    ws = None
+    if want_stats:
+        ws = torch.empty(max(1, lib.bnn_flipout_prepare_workspace_bytes(D, K, N) // 8), dtype=torch.float64, device=dev)
+    a = L.FlipoutPrepareArgs()
+    a.struct_bytes = C.sizeof(L.FlipoutPrepareArgs)
+    a.n_samples, a.n_draws, a.in_features, a.out_features = int(n_samples), D, K, N
+    a.eps_mode, a.math = eps_mode, math_mode
+    a.layer_id, a.sample_offset = layer_id, sample_offset & 0xFFFFFFFF
+    a.seed, a.sample_counter = seed & 0xFFFFFFFFFFFFFFFF, _ptr(sample_counter)
+    a.w_mu, a.w_rho, a.b_mu, a.b_rho = w_mu.data_ptr(), w_rho.data_ptr(), b_mu.data_ptr(), b_rho.data_ptr()
+    a.eps_w, a.eps_b = _ptr(eps_w), _ptr(eps_b)
+    a.prior, a.want_stats = prior.c(), int(bool(want_stats))
+    a.delta, a.b_draw, a.delta_bf16, a.mu_bf16 = out["delta"].data_ptr(), out["b_draw"].data_ptr(), _ptr(out["delta_bf16"]), _ptr(out["mu_bf16"])
+    a.log_prior, a.log_q, a.eps_w_dump, a.eps_b_dump = _ptr(out["log_prior"]), _ptr(out["log_q"]), _ptr(out["eps_w"]), _ptr(out["eps_b"])
+    a.workspace, a.workspace_bytes = _ptr(ws), 0 if ws is None else ws.numel() * 8
+    L.check(lib.bnn_flipout_prepare(C.byref(a), _stream()), "bnn_flipout_prepare")
+    out["_keep"] = (w_mu, w_rho, b_mu, b_rho, eps_w, eps_b, ws, sample_counter)
+    return out
+
+
+def flipout_fwd(x, prep: dict, w_mu, b_mu, *, n_samples: int, n_draws: int, math_mode: int, relu: bool, eps_mode: int,
+                y_dtype: torch.dtype = torch.float32, seed: int = 0, layer_id: int = 0, sample_offset: int = 0, sample_counter=None,
+                row_offset: int = 0) -> torch.Tensor:
+    """The Flipout layer (bnn_flipout_fwd) over flipout_prepare's operands: x [batch, in] (one minibatch for every sample) or
+    [S, batch, in] -> y [S, batch, out].  BNN_EPS_ZERO (prep may be None then, except in bf16 math): y = act(x mu^T + b_mu)."""
+    lib = L.load()
+    require_device(x, w_mu)
+    math_mode = _flipout_math(math_mode)
+    S, D = int(n_samples), int(n_draws)
+    N, K = w_mu.shape
+    if x.dim() not in (2, 3) or x.shape[-1] != K or (x.dim() == 3 and x.shape[0] != S):
+        raise BnnHipError(f"flipout_fwd: x must be [batch, {K}] or [{S}, batch, {K}], got {tuple(x.shape)}")
+    x = x if x.is_contiguous() else x.contiguous()
+    B = x.shape[-2]
+    bf16 = math_mode == L.MATH_BF16
+    if not bf16 and x.dtype != torch.float32:
+        raise BnnHipError("flipout_fwd: exact-fp32 math takes float32 activations")
+    zero = eps_mode == L.EPS_ZERO
+    y = torch.empty((S, B, N), dtype=y_dtype if bf16 else torch.float32, device=x.device)
+    a = L.FlipoutFwdArgs()
+    a.struct_bytes = C.sizeof(L.FlipoutFwdArgs)
+    a.n_samples, a.n_draws, a.batch, a.in_features, a.out_features = S, D, B, K, N
+    a.x_dtype, a.x_per_sample, a.math, a.eps_mode = _dt(x), int(x.dim() == 3), math_mode, eps_mode
+    a.relu, a.y_dtype = int(bool(relu)), _dt(y)
+    a.layer_id, a.sample_offset, a.row_offset = layer_id, sample_offset & 0xFFFFFFFF, row_offset & 0xFFFFFFFF
+    a.seed, a.sample_counter, a.x = seed & 0xFFFFFFFFFFFFFFFF, _ptr(sample_counter), x.data_ptr()
+    w_mu = _f32c(w_mu, "w_mu")
+    b = _f32c(b_mu, "b_mu") if zero else prep["b_draw"]
+    a.w_mu = w_mu.data_ptr()
+    if prep is not None:
+        a.delta, a.mu_bf16, a.delta_bf16 = _ptr(prep["delta"]), _ptr(prep["mu_bf16"]), _ptr(prep["delta_bf16"])
+    a.b_draw, a.y = b.data_ptr(), y.data_ptr()
+    L.check(lib.bnn_flipout_fwd(C.byref(a), _stream()), "bnn_flipout_fwd")
+    return y
+
+
+def flipout_bwd(x, gy, y, w_mu, w_rho, b_mu, b_rho, eps_w, eps_b, *, n_samples: int, n_draws: int, prior: PriorSpec, relu: bool,
+                seed: int = 0, layer_id: int = 0, sample_offset: int = 0, sample_counter=None, row_offset: int = 0,
+                g_log_prior=None, g_log_q=None, want_gx: bool = True, out=None):
+    """bnn_flipout_bwd: (g_w_mu, g_w_rho, g_b_mu, g_b_rho, g_x [S, batch, in] | None).  `out`: four tensors to write the
+    parameter gradients into."""
+    lib = L.load()
+    require_device(x, gy, w_mu)
+    S, D = int(n_samples), int(n_draws)
+    N, K = w_mu.shape
+    x, gy = _f32c(x, "x"), _f32c(gy, "gy")
+    B = x.shape[-2]
+    dev = x.device
+    g = list(out) if out is not None else [torch.empty_like(t, dtype=torch.float32) for t in (w_mu, w_rho, b_mu, b_rho)]
+    gx = torch.empty((S, B, K), dtype=torch.float32, device=dev) if want_gx else None
+    ws = torch.empty(lib.bnn_flipout_bwd_workspace_bytes(S, B, K, N) // 4, dtype=torch.float32, device=dev)
+    keep = [_f32c(t, "parameter") for t in (w_mu, w_rho, b_mu, b_rho, eps_w, eps_b)]
+    glp = None if g_log_prior is None else _f32c(g_log_prior, "g_log_prior")
+    glq = None if g_log_q is None else _f32c(g_log_q, "g_log_q")
+    a = L.FlipoutBwdArgs()
+    a.struct_bytes = C.sizeof(L.FlipoutBwdArgs)
+    a.n_samples, a.n_draws, a.batch, a.in_features, a.out_features = S, D, B, K, N
+    a.x_per_sample, a.relu = int(x.dim() == 3), int(bool(relu))
+    a.layer_id, a.sample_offset, a.row_offset = layer_id, sample_offset & 0xFFFFFFFF, row_offset & 0xFFFFFFFF
+    a.seed, a.sample_counter = seed & 0xFFFFFFFFFFFFFFFF, _ptr(sample_counter)
+    a.x, a.gy, a.y = x.data_ptr(), gy.data_ptr(), _ptr(y) if relu else None
+    a.w_mu, a.w_rho, a.b_mu, a.b_rho, a.eps_w, a.eps_b = (t.data_ptr() for t in keep)
+    a.prior = prior.c()
+    a.g_log_prior, a.g_log_q = _ptr(glp), _ptr(glq)
+    a.g_w_mu, a.g_w_rho, a.g_b_mu, a.g_b_rho = (t.data_ptr() for t in g)
+    a.g_x, a.workspace, a.workspace_bytes = _ptr(gx), ws.data_ptr(), ws.numel() * 4
+    L.check(lib.bnn_flipout_bwd(C.byref(a), _stream()), "bnn_flipout_bwd")
+    return g[0], g[1], g[2], g[3], gx

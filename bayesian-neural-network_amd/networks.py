@@ -27,6 +27,7 @@ from bnn_hip import _lib as _L
 from bnn_hip import engine as _engine
 from bnn_hip import dense_train as _dense_train
 from bnn_hip import mcdropout as _mcdropout
+from bnn_hip import flipout as _flipout
 from bnn_hip.functional import BBBLinearFn as _BBBLinearFn
 from bnn_hip.functional import LayerCall as _LayerCall
 from bnn_hip.functional import LRLinearFn as _LRLinearFn
@@ -133,6 +134,10 @@ class BayesianLinear(nn.Module):
         else:
             self.log_prior, self.log_variational_posterior = 0, 0
         return y[0]
+
+
+BayesianLinearFlipout = _flipout.FlipoutLinear     # Flipout layer (bnn_hip.flipout): BayesianLinear's parameters, per-row weight noise
+FlipoutNetwork = _flipout.FlipoutNetwork
 
 
 class BayesianLinearLR(nn.Module):
@@ -311,6 +316,12 @@ class BayesianNetwork(nn.Module):
         bnn_hip.engine.GraphedScore).  `capture`: True (hipGraph), "calls" or False."""
         return _engine.GraphedScore(self, x, y, int(samples), sigma=float(sigma), bins=int(bins), capture=capture,
                                     stacked=stacked, scores=scores)
+
+    def flipout(self, base_draws=1):
+        """Extension (not in the reference): a bnn_hip.flipout.FlipoutNetwork on the SAME Parameters (no copy) -- the Flipout
+        estimator (Wen et al., ICLR 2018): every batch row sees a base draw through its own sign pattern.  Train or evaluate
+        through it; this network remains the BBB view of the same posterior (pruning, compression, statistics, BatchBALD)."""
+        return _flipout.FlipoutNetwork.view_of(self, base_draws=base_draws)
 
     def elbo_many(self, inputs, targets, samples, sigma=1.):
         """Extension (not in the reference): the forward-only ELBO terms of G independent minibatches -- inputs

@@ -2002,6 +2002,175 @@ int bnn_batchbald_begin(const bnn_batchbald_state_args* args, void* stream);
 int bnn_batchbald_extend(const bnn_batchbald_state_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F16  Flipout (Wen, Vicol, Ba, Tran, Grosse, ICLR 2018): the third estimator of a factorised Gaussian posterior, beside
+ * weight sampling (K1) and local reparameterisation (K3).  One BASE DRAW Delta = sigma o eps per layer is seen by every batch
+ * row through its own rank-one sign pattern, W_n = mu + Delta o (s_n r_n^T): two dense products give each row of the minibatch
+ * its own, marginally exact, weight sample.  Weights are [out, in] (the BayesianLinear layout).  A call evaluates S = n_samples
+ * MC samples from D = n_draws base draws, D | S; sample s belongs to draw d = s / (S / D); the global index of sample s is
+ * g_s = sample_offset + *sample_counter + s (sample groups as in K1).
+ *
+ * Base draw.  eps_d [out, in] and eps_b,d [out] are the kind-0 and kind-1 epsilon maps of this layer (top of this file) at the
+ *   global index of the FIRST sample of block d -- with D = S every sample draws exactly the epsilon K1 draws for it.
+ *   sigma = softplus(rho) (bnn_softplus's bits), Delta_d = fl32(sigma * eps_d), b_d = fmaf(b_sigma, eps_b,d, b_mu): the bias is
+ *   not flipped.
+ * Signs.  A sign tensor of logical shape [rows, cols]; kind 0: the input signs r (cols = in), kind 1: the output signs s
+ *   (cols = out):
+ *       group = (row_offset + row) * ceil(cols / 128) + (col >> 7)                  (uint32)
+ *       (w0, w1, w2, w3) = Philox4x32-R((group, g_s, 4 * layer_id + kind, 2), key = (seed_lo, seed_hi))
+ *       b = col & 127;   sign[row, col] = -1 iff bit (b & 31) of w_(b >> 5) is set, else +1
+ *   Counter word 3 = 2: every epsilon stream has word 3 = 0, the bandit / epoch / acquisition / BatchBALD streams word 3 = 1, so
+ *   no existing stream moved and BNN_EPS_MAP_VERSION stays 2.  row_offset makes the signs of a batch independent of how it is
+ *   cut into calls; they depend on neither tiling nor S.  bnn_flipout_signs materialises the map (tests and tools).
+ * Forward.  y[s, n, o] = act( sum_k x[n, k] mu[o, k]  +  s[s, n, o] * sum_k (x[n, k] r[s, n, k]) Delta_d[o, k]  +  b_d[o] ).
+ *   Sign flips are sign-bit XORs, never multiplies.  BNN_EPS_ZERO: y = act(x mu^T + b_mu).
+ * ELBO terms.  log_q[d], log_prior[d] are evaluated at the base draw w = fmaf(sigma, eps_d, mu) and b_d, from fp32 block
+ *   partials {sum eps^2, sum w^2 | sum log p_mix(w), sum log sigma} folded in fp64 as bnn_elbo_finalize folds K1's: unbiased,
+ *   since every row's marginal is that distribution.
+ * Backward.  gz = gy o (y > 0) where ReLU applies;  G = sum_{s,n} gz^T x;  H_d = sum_{s in d, n} (gz o s)^T (x o r);
+ *   t_d = H_d + g_log_prior[d] dlogp/dw(mu + Delta_d);   g_mu = G + sum_d g_log_prior[d] dlogp/dw(mu + Delta_d);
+ *   g_rho = (sum_d t_d o eps_d - (sum_d g_log_q[d]) / sigma) sigmoid(rho);  the bias likewise from the row sums of gz (not
+ *   flipped);  g_x = gz mu + ((gz o s) Delta_d) o r.
+ *
+ * bnn_flipout_prepare   everything that depends on no activation, one read of (mu, rho) for all D draws: delta [D, out, in]
+ *     fp32, b_draw [D, out], with BNN_MATH_BF16 also delta_bf16 [D, out, in] and mu_bf16 [out, in] (RNE), with want_stats
+ *     log_prior[D] / log_q[D], and optionally the epsilon used (eps_w_dump [D, out, in], eps_b_dump [D, out]: what
+ *     bnn_flipout_bwd reads).  eps_mode: BNN_EPS_PHILOX, BNN_EPS_MEMORY (eps_w [D, out, in], eps_b [D, out]) or BNN_EPS_ZERO.
+ *     Workspace (want_stats): bnn_flipout_prepare_workspace_bytes(D, in, out), 8-byte aligned, any contents.
+ *   Errors, in this order: args NULL: BNN_ERR_NULL; struct_bytes: BNN_ERR_ABI; S, D < 1, S % D != 0, in / out outside
+ *   [1, BNN_FLIPOUT_MAX_FEATURES], Gaussian sigma_p or a mixture sigma <= 0: BNN_ERR_SHAPE; eps_mode, math (BNN_MATH_BF16X3 is
+ *   refused: use bf16 or f32), prior kind: BNN_ERR_ENUM; w_mu, w_rho, b_mu, b_rho, delta, b_draw, (MEMORY) eps_w, eps_b, (bf16)
+ *   delta_bf16, mu_bf16, (want_stats) log_prior, log_q NULL: BNN_ERR_NULL; workspace NULL or short with want_stats:
+ *   BNN_ERR_WORKSPACE; an fp32 pointer not 4-byte, a bf16 pointer not 2-byte, the workspace not 8-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_flipout_fwd   the layer on the matrix core: v_mfma_f32_16x16x4_f32 (BNN_MATH_F32, x and y fp32) or
+ *     v_mfma_f32_16x16x32_bf16 (BNN_MATH_BF16: mu_bf16 / delta_bf16, x fp32 or bf16 -- rounded RNE as it is staged --, y fp32 or
+ *     bf16), operands staged through LDS, two fp32 accumulator tiles per output tile (mean and perturbation).  r is XORed into
+ *     the staged x tile, s into the perturbation accumulator before it joins the mean accumulator; then bias, ReLU, store.
+ *     x [x_rows, batch, in], x_rows = 1 (x_per_sample = 0: x mu^T is computed once per block and shared by the samples the
+ *     block walks) or S (x_per_sample = 1).  y [S, batch, out].  BNN_EPS_ZERO: delta is not read, b_draw = b_mu, S = D = 1.
+ *     One fixed summation order per shape: ascending k inside each accumulator, then mean + perturbation + bias.
+ *   Errors, in this order: NULL args; ABI; S, D, batch < 1, S % D != 0, in / out outside [1, BNN_FLIPOUT_MAX_FEATURES],
+ *   x_per_sample not 0 / 1, (BNN_EPS_ZERO) S != 1: BNN_ERR_SHAPE; math (BF16X3 refused), eps_mode, x_dtype, y_dtype (fp32 only
+ *   in BNN_MATH_F32): BNN_ERR_ENUM; x, y, b_draw, (f32) w_mu, (bf16) mu_bf16, and unless BNN_EPS_ZERO delta / delta_bf16 NULL:
+ *   BNN_ERR_NULL; misaligned (element size) pointers: BNN_ERR_ALIGN.
+ *
+ * bnn_flipout_bwd   exact fp32, no float atomics, one fixed summation order per shape (rows in ascending (s, n) order per
+ *     weight; a repeated call gives the same bits).  Three launches: (1) gz, gz o s and x o r into the workspace; (2) one
+ *     thread per weight: G, H_d for d = 0 .. D-1 in turn, the prior / posterior terms and the rho chain, and per output the
+ *     bias gradients; (3) with g_x: the input gradient [S, batch, in] (sum it over S where x_per_sample = 0).  eps_w / eps_b are
+ *     the forward's epsilon as bnn_flipout_prepare dumped it (D |W| floats kept between forward and backward instead of a
+ *     second pass of the generator); Delta_d = fl32(sigma * eps_d) is re-formed from them.  g_log_prior / g_log_q: optional [D].
+ *     gx_relu_mask is not offered: the previous layer's backward applies its own ReLU mask through `y`.
+ *     Workspace: bnn_flipout_bwd_workspace_bytes(S, batch, in, out), 4-byte aligned, any contents.
+ *   Errors, in this order: NULL args; ABI; S, D, batch < 1, S % D != 0, in / out outside the limits, x_per_sample not 0 / 1, a
+ *   prior sigma <= 0: BNN_ERR_SHAPE; prior kind: BNN_ERR_ENUM; x, gy, w_mu, w_rho, b_mu, b_rho, eps_w, eps_b, g_w_mu, g_w_rho,
+ *   g_b_mu, g_b_rho, (relu) y NULL: BNN_ERR_NULL; workspace NULL or short: BNN_ERR_WORKSPACE; a pointer not 4-byte aligned:
+ *   BNN_ERR_ALIGN.
+ *
+ * bnn_flipout_signs   out[n_samples, rows, cols] int8 = +1 / -1, sample i at global index sample_offset + i.
+ *   Errors, in this order: NULL args; ABI; n_samples, rows, cols < 1: BNN_ERR_SHAPE; kind not 0 / 1: BNN_ERR_ENUM; out NULL.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_FLIPOUT_MAX_FEATURES 16384   /* in / out features of a Flipout layer */
+/* layout: 8 x 4-byte words, uint64, pointer */
+typedef struct bnn_flipout_signs_args {
+  uint32_t struct_bytes;
+  int32_t n_samples, rows, cols;
+  int32_t kind;                   /* 0: r (input signs), 1: s (output signs) */
+  uint32_t layer_id;
+  uint32_t sample_offset, row_offset;
+  uint64_t seed;
+  int8_t* out;                    /* device [n_samples, rows, cols] */
+} bnn_flipout_signs_args;
+/* layout: 12 x 4-byte words, uint64, 7 pointers, prior (5 words) + want_stats, 8 pointers, size_t */
+typedef struct bnn_flipout_prepare_args {
+  uint32_t struct_bytes;
+  int32_t n_samples, n_draws;     /* S, D */
+  int32_t in_features, out_features;
+  int32_t eps_mode, math;
+  uint32_t layer_id, sample_offset, sample_group, sample_group_stride;
+  int32_t reserved;
+  uint64_t seed;
+  const uint32_t* sample_counter; /* optional device word (K1) */
+  const float* w_mu;
+  const float* w_rho;
+  const float* b_mu;
+  const float* b_rho;
+  const float* eps_w;             /* BNN_EPS_MEMORY: [D, out, in] */
+  const float* eps_b;             /* BNN_EPS_MEMORY: [D, out] */
+  bnn_prior prior;
+  int32_t want_stats;
+  float* delta;                   /* [D, out, in] */
+  float* b_draw;                  /* [D, out] */
+  void* delta_bf16;               /* BNN_MATH_BF16: [D, out, in] */
+  void* mu_bf16;                  /* BNN_MATH_BF16: [out, in] */
+  float* log_prior;               /* want_stats: [D] */
+  float* log_q;                   /* want_stats: [D] */
+  float* eps_w_dump;              /* optional [D, out, in] */
+  float* eps_b_dump;              /* optional [D, out] */
+  void* workspace;
+  size_t workspace_bytes;
+} bnn_flipout_prepare_args;
+/* layout: 18 x 4-byte words, uint64, 8 pointers */
+typedef struct bnn_flipout_fwd_args {
+  uint32_t struct_bytes;
+  int32_t n_samples, n_draws;     /* S, D */
+  int32_t batch, in_features, out_features;
+  int32_t x_dtype, x_per_sample;  /* bnn_dtype; 0: one x for all samples, 1: one per sample */
+  int32_t math, eps_mode;
+  int32_t relu, y_dtype;
+  uint32_t layer_id, sample_offset, sample_group, sample_group_stride;
+  uint32_t row_offset;            /* first batch row's index in the sign maps */
+  int32_t reserved;
+  uint64_t seed;
+  const uint32_t* sample_counter;
+  const void* x;
+  const float* w_mu;              /* BNN_MATH_F32 */
+  const float* delta;             /* BNN_MATH_F32: [D, out, in] */
+  const void* mu_bf16;            /* BNN_MATH_BF16 */
+  const void* delta_bf16;         /* BNN_MATH_BF16 */
+  const float* b_draw;            /* [D, out]; BNN_EPS_ZERO: b_mu */
+  void* y;                        /* [S, batch, out] */
+} bnn_flipout_fwd_args;
+/* layout: 14 x 4-byte words, uint64, 10 pointers, prior (5 words) + reserved2, 7 pointers, workspace, size_t */
+typedef struct bnn_flipout_bwd_args {
+  uint32_t struct_bytes;
+  int32_t n_samples, n_draws;
+  int32_t batch, in_features, out_features;
+  int32_t x_per_sample, relu;
+  uint32_t layer_id, sample_offset, sample_group, sample_group_stride;
+  uint32_t row_offset;
+  int32_t reserved;
+  uint64_t seed;
+  const uint32_t* sample_counter;
+  const float* x;                 /* [x_rows, batch, in] */
+  const float* gy;                /* [S, batch, out] */
+  const float* y;                 /* relu: the forward's output */
+  const float* w_mu;
+  const float* w_rho;
+  const float* b_mu;
+  const float* b_rho;
+  const float* eps_w;             /* [D, out, in]: the forward's epsilon */
+  const float* eps_b;             /* [D, out] */
+  bnn_prior prior;
+  int32_t reserved2;
+  const float* g_log_prior;       /* optional [D] */
+  const float* g_log_q;           /* optional [D] */
+  float* g_w_mu;
+  float* g_w_rho;
+  float* g_b_mu;
+  float* g_b_rho;
+  float* g_x;                     /* optional [S, batch, in] */
+  void* workspace;
+  size_t workspace_bytes;
+} bnn_flipout_bwd_args;
+size_t bnn_flipout_prepare_workspace_bytes(int32_t n_draws, int32_t in_features, int32_t out_features);   /* 0 outside the limits */
+size_t bnn_flipout_bwd_workspace_bytes(int32_t n_samples, int32_t batch, int32_t in_features, int32_t out_features);
+int bnn_flipout_signs(const bnn_flipout_signs_args* args, void* stream);
+int bnn_flipout_prepare(const bnn_flipout_prepare_args* args, void* stream);
+int bnn_flipout_fwd(const bnn_flipout_fwd_args* args, void* stream);
+int bnn_flipout_bwd(const bnn_flipout_bwd_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
