@@ -12,10 +12,13 @@
 `active`     ActivePool / ActiveLearner: pool scoring, top-k acquisition and training on the labelled subset (F10); BatchBALD batches
              chosen jointly (joint_probs / acquire_batchbald, F15)
 `flipout`    FlipoutLinear / FlipoutNetwork: the Flipout estimator on BayesianLinear's parameters, per-row weight noise (F16)
+`laplace`    DiagLaplace: a diagonal Laplace posterior for a trained MLP / MLP_Dropout, Fisher accumulation on the device, the prior
+             precision by the marginal likelihood, the result a BayesianNetwork (F17)
 `diagnostics` PosteriorStats: weight / sigma / SNR / posterior-sample histograms of a model in one device pass (F11)
 """
 from .runtime import get_math, manual_seed, set_host_eps, set_math, shard_samples  # noqa: F401
 from ._lib import BnnHipError  # noqa: F401
 from .active import ActiveLearner, ActivePool  # noqa: F401
+from .laplace import DiagLaplace  # noqa: F401
 
-__all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError", "ActiveLearner", "ActivePool"]
+__all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError", "ActiveLearner", "ActivePool", "DiagLaplace"]

@@ -45,6 +45,7 @@ EXPORTS = (
     "bnn_batchbald_begin", "bnn_batchbald_extend",
     "bnn_flipout_signs", "bnn_flipout_prepare", "bnn_flipout_fwd", "bnn_flipout_bwd",
     "bnn_flipout_prepare_workspace_bytes", "bnn_flipout_bwd_workspace_bytes",
+    "bnn_laplace_seed", "bnn_laplace_layer", "bnn_laplace_evidence", "bnn_laplace_posterior", "bnn_laplace_evidence_workspace_bytes",
 )
 
 
@@ -505,6 +506,45 @@ class FlipoutBwdArgs(C.Structure):
                 ("g_x", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+LAPLACE_MAX_PRECISIONS = 64
+LAPLACE_MAX_TENSORS = 16
+LAPLACE_CHUNK = 4096
+LAPLACE_RECORD_DOUBLES = 2
+LAPLACE_GGN, LAPLACE_EMPIRICAL = 0, 1
+
+
+class LaplaceSeedArgs(C.Structure):
+    """bnn_laplace_seed_args (include/bnn_hip.h F17)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("batch", C.c_int32), ("classes", C.c_int32), ("loss_mode", C.c_int32),
+                ("curvature", C.c_int32), ("reserved", C.c_int32), ("sigma", C.c_double),
+                ("logits", C.c_void_p), ("target", C.c_void_p), ("gy", C.c_void_p), ("record", C.c_void_p)]
+
+
+class LaplaceLayerArgs(C.Structure):
+    """bnn_laplace_layer_args (include/bnn_hip.h F17)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("batch", C.c_int32), ("rows", C.c_int32), ("in_features", C.c_int32),
+                ("out_features", C.c_int32), ("math", C.c_int32), ("gx_mask", C.c_int32), ("reserved", C.c_int32),
+                ("x", C.c_void_p), ("gy", C.c_void_p), ("y", C.c_void_p), ("w", C.c_void_p),
+                ("f_w", C.c_void_p), ("f_b", C.c_void_p), ("g_x", C.c_void_p), ("s_out", C.c_void_p)]
+
+
+class LaplaceEvidenceArgs(C.Structure):
+    """bnn_laplace_evidence_args (include/bnn_hip.h F17)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_tensors", C.c_int32), ("n_precisions", C.c_int32), ("reserved", C.c_int32),
+                ("param", C.c_void_p * LAPLACE_MAX_TENSORS), ("curv", C.c_void_p * LAPLACE_MAX_TENSORS),
+                ("numel", C.c_int64 * LAPLACE_MAX_TENSORS), ("precision", C.c_double * LAPLACE_MAX_PRECISIONS),
+                ("record", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("log_evidence", C.c_void_p), ("best_index", C.c_void_p), ("best", C.c_void_p)]
+
+
+class LaplacePosteriorArgs(C.Structure):
+    """bnn_laplace_posterior_args (include/bnn_hip.h F17)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_tensors", C.c_int32),
+                ("param", C.c_void_p * LAPLACE_MAX_TENSORS), ("curv", C.c_void_p * LAPLACE_MAX_TENSORS),
+                ("mu", C.c_void_p * LAPLACE_MAX_TENSORS), ("rho", C.c_void_p * LAPLACE_MAX_TENSORS),
+                ("numel", C.c_int64 * LAPLACE_MAX_TENSORS), ("precision", C.c_double), ("precision_device", C.c_void_p)]
+
+
 HIST_MAX_JOBS = 16
 HIST_MAX_EDGES = 2048
 HIST_CHUNK = 8192
@@ -829,6 +869,12 @@ def _load_real():
     lib.bnn_flipout_prepare_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     lib.bnn_flipout_bwd_workspace_bytes.restype = C.c_size_t
     lib.bnn_flipout_bwd_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    for name, cls in (("bnn_laplace_seed", LaplaceSeedArgs), ("bnn_laplace_layer", LaplaceLayerArgs),
+                      ("bnn_laplace_evidence", LaplaceEvidenceArgs), ("bnn_laplace_posterior", LaplacePosteriorArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    lib.bnn_laplace_evidence_workspace_bytes.restype = C.c_size_t
+    lib.bnn_laplace_evidence_workspace_bytes.argtypes = [C.POINTER(LaplaceEvidenceArgs)]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

@@ -2695,3 +2695,149 @@ def flipout_bwd(x, gy, y, w_mu, w_rho, b_mu, b_rho, eps_w, eps_b, *, n_samples: 
     a.g_x, a.workspace, a.workspace_bytes = _ptr(gx), ws.data_ptr(), ws.numel() * 4
     L.check(lib.bnn_flipout_bwd(C.byref(a), _stream()), "bnn_flipout_bwd")
     return g[0], g[1], g[2], g[3], gx
+
+
+# ---------------------------------------------------------------------------------------------- F17: diagonal Laplace
+LAPLACE_CURVATURES = {"ggn": L.LAPLACE_GGN, "empirical": L.LAPLACE_EMPIRICAL}
+
+
+def _lap_f32(t, name: str, shape=None):
+    """A contiguous float32 device tensor (of `shape`), or None."""
+    if t is None:
+        return None
+    require_device(t)
+    if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = "" if shape is None else f" of shape {tuple(shape)}"
+        raise BnnHipError(f"laplace: {name} must be a contiguous float32 tensor{want}, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def _lap_f64(t, name: str, numel: int):
+    require_device(t)
+    if t.dtype != torch.float64 or not t.is_contiguous() or t.numel() != numel:
+        raise BnnHipError(f"laplace: {name} must be a contiguous float64 tensor of {numel} elements")
+    return t
+
+
+def laplace_rows(batch: int, classes: int, curvature: str) -> int:
+    """The virtual rows R of a minibatch: batch * classes under the GGN (one per class), batch under the empirical Fisher."""
+    if curvature not in LAPLACE_CURVATURES:
+        raise BnnHipError(f"laplace: curvature must be one of {tuple(LAPLACE_CURVATURES)}, got {curvature!r}")
+    return batch * classes if curvature == "ggn" else batch
+
+
+def laplace_seed(logits, target, mode: str, *, curvature: str = "ggn", sigma: float = 1.0, gy=None, record):
+    """F17 bnn_laplace_seed: the output-layer deltas gy [R, C] (virtual row c * B + n under the GGN) of logits [B, C], and
+    record (float64 [2]) += (sum of log-likelihoods, B).  `target`: int64 [B] (classification) or float32 of B * C elements
+    (regression); None under the GGN leaves record[0] alone."""
+    lib = L.load()
+    logits = _lap_f32(logits, "logits")
+    if logits.dim() != 2:
+        raise BnnHipError(f"laplace_seed: logits must be [batch, classes], got {tuple(logits.shape)}")
+    B, Cc = logits.shape
+    R = laplace_rows(B, Cc, curvature)
+    if mode not in ("classification", "regression"):
+        raise BnnHipError(f"laplace_seed: unknown mode {mode!r}")
+    if target is not None:
+        require_device(target)
+        if mode == "classification" and (target.dtype != torch.int64 or target.numel() != B):
+            raise BnnHipError("laplace_seed: classification targets must be int64 labels, one per row")
+        if mode == "regression" and (target.dtype != torch.float32 or target.numel() != B * Cc):
+            raise BnnHipError(f"laplace_seed: regression targets must be float32 with {B * Cc} elements")
+        target = target if target.is_contiguous() else target.contiguous()
+    gy = torch.empty((R, Cc), dtype=torch.float32, device=logits.device) if gy is None else _lap_f32(gy, "gy", (R, Cc))
+    a = L.LaplaceSeedArgs()
+    a.struct_bytes = C.sizeof(L.LaplaceSeedArgs)
+    a.batch, a.classes = B, Cc
+    a.loss_mode = L.NLL_CLASSIFICATION if mode == "classification" else L.NLL_REGRESSION
+    a.curvature, a.sigma = LAPLACE_CURVATURES[curvature], float(sigma)
+    a.logits, a.target, a.gy = logits.data_ptr(), _ptr(target), gy.data_ptr()
+    a.record = _lap_f64(record, "record", L.LAPLACE_RECORD_DOUBLES).data_ptr()
+    L.check(lib.bnn_laplace_seed(C.byref(a), _stream()), "bnn_laplace_seed")
+    return gy
+
+
+def laplace_layer(x, gy, w, *, f_w, f_b=None, g_x=None, y=None, gx_mask: bool = False, s_out=None,
+                  math_mode: int = L.MATH_F32):
+    """F17 bnn_laplace_layer: one Linear -> [ReLU] group.  x [B, in], gy [R, out] (R a multiple of B), the saved output
+    y [B, out] (gz = y > 0 ? gy : 0) or None; f_w [out, in] += S^T x^2, f_b [out] += colsum(S) with S[n, o] the sum over
+    the virtual rows of data row n of gz^2; g_x [R, in] = gz w, times (x > 0) when gx_mask; s_out [B, out] = S."""
+    lib = L.load()
+    x = _lap_f32(x, "x")
+    B, K = x.shape
+    N = w.shape[0]
+    gy = _lap_f32(gy, "gy")
+    R = gy.shape[0]
+    if gy.dim() != 2 or R % B != 0:
+        raise BnnHipError(f"laplace_layer: gy must be [rows, out] with rows a multiple of the batch {B}, got {tuple(gy.shape)}")
+    _lap_f32(gy, "gy", (R, N)), _lap_f32(w, "w", (N, K)), _lap_f32(f_w, "f_w", (N, K)), _lap_f32(f_b, "f_b", (N,))
+    _lap_f32(g_x, "g_x", (R, K)), _lap_f32(y, "y", (B, N)), _lap_f32(s_out, "s_out", (B, N))
+    a = L.LaplaceLayerArgs()
+    a.struct_bytes = C.sizeof(L.LaplaceLayerArgs)
+    a.batch, a.rows, a.in_features, a.out_features = B, R, K, N
+    a.math, a.gx_mask = _exact_unless_bf16(math_mode), int(bool(gx_mask))
+    a.x, a.gy, a.y, a.w = x.data_ptr(), gy.data_ptr(), _ptr(y), w.data_ptr()
+    a.f_w, a.f_b, a.g_x, a.s_out = f_w.data_ptr(), _ptr(f_b), _ptr(g_x), _ptr(s_out)
+    L.check(lib.bnn_laplace_layer(C.byref(a), _stream()), "bnn_laplace_layer")
+
+
+def _lap_pairs(a, params, curvs):
+    n = len(params)
+    if not 1 <= n <= L.LAPLACE_MAX_TENSORS or len(curvs) != n:
+        raise BnnHipError(f"laplace: between 1 and {L.LAPLACE_MAX_TENSORS} (parameter, curvature) pairs, got {n} / {len(curvs)}")
+    a.n_tensors = n
+    for j, (p, f) in enumerate(zip(params, curvs)):
+        _lap_f32(p, "parameter"), _lap_f32(f, "curvature", p.shape)
+        a.param[j], a.curv[j], a.numel[j] = p.data_ptr(), f.data_ptr(), p.numel()
+
+
+def laplace_evidence(params, curvs, precisions, *, record, log_evidence=None, best_index=None, best=None, workspace=None):
+    """F17 bnn_laplace_evidence: the Laplace log marginal likelihood at every candidate prior precision (host floats), in
+    fp64 on the device -> (log_evidence float64 [G], best_index int32 [1], best float64 [2] = (maximum, its precision)).
+    Nothing is read back."""
+    lib = L.load()
+    taus = [float(t) for t in precisions]
+    G = len(taus)
+    if not 1 <= G <= L.LAPLACE_MAX_PRECISIONS:
+        raise BnnHipError(f"laplace_evidence: between 1 and {L.LAPLACE_MAX_PRECISIONS} candidate precisions, got {G}")
+    if not all(0.0 < t < math.inf for t in taus):
+        raise BnnHipError("laplace_evidence: prior precisions must be positive and finite")
+    a = L.LaplaceEvidenceArgs()
+    a.struct_bytes = C.sizeof(L.LaplaceEvidenceArgs)
+    _lap_pairs(a, params, curvs)
+    a.n_precisions = G
+    for g, t in enumerate(taus):
+        a.precision[g] = t
+    dev = params[0].device
+    need = lib.bnn_laplace_evidence_workspace_bytes(C.byref(a))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    log_evidence = torch.empty(G, dtype=torch.float64, device=dev) if log_evidence is None else _lap_f64(log_evidence, "log_evidence", G)
+    best_index = torch.zeros(1, dtype=torch.int32, device=dev) if best_index is None else _typed(best_index, torch.int32, "best_index", 1)
+    best = torch.zeros(2, dtype=torch.float64, device=dev) if best is None else _lap_f64(best, "best", 2)
+    a.record = _lap_f64(record, "record", L.LAPLACE_RECORD_DOUBLES).data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a.log_evidence, a.best_index, a.best = log_evidence.data_ptr(), best_index.data_ptr(), best.data_ptr()
+    L.check(lib.bnn_laplace_evidence(C.byref(a), _stream()), "bnn_laplace_evidence")
+    return log_evidence, best_index, best
+
+
+def laplace_posterior(params, curvs, mus, rhos, *, precision=None, precision_device=None):
+    """F17 bnn_laplace_posterior: mu = w, rho = softplus^-1((F + tau)^-1/2) for every tensor in one launch; tau a host float
+    or a one-element float64 device tensor (best[1:2] of laplace_evidence)."""
+    lib = L.load()
+    a = L.LaplacePosteriorArgs()
+    a.struct_bytes = C.sizeof(L.LaplacePosteriorArgs)
+    _lap_pairs(a, params, curvs)
+    if len(mus) != len(params) or len(rhos) != len(params):
+        raise BnnHipError("laplace_posterior: one (mu, rho) pair per parameter")
+    for j, (p, m, r) in enumerate(zip(params, mus, rhos)):
+        _lap_f32(m, "mu", p.shape), _lap_f32(r, "rho", p.shape)
+        a.mu[j], a.rho[j] = m.data_ptr(), r.data_ptr()
+    if precision_device is not None:
+        a.precision, a.precision_device = 1.0, _lap_f64(precision_device, "precision_device", 1).data_ptr()
+    else:
+        if precision is None or not 0.0 < float(precision) < math.inf:
+            raise BnnHipError(f"laplace_posterior: the prior precision must be positive and finite, got {precision!r}")
+        a.precision, a.precision_device = float(precision), None
+    L.check(lib.bnn_laplace_posterior(C.byref(a), _stream()), "bnn_laplace_posterior")

@@ -4,7 +4,7 @@
 //
 // bnn_dense_bwd.  Two GEMMs share one grid: blocks [0, tiles_x) own 64 x 64 tiles of g_x = gz . W (K = out), the rest
 // 64 x 64 tiles of g_w = gz^T . x (K = batch).  The g_x tiles come first: at the MNIST shape they have ~10 x the k
-// stages of a weight-gradient tile, so they start in the first dispatch wave.  The GEMM core is K5's: a 256-thread block
+// stages of a weight-gradient tile, so they start in the first dispatch wave.  The GEMM core (dense_tile.h) is K5's: a 256-thread block
 // of 2 x 2 waves, 2 x 2 accumulators of 16 x 16 per wave, K walked in 32-wide stages through two LDS buffers (next
 // stage loaded into registers during the current stage's MFMAs), the same XOR-swizzled [row][k] image.  What differs is
 // the operands' memory order: gz^T, x and W are read along their contiguous (row) dimension -- a thread loads 8
@@ -15,153 +15,13 @@
 #include <math.h>
 
 #include "bnn_device.h"
+#include "dense_tile.h"
 #include "../../include/bnn_hip.h"
 
 namespace bnn {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kBK = 32;      // k per LDS stage
-constexpr int kT = 64;       // tile rows and columns (2 waves x 2 accumulators x 16)
 constexpr int kSgdChunk = 4096;
-
-// An operand of C[m, n] = sum_k A(m, k) B(n, k): element (r, k) at p[r * ld + k] (kc: k contiguous) or p[k * ld + r].
-// msk (optional): the value is p[.] * (msk[.] > 0 ? s : 0) -- gz formed from gy and the saved output y.
-struct Opnd {
-  const float* p;
-  const float* msk;
-  float s;
-  int ld, rows, vec;
-};
-
-__device__ __forceinline__ float gz_of(float g, const float* msk, long i, float s) {
-  return msk ? (msk[i] > 0.f ? g * s : 0.f) : g;
-}
-
-template <typename T>
-__device__ __forceinline__ int swz(int row, int chunk) {
-  constexpr int CH = kBK * (int)sizeof(T) / 16;
-  return row * CH + (chunk ^ ((row >> 1) & (CH - 1)));
-}
-
-// the element index (in T) of (row, k) in the stage image
-template <typename T>
-__device__ __forceinline__ int elem(int row, int k) {
-  constexpr int PER = 16 / (int)sizeof(T);
-  return swz<T>(row, k / PER) * PER + (k % PER);
-}
-
-// 8 elements p[base + j * step] (j < valid; zero beyond), masked; vec: two 16-byte loads (step 1, valid == 8)
-__device__ __forceinline__ void load8(const Opnd& o, long base, long step, int valid, bool vec, float v[8]) {
-  if (vec && valid == 8) {
-    const float4 a = *reinterpret_cast<const float4*>(o.p + base), b = *reinterpret_cast<const float4*>(o.p + base + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    if (o.msk) {
-      const float4 c = *reinterpret_cast<const float4*>(o.msk + base), d = *reinterpret_cast<const float4*>(o.msk + base + 4);
-      const float m[8] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = m[j] > 0.f ? v[j] * o.s : 0.f;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = j < valid ? gz_of(o.p[base + j * step], o.msk, base + j * step, o.s) : 0.f;
-  }
-}
-
-// One thread's segment of an operand's stage: 8 elements.  kc: row r = s / 4, k = 8 (s % 4) .. +7 (along k);
-// otherwise k = s / 8, rows 8 (s % 8) .. +7 (along the rows).  r0: the tile's first row, k0: the stage's first k.
-template <bool KC>
-__device__ __forceinline__ void fetch_seg(const Opnd& o, int K, int r0, int k0, int s, float v[8]) {
-  if constexpr (KC) {
-    const int r = r0 + (s >> 2), k = k0 + 8 * (s & 3);
-    const int valid = r < o.rows ? min(8, max(0, K - k)) : 0;
-    load8(o, (long)r * o.ld + k, 1, valid, o.vec, v);
-  } else {
-    const int k = k0 + (s >> 3), r = r0 + 8 * (s & 7);
-    const int valid = k < K ? min(8, max(0, o.rows - r)) : 0;
-    load8(o, (long)k * o.ld + r, 1, valid, o.vec, v);
-  }
-}
-
-template <typename T, bool KC>
-__device__ __forceinline__ void stash_seg(T* img, int s, const float v[8]) {
-  if constexpr (KC) {
-    const int r = s >> 2, k = 8 * (s & 3);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) img[elem<T>(r, k + j)] = (T)v[j];
-  } else {
-    const int k = s >> 3, r = 8 * (s & 7);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) img[elem<T>(r + j, k)] = (T)v[j];
-  }
-}
-
-// acc[i][j] (rows wm 32 + 16 i, columns wn 32 + 16 j of the tile) = sum_k A(m0 + ., k) B(n0 + ., k) over k < K
-template <typename T, bool AKC, bool BKC>
-__device__ __forceinline__ void gemm_tile(const Opnd& A, const Opnd& Bo, int m0, int n0, int K, uint4* lds, f32x4 acc[2][2]) {
-  constexpr int ROW_CHUNKS = kBK * (int)sizeof(T) / 16;
-  constexpr int STAGE = 2 * kT * ROW_CHUNKS;                  // uint4 per stage buffer (A rows, then B rows)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int fr = lane & 15, fg = lane >> 4;
-  float ra[8], rb[8];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto stash = [&](int buf) {
-    T* img = reinterpret_cast<T*>(lds + buf * STAGE);
-    stash_seg<T, AKC>(img, tid, ra);
-    stash_seg<T, BKC>(img + kT * ROW_CHUNKS * (16 / (int)sizeof(T)), tid, rb);
-  };
-  const int nk = (K + kBK - 1) / kBK;
-  fetch_seg<AKC>(A, K, m0, 0, tid, ra);
-  fetch_seg<BKC>(Bo, K, n0, 0, tid, rb);
-  stash(0);
-  __syncthreads();
-#pragma unroll 1
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + 1 < nk) {
-      fetch_seg<AKC>(A, K, m0, (kt + 1) * kBK, tid, ra);
-      fetch_seg<BKC>(Bo, K, n0, (kt + 1) * kBK, tid, rb);
-    }
-    const uint4* img = lds + (kt & 1) * STAGE;
-    if constexpr (sizeof(T) == 2) {
-      bf16x8 af[2], bf[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) af[i] = __builtin_bit_cast(bf16x8, img[swz<T>(wm * 32 + i * 16 + fr, fg)]);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bf[j] = __builtin_bit_cast(bf16x8, img[kT * ROW_CHUNKS + swz<T>(wn * 32 + j * 16 + fr, fg)]);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
-    } else {
-      f32x4 af[2][2], bf[2][2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int r = wm * 32 + i * 16 + fr;
-        af[i][0] = __builtin_bit_cast(f32x4, img[swz<T>(r, fg)]);
-        af[i][1] = __builtin_bit_cast(f32x4, img[swz<T>(r, fg + 4)]);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int r = wn * 32 + j * 16 + fr;
-        bf[j][0] = __builtin_bit_cast(f32x4, img[kT * ROW_CHUNKS + swz<T>(r, fg)]);
-        bf[j][1] = __builtin_bit_cast(f32x4, img[kT * ROW_CHUNKS + swz<T>(r, fg + 4)]);
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][e >> 2][e & 3], bf[j][e >> 2][e & 3], acc[i][j], 0, 0, 0);
-    }
-    if (kt + 1 < nk) stash((kt + 1) & 1);
-    __syncthreads();
-  }
-}
 
 struct BwdParams {
   const float* x;
@@ -177,10 +37,6 @@ struct BwdParams {
   int tiles_x, tiles_x_n, tiles_w_n;
   int vec_x, vec_g, vec_w, vec_out;
 };
-
-constexpr int kOutLd = kT + 4;                                  // the epilogue's fp32 tile row, 16-byte rows
-constexpr int kLdsUint4 = 2 * 2 * kT * (kBK * 4 / 16);          // two fp32 stages (the larger image)
-static_assert(kLdsUint4 * 4 >= kT * kOutLd, "the epilogue tile fits the stage buffers");
 
 // the tile through LDS (lane: column lane & 15, rows 4 (lane >> 4) + e of each 16 x 16 accumulator), then 4 consecutive
 // columns of a row per thread: out[row, col] (row pitch IN) = v, times (x[row, col] > 0 ? s : 0) when mask

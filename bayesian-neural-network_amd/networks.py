@@ -28,6 +28,7 @@ from bnn_hip import engine as _engine
 from bnn_hip import dense_train as _dense_train
 from bnn_hip import mcdropout as _mcdropout
 from bnn_hip import flipout as _flipout
+from bnn_hip import laplace as _laplace
 from bnn_hip.functional import BBBLinearFn as _BBBLinearFn
 from bnn_hip.functional import LayerCall as _LayerCall
 from bnn_hip.functional import LRLinearFn as _LRLinearFn
@@ -408,6 +409,13 @@ class _PlainMLP(nn.Module):
         bnn_hip.optim.FusedSGD or FusedAdam with capturable=True; keywords: loss ('cross_entropy' | 'mse'), capture.
         Dropout is always on (train mode), with fresh masks every step (bnn_hip.dense_train.GraphedDenseTrainStep)."""
         return _dense_train.GraphedDenseTrainStep(self, optimizer, x, y, **kw)
+
+    def laplace(self, **kw):
+        """Extension (not in the reference): a bnn_hip.laplace.DiagLaplace on this trained network -- the diagonal Laplace
+        posterior (keywords: curvature 'ggn' | 'empirical', sigma).  `la = mlp.laplace(); la.fit(loader);
+        la.fit_prior_precision(); bnn = la.network()` gives a BayesianNetwork centred on these weights.  MLP_Dropout: with
+        the dropout off (mlp.eval())."""
+        return _laplace.DiagLaplace(self, **kw)
 
 
 class MLP(_PlainMLP):

@@ -2171,6 +2171,133 @@ int bnn_flipout_fwd(const bnn_flipout_fwd_args* args, void* stream);
 int bnn_flipout_bwd(const bnn_flipout_bwd_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F17  Diagonal Laplace posterior of MLP / MLP_Dropout (MacKay 1992; Ritter et al. 2018; Daxberger et al. 2021): a Gaussian
+ * centred on the trained weights w with precision diag(F) + tau, F the diagonal of the generalised Gauss-Newton matrix (or of
+ * the empirical Fisher) of the data term summed over the data set, tau a prior precision chosen by the Laplace estimate of
+ * the marginal likelihood.  A mean-field Gaussian: (mu, rho) of a BayesianLinear.  The forward is bnn_dense_fwd (one sample,
+ * fp32 outputs, no dropout); these four do the rest.  No float atomics anywhere: the same inputs give the same bits.
+ *
+ * Virtual rows.  The GGN of softmax cross-entropy is J^T (diag(p) - p p^T) J and diag(p) - p p^T = sum_c p_c (e_c - p)(e_c - p)^T,
+ * so data row n contributes C back-propagations with output deltas sqrt(p_c) (e_c - p); a Gaussian likelihood N(z, sigma^2)
+ * gives e_c / sigma.  Virtual row r = c * batch + n, R = batch * C rows; the empirical Fisher has R = batch (the gradient of
+ * the row's log-likelihood).  For a linear layer the diagonal is a product of squares, and the input x of a data row is shared
+ * by its C virtual rows:
+ *     F_w[o, i] = sum_n S[n, o] x[n, i]^2,   F_b[o] = sum_n S[n, o],   S[n, o] = sum_c gz[c * batch + n, o]^2
+ * -- a K = batch product whatever C.  Only the deltas of the layer below, g_x = gz . W, need all R rows.
+ *
+ * bnn_laplace_seed — ONE block (as bnn_dense_loss).  From logits [batch, classes]:
+ *   BNN_LAPLACE_GGN,       classification: gy[c * batch + n, :] = sqrt(p_nc) (e_c - p_n);  regression: e_c / sigma
+ *   BNN_LAPLACE_EMPIRICAL, classification: gy[n, :] = p_n - onehot(y_n);                    regression: (z_n - y_n) / sigma^2
+ *   record[0] += sum_n log p(y_n | x_n) (fp64; classification log softmax(z_n)[y_n], regression the Gaussian log density with
+ *   its normaliser, summed over the outputs), record[1] += batch: one read-modify-write by the one block, per-thread fp64 sums
+ *   of a fixed set of rows met in a fixed-order tree.  target (int64 [batch] | fp32 [batch, classes]) is optional under
+ *   BNN_LAPLACE_GGN (record[0] is left alone then).  A label outside [0, classes) makes every delta of its row and record[0]
+ *   NaN and never reads out of bounds.
+ *   Errors, in this order: args NULL; struct_bytes: BNN_ERR_ABI; batch, classes < 1, sigma not in (0, inf), more than 2^31
+ *   deltas: BNN_ERR_SHAPE; loss_mode, curvature: BNN_ERR_ENUM; logits, gy, record, (empirical) target NULL: BNN_ERR_NULL;
+ *   alignment (4 bytes; record and int64 labels 8): BNN_ERR_ALIGN.
+ *
+ * bnn_laplace_layer — one Linear -> [ReLU] group in ONE launch; two products share the grid as in bnn_dense_bwd:
+ *   gz   = gy [rows, out]                        (y == NULL), or  y[r mod batch, o] > 0 ? gy : 0  (y [batch, out]: the saved output)
+ *   S    = sum_c gz^2: an fmaf chain from 0 in c order; x^2 and gz^2 are formed while staging, no squared copy exists
+ *   F_w += S^T . x^2  [out, in] on v_mfma_f32_16x16x4_f32, the accumulator INITIALISED FROM THE STORED F_w: an element is one
+ *          fixed chain over every minibatch accumulated; no K-split.  F_b += colsum(S): four strided partial sums per column,
+ *          the first starting from the stored F_b, added in bnn_dense_bwd's order.  Always exact fp32.
+ *   g_x  = gz . W [rows, in] (optional), times (x[r mod batch, i] > 0) when gx_mask: the deltas of the layer below (x is its
+ *          output).  BNN_MATH_BF16: gz and W rounded to bf16 (RNE), fp32 accumulate; other modes exact fp32.
+ *   s_out (optional, [batch, out]): S itself, for tests.
+ *   rows = batch * C, C >= 1.  Any shape >= 1; 4-byte aligned pointers, 16-byte loads / stores where rows and bases allow.
+ *   Errors, in this order: NULL args; ABI; batch, rows, in, out < 1, rows % batch != 0, a matrix over 2^31 elements:
+ *   BNN_ERR_SHAPE; math: BNN_ERR_ENUM; x, gy, f_w, (g_x) w NULL: BNN_ERR_NULL; BNN_ERR_ALIGN.
+ *
+ * bnn_laplace_evidence — log_evidence[g] = loglik - tau_g |w|^2 / 2 + P log(tau_g) / 2 - sum_i log(F_i + tau_g) / 2 for up
+ *   to BNN_LAPLACE_MAX_PRECISIONS candidates in one pass over up to BNN_LAPLACE_MAX_TENSORS (parameter, curvature) pairs; P the
+ *   number of parameters, loglik = record[0].  fp64 throughout, two stages: a block sums one BNN_LAPLACE_CHUNK of one tensor
+ *   (thread t the elements t, t + 256, ...; then a fixed tree), one final block sums the blocks (thread t blocks t, t + 256,
+ *   ...; the tree), writes log_evidence [n_precisions] and the maximum: *best_index (the lowest index on ties), best[0] its
+ *   value, best[1] its precision -- device words; nothing is read back.  Workspace: bnn_laplace_evidence_workspace_bytes(args)
+ *   (0 for arguments the call would refuse), 8-byte aligned, any contents.
+ *   Errors, in this order: NULL args; ABI; n_tensors outside [1, BNN_LAPLACE_MAX_TENSORS], n_precisions outside
+ *   [1, BNN_LAPLACE_MAX_PRECISIONS], a numel < 1, a precision not in (0, inf): BNN_ERR_SHAPE; a param / curv, record,
+ *   log_evidence NULL: BNN_ERR_NULL; workspace NULL or short: BNN_ERR_WORKSPACE; BNN_ERR_ALIGN (fp64 words 8 bytes).
+ *
+ * bnn_laplace_posterior — for every tensor pair: mu = w (the bits), rho = softplus^-1((F + tau)^-1/2) in ONE launch; tau =
+ *   *precision_device (best + 1 of bnn_laplace_evidence) or `precision`.  s = (F + tau)^-1/2 and log(expm1(s)) are formed in
+ *   fp64 (expm1 keeps the small-sigma end: rho -> log s; s > 40: rho = s, where exp(-s) is below fp64's epsilon), so rho
+ *   neither overflows nor loses small sigmas; finite for every F >= 0.
+ *   Errors, in this order: NULL args; ABI; n_tensors, numel, a host precision not in (0, inf): BNN_ERR_SHAPE; a tensor NULL:
+ *   BNN_ERR_NULL; BNN_ERR_ALIGN.
+ * ---------------------------------------------------------------------------------- */
+#define BNN_LAPLACE_MAX_PRECISIONS 64
+#define BNN_LAPLACE_MAX_TENSORS 16
+#define BNN_LAPLACE_CHUNK 4096           /* consecutive elements of a tensor per block (evidence, posterior) */
+#define BNN_LAPLACE_RECORD_DOUBLES 2     /* {sum of log-likelihoods, rows} */
+enum bnn_laplace_curvature { BNN_LAPLACE_GGN = 0, BNN_LAPLACE_EMPIRICAL = 1 };
+
+typedef struct bnn_laplace_seed_args {
+  uint32_t struct_bytes;
+  int32_t batch, classes;
+  int32_t loss_mode;        /* bnn_nll_mode */
+  int32_t curvature;        /* bnn_laplace_curvature */
+  int32_t reserved;
+  double sigma;             /* the Gaussian likelihood's scale (regression) */
+  const float* logits;      /* [batch, classes] */
+  const void* target;       /* int64 [batch] | fp32 [batch, classes]; optional under BNN_LAPLACE_GGN */
+  float* gy;                /* [R, classes] */
+  double* record;           /* [BNN_LAPLACE_RECORD_DOUBLES], device */
+} bnn_laplace_seed_args;
+
+typedef struct bnn_laplace_layer_args {
+  uint32_t struct_bytes;
+  int32_t batch, rows, in_features, out_features;
+  int32_t math;             /* bnn_math of the g_x product */
+  int32_t gx_mask;
+  int32_t reserved;
+  const float* x;           /* [batch, in] */
+  const float* gy;          /* [rows, out] */
+  const float* y;           /* optional [batch, out] */
+  const float* w;           /* [out, in]; read for g_x only */
+  float* f_w;               /* [out, in], accumulated */
+  float* f_b;               /* optional [out], accumulated */
+  float* g_x;               /* optional [rows, in] */
+  float* s_out;             /* optional [batch, out] */
+} bnn_laplace_layer_args;
+
+typedef struct bnn_laplace_evidence_args {
+  uint32_t struct_bytes;
+  int32_t n_tensors, n_precisions;
+  int32_t reserved;
+  const float* param[BNN_LAPLACE_MAX_TENSORS];
+  const float* curv[BNN_LAPLACE_MAX_TENSORS];
+  int64_t numel[BNN_LAPLACE_MAX_TENSORS];
+  double precision[BNN_LAPLACE_MAX_PRECISIONS];
+  const double* record;
+  void* workspace;
+  size_t workspace_bytes;
+  double* log_evidence;     /* [n_precisions] */
+  int32_t* best_index;      /* optional device word */
+  double* best;             /* optional [2]: the maximum, its precision */
+} bnn_laplace_evidence_args;
+
+typedef struct bnn_laplace_posterior_args {
+  uint32_t struct_bytes;
+  int32_t n_tensors;
+  const float* param[BNN_LAPLACE_MAX_TENSORS];
+  const float* curv[BNN_LAPLACE_MAX_TENSORS];
+  float* mu[BNN_LAPLACE_MAX_TENSORS];
+  float* rho[BNN_LAPLACE_MAX_TENSORS];
+  int64_t numel[BNN_LAPLACE_MAX_TENSORS];
+  double precision;               /* host value; ignored with precision_device */
+  const double* precision_device; /* optional */
+} bnn_laplace_posterior_args;
+
+size_t bnn_laplace_evidence_workspace_bytes(const bnn_laplace_evidence_args* args);
+int bnn_laplace_seed(const bnn_laplace_seed_args* args, void* stream);
+int bnn_laplace_layer(const bnn_laplace_layer_args* args, void* stream);
+int bnn_laplace_evidence(const bnn_laplace_evidence_args* args, void* stream);
+int bnn_laplace_posterior(const bnn_laplace_posterior_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
