@@ -3,8 +3,10 @@
 `ECELoss` mirrors compute_ece.py:14-57 (same constructor, same return triple) and `compute_snr` /
 `prune_weights` mirror weight_pruning.py:85-115 (same names and argument meaning), so the reference's scripts can
 call them with the tensors they already hold; the per-element work runs in bnn_ece / bnn_snr_db / bnn_snr_prune.
-Neither reference module can be imported in the build container (both need seaborn at import), so these two rows
-have no reference-recorded vectors: the oracle restates them from the source text (parity UNPINNED).
+Parity pinned by tests/golden/posthoc.npz: what the real ECELoss, collect_weights, compute_snr and prune_weights
+returned on seeded cases (oracle/make_golden_posthoc.py).  Two behaviours differ from the reference on purpose (DESIGN.md
+section 2): a NaN in a device-side SNR list orders last (the reference's np.percentile turns NaN and everything is masked),
+and a local_reparam network is pruned (the reference's isinstance(layer, BayesianLinear) leaves it unchanged).
 """
 from __future__ import annotations
 

@@ -81,7 +81,8 @@ __global__ __launch_bounds__(kEceBlock) void ece_partial_kernel(const float* __r
   }
 }
 
-// out = {ece, then per bin: count, corrects, confidence sum}.  Bins without data contribute nothing (the reference's
+// out = {ece, then per bin: count, corrects, confidence sum}.  The per-bin counts and corrects leave as fp32: exact up to
+// 2^24 entries per bin (n x C probabilities in one bin), rounded above; the ECE itself is formed from the fp64 sums.  Bins without data contribute nothing (the reference's
 // loop indexes a compressed accuracy array and a NaN mean there: it only runs when every bin has data).
 __global__ void ece_final_kernel(const double* __restrict__ part, int nblocks, int nb, float* __restrict__ out) {
   __shared__ double cnt[kEceMaxBins], cor[kEceMaxBins], conf[kEceMaxBins];

@@ -499,9 +499,12 @@ def philox_eps_for_network(p: NetParams, batch: int, seed: int, sample: int) -> 
 
 
 # --------------------------------------------------------------------------------------
-# F3 / F4 restatements.  compute_ece.py and weight_pruning.py cannot be imported in the build container (both
-# import seaborn at module scope; nothing can be installed), so these follow the SOURCE TEXT line by line and are
-# NOT pinned by reference-recorded vectors: parity UNPINNED for these two rows.
+# F3 / F4 restatements of compute_ece.py:14-57 and weight_pruning.py:85-115, line by line.  Parity:
+# pinned by tests/golden/posthoc.npz (groups G10, G11), which oracle/make_golden_posthoc.py records from the REAL modules (empty
+# placeholders stand in for the plotting / loading packages they import and never use here) and
+# tests/test_posthoc_golden_cpu.py holds these functions to (float64 results at rtol 1e-12, masks under the band rule of
+# DESIGN.md section 2).  Recorded with them: ECELoss raises IndexError once a bin is empty (always at bin_step 0.05); a NaN
+# in the SNR list makes every threshold NaN; prune_weights leaves a local_reparam network unchanged.
 # --------------------------------------------------------------------------------------
 def get_one_hot(targets: np.ndarray, nb_classes: int) -> np.ndarray:
     """compute_ece.py:59-61."""

@@ -1,8 +1,10 @@
 """The F9 pruning sweep on an MI355X (posthoc.snr_thresholds, posthoc.PruneSweep; bnn_snr_select, bnn_prune_codes,
 bnn_pruned_fwd, bnn_prune_sweep_tail): thresholds and masks bit for bit against today's path (snr_threshold,
 prune_weights on a copy), the forward and the evaluation against the fp64 restatement of tests/test_prune_sweep_cpu.py,
-the loader forms, no model copy and no host synchronisation."""
+the loader forms, no model copy and no host synchronisation; the level masks and the compressed network's keep pattern
+against the masks the REAL weight_pruning.py left (tests/golden/posthoc.npz, group G11)."""
 import copy
+import os
 
 import numpy as np
 import pytest
@@ -12,6 +14,8 @@ pytestmark = pytest.mark.gpu
 
 import bnn_hip
 from bnn_hip import epoch, ops, posthoc, synth
+import posthoc_cases as C
+from oracle import bnn_oracle as O
 from test_prune_sweep_cpu import PAPER_LEVELS, codes_ref, masked_forward_ref, thresholds_ref
 
 FWD_TOL = {"f32": 1e-5, "bf16": 2e-3}          # of the output scale: the bounds of tests/test_gpu_dense_train.py
@@ -309,3 +313,68 @@ def test_sweep_needs_no_model_copies_and_no_host_wait(dev):
         torch.cuda.set_sync_debug_mode(0)
     assert torch.equal(r1.correct, warm[0].correct) and torch.equal(r2.correct, r1.correct)
     assert torch.equal(thr.view(torch.int64), sweep.thresholds.view(torch.int64)) and tuple(y.shape) == (5, 128, 10)
+
+
+# ------------------------------------------------------------------------------------------------- 7. recorded masks
+@pytest.fixture(scope="module")
+def fx():
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "posthoc.npz"))
+
+
+def _fixture_net(fx, name, dev):
+    import networks
+    dims, lr, sd = C.snr_net(name)
+    np.testing.assert_array_equal(C.state_hash(sd), fx[f"G11/{name}/sha256"])
+    mp = dict(input_shape=dims[0], classes=dims[2], batch_size=8, hidden_units=dims[1], mode="classification", mu_init=[-0.2, 0.2],
+              rho_init=[-5, -4], prior_init=[1.0], mixture_prior=False, local_reparam=lr)
+    net = networks.BayesianNetwork(mp)
+    net.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()})
+    if f"G11/{name}/snr" in fx:
+        snr = fx[f"G11/{name}/snr"]
+    else:
+        with np.errstate(all="ignore"):
+            snr = O.compute_snr(C.flat_order(sd, "mu").astype(np.float64), np.log(1 + np.exp(C.flat_order(sd, "rho").astype(np.float64))))
+        np.testing.assert_array_equal(C.sha256(snr), fx[f"G11/{name}/snr_sha256"])
+    return net.to(dev).eval(), sd, snr, lr
+
+
+def _check_mask(fx, name, di, keep, kept, snr, label):
+    """The band rule of tests/test_gpu_posthoc.py with the device's own threshold: 2 x 3e-5 dB around the recorded one."""
+    thr = float(fx[f"G11/{name}/thresholds"][di])
+    if f"G11/{name}/keep/{di}" in fx:
+        ref_keep = np.unpackbits(fx[f"G11/{name}/keep/{di}"])[:snr.size].astype(bool)
+    else:               # local_reparam: the reference left the network unchanged (recorded); here snr > the recorded threshold
+        assert int(fx[f"G11/{name}/unchanged"]) == 1
+        ref_keep = snr > thr
+    out, band = C.band_differs(keep, ref_keep, snr, thr, 2 * C.BAND_DB)
+    print(f"{label} {name} drop {C.DROPS[di]}: {band} in the band, {int((keep != ref_keep).sum())} differ, kept {kept}")
+    assert band <= 2 * max(1, snr.size // 1000) and out.size == 0, (label, name, C.DROPS[di], out[:8])
+    assert kept == int(keep.sum())
+
+
+@pytest.mark.parametrize("name", ["small", "large", "lr"])
+def test_level_masks_match_the_recorded_reference(dev, fx, name):
+    net, sd, snr, lr = _fixture_net(fx, name, dev)
+    order = (3, 0, 5, 1, 4, 2)                                       # the levels out of order
+    sweep = posthoc.PruneSweep(net, [C.DROPS[i] for i in order])
+    thr, kept = sweep.thresholds.cpu().numpy(), sweep.kept.cpu().numpy()
+    codes = [(wc.cpu().numpy(), bc.cpu().numpy()) for wc, bc in sweep.codes()]
+    for j, di in enumerate(order):
+        assert abs(thr[j] - float(fx[f"G11/{name}/thresholds"][di])) <= C.BAND_DB
+        keep = np.concatenate([np.concatenate([(wc.T if lr else wc).ravel(), bc]) > sweep.level_rank[j] for wc, bc in codes])
+        _check_mask(fx, name, di, keep, int(kept[j]), snr, "codes")
+
+
+@pytest.mark.parametrize("name,drops", [("small", (1, 2, 4)), ("large", (2, 3)), ("lr", (2,))])
+def test_compressed_keep_pattern_matches_the_recorded_reference(dev, fx, name, drops):
+    net, sd, snr, lr = _fixture_net(fx, name, dev)
+    for di in drops:
+        cn = posthoc.compress(net, C.DROPS[di])
+        dense = {k: v.cpu().numpy() for k, v in cn.to_dense().items()}
+        keep = C.flat_order(dense, "rho") != 0                       # no generated rho is 0: a zero rho is a pruned pair
+        assert all(dense[k].shape == sd[k].shape for k in sd)
+        same = (C.flat_order(dense, "mu") == C.flat_order(sd, "mu")) & (C.flat_order(dense, "rho") == C.flat_order(sd, "rho"))
+        assert same[keep].all() and not C.flat_order(dense, "mu")[~keep].any()
+        biases = sum(int((dense[f"{l}.bias_rho"] != 0).sum()) for l in C.LAYERS)
+        assert sum(cn.nnz) + biases == int(keep.sum())
+        _check_mask(fx, name, di, keep, int(keep.sum()), snr, "compress")

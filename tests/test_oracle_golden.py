@@ -284,7 +284,7 @@ def test_philox_normal_moments():
 
 
 def test_ece_restatement_known_answer():
-    """F3 oracle (parity UNPINNED: compute_ece.py needs seaborn to import): a hand-computed case.  Two classes, bins of
+    """F3 oracle (parity pinned by tests/golden/posthoc.npz, tests/test_posthoc_golden_cpu.py): a hand-computed case.  Two classes, bins of
     width 0.5: rows (0.9, 0.1) label 0, (0.6, 0.4) label 1, (0.2, 0.8) label 1.  Bin (0, 0.5] holds {0.1, 0.4, 0.2}
     with no "correct" entry; bin (0.5, 1] holds {0.9, 0.6, 0.8} of which 0.9 and 0.8 are correct argmax entries.
     ECE = |0.7/3 - 0| * 3/6 + |2.3/3 - 2/3| * 3/6 = 0.11666.. + 0.05 = 0.16666.."""
@@ -298,7 +298,7 @@ def test_ece_restatement_known_answer():
 
 
 def test_snr_pruning_restatement():
-    """F4 oracle (parity UNPINNED): half of the weights go, the survivors are exactly those above the median SNR, a
+    """F4 oracle (parity pinned by tests/golden/posthoc.npz): half of the weights go, the survivors are exactly those above the median SNR, a
     pruned weight is left at rho = 0 (weight_pruning.py:106-107 multiplies rho by the mask too)."""
     rs = np.random.RandomState(3)
     layers = [tuple(t(rs.uniform(lo, hi, sh).astype(np.float32)) for lo, hi, sh in
