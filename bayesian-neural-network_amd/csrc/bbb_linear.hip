@@ -1282,6 +1282,17 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
   constexpr bool XTL = (LAY & 1) != 0, YTL = (LAY & 2) != 0, WTL = (LAY & 4) != 0;
   static_assert(!X3 || LAY == 0, "piece order: bf16 form only");
   static_assert(NB == 2, "two staging buffers");
+  // the parts of the bf16 form's k-step that can be taken out again for measurement (-DBNN_K1B2_STEP_PARTS=<bits>; csrc/Makefile):
+  // bit 0 = a step body per wave and unconditional staging in the maskless loop, bit 1 = the x fragments ahead of the generator
+#ifndef BNN_K1B2_STEP_PARTS
+#define BNN_K1B2_STEP_PARTS 3
+#endif
+  constexpr bool STEP_FORMS = !X3 && (BNN_K1B2_STEP_PARTS & 1);
+#ifdef BNN_TUNE
+  constexpr bool X_EARLY = false;             // (the tuning build's "no x reads" / "no MFMAs" switches live in mfma_phase)
+#else
+  constexpr bool X_EARLY = !X3 && (BNN_K1B2_STEP_PARTS & 2);
+#endif
   constexpr int WPW = 4 / SB;                 // parameter pieces (of a tile's four) each of the SB waves of a tile brings
   constexpr int XPW = 8 / NF;                 // x pieces (batch tiles of its pair) each of the NF waves of a pair brings
   constexpr int XT = X3 ? 1024 : 512;         // float4s of one pair's x tile (X3: the hi plane's 8 pieces, then the lo plane's)
@@ -1533,16 +1544,31 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
     }
   };
   // cur: the staging buffer of step t (t % NB).  (mfma_phase is captured explicitly, ahead of the implicit captures: the order
-  // of the closure's members steers the optimizer's value order and with it the register allocation of the loop -- this one
-  // reproduces the code that profiles/ measured.)
-  auto step = [&, &mfma_phase = mfma_phase](int t, int cur, auto full_) __attribute__((always_inline)) {
+  // of the closure's members steers the optimizer's value order and with it the register allocation of the loop.)
+  // BODY (compile-time, chosen once per wave ahead of the loop; bf16 form with the on-chip generator): what the launch- and
+  // wave-uniform conditions of a step come to.  0 = generic: prior kind, epsilon dump and statistics tested in the step, as
+  // every launch ran it before (mixture prior, epsilon dump, epsilon from memory or zero, X3, every masked step);
+  // 1 / 2 / 3 = Gaussian prior, no epsilon dump, {no statistics, statistics, statistics + sum of log sigma}: nothing to test.
+  // FAST (compile-time): step t + 1 exists and its 32 k lie inside K -- its pieces are requested with stage_fast, no test.
+  auto step = [&, &mfma_phase = mfma_phase](int t, int cur, auto full_, auto body_, auto fast_) __attribute__((always_inline)) {
     constexpr bool FULL = decltype(full_)::value;
+    constexpr int BODY = decltype(body_)::value;
+    constexpr bool FAST = decltype(fast_)::value;
+    static_assert(!BODY || (FULL && !X3 && EPS == BNN_EPS_PHILOX), "step bodies: maskless bf16 steps of the on-chip generator");
+    static_assert(!FAST || (FULL && !X3), "unconditional staging: the maskless bf16 loop");
     const int k = t * 32 + q * 8;
     const bool lane_ok = FULL || (n_ok && k < K);
     const bool real = FULL || !phantom;                          // wave-uniform
+    // (the early x reads go with the straight-line bodies: across the generic body's branches the compiler lays blocks out of
+    // line, and tools/lint_hand_loads.py follows a load to its wait in textual order; with the bodies taken out, the maskless step)
+    constexpr bool XE = X_EARLY && (BODY != 0 || (!STEP_FORMS && FULL));
+    const bool st_dump = BODY ? false : (p.eps_w_dump && do_dump);
+    const bool st_stats = BODY ? BODY >= 2 : do_stats;
+    const bool st_gauss = BODY ? true : p.prior_kind == BNN_PRIOR_GAUSS;
+    const bool st_ls = BODY ? BODY == 3 : do_ls;
     K2_T(st0);
     // the buffer staged here was last read in step t - 1 (barrier since)
-    const bool staged = t + 1 < ksteps;                          // block-uniform
+    const bool staged = FAST || t + 1 < ksteps;                  // block-uniform
 #ifdef BNN_TUNE
     // tuning build only (wrong results; tools/k1b_ablate.py): BNN_TUNE_K1B bit 0 = no barrier, 1 = no waits, 3 = no DMA (the LDS
     // reads of the parameters stay: stale bytes, the same vector work), 4 = no x reads, 5 = no MFMAs
@@ -1550,7 +1576,8 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
 #else
     if (staged) {
 #endif
-      if (X3 || !real) stage_sel(t + 1, 0, cur ^ 1, std::false_type{}, std::true_type{});   // x of step t + 1 now (X3: its parameters below)
+      if (FAST) stage_fast(t + 1, cur ^ 1, cur ^ 1, std::true_type{}, std::true_type{});
+      else if (X3 || !real) stage_sel(t + 1, 0, cur ^ 1, std::false_type{}, std::true_type{});   // x of step t + 1 now (X3: its parameters below)
       else stage(t + 1, cur ^ 1);
     }
     // LDS reads by hand (ds_read_b128 in asm): a compiler-visible read of `sm` would be ordered behind EVERY LDS-DMA in
@@ -1578,17 +1605,30 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
 #endif
     }
     if (real) {
+      // the Philox counter of the lane's eight weights (an operand of the early x reads below: the generator stays behind them)
+      uint32_t g = (uint32_t)n * (uint32_t)gpr + (uint32_t)(k >> 2);
+      // XE: the first half of the pair's x tile (batch tiles 0 .. 3) is requested here, behind the parameter reads and ahead
+      // of the generator -- buffer `cur` was complete at the barrier that closed the previous step, so the reads depend on nothing
+      // this step computes -- and waited for in front of the first MFMA; LDS returns in order, so the parameter wait counts
+      // lgkmcnt(4).  A phantom wave issues none of them (inside `real`), and every path from here reaches their wait below.
+      f32x4 xe0, xe1, xe2, xe3;
+      const uint32_t xa = lds0 + (uint32_t)((x_idx(cur) + sb * XT + q * 16 + r) * 16);
       if (!X3) {
         asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072"
                      : "=&v"(m_lo), "=&v"(m_hi), "=&v"(g_lo), "=&v"(g_hi) : "v"(pa));
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(m_lo), "+v"(m_hi), "+v"(g_lo), "+v"(g_hi));
+        if (XE) {
+          asm volatile("ds_read_b128 %0, %5\n\tds_read_b128 %1, %5 offset:1024\n\tds_read_b128 %2, %5 offset:2048\n\tds_read_b128 %3, %5 offset:3072"
+                       : "=&v"(xe0), "=&v"(xe1), "=&v"(xe2), "=&v"(xe3), "+v"(g) : "v"(xa));
+          asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(m_lo), "+v"(m_hi), "+v"(g_lo), "+v"(g_hi));
+        } else {
+          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(m_lo), "+v"(m_hi), "+v"(g_lo), "+v"(g_hi));
+        }
       }
       K2_T(st1);
       const f32x2 mu2[4] = {{m_lo[0], m_lo[1]}, {m_lo[2], m_lo[3]}, {m_hi[0], m_hi[1]}, {m_hi[2], m_hi[3]}};
       const f32x2 sg2[4] = {{g_lo[0], g_lo[1]}, {g_lo[2], g_lo[3]}, {g_hi[0], g_hi[1]}, {g_hi[2], g_hi[3]}};
       float e[8];
       if (EPS == BNN_EPS_PHILOX) {
-        const uint32_t g = (uint32_t)n * (uint32_t)gpr + (uint32_t)(k >> 2);
         uint4 pa_, pb_;
         philox_pair<>(g, gs, wid, p.k0, p.k1, pa_, pb_);
         box_muller8(pa_, pb_, e);
@@ -1598,7 +1638,7 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
 #pragma unroll
         for (int j = 0; j < 8; ++j) e[j] = 0.f;
       }
-      if (p.eps_w_dump && do_dump) store8<true>(p.eps_w_dump + ((size_t)s * N + n) * K + k, lane_ok ? 8 : 0, e);
+      if (st_dump) store8<true>(p.eps_w_dump + ((size_t)s * N + n) * K + k, lane_ok ? 8 : 0, e);
       f32x2 w2[4], e2v = {0.f, 0.f}, av = {0.f, 0.f};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -1606,9 +1646,9 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
         w2[j] = __builtin_elementwise_fma(sg2[j], ev, mu2[j]);
         e2v = __builtin_elementwise_fma(ev, ev, e2v);
       }
-      if (do_stats) {
+      if (st_stats) {
         float a, ls = 0.f;
-        if (p.prior_kind == BNN_PRIOR_GAUSS) {
+        if (st_gauss) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) av = __builtin_elementwise_fma(w2[j], w2[j], av);
           a = av[0] + av[1];
@@ -1620,7 +1660,7 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
             a = add_log(a, mix_p(p, w2[j][1]));
           }
         }
-        if (do_ls) {
+        if (st_ls) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             ls = add_log(ls, sg2[j][0]);
@@ -1659,7 +1699,27 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
       asm volatile("" :: "v"(wa));
 #endif
       K2_T(st2);
-      mfma_phase(wa, wl, x_idx(cur) + sb * XT, m_lo);
+      if (XE) {
+        // the second half of the x tile goes out once the generator's registers are free; the first half (requested at the top
+        // of the step) has landed when at most these four reads are outstanding, and its four MFMAs run under their round trip
+        f32x4 xl0, xl1, xl2, xl3;
+        asm volatile("ds_read_b128 %0, %4 offset:4096\n\tds_read_b128 %1, %4 offset:5120\n\tds_read_b128 %2, %4 offset:6144\n\tds_read_b128 %3, %4 offset:7168"
+                     : "=&v"(xl0), "=&v"(xl1), "=&v"(xl2), "=&v"(xl3) : "v"(xa), "v"(wa));
+        asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(xe0), "+v"(xe1), "+v"(xe2), "+v"(xe3));
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xe0), acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xe1), acc[1], 0, 0, 0);
+        acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xe2), acc[2], 0, 0, 0);
+        acc[3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xe3), acc[3], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);     // (the scheduler otherwise sinks these four below the next wait, and all eight below the barrier)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xl0), "+v"(xl1), "+v"(xl2), "+v"(xl3));
+        acc[4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xl0), acc[4], 0, 0, 0);
+        acc[5] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xl1), acc[5], 0, 0, 0);
+        acc[6] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xl2), acc[6], 0, 0, 0);
+        acc[7] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xl3), acc[7], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);     // the matrix pipe drains while the wave waits for its pieces and for the block
+      } else {
+        mfma_phase(wa, wl, x_idx(cur) + sb * XT, m_lo);
+      }
 #ifdef BNN_STAMPS
       asm volatile("" :: "v"(acc[0]), "v"(acc[7]));
       K2_T(st3);
@@ -1686,11 +1746,37 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
   {
     const bool tile_full = (tile + 1) * 16 <= N;                // wave-uniform
     const int full_steps = tile_full ? (K >> 5) : 0;            // steps whose 32 k are all inside K
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    constexpr std::integral_constant<int, 0> generic{};
     int t = 0, cur = 0;
+    if constexpr (STEP_FORMS) {
+      // The wave's step body, chosen ONCE (every condition is launch- or wave-uniform and constant over the loop).  The maskless
+      // loop ends one step early: each of its steps requests a step whose 32 k lie inside K (stage_fast, nothing to test), and the
+      // last whole step runs with the masked ones below, where the choice between stage_fast, the tail form and no staging is made
+      // per step -- with all its masks true it gives the bits of the maskless body.
+      // BARRIER INVARIANT (stated in `step`): every body passes the one barrier of a step exactly once per step, on every path, and
+      // the loops below run `ksteps` steps in all, whichever body a wave takes: t counts 0 .. ksteps - 1 through both of them.
+      const int fast_steps = full_steps - 1;
+      auto run = [&](auto body_) __attribute__((always_inline)) {
 #pragma nounroll
-    for (; t < full_steps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, std::true_type{});
+        for (; t < fast_steps; ++t, cur ^= 1) step(t, cur, yes, body_, yes);
+      };
+      if constexpr (EPS != BNN_EPS_PHILOX) {
+        run(generic);
+      } else {
+        const bool plain = p.prior_kind == BNN_PRIOR_GAUSS && !(p.eps_w_dump && do_dump);
+        if (!plain) run(generic);
+        else if (do_ls) run(std::integral_constant<int, 3>{});
+        else if (do_stats) run(std::integral_constant<int, 2>{});
+        else run(std::integral_constant<int, 1>{});
+      }
+    } else {
 #pragma nounroll
-    for (; t < ksteps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, std::false_type{});
+      for (; t < full_steps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, yes, generic, no);
+    }
+#pragma nounroll
+    for (; t < ksteps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, no, generic, no);
   }
 
 #ifdef BNN_STAMPS
