@@ -138,13 +138,18 @@ __device__ __forceinline__ float add_log(float acc, float x) { return __builtin_
 // it underflows, like the reference.  With u = fl(1 + e) and d = u - 1 (exact),
 //   log1p(e) = log(u) + log1p((e - d)/u) = log(u) + (e - d) * (1 + O(d)),
 // so adding back the rounding residue (e - d) restores the bits that forming 1 + e drops when
-// e is small (rho ~ -5), without a division: 7 VALU ops + the overflow select.
+// e is small (rho ~ -5), without a division: 7 VALU ops + one select.
+// The residue is added UNDIVIDED, which is right to one u only while u < 2: there |e - d| <= 2^-24 and leaving out the
+// 1 / u costs 2^-24 e / u <= 2^-24 log1p(e).  From e = 1 on it is left out: log(u) alone is then log1p(e) to 2^-24
+// absolute (sigma >= log 2), whereas the undivided residue is as large as half an ulp of u wherever 1 + e crosses a
+// binade (2^-16 at e ~ 256), comes out as 0 or +-2 once 1 + e and u - 1 both round to even (e in [2^24, 2^25): sigma
+// off by up to 12 % for rho in [16.64, 17.33)) and is inf - inf once exp overflows (log(u) is +inf there by itself).
 __device__ __forceinline__ float softplus(float rho) {
   const float e = fast_exp(rho);
   const float u = 1.0f + e;
   const float d = u - 1.0f;
-  const float s = __builtin_fmaf(__builtin_amdgcn_logf(u), kLn2, e - d);
-  return (e > 3.0e38f) ? e : s;   // exp overflowed: +inf (e - d would be inf - inf)
+  const float r = (e < 1.0f) ? e - d : 0.0f;
+  return __builtin_fmaf(__builtin_amdgcn_logf(u), kLn2, r);
 }
 
 // ---------------------------------------------------------------------------- reductions
