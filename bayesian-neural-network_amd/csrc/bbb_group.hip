@@ -59,8 +59,6 @@ struct BgLayout {
   __host__ __device__ size_t floats() const { return (size_t)4 * P + (size_t)((n[2] + 3) & ~3); }
 };
 
-__device__ __forceinline__ float bg_sigmoid(float r) { return __builtin_amdgcn_rcpf(1.0f + fast_exp(-r)); }
-
 __device__ __forceinline__ float bg_log_prior(const BgPrior& p, float w) {
   const float w2 = w * w;
   if (p.kind == BNN_PRIOR_GAUSS) return __builtin_fmaf(-w2, p.inv2var_p, p.c_p);
@@ -315,7 +313,7 @@ __global__ __launch_bounds__(kMgThreads) void bbb_group_train_kernel(BgK p) {
       const int o = L.o[q];
       for (int e = tid; e < L.n[q]; e += kMgThreads) {
         const float r = rho[e];
-        const float g_rho = (Hh[o + e] - beta * __builtin_amdgcn_rcpf(softplus(r))) * bg_sigmoid(r);
+        const float g_rho = (Hh[o + e] - beta * __builtin_amdgcn_rcpf(softplus(r))) * sigmoidf(r);
         adam_elem(mu, ag.exp_avg[pm], ag.exp_avg_sq[pm], e, G[o + e], as);
         adam_elem(rho, ag.exp_avg[pr], ag.exp_avg_sq[pr], e, g_rho, as);
       }

@@ -133,6 +133,8 @@ __device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_log
 // into: with -ffp-contract=fast `acc += fast_log(x)` is an fma in one kernel and mul + add in another (the pipelined
 // evaluator's results are compared bitwise with the plain sequence's), so every accumulation states its contraction.
 __device__ __forceinline__ float add_log(float acc, float x) { return __builtin_fmaf(__builtin_amdgcn_logf(x), kLn2, acc); }
+// d sigma / d rho of sigma = softplus(rho)
+__device__ __forceinline__ float sigmoidf(float r) { return __builtin_amdgcn_rcpf(1.0f + fast_exp(-r)); }
 
 // sigma = log1p(exp(rho)) (networks.py:39), no threshold trick: +inf once exp overflows, 0 once
 // it underflows, like the reference.  With u = fl(1 + e) and d = u - 1 (exact),
@@ -192,6 +194,64 @@ __device__ __forceinline__ T block_sum(T v, T* scratch) {
     for (int w = 0; w < nw; ++w) tot += scratch[w];
   return tot;
 }
+
+// Max over the 64 lanes of a wave, the same value in every lane.
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
+  return v;
+}
+
+// The values of a THREADS-thread block meet in a fixed-order tree (thread t adds thread t + h's, h = THREADS / 2 ... 1);
+// every thread gets the total.  `part` holds THREADS Ts.
+template <int THREADS, typename T>
+__device__ __forceinline__ T tree_sum(T v, T* part) {
+  part[threadIdx.x] = v;
+  __syncthreads();
+#pragma unroll
+  for (int h = THREADS / 2; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+    __syncthreads();
+  }
+  const T r = part[0];
+  __syncthreads();
+  return r;
+}
+
+// Up to MAX tensors cut into chunks, one chunk per block, the chunk -> tensor table riding in the kernel arguments.
+// Host: add() each tensor, then finish(); device: find().  The owner keeps its pointer arrays and its chunk size.
+template <int MAX>
+struct ChunkList {
+  long numel[MAX];
+  int first_chunk[MAX + 1] = {0};
+  int n = 0;
+
+  // BNN_ERR_SHAPE for an empty tensor or more chunks than a grid takes
+  int add(long count, int chunk) {
+    if (count <= 0) return BNN_ERR_SHAPE;
+    const long chunks = first_chunk[n] + (count + chunk - 1) / chunk;
+    if (chunks > 0x3fffffff) return BNN_ERR_SHAPE;
+    numel[n] = count;
+    first_chunk[++n] = (int)chunks;
+    return BNN_OK;
+  }
+  // fills the unused entries; the number of chunks (= blocks)
+  int finish() {
+    for (int t = n; t < MAX; ++t) {
+      numel[t] = 0;
+      first_chunk[t + 1] = first_chunk[n];
+    }
+    return first_chunk[n];
+  }
+  // the tensor of chunk `block` and the chunk's first element in it
+  __device__ __forceinline__ int find(int block, int chunk, long& base) const {
+    int t = 0;
+#pragma unroll 1
+    while (t + 1 < n && block >= first_chunk[t + 1]) ++t;
+    base = (long)(block - first_chunk[t]) * chunk;
+    return t;
+  }
+};
 
 // XCD-aware block -> work mapping (speed only, never correctness).  Blocks are dealt round-robin
 // over the 8 XCDs (block b and b+8 share an L2), so XCD x = b % 8 is given the contiguous

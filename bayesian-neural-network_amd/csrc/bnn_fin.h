@@ -6,6 +6,7 @@
 // bnn_finalize_args.scratch (fin_scratch).
 #pragma once
 #include "bnn_device.h"
+#include "bnn_nll_row.h"
 #include "../../include/bnn_hip.h"
 #include <math.h>
 
@@ -469,21 +470,8 @@ __device__ __forceinline__ void fin_loss_assemble(const FinK& fk, const FinLoss&
 // d (summed NLL of row `brow` of sample s) / d logits, scaled by grad_scale / total, from the block's logits in LDS
 // (`lgrow`: the row's C logits)
 __device__ __forceinline__ void fin_loss_row_grad(const FinK& fk, const FinLoss& tr, int s, int B, int brow, const float* lgrow) {
-  const int C = fk.C;
-  float* go = tr.g_logits + ((size_t)s * B + brow) * C;
-  const float gs = tr.grad_scale / tr.total;
-  if (fk.nll_mode == BNN_NLL_CLASSIFICATION) {
-    const long long tc = reinterpret_cast<const long long*>(fk.target)[brow];
-    float mx = lgrow[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, lgrow[c]);
-    float se = 0.f;
-    for (int c = 0; c < C; ++c) se += expf(lgrow[c] - mx);
-    const float inv = (tc >= 0 && tc < C) ? 1.0f / se : __builtin_nanf("");   // bad label: NaN, as in nll_bwd_kernel
-    for (int c = 0; c < C; ++c) go[c] = (expf(lgrow[c] - mx) * inv - (c == tc ? 1.f : 0.f)) * gs;
-  } else {
-    const float* tg = reinterpret_cast<const float*>(fk.target) + (size_t)brow * C;
-    for (int c = 0; c < C; ++c) go[c] = (lgrow[c] - tg[c]) * tr.inv_var * gs;
-  }
+  nll_row_grad(lgrow, fk.C, fk.nll_mode, fk.target, brow, tr.grad_scale / tr.total, tr.inv_var,
+               tr.g_logits + ((size_t)s * B + brow) * fk.C);
 }
 
 // ---- The hand-offs that finish an evaluation.  Both are placement-independent and nobody waits: whoever has something to hand

@@ -1,5 +1,5 @@
 // The prior's share of the backward, shared by the dense layer backward (bbb_bwd.hip) and the sparse one
-// (sparse_train.hip): d log p(w) / dw of the Gaussian and the scale-mixture prior, the sigmoid of d sigma / d rho, and the
+// (sparse_train.hip): d log p(w) / dw of the Gaussian and the scale-mixture prior, and the
 // host-side fill of their constants.  Both backward paths give a weight the same bits for the same w.  (bbb_group.hip keeps
 // its own BgPrior, which also carries the log-prior constants.)
 #pragma once
@@ -18,8 +18,6 @@ __device__ __forceinline__ float prior_dlogp(const P& p, float w) {
   const float n2 = p.a2 * fast_exp(-w2 * p.inv2var2);
   return -w * (n1 * p.invvar1 + n2 * p.invvar2) * __builtin_amdgcn_rcpf(n1 + n2);
 }
-
-__device__ __forceinline__ float sigmoidf(float r) { return __builtin_amdgcn_rcpf(1.0f + fast_exp(-r)); }
 
 // The constants above from a bnn_prior.  BNN_ERR_SHAPE for a non-positive scale.
 template <class P>

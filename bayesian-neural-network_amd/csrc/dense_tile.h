@@ -1,4 +1,5 @@
-// The 64 x 64 tile GEMM core of K6's backward (dense_train.hip) and of the Laplace curvature (laplace.hip): a 256-thread
+// The 64 x 64 tile GEMM core, tile epilogue and column sum of K6's backward (dense_train.hip) and of the Laplace curvature
+// (laplace.hip); K5's forward (mlp_dropout.hip) shares the stage image (swz), the constants and the LDS size.  A 256-thread
 // block of 2 x 2 waves, 2 x 2 accumulators of 16 x 16 per wave, K walked in 32-wide stages through two LDS buffers (next
 // stage loaded into registers during the current stage's MFMAs), the XOR-swizzled [row][k] image of K5.  Operands are
 // read along their contiguous dimension -- a thread loads 8 consecutive elements and writes them into the [row][k] image
@@ -156,9 +157,72 @@ __device__ __forceinline__ void gemm_tile(const OA& A, const OB& Bo, int m0, int
   }
 }
 
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
+
+// uint4 words of the LDS buffer of a kernel that owns a 32 TM x 32 TN tile staged as T: the union of the two stage buffers
+// and the epilogue's fp32 tile (rows of 32 TN + 4 floats).  K5 (mlp_dropout.hip) sizes its own tiles with it too.
+template <typename T, int TM, int TN>
+constexpr int tile_lds_uint4() {
+  return cmax(2 * 32 * (TM + TN) * (kBK * (int)sizeof(T) / 16), 32 * TM * (32 * TN + 4) / 4);
+}
+
 constexpr int kOutLd = kT + 4;                                  // the epilogue's fp32 tile row, 16-byte rows
-constexpr int kLdsUint4 = 2 * 2 * kT * (kBK * 4 / 16);          // two fp32 stages (the larger image)
-static_assert(kLdsUint4 * 4 >= kT * kOutLd, "the epilogue tile fits the stage buffers");
+constexpr int kLdsUint4 = tile_lds_uint4<float, 2, 2>();        // (fp32 stages: the larger image)
+
+// The epilogue.  The accumulators go through LDS (lane: column lane & 15, rows 4 (lane >> 4) + e of each 16 x 16 accumulator)
+// so that a thread then owns 4 consecutive columns of a row: f(row, col0, ncol, o) for every group inside [rows, cols), o the
+// group's 4 values (the first ncol of them inside).  Follows gemm_tile's last barrier.
+template <typename F>
+__device__ __forceinline__ void tile_epilogue(uint4* lds, f32x4 acc[2][2], int m0, int n0, int rows, int cols, F&& f) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, fr = lane & 15, fg = lane >> 4;
+  float* t = reinterpret_cast<float*>(lds);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) t[(wm * 32 + i * 16 + fg * 4 + e) * kOutLd + wn * 32 + j * 16 + fr] = acc[i][j][e];
+  __syncthreads();
+#pragma unroll 1
+  for (int q = tid; q < kT * (kT / 4); q += kThreads) {
+    const int r = q / (kT / 4), c4 = (q % (kT / 4)) * 4;
+    const int row = m0 + r, col0 = n0 + c4;
+    if (row >= rows || col0 >= cols) continue;
+    const float4 a4 = *reinterpret_cast<const float4*>(t + r * kOutLd + c4);
+    float o[4] = {a4.x, a4.y, a4.z, a4.w};
+    f(row, col0, min(4, cols - col0), o);
+  }
+}
+
+// 4 consecutive fp32 of a row: one 16-byte store (vec, all 4 inside) or the first ncol one by one
+__device__ __forceinline__ void store_group(float* dst, const float o[4], int ncol, bool vec) {
+  if (ncol == 4 && vec) {
+    *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+    for (int c = 0; c < ncol; ++c) dst[c] = o[c];
+  }
+}
+
+// out[o] = sum_n value(n, o) over n < N for the columns o = m0 .. m0 + 63 below cols: partial g of four sums n = g, g + 4, ...
+// in order (partial 0 starting from init[o] when init is given), then ((0 + 1) + 2) + 3.  value may store on the side; out
+// may be NULL (then that is all it is called for).  All 256 threads; no float atomics, one fixed chain per column.
+// UNROLL: of the loop over n (loads in flight against code size: value is inlined into it).
+template <int UNROLL, typename V>
+__device__ __forceinline__ void col_sum4(uint4* lds, int m0, int cols, int N, const float* init, float* out, V&& value) {
+  __syncthreads();
+  float* part = reinterpret_cast<float*>(lds);
+  const int c = threadIdx.x & 63, g = threadIdx.x >> 6, o = m0 + c;
+  float s = 0.f;
+  if (o < cols) {
+    if (g == 0 && init) s = init[o];
+#pragma unroll UNROLL
+    for (int n = g; n < N; n += 4) s += value(n, o);
+  }
+  part[g * 64 + c] = s;
+  __syncthreads();
+  if (threadIdx.x < 64 && o < cols && out) out[o] = ((part[c] + part[64 + c]) + part[128 + c]) + part[192 + c];
+}
 
 }  // namespace
 }  // namespace bnn

@@ -4,17 +4,17 @@
 //
 // bnn_dense_bwd.  Two GEMMs share one grid: blocks [0, tiles_x) own 64 x 64 tiles of g_x = gz . W (K = out), the rest
 // 64 x 64 tiles of g_w = gz^T . x (K = batch).  The g_x tiles come first: at the MNIST shape they have ~10 x the k
-// stages of a weight-gradient tile, so they start in the first dispatch wave.  The GEMM core (dense_tile.h) is K5's: a 256-thread block
-// of 2 x 2 waves, 2 x 2 accumulators of 16 x 16 per wave, K walked in 32-wide stages through two LDS buffers (next
-// stage loaded into registers during the current stage's MFMAs), the same XOR-swizzled [row][k] image.  What differs is
+// stages of a weight-gradient tile, so they start in the first dispatch wave.  The GEMM core, the tile epilogue and the
+// column sum are dense_tile.h's, shared with the Laplace curvature; the stage image is K5's.  What differs from K5 is
 // the operands' memory order: gz^T, x and W are read along their contiguous (row) dimension -- a thread loads 8
 // consecutive rows of one k and writes them into the [row][k] image element by element -- and gz is formed on load
 // from gy (and the layer's saved output y: gz = y > 0 ? gy * y_scale : 0), so no masked copy is materialised.
-// g_b = colsum(gz) rides on the weight-gradient blocks of tile column 0: four strided partial sums per column, added in
-// a fixed order.  No float atomics, no K-split: every element is one fixed chain, whatever the grid.
+// g_b = colsum(gz) rides on the weight-gradient blocks of tile column 0.  No float atomics, no K-split: every element is
+// one fixed chain, whatever the grid.
 #include <math.h>
 
 #include "bnn_device.h"
+#include "bnn_nll_row.h"
 #include "dense_tile.h"
 #include "../../include/bnn_hip.h"
 
@@ -38,42 +38,6 @@ struct BwdParams {
   int vec_x, vec_g, vec_w, vec_out;
 };
 
-// the tile through LDS (lane: column lane & 15, rows 4 (lane >> 4) + e of each 16 x 16 accumulator), then 4 consecutive
-// columns of a row per thread: out[row, col] (row pitch IN) = v, times (x[row, col] > 0 ? s : 0) when mask
-__device__ __forceinline__ void store_tile(const BwdParams& p, uint4* lds, f32x4 acc[2][2], int m0, int n0, int rows,
-                                           float* out, bool mask) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, fr = lane & 15, fg = lane >> 4;
-  float* t = reinterpret_cast<float*>(lds);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) t[(wm * 32 + i * 16 + fg * 4 + e) * kOutLd + wn * 32 + j * 16 + fr] = acc[i][j][e];
-  __syncthreads();
-#pragma unroll 1
-  for (int q = tid; q < kT * (kT / 4); q += kThreads) {
-    const int r = q / (kT / 4), c4 = (q % (kT / 4)) * 4;
-    const int row = m0 + r, col0 = n0 + c4;
-    if (row >= rows || col0 >= p.IN) continue;
-    const float4 a4 = *reinterpret_cast<const float4*>(t + r * kOutLd + c4);
-    float o[4] = {a4.x, a4.y, a4.z, a4.w};
-    const int ncol = min(4, p.IN - col0);
-    const long at = (long)row * p.IN + col0;
-    if (mask) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (c < ncol) o[c] = p.x[at + c] > 0.f ? o[c] * p.gx_scale : 0.f;
-    }
-    if (ncol == 4 && p.vec_out) {
-      *reinterpret_cast<float4*>(out + at) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-      for (int c = 0; c < ncol; ++c) out[at + c] = o[c];
-    }
-  }
-}
-
 template <typename TX>
 __global__ __launch_bounds__(kThreads) void dense_bwd_kernel(BwdParams p) {
   __shared__ uint4 lds[kLdsUint4];
@@ -85,7 +49,16 @@ __global__ __launch_bounds__(kThreads) void dense_bwd_kernel(BwdParams p) {
     const Opnd A{p.gy, p.y, p.y_scale, p.OUT, p.B, p.vec_g};
     const Opnd Bo{p.w, nullptr, 1.f, p.IN, p.IN, p.vec_w};
     gemm_tile<TX, true, false>(A, Bo, tm * kT, tn * kT, p.OUT, lds, acc);
-    store_tile(p, lds, acc, tm * kT, tn * kT, p.B, p.gx, p.gx_mask != 0);
+    // times (x > 0 ? gx_scale : 0) when masked
+    tile_epilogue(lds, acc, tm * kT, tn * kT, p.B, p.IN, [&](int row, int col0, int ncol, float o[4]) {
+      const long at = (long)row * p.IN + col0;
+      if (p.gx_mask) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (c < ncol) o[c] = p.x[at + c] > 0.f ? o[c] * p.gx_scale : 0.f;
+      }
+      store_group(p.gx + at, o, ncol, p.vec_out);
+    });
     return;
   }
   item -= p.tiles_x;
@@ -95,20 +68,12 @@ __global__ __launch_bounds__(kThreads) void dense_bwd_kernel(BwdParams p) {
   const Opnd A{p.gy, p.y, p.y_scale, p.OUT, p.OUT, p.vec_g};
   const Opnd Bo{p.x, nullptr, 1.f, p.IN, p.IN, p.vec_x};
   gemm_tile<float, false, false>(A, Bo, m0, tn * kT, p.B, lds, acc);
-  store_tile(p, lds, acc, m0, tn * kT, p.OUT, p.gw, false);
-  if (tn != 0 || !p.gb) return;
-  // g_b[o] = sum_b gz[b, o] for the tile's 64 rows: partial g sums rows b = g, g + 4, ... in order; then ((0 + 1) + 2) + 3
-  __syncthreads();
-  float* part = reinterpret_cast<float*>(lds);
-  const int c = threadIdx.x & 63, g = threadIdx.x >> 6, o = m0 + c;
-  float s = 0.f;
-  if (o < p.OUT) {
-#pragma unroll 4
-    for (int b = g; b < p.B; b += 4) s += gz_of(p.gy[(long)b * p.OUT + o], p.y, (long)b * p.OUT + o, p.y_scale);
-  }
-  part[g * 64 + c] = s;
-  __syncthreads();
-  if (threadIdx.x < 64 && o < p.OUT) p.gb[o] = ((part[c] + part[64 + c]) + part[128 + c]) + part[192 + c];
+  tile_epilogue(lds, acc, m0, tn * kT, p.OUT, p.IN, [&](int row, int col0, int ncol, float o[4]) {
+    store_group(p.gw + (long)row * p.IN + col0, o, ncol, p.vec_out);
+  });
+  // g_b[o] = sum_b gz[b, o] for the tile's 64 rows
+  if (tn == 0 && p.gb)
+    col_sum4<4>(lds, m0, p.OUT, p.B, nullptr, p.gb, [&](int b, int o) { return gz_of(p.gy[(long)b * p.OUT + o], p.y, (long)b * p.OUT + o, p.y_scale); });
 }
 
 // one block; thread t owns rows t, t + 256, ...; the per-thread sums then meet in a fixed-order tree
@@ -124,14 +89,11 @@ __global__ __launch_bounds__(kThreads) void dense_loss_kernel(const float* __res
     if (mode == BNN_NLL_CLASSIFICATION) {
       const long long tc = reinterpret_cast<const long long*>(target)[b];
       const bool ok = tc >= 0 && tc < C;
-      float mx = row[0];
-      for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
-      float se = 0.f;
-      for (int c = 0; c < C; ++c) se += expf(row[c] - mx);
+      float mx, se;
+      row_max_sumexp(row, C, mx, se);
       // an out-of-range label: NaN loss and row gradient, and z[label] is never read
       acc += ok ? (mx + logf(se)) - row[ok ? tc : 0] : __builtin_nanf("");
-      const float inv = ok ? 1.0f / se : __builtin_nanf("");
-      for (int c = 0; c < C; ++c) grow[c] = (expf(row[c] - mx) * inv - (c == tc ? 1.f : 0.f)) * gs;
+      softmax_row_grad(row, C, tc, mx, se, gs, grow);
     } else {
       const float* tg = reinterpret_cast<const float*>(target) + (long)b * C;
       for (int c = 0; c < C; ++c) {
@@ -141,33 +103,23 @@ __global__ __launch_bounds__(kThreads) void dense_loss_kernel(const float* __res
       }
     }
   }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-#pragma unroll
-  for (int h = kThreads / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *loss = part[0];
+  const float total = tree_sum<kThreads>(acc, part);
+  if (threadIdx.x == 0) *loss = total;
 }
 
 struct SgdK {
   float* p[BNN_SGD_MAX_TENSORS];
   const float* g[BNN_SGD_MAX_TENSORS];
-  long numel[BNN_SGD_MAX_TENSORS];
-  int first_chunk[BNN_SGD_MAX_TENSORS + 1];
-  int n;
+  ChunkList<BNN_SGD_MAX_TENSORS> list;
   float lr, wd;
   const float* lr_dev;
 };
 
 // one block = one 4096-element chunk of one tensor; 16-byte accesses
 __global__ __launch_bounds__(kThreads) void sgd_kernel(const SgdK k) {
-  int t = 0;
-#pragma unroll 1
-  while (t + 1 < k.n && (int)blockIdx.x >= k.first_chunk[t + 1]) ++t;
-  const long base = (long)((int)blockIdx.x - k.first_chunk[t]) * kSgdChunk;
-  const long n = k.numel[t];
+  long base;
+  const int t = k.list.find((int)blockIdx.x, kSgdChunk, base);
+  const long n = k.list.numel[t];
   float* __restrict__ p = k.p[t];
   const float* __restrict__ g = k.g[t];
   const float nlr = -(k.lr_dev ? *k.lr_dev : k.lr);
@@ -255,24 +207,19 @@ extern "C" int bnn_sgd_step(const bnn_sgd_args* a, void* stream_) {
   if (a->n_tensors <= 0 || a->n_tensors > BNN_SGD_MAX_TENSORS) return BNN_ERR_SHAPE;
   if (!(a->lr >= 0.0) || !(a->weight_decay >= 0.0)) return BNN_ERR_SHAPE;
   SgdK k;
-  long chunks = 0;
+  for (int t = 0; t < BNN_SGD_MAX_TENSORS; ++t) {
+    k.p[t] = nullptr; k.g[t] = nullptr;
+  }
   for (int t = 0; t < a->n_tensors; ++t) {
     if (!a->param[t] || !a->grad[t]) return BNN_ERR_NULL;
-    if (a->numel[t] <= 0) return BNN_ERR_SHAPE;
+    const int st = k.list.add(a->numel[t], kSgdChunk);
+    if (st != BNN_OK) return st;
     if (misaligned(a->param[t], 16) || misaligned(a->grad[t], 16)) return BNN_ERR_ALIGN;
     k.p[t] = a->param[t];
     k.g[t] = a->grad[t];
-    k.numel[t] = (long)a->numel[t];
-    k.first_chunk[t] = (int)chunks;
-    chunks += (a->numel[t] + kSgdChunk - 1) / kSgdChunk;
-    if (chunks > 0x3fffffff) return BNN_ERR_SHAPE;
   }
   if (misaligned(a->lr_device, 4)) return BNN_ERR_ALIGN;
-  for (int t = a->n_tensors; t <= BNN_SGD_MAX_TENSORS; ++t) k.first_chunk[t] = (int)chunks;
-  for (int t = a->n_tensors; t < BNN_SGD_MAX_TENSORS; ++t) {
-    k.p[t] = nullptr; k.g[t] = nullptr; k.numel[t] = 0;
-  }
-  k.n = a->n_tensors;
+  const int chunks = k.list.finish();
   k.lr = (float)a->lr;
   k.wd = (float)a->weight_decay;
   k.lr_dev = a->lr_device;

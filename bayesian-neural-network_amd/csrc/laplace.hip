@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "bnn_device.h"
+#include "bnn_nll_row.h"
 #include "dense_tile.h"
 #include "../../include/bnn_hip.h"
 
@@ -111,43 +112,6 @@ struct LayerParams {
   int vec_x, vec_g, vec_w, vec_gx, vec_fw;
 };
 
-// the tile through LDS (lane: column lane & 15, rows 4 (lane >> 4) + e of each 16 x 16 accumulator), then 4 consecutive
-// columns of a row per thread: out[row, col] (row pitch cols) = v, or (mask[row mod mask_rows, col] > 0 ? v : 0)
-__device__ __forceinline__ void store_tile(uint4* lds, f32x4 acc[2][2], int m0, int n0, int rows, int cols, float* out,
-                                           const float* mask, int mask_rows, bool vec) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, fr = lane & 15, fg = lane >> 4;
-  float* t = reinterpret_cast<float*>(lds);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) t[(wm * 32 + i * 16 + fg * 4 + e) * kOutLd + wn * 32 + j * 16 + fr] = acc[i][j][e];
-  __syncthreads();
-#pragma unroll 1
-  for (int q = tid; q < kT * (kT / 4); q += kThreads) {
-    const int r = q / (kT / 4), c4 = (q % (kT / 4)) * 4;
-    const int row = m0 + r, col0 = n0 + c4;
-    if (row >= rows || col0 >= cols) continue;
-    const float4 a4 = *reinterpret_cast<const float4*>(t + r * kOutLd + c4);
-    float o[4] = {a4.x, a4.y, a4.z, a4.w};
-    const int ncol = min(4, cols - col0);
-    const long at = (long)row * cols + col0;
-    if (mask) {
-      const long mat = (long)(row % mask_rows) * cols + col0;
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (c < ncol) o[c] = mask[mat + c] > 0.f ? o[c] : 0.f;
-    }
-    if (ncol == 4 && vec) {
-      *reinterpret_cast<float4*>(out + at) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-      for (int c = 0; c < ncol; ++c) out[at + c] = o[c];
-    }
-  }
-}
-
 template <typename TX>
 __global__ __launch_bounds__(kThreads) void laplace_layer_kernel(LayerParams p) {
   __shared__ uint4 lds[kLdsUint4];
@@ -159,7 +123,16 @@ __global__ __launch_bounds__(kThreads) void laplace_layer_kernel(LayerParams p) 
     const GzOpnd A{p.gy, p.y, p.B, p.OUT, p.R, p.vec_g};
     const Opnd Bo{p.w, nullptr, 1.f, p.IN, p.IN, p.vec_w};
     gemm_tile<TX, true, false>(A, Bo, tm * kT, tn * kT, p.OUT, lds, acc);
-    store_tile(lds, acc, tm * kT, tn * kT, p.R, p.IN, p.gx, p.gx_mask ? p.x : nullptr, p.B, p.vec_gx != 0);
+    // masked by the input of data row r mod B
+    tile_epilogue(lds, acc, tm * kT, tn * kT, p.R, p.IN, [&](int row, int col0, int ncol, float o[4]) {
+      if (p.gx_mask) {
+        const long mat = (long)(row % p.B) * p.IN + col0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (c < ncol) o[c] = p.x[mat + c] > 0.f ? o[c] : 0.f;
+      }
+      store_group(p.gx + (long)row * p.IN + col0, o, ncol, p.vec_gx != 0);
+    });
     return;
   }
   item -= p.tiles_x;
@@ -184,40 +157,16 @@ __global__ __launch_bounds__(kThreads) void laplace_layer_kernel(LayerParams p) 
   const SOpnd A{Opnd{p.gy, nullptr, 1.f, p.OUT, p.OUT, p.vec_g}, Opnd{p.y, nullptr, 1.f, p.OUT, p.OUT, p.vec_g}, cstride, p.C};
   const SqOpnd Bo{Opnd{p.x, nullptr, 1.f, p.IN, p.IN, p.vec_x}};
   gemm_tile<float, false, false, false>(A, Bo, m0, n0, p.B, lds, acc);
-  store_tile(lds, acc, m0, n0, p.OUT, p.IN, p.fw, nullptr, 1, p.vec_fw != 0);
-  if (tn != 0 || (!p.fb && !p.s_out)) return;
-  // F_b[o] += sum_n S[n, o] for the tile's 64 rows: partial g sums rows n = g, g + 4, ... in order (partial 0 from the stored
-  // F_b); then ((0 + 1) + 2) + 3.  The same blocks write S where it is asked for.
-  __syncthreads();
-  float* part = reinterpret_cast<float*>(lds);
-  const int c = threadIdx.x & 63, g = threadIdx.x >> 6, o = m0 + c;
-  float s = 0.f;
-  if (o < p.OUT) {
-    if (g == 0 && p.fb) s = p.fb[o];
-#pragma unroll 1
-    for (int n = g; n < p.B; n += 4) {
+  tile_epilogue(lds, acc, m0, n0, p.OUT, p.IN, [&](int row, int col0, int ncol, float o[4]) {
+    store_group(p.fw + (long)row * p.IN + col0, o, ncol, p.vec_fw != 0);
+  });
+  // F_b[o] += sum_n S[n, o] for the tile's 64 rows, partial 0 from the stored F_b.  The same blocks write S where it is asked for.
+  if (tn == 0 && (p.fb || p.s_out))
+    col_sum4<1>(lds, m0, p.OUT, p.B, p.fb, p.fb, [&](int n, int o) {
       const float sv = s_of(p.gy, p.y, (long)n * p.OUT + o, cstride, p.C);
       if (p.s_out) p.s_out[(long)n * p.OUT + o] = sv;
-      s += sv;
-    }
-  }
-  part[g * 64 + c] = s;
-  __syncthreads();
-  if (threadIdx.x < 64 && o < p.OUT && p.fb) p.fb[o] = ((part[c] + part[64 + c]) + part[128 + c]) + part[192 + c];
-}
-
-// a block's fp64 values meet in a fixed-order tree; every thread gets the total
-__device__ __forceinline__ double block_sum(double v, double* part) {
-  part[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int h = kThreads / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
-    __syncthreads();
-  }
-  const double r = part[0];
-  __syncthreads();
-  return r;
+      return sv;
+    });
 }
 
 constexpr double kHalfLog2Pi = 0.91893853320467274178;
@@ -236,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void laplace_seed_kernel(const float* __r
     if (mode == BNN_NLL_CLASSIFICATION) {
       const long long tc = target ? reinterpret_cast<const long long*>(target)[n] : 0;
       const bool ok = tc >= 0 && tc < C;                       // an out-of-range label: NaN row, and z[label] is never read
-      float mx = row[0];
+      float mx = row[0];                                       // (row_max_sumexp's order, with the fp64 sum riding along)
       for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
       float se = 0.f;
       double sed = 0.0;
@@ -253,8 +202,7 @@ __global__ __launch_bounds__(kThreads) void laplace_seed_kernel(const float* __r
           for (int k = 0; k < C; ++k) g[k] = sq * ((k == c ? 1.f : 0.f) - expf(row[k] - mx) * inv);
         }
       } else {
-        float* g = gy + (long)n * C;
-        for (int k = 0; k < C; ++k) g[k] = expf(row[k] - mx) * inv - (k == tc ? 1.f : 0.f);
+        softmax_row_grad(row, C, tc, mx, se, 1.f, gy + (long)n * C);
       }
     } else {
       const float* tg = target ? reinterpret_cast<const float*>(target) + (long)n * C : nullptr;
@@ -270,12 +218,11 @@ __global__ __launch_bounds__(kThreads) void laplace_seed_kernel(const float* __r
           for (int k = 0; k < C; ++k) g[k] = k == c ? inv_sigma : 0.f;
         }
       } else {
-        float* g = gy + (long)n * C;
-        for (int k = 0; k < C; ++k) g[k] = (row[k] - tg[k]) * inv_var;
+        gauss_row_grad(row, tg, C, inv_var, 1.f, gy + (long)n * C);
       }
     }
   }
-  const double total = block_sum(ll, part);
+  const double total = tree_sum<kThreads>(ll, part);
   if (threadIdx.x == 0) {
     if (target) record[0] += total;
     record[1] += (double)B;
@@ -287,17 +234,8 @@ struct TensorList {
   const float* f[BNN_LAPLACE_MAX_TENSORS];
   float* mu[BNN_LAPLACE_MAX_TENSORS];
   float* rho[BNN_LAPLACE_MAX_TENSORS];
-  long numel[BNN_LAPLACE_MAX_TENSORS];
-  int first_chunk[BNN_LAPLACE_MAX_TENSORS + 1];
-  int n;
+  ChunkList<BNN_LAPLACE_MAX_TENSORS> list;
 };
-
-__device__ __forceinline__ int tensor_of(const TensorList& k, int chunk) {
-  int t = 0;
-#pragma unroll 1
-  while (t + 1 < k.n && chunk >= k.first_chunk[t + 1]) ++t;
-  return t;
-}
 
 struct Precisions {
   double tau[BNN_LAPLACE_MAX_PRECISIONS];
@@ -308,9 +246,9 @@ struct Precisions {
 // (g < G), ws[G * blocks + block] = sum of w^2: per-thread sums of elements tid, tid + 256, ... then the fixed-order tree.
 __global__ __launch_bounds__(kThreads) void laplace_evidence_partials(const TensorList k, const Precisions pr, double* __restrict__ ws) {
   __shared__ double part[kThreads];
-  const int t = tensor_of(k, (int)blockIdx.x);
-  const long base = (long)((int)blockIdx.x - k.first_chunk[t]) * kChunk;
-  const long n = k.numel[t];
+  long base;
+  const int t = k.list.find((int)blockIdx.x, kChunk, base);
+  const long n = k.list.numel[t];
   const float* __restrict__ w = k.p[t];
   const float* __restrict__ f = k.f[t];
   double fv[kPerThread];
@@ -324,7 +262,7 @@ __global__ __launch_bounds__(kThreads) void laplace_evidence_partials(const Tens
     sw = fma(wv, wv, sw);
   }
   const long blocks = gridDim.x;
-  const double tot_w = block_sum(sw, part);
+  const double tot_w = tree_sum<kThreads>(sw, part);
   if (threadIdx.x == 0) ws[(long)pr.n * blocks + blockIdx.x] = tot_w;
 #pragma unroll 1
   for (int g = 0; g < pr.n; ++g) {
@@ -333,7 +271,7 @@ __global__ __launch_bounds__(kThreads) void laplace_evidence_partials(const Tens
 #pragma unroll
     for (int it = 0; it < kPerThread; ++it)
       if (base + (long)it * kThreads + threadIdx.x < n) s += log(fv[it] + tau);
-    const double tot = block_sum(s, part);
+    const double tot = tree_sum<kThreads>(s, part);
     if (threadIdx.x == 0) ws[(long)g * blocks + blockIdx.x] = tot;
   }
 }
@@ -349,7 +287,7 @@ __global__ __launch_bounds__(kThreads) void laplace_evidence_final(const Precisi
   for (int q = 0; q <= pr.n; ++q) {
     double s = 0.0;
     for (int b = threadIdx.x; b < blocks; b += kThreads) s += ws[(long)q * blocks + b];
-    const double v = block_sum(s, part);
+    const double v = tree_sum<kThreads>(s, part);
     if (threadIdx.x == 0) tot[q] = v;
   }
   if (threadIdx.x != 0) return;
@@ -377,9 +315,9 @@ __device__ __forceinline__ double inv_softplus(double s) { return s > 40.0 ? s :
 
 // one block = one 4096-element chunk of one tensor: mu = w, rho = softplus^-1((F + tau)^-1/2), formed in fp64
 __global__ __launch_bounds__(kThreads) void laplace_posterior_kernel(const TensorList k, double tau_host, const double* __restrict__ tau_dev) {
-  const int t = tensor_of(k, (int)blockIdx.x);
-  const long base = (long)((int)blockIdx.x - k.first_chunk[t]) * kChunk;
-  const long n = k.numel[t];
+  long base;
+  const int t = k.list.find((int)blockIdx.x, kChunk, base);
+  const long n = k.list.numel[t];
   const float* __restrict__ w = k.p[t];
   const float* __restrict__ f = k.f[t];
   float* __restrict__ mu = k.mu[t];
@@ -464,21 +402,14 @@ namespace {
 
 // the chunk table of a tensor list; BNN_OK or the status of the first bad entry
 int chunk_table(int n_tensors, const int64_t* numel, TensorList* k, long* chunks_out) {
-  long chunks = 0;
   for (int t = 0; t < n_tensors; ++t) {
-    if (numel[t] <= 0) return BNN_ERR_SHAPE;
-    k->numel[t] = (long)numel[t];
-    k->first_chunk[t] = (int)chunks;
-    chunks += (numel[t] + kChunk - 1) / kChunk;
-    if (chunks > 0x3fffffff) return BNN_ERR_SHAPE;
+    const int st = k->list.add(numel[t], kChunk);
+    if (st != BNN_OK) return st;
   }
-  for (int t = n_tensors; t <= BNN_LAPLACE_MAX_TENSORS; ++t) k->first_chunk[t] = (int)chunks;
-  for (int t = n_tensors; t < BNN_LAPLACE_MAX_TENSORS; ++t) k->numel[t] = 0;
   for (int t = 0; t < BNN_LAPLACE_MAX_TENSORS; ++t) {
     k->p[t] = nullptr; k->f[t] = nullptr; k->mu[t] = nullptr; k->rho[t] = nullptr;
   }
-  k->n = n_tensors;
-  *chunks_out = chunks;
+  *chunks_out = k->list.finish();
   return BNN_OK;
 }
 

@@ -52,8 +52,6 @@ struct LrBwdK {
   float inv_var_p;
 };
 
-__device__ __forceinline__ float lr_sigmoid(float r) { return __builtin_amdgcn_rcpf(1.0f + fast_exp(-r)); }
-
 // gz = gy * (y > 0);  h = gz * eps_act / (2 sqrt(v))  (0 where v == 0, as the tensor-op form)
 __global__ void lr_bwd_prep_kernel(const float* __restrict__ gy, const float* __restrict__ y, const float* __restrict__ v,
                                    const float* __restrict__ eps_act, float* __restrict__ gz, float* __restrict__ h, int S,
@@ -278,7 +276,7 @@ __global__ __launch_bounds__(256, 3) void lr_bwd_weights_kernel(const LrBwdK p) 
         if (half) {
           const float sg = softplus(wv);
           const float gsig = 2.f * sg * acc[i][j][reg] + cw * (sg * p.inv_var_p - __builtin_amdgcn_rcpf(sg));
-          o[j] = gsig * lr_sigmoid(wv);
+          o[j] = gsig * sigmoidf(wv);
         } else {
           o[j] = acc[i][j][reg] + cw * wv * p.inv_var_p;
         }
@@ -302,7 +300,7 @@ __global__ __launch_bounds__(256, 3) void lr_bwd_weights_kernel(const LrBwdK p) 
         const float bm = p.b_mu[n], br = p.b_rho[n];
         const float sb = softplus(br);
         p.g_bmu[n] = Gb[j] + cb * bm * p.inv_var_p;
-        p.g_brho[n] = (Hb[j] + cb * (sb * p.inv_var_p - __builtin_amdgcn_rcpf(sb))) * lr_sigmoid(br);
+        p.g_brho[n] = (Hb[j] + cb * (sb * p.inv_var_p - __builtin_amdgcn_rcpf(sb))) * sigmoidf(br);
       }
     }
   }
@@ -520,7 +518,6 @@ __global__ __launch_bounds__(512) void lr_bwd_input_kernel(const LrBwdK p) {
   }
 }
 
-
 // Backward of a NARROW LR output layer (N <= 16: the 10 classes / the 1 regression output, batch <= 128) in ONE launch,
 // plain fp32 FMAs: the three general launches (prep, weights, input) are built for wide layers and cost 4.7 + 12 + 5.3 us
 // at 1200 -> 10, mostly their launch and latency chains.  Every block forms the gz / h rows it needs itself (eps_act
@@ -654,7 +651,7 @@ __device__ __forceinline__ void lr_out_weight_role(const LrBwdK& p, const LrOutB
       const float m = p.w_mu[off], r = p.w_rho[off];
       const float sg = softplus(r);
       p.g_wmu[off] = gm + cw * m * p.inv_var_p;
-      p.g_wrho[off] = (2.f * sg * gsv + cw * (sg * p.inv_var_p - __builtin_amdgcn_rcpf(sg))) * lr_sigmoid(r);
+      p.g_wrho[off] = (2.f * sg * gsv + cw * (sg * p.inv_var_p - __builtin_amdgcn_rcpf(sg))) * sigmoidf(r);
     }
   }
   if (b_ok) {
@@ -662,7 +659,7 @@ __device__ __forceinline__ void lr_out_weight_role(const LrBwdK& p, const LrOutB
     const float bm = p.b_mu[tid], br = p.b_rho[tid];
     const float sb = softplus(br);
     p.g_bmu[tid] = Gb + cb * bm * p.inv_var_p;
-    p.g_brho[tid] = (Hb + cb * (sb * p.inv_var_p - __builtin_amdgcn_rcpf(sb))) * lr_sigmoid(br);
+    p.g_brho[tid] = (Hb + cb * (sb * p.inv_var_p - __builtin_amdgcn_rcpf(sb))) * sigmoidf(br);
   }
 }
 

@@ -6,27 +6,22 @@
 // 4: 128 x 128); a wave owns TM x TN accumulators of 16 x 16.  K is walked in 32-wide stages through two LDS buffers:
 // every thread loads its 8-element row segments of the next stage into registers (fp32 x / W converted to bf16 there in
 // bf16 math: no cast launch) while the waves run the MFMAs of the current stage, then stores them into the other buffer;
-// one barrier per stage.  The shapes that matter are small in M (S * B = 1280 rows against 1200 x 1200 at the reference's
-// test_samples = 10), where K1g's 256 x 256 tile would leave most CUs idle.
-//
-// LDS image.  A stage holds BM (and BN) rows of 32 k; a row is 64 B (bf16) or 128 B (fp32) = 4 or 8 16-byte chunks, and
-// chunk c of row r sits at chunk c ^ ((r >> 1) & (chunks - 1)).  A lane reads row (l & 15) of its 16-row tile at chunk
-// (l >> 4) (bf16: the 8 k of its v_mfma_f32_16x16x32_bf16 operand) or chunks (l >> 4) and (l >> 4) + 4 (fp32: its k
-// for the 8 v_mfma_f32_16x16x4_f32 of the stage; MFMA j takes element j, the same k for both operands).  With the XOR
-// every 16-lane group of a ds_read_b128 covers the 64 banks once (unswizzled: 2-way for bf16, 4-way for fp32).
+// one barrier per stage.  The stage image (swz) and the LDS buffer's size are dense_tile.h's, shared with K6 and the
+// Laplace curvature; the k loop and the epilogue are this kernel's own measured forms.  The shapes that matter are small
+// in M (S * B = 1280 rows against 1200 x 1200 at the reference's test_samples = 10), where K1g's 256 x 256 tile would
+// leave most CUs idle.
 //
 // Reduction order.  An output element is the same chain of MFMAs over the same 32-wide k stages whatever the tile size,
 // M and the sample split, so results do not depend on how samples are split over calls or on the plan's tile.
 #include <math.h>
 
 #include "bnn_device.h"
+#include "dense_tile.h"
 #include "../../include/bnn_hip.h"
 
 namespace bnn {
 namespace {
 
-constexpr int kDenseThreads = 256;
-constexpr int kBK = 32;                 // k per LDS stage
 constexpr int kMinBlocks = 512;         // 2 blocks per CU: below this the larger tile / fewer sample runs would idle CUs
 constexpr int kMinSamplesPerRun = 4;    // shared x: a block applies its tile to at least this many samples when it can
 
@@ -64,12 +59,6 @@ __device__ __forceinline__ void load_seg(const XT* __restrict__ src, int rows, i
   }
 }
 
-template <typename T>
-__device__ __forceinline__ int swz(int row, int chunk) {
-  constexpr int CH = kBK * (int)sizeof(T) / 16;
-  return row * CH + (chunk ^ ((row >> 1) & (CH - 1)));
-}
-
 // store a row segment (8 elements: k = 8 seg .. 8 seg + 7) into the stage image (uint4 = one 16-byte chunk)
 template <typename T>
 __device__ __forceinline__ void store_seg(uint4* img, int row, int seg, const T v[8]) {
@@ -91,13 +80,11 @@ __device__ __forceinline__ void store4(__bf16* dst, const float o[4]) {
 }
 
 template <typename T, typename XT, typename YT, int TM, int TN>
-__global__ __launch_bounds__(kDenseThreads) void dense_fwd_kernel(DenseParams p) {
+__global__ __launch_bounds__(kThreads) void dense_fwd_kernel(DenseParams p) {
   constexpr int BM = 32 * TM, BN = 32 * TN;
   constexpr int ROW_CHUNKS = kBK * (int)sizeof(T) / 16;
   constexpr int STAGE = (BM + BN) * ROW_CHUNKS;            // uint4 per stage buffer
-  constexpr int OUT_LD = BN + 4;                           // fp32 output tile row (the epilogue's image), 16-byte rows
-  constexpr int OUT = BM * OUT_LD / 4;
-  __shared__ uint4 lds_raw[2 * STAGE > OUT ? 2 * STAGE : OUT];
+  __shared__ uint4 lds_raw[tile_lds_uint4<T, TM, TN>()];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -111,29 +98,29 @@ __global__ __launch_bounds__(kDenseThreads) void dense_fwd_kernel(DenseParams p)
   const float* __restrict__ w = p.w;
 
   // this thread's staging segments: segment i < BM * 4 of A is (row i / 4, k 8 (i % 4)); of B likewise over BN rows
-  constexpr int A_SEGS = BM * 4 / kDenseThreads, B_SEGS = BN * 4 / kDenseThreads;
+  constexpr int A_SEGS = BM * 4 / kThreads, B_SEGS = BN * 4 / kThreads;
   T ra[A_SEGS][8], rb[B_SEGS][8];
   auto fetch = [&](int k0) {
 #pragma unroll
     for (int i = 0; i < A_SEGS; ++i) {
-      const int s = tid + i * kDenseThreads;
+      const int s = tid + i * kThreads;
       load_seg<XT, T>(x, p.M, p.K, m0 + (s >> 2), k0 + 8 * (s & 3), p.vec_x, ra[i]);
     }
 #pragma unroll
     for (int i = 0; i < B_SEGS; ++i) {
-      const int s = tid + i * kDenseThreads;
+      const int s = tid + i * kThreads;
       load_seg<float, T>(w, p.N, p.K, n0 + (s >> 2), k0 + 8 * (s & 3), p.vec_w, rb[i]);
     }
   };
   auto stash = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < A_SEGS; ++i) {
-      const int s = tid + i * kDenseThreads;
+      const int s = tid + i * kThreads;
       store_seg<T>(lds_raw + buf * STAGE, s >> 2, s & 3, ra[i]);
     }
 #pragma unroll
     for (int i = 0; i < B_SEGS; ++i) {
-      const int s = tid + i * kDenseThreads;
+      const int s = tid + i * kThreads;
       store_seg<T>(lds_raw + buf * STAGE + BM * ROW_CHUNKS, s >> 2, s & 3, rb[i]);
     }
   };
@@ -194,6 +181,7 @@ __global__ __launch_bounds__(kDenseThreads) void dense_fwd_kernel(DenseParams p)
   // epilogue.  The accumulators go through LDS (lane: column lane & 15, rows 4 (lane >> 4) + e of each 16 x 16 tile) so
   // that a thread then owns 4 consecutive columns of a row: one Philox call per 4 elements (one mask group) and
   // coalesced stores.  Then bias, ReLU, the mask, store; a shared-x block repeats the last step for its run of samples.
+  constexpr int OUT_LD = BN + 4;                           // fp32 output tile row (tile_lds_uint4 counts it), 16-byte rows
   float* tile_out = reinterpret_cast<float*>(lds_raw);
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -215,7 +203,7 @@ __global__ __launch_bounds__(kDenseThreads) void dense_fwd_kernel(DenseParams p)
   }
   constexpr int GROUPS = BM * (BN / 4);
 #pragma unroll 1
-  for (int q = tid; q < GROUPS; q += kDenseThreads) {
+  for (int q = tid; q < GROUPS; q += kThreads) {
     const int r = q / (BN / 4), c4 = (q % (BN / 4)) * 4;
     const int row = m0 + r, col0 = n0 + c4;
     if (row >= p.M || col0 >= p.N) continue;
@@ -324,14 +312,15 @@ int dense_check(const bnn_dense_fwd_args* a, DenseLaunch& L) {
   }
   if (tiles * L.runs > INT32_MAX) return BNN_ERR_SHAPE;
   L.blocks = (int)(tiles * L.runs);
-  const int stage = 2 * 2 * L.bm * kBK * (L.math_bf16 ? 2 : 4), out = L.bm * (L.bm + 4) * 4;   // (the kernel's union)
-  L.lds_bytes = stage > out ? stage : out;
+  L.lds_bytes = 16 * (!L.math_bf16 ? tile_lds_uint4<float, 2, 2>()
+                      : L.big      ? tile_lds_uint4<__bf16, 4, 4>()
+                                   : tile_lds_uint4<__bf16, 2, 2>());
   return BNN_OK;
 }
 
 template <typename T, typename XT, typename YT, int TM>
 void launch(const DenseParams& p, int blocks, hipStream_t st) {
-  hipLaunchKernelGGL((dense_fwd_kernel<T, XT, YT, TM, TM>), dim3((unsigned)blocks), dim3(kDenseThreads), 0, st, p);
+  hipLaunchKernelGGL((dense_fwd_kernel<T, XT, YT, TM, TM>), dim3((unsigned)blocks), dim3(kThreads), 0, st, p);
 }
 
 }  // namespace
@@ -346,7 +335,7 @@ extern "C" int bnn_dense_plan(const bnn_dense_fwd_args* a, bnn_plan* plan) {
   if (rc) return rc;
   plan->form = BNN_FORM_GEMM;
   plan->k_classes = 1;
-  plan->waves = kDenseThreads / 64;
+  plan->waves = kThreads / 64;
   plan->batch_rows = L.bm;
   plan->k_slices = L.runs;
   plan->blocks = L.blocks;

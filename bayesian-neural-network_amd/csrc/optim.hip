@@ -6,6 +6,7 @@
 // reuse: HBM-bound, 28 B/param.  One block = one 4096-element chunk of one tensor; the
 // chunk -> tensor table rides in the kernel arguments; 16-byte accesses.
 #include "bnn_device.h"
+#include "bnn_nll_row.h"
 #include "../../include/bnn_hip.h"
 #include <math.h>
 
@@ -18,9 +19,7 @@ struct AdamK {
   const float* g[BNN_ADAM_MAX_TENSORS];
   float* m[BNN_ADAM_MAX_TENSORS];
   float* v[BNN_ADAM_MAX_TENSORS];
-  long numel[BNN_ADAM_MAX_TENSORS];
-  int first_chunk[BNN_ADAM_MAX_TENSORS + 1];
-  int n;
+  ChunkList<BNN_ADAM_MAX_TENSORS> list;
   double lr, beta1, beta2;
   float beta2f, omb1, omb2, eps, wd;
   uint32_t step;
@@ -36,11 +35,9 @@ __global__ void adam_tick_kernel(uint32_t* step) { *step += 1u; }
 // GBF16: the gradients arrive in bf16 (a data-parallel step's all-reduced 2-byte bucket)
 template <bool GBF16>
 __global__ __launch_bounds__(256) void adam_kernel(const AdamK k) {
-  int t = 0;
-#pragma unroll 1
-  while (t + 1 < k.n && (int)blockIdx.x >= k.first_chunk[t + 1]) ++t;
-  const long base = (long)((int)blockIdx.x - k.first_chunk[t]) * kAdamChunk;
-  const long n = k.numel[t];
+  long base;
+  const int t = k.list.find((int)blockIdx.x, kAdamChunk, base);
+  const long n = k.list.numel[t];
   float* __restrict__ p = k.p[t];
   const float* __restrict__ g = k.g[t];
   const __bf16* __restrict__ g16 = reinterpret_cast<const __bf16*>(k.g[t]);
@@ -87,8 +84,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamK k) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float gg = k.wd != 0.f ? __builtin_fmaf(k.wd, pv[j], gv[j]) : gv[j];
-        mv[j] = mv[j] + (gg - mv[j]) * omb1;                       // the arithmetic of the general loop below
-        vv[j] = vv[j] * k.beta2f + omb2 * gg * gg;
+        mv[j] = __builtin_fmaf(gg - mv[j], omb1, mv[j]);           // the arithmetic of the general loop below
+        vv[j] = __builtin_fmaf(vv[j], k.beta2f, omb2 * gg * gg);
         const float denom = __builtin_sqrtf(vv[j]) / sqrt_bc2 + k.eps;
         pv[j] = pv[j] - step_size * (mv[j] / denom);
       }
@@ -120,8 +117,10 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamK k) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float gg = k.wd != 0.f ? __builtin_fmaf(k.wd, pv[j], gv[j]) : gv[j];
-      mv[j] = mv[j] + (gg - mv[j]) * omb1;                       // exp_avg.lerp_(grad, 1 - beta1)
-      vv[j] = vv[j] * k.beta2f + omb2 * gg * gg;     // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
+      mv[j] = __builtin_fmaf(gg - mv[j], omb1, mv[j]);           // exp_avg.lerp_(grad, 1 - beta1); stated, like the next one
+      // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2).  The fma is stated: left to -ffp-contract=fast the compiler forms
+      // fma(v, beta2, (omb2 g) g) or fma(omb2 g, g, v beta2), and which one has flipped with unrelated code around it
+      vv[j] = __builtin_fmaf(vv[j], k.beta2f, omb2 * gg * gg);
       const float denom = __builtin_sqrtf(vv[j]) / sqrt_bc2 + k.eps;
       pv[j] = pv[j] - step_size * (mv[j] / denom);
     }
@@ -165,23 +164,7 @@ __global__ void nll_bwd_kernel(const float* __restrict__ logits, const void* __r
   const long total = (long)S * B;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
     const int b = (int)(idx % B), s = (int)(idx / B);
-    const float* row = logits + idx * C;
-    float* out = g_logits + idx * C;
-    const float gs = g_nll[s];
-    if (mode == BNN_NLL_CLASSIFICATION) {
-      const long long tc = reinterpret_cast<const long long*>(target)[b];
-      float mx = row[0];
-      for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
-      float se = 0.f;
-      for (int c = 0; c < C; ++c) se += expf(row[c] - mx);
-      // a label outside [0, C) poisons the row's gradient (and the forward's NLL) with NaN instead of training
-      // silently on a wrong loss (nn.CrossEntropyLoss, networks.py:186, raises there; ignore_index is not supported)
-      const float inv = (tc >= 0 && tc < C) ? 1.0f / se : __builtin_nanf("");
-      for (int c = 0; c < C; ++c) out[c] = (expf(row[c] - mx) * inv - (c == tc ? 1.f : 0.f)) * gs;
-    } else {
-      const float* tg = reinterpret_cast<const float*>(target) + (size_t)b * C;
-      for (int c = 0; c < C; ++c) out[c] = (row[c] - tg[c]) * inv_var * gs;
-    }
+    nll_row_grad(logits + idx * C, C, mode, target, b, g_nll[s], inv_var, g_logits + idx * C);
   }
 }
 
@@ -196,24 +179,19 @@ extern "C" int bnn_adam_step(const bnn_adam_args* a, void* stream_) {
   if (!a->step_device && a->step == 0) return BNN_ERR_SHAPE;
   if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0) || !(a->eps >= 0.0)) return BNN_ERR_SHAPE;
   AdamK k;
-  long chunks = 0;
+  for (int t = 0; t < BNN_ADAM_MAX_TENSORS; ++t) {
+    k.p[t] = nullptr; k.g[t] = nullptr; k.m[t] = nullptr; k.v[t] = nullptr;
+  }
   for (int t = 0; t < a->n_tensors; ++t) {
     if (!a->param[t] || !a->grad[t] || !a->exp_avg[t] || !a->exp_avg_sq[t]) return BNN_ERR_NULL;
-    if (a->numel[t] <= 0) return BNN_ERR_SHAPE;
+    const int st = k.list.add(a->numel[t], kAdamChunk);
+    if (st != BNN_OK) return st;
     const uintptr_t al = reinterpret_cast<uintptr_t>(a->param[t]) | reinterpret_cast<uintptr_t>(a->grad[t]) |
                          reinterpret_cast<uintptr_t>(a->exp_avg[t]) | reinterpret_cast<uintptr_t>(a->exp_avg_sq[t]);
     if (al & 15) return BNN_ERR_ALIGN;
     k.p[t] = a->param[t]; k.g[t] = a->grad[t]; k.m[t] = a->exp_avg[t]; k.v[t] = a->exp_avg_sq[t];
-    k.numel[t] = (long)a->numel[t];
-    k.first_chunk[t] = (int)chunks;
-    chunks += (a->numel[t] + kAdamChunk - 1) / kAdamChunk;
-    if (chunks > 0x3fffffff) return BNN_ERR_SHAPE;
   }
-  for (int t = a->n_tensors; t <= BNN_ADAM_MAX_TENSORS; ++t) k.first_chunk[t] = (int)chunks;
-  for (int t = a->n_tensors; t < BNN_ADAM_MAX_TENSORS; ++t) {
-    k.p[t] = nullptr; k.g[t] = nullptr; k.m[t] = nullptr; k.v[t] = nullptr; k.numel[t] = 0;
-  }
-  k.n = a->n_tensors;
+  const int chunks = k.list.finish();
   k.lr = a->lr; k.beta1 = a->beta1; k.beta2 = a->beta2; k.eps = (float)a->eps; k.wd = (float)a->weight_decay;
   k.beta2f = (float)a->beta2; k.omb1 = (float)(1.0 - a->beta1); k.omb2 = (float)(1.0 - a->beta2);
   k.step = a->step; k.lr_dev = a->lr_device; k.step_dev = a->step_device;

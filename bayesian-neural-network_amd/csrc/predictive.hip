@@ -12,12 +12,6 @@ constexpr int kPredBlock = 256;
 constexpr int kQuantLdsFloats = 16384;          // 64 KB: the per-column sorts of one quantile block
 constexpr int kQuantMaxCols = 64;
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
-}
-
 // ----------------------------------------------------------------------------- classification
 // One wave per (minibatch g, batch row b), as mc_softmax_mean_kernel (reduce.hip): lane c owns classes c, c + 64, ...;
 // the mean probability is kept in registers (C <= 64) and the samples' logits are fetched eight at a time.  Per sample,

@@ -457,21 +457,7 @@ __global__ __launch_bounds__(256) void elbo_loss_nll_bwd_kernel(
   const float gs = grad_scale / total;
   const long rows = (long)S * B;
   for (long idx = (long)(blockIdx.x - 1) * blockDim.x + threadIdx.x; idx < rows; idx += (long)(gridDim.x - 1) * blockDim.x) {
-    const int brow = (int)(idx % B);
-    const float* row = logits + idx * C;
-    float* out = g_logits + idx * C;
-    if (mode == BNN_NLL_CLASSIFICATION) {
-      const long long tc = reinterpret_cast<const long long*>(target)[brow];
-      float mx = row[0];
-      for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
-      float se = 0.f;
-      for (int c = 0; c < C; ++c) se += expf(row[c] - mx);
-      const float inv = (tc >= 0 && tc < C) ? 1.0f / se : __builtin_nanf("");   // bad label: NaN, as in nll_bwd_kernel
-      for (int c = 0; c < C; ++c) out[c] = (expf(row[c] - mx) * inv - (c == tc ? 1.f : 0.f)) * gs;
-    } else {
-      const float* tg = reinterpret_cast<const float*>(target) + (size_t)brow * C;
-      for (int c = 0; c < C; ++c) out[c] = (row[c] - tg[c]) * inv_var * gs;
-    }
+    nll_row_grad(logits + idx * C, C, mode, target, (int)(idx % B), gs, inv_var, g_logits + idx * C);
   }
 }
 

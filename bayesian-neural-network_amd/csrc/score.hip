@@ -40,12 +40,6 @@ struct ScoreK {
   double sigma;
 };
 
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-
 __device__ __forceinline__ unsigned long long bits(double v) { return (unsigned long long)__double_as_longlong(v); }
 
 // running logsumexp (M, A): sum_s exp(lp_s) = A exp(M).  -inf terms add nothing, a NaN term makes A NaN.
@@ -93,7 +87,7 @@ __global__ __launch_bounds__(kScoreBlock) void mc_score_class_kernel(ScoreK k) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           if (s0 + j < S) {                                       // wave-uniform
-            const float mx = wave_max_f(v[j]);
+            const float mx = wave_max(v[j]);
             const double e = lane < C ? exp((double)v[j] - (double)mx) : 0.0;
             const double se = wave_sum(e);
             const unsigned long long hit = __ballot(lane < C && (long long)lane == y);
@@ -127,7 +121,7 @@ __global__ __launch_bounds__(kScoreBlock) void mc_score_class_kernel(ScoreK k) {
             mine = true;
           }
         }
-        mx = wave_max_f(mx);
+        mx = wave_max(mx);
         double se = 0.0;
         for (int c = lane; c < C; c += 64) se += exp((double)lg[c] - (double)mx);
         se = wave_sum(se);

@@ -161,6 +161,28 @@ def test_fused_loss_and_nll_backward_equal_the_two_launches(mode, local_reparam)
                                                   tgt, mode, 0.7, grad_scale=0.5)
         assert torch.equal(o4[:2], out4[:2]) and torch.equal(o4[3], out4[3]) and torch.equal(gk, g_kl3)
         assert torch.equal(ga, g_a) and torch.equal(gb, g_b) and torch.equal(g, g_ref)
+    if mode != "classification" or local_reparam:
+        return
+    # every kernel that forms the softmax row gradient gives bnn_nll_bwd's bits (the one row of csrc/bnn_nll_row.h): K6's
+    # bnn_dense_loss and the empirical-Fisher seed of bnn_laplace_seed too; an out-of-range label is NaN in that row everywhere
+    B, bad = 5, 3
+    bits = lambda t: t.reshape(B, -1).view(torch.int32)
+    for C in (1, 3, 10, 17):
+        logits = torch.from_numpy(rs.standard_normal((1, B, C)).astype(np.float32) * 3).to(dev)
+        labels = rs.randint(0, C, B)
+        labels[bad] = C
+        tgt = torch.from_numpy(labels).to(dev)
+        for gs in (0.37, 1.0):
+            g_ref = ops.nll_bwd(logits, tgt, torch.tensor([gs], device=dev), mode)
+            assert torch.equal(torch.isnan(g_ref[0]).all(1).cpu(), torch.arange(B) == bad)
+            assert not torch.isnan(g_ref[0, torch.arange(B) != bad]).any()
+            _, g = ops.dense_loss(logits[0], tgt, mode, grad_scale=gs)
+            assert torch.equal(bits(g), bits(g_ref)), (C, gs)
+            one = torch.ones(1, device=dev)
+            g = ops.elbo_loss_nll_bwd(one, one, one, one[0], 1, False, logits, tgt, mode, 1.0, grad_scale=gs)[4]
+            assert torch.equal(bits(g), bits(g_ref)), (C, gs)
+        seed = ops.laplace_seed(logits[0], tgt, mode, curvature="empirical", record=torch.zeros(2, dtype=torch.float64, device=dev))
+        assert torch.equal(bits(seed), bits(g_ref)), C                   # (the seed is unscaled: the last g_ref, gs = 1)
 
 
 def test_stage_inputs_copies_and_sets_the_word():
