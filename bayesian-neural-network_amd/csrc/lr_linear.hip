@@ -364,8 +364,13 @@ __device__ __forceinline__ void lr_fwd_body(const LrK& p) {
               if (XDT == BNN_BF16) {
                 xb = __builtin_bit_cast(bf16x8, xraw[mm * R + cc]);      // already the MFMA operand
               } else {
+                // fp32 x: rounded here, and the square below is of the ROUNDED value -- bf16(bf16(x)^2), the one definition of
+                // this math mode's x^2 operand (include/bnn_hip.h, bnn_math)
 #pragma unroll
-                for (int j = 0; j < 8; ++j) xb[j] = (__bf16)xv[j];
+                for (int j = 0; j < 8; ++j) {
+                  xb[j] = (__bf16)xv[j];
+                  xv[j] = (float)xb[j];
+                }
               }
               // squares two at a time (v_pk_mul_f32): the x handling is what the vector pipe spends this kernel on
               typedef __attribute__((ext_vector_type(2))) float f32x2;
