@@ -46,6 +46,7 @@ EXPORTS = (
     "bnn_flipout_signs", "bnn_flipout_prepare", "bnn_flipout_fwd", "bnn_flipout_bwd",
     "bnn_flipout_prepare_workspace_bytes", "bnn_flipout_bwd_workspace_bytes",
     "bnn_laplace_seed", "bnn_laplace_layer", "bnn_laplace_evidence", "bnn_laplace_posterior", "bnn_laplace_evidence_workspace_bytes",
+    "bnn_laplace_glm_layer", "bnn_laplace_glm_finish", "bnn_laplace_glm_sample",
 )
 
 
@@ -545,6 +546,37 @@ class LaplacePosteriorArgs(C.Structure):
                 ("numel", C.c_int64 * LAPLACE_MAX_TENSORS), ("precision", C.c_double), ("precision_device", C.c_void_p)]
 
 
+LAPLACE_GLM_MAX_CLASSES = 16
+LAPLACE_GLM_MAX_LAYERS = LAPLACE_MAX_TENSORS // 2
+
+
+class LaplaceGlmLayerArgs(C.Structure):
+    """bnn_laplace_glm_layer_args (include/bnn_hip.h F18)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("batch", C.c_int32), ("rows", C.c_int32), ("in_features", C.c_int32),
+                ("out_features", C.c_int32), ("math", C.c_int32), ("gx_mask", C.c_int32), ("reserved", C.c_int32),
+                ("precision", C.c_double), ("precision_device", C.c_void_p),
+                ("x", C.c_void_p), ("gy", C.c_void_p), ("y", C.c_void_p), ("w", C.c_void_p),
+                ("f_w", C.c_void_p), ("f_b", C.c_void_p), ("g_x", C.c_void_p), ("cov_part", C.c_void_p), ("v_out", C.c_void_p)]
+
+
+class LaplaceGlmFinishArgs(C.Structure):
+    """bnn_laplace_glm_finish_args (include/bnn_hip.h F18)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("batch", C.c_int32), ("classes", C.c_int32), ("n_layers", C.c_int32),
+                ("mode", C.c_int32), ("n_quantiles", C.c_int32), ("n_samples", C.c_int32), ("reserved", C.c_int32),
+                ("sigma", C.c_double), ("z", C.c_double * PREDICTIVE_MAX_QUANTILES),
+                ("cov_part", C.c_void_p * LAPLACE_GLM_MAX_LAYERS), ("tiles", C.c_int32 * LAPLACE_GLM_MAX_LAYERS),
+                ("mean", C.c_void_p), ("cov", C.c_void_p), ("var", C.c_void_p), ("chol", C.c_void_p),
+                ("probs", C.c_void_p), ("preds", C.c_void_p), ("entropy", C.c_void_p),
+                ("predictive_variance", C.c_void_p), ("quantiles", C.c_void_p), ("sample_counter", C.c_void_p)]
+
+
+class LaplaceGlmSampleArgs(C.Structure):
+    """bnn_laplace_glm_sample_args (include/bnn_hip.h F18)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_samples", C.c_int32), ("batch", C.c_int32), ("classes", C.c_int32),
+                ("seed", C.c_uint64), ("sample_base", C.c_uint32), ("reserved", C.c_int32),
+                ("mean", C.c_void_p), ("chol", C.c_void_p), ("logits", C.c_void_p), ("sample_counter", C.c_void_p)]
+
+
 HIST_MAX_JOBS = 16
 HIST_MAX_EDGES = 2048
 HIST_CHUNK = 8192
@@ -870,7 +902,9 @@ def _load_real():
     lib.bnn_flipout_bwd_workspace_bytes.restype = C.c_size_t
     lib.bnn_flipout_bwd_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     for name, cls in (("bnn_laplace_seed", LaplaceSeedArgs), ("bnn_laplace_layer", LaplaceLayerArgs),
-                      ("bnn_laplace_evidence", LaplaceEvidenceArgs), ("bnn_laplace_posterior", LaplacePosteriorArgs)):
+                      ("bnn_laplace_evidence", LaplaceEvidenceArgs), ("bnn_laplace_posterior", LaplacePosteriorArgs),
+                      ("bnn_laplace_glm_layer", LaplaceGlmLayerArgs), ("bnn_laplace_glm_finish", LaplaceGlmFinishArgs),
+                      ("bnn_laplace_glm_sample", LaplaceGlmSampleArgs)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     lib.bnn_laplace_evidence_workspace_bytes.restype = C.c_size_t

@@ -8,7 +8,12 @@ networks (predict_mc, predictive, score, PruneSweep, compress, BatchBALD, the ba
 One minibatch is a fixed chain of launches: bnn_dense_fwd per layer (one sample, fp32 activations, no dropout) ->
 bnn_laplace_seed (the output deltas of the C virtual rows of every data row, and the log-likelihood record) ->
 bnn_laplace_layer per layer, top down (the layer's curvature diagonal, accumulated in place, and the deltas of the layer
-below).  Three layers: 3 + 1 + 3 = 7 launches, no parallel branches; accumulate_graph captures them once."""
+below).  Three layers: 3 + 1 + 3 = 7 launches, no parallel branches; accumulate_graph captures them once.
+
+F18: the predictive that belongs to this curvature is the linearised (GLM) one -- the GGN is the exact Hessian of the network
+linearised at the trained weights (Immer et al. 2021), and sampling weights through the non-linear network (network().predict_mc)
+underfits against it.  glm_moments / glm_predictive / glm_predictive_graph / glm_score: 3 bnn_dense_fwd + 1 seed +
+3 bnn_laplace_glm_layer + 1 bnn_laplace_glm_finish (+ 1 bnn_laplace_glm_sample + 1 bnn_mc_predictive) launches."""
 from __future__ import annotations
 
 from typing import Dict, Iterable, Optional, Sequence
@@ -20,8 +25,9 @@ from torch import nn
 from . import _lib as L
 from . import ops
 from .mcdropout import _math, flat_input, layers_of
-from .ops import BnnHipError
-from .runtime import state
+from .engine import _first_minibatch
+from .ops import BnnHipError, Predictive
+from .runtime import state, take_samples
 
 DEFAULT_PRECISIONS = np.logspace(-4, 4, 33)
 
@@ -120,6 +126,135 @@ class LaplaceStep:
         self._chain.run()
 
 
+GLM_LINKS = ("probit", "mc")
+
+
+def _word(v: int) -> int:
+    """A uint32 sample index as the int32 a torch word stores."""
+    v = int(v) & 0xFFFFFFFF
+    return v - (1 << 32) if v >= 1 << 31 else v
+
+
+class _GlmChain:
+    """F18: the static buffers of the linearised predictive for one batch size and the launches over them -- bnn_dense_fwd
+    per layer, bnn_laplace_seed (regression mode, GGN, sigma 1, no target: gy[c B + n, k] = delta_kc; its row count goes into
+    a scratch record, never into la.record), bnn_laplace_glm_layer per layer top down, bnn_laplace_glm_finish, and for
+    link 'mc' bnn_laplace_glm_sample (+ bnn_mc_predictive).  No parallel branches."""
+
+    def __init__(self, la: "DiagLaplace", B: int):
+        self.la, self.B = la, B
+        dev, layers = la.device, la.layers
+        C_out = layers[-1].linear.out_features
+        P = ops.glm_pairs(C_out)                                              # (refuses more than 16 outputs)
+        self.C, self.R = C_out, B * C_out
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.x = torch.zeros((B, layers[0].linear.in_features), **f32)
+        self.acts = [torch.empty((1, B, d.linear.out_features), **f32) for d in layers]
+        self.gy = torch.empty((self.R, C_out), **f32)
+        self.g_hidden = [torch.empty((self.R, d.linear.out_features), **f32) for d in layers[:-1]]
+        self.parts = [torch.empty((ops.glm_tiles(d.linear.out_features), B, P), **f32) for d in layers]
+        self.scratch = torch.zeros(L.LAPLACE_RECORD_DOUBLES, dtype=torch.float64, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def stage(self, x: torch.Tensor):
+        xf = flat_input(self.la.mlp, x)
+        if xf.numel() != self.x.numel():
+            raise BnnHipError(f"DiagLaplace: a batch of {self.B} rows needs x of {self.x.numel()} float32 elements")
+        self.x.copy_(xf.reshape(self.x.shape), non_blocking=True)
+
+    @property
+    def mean(self) -> torch.Tensor:
+        return self.acts[-1][0]
+
+    def moments(self, tau, tau_dev, *, quantiles=(), sigma: float = 1.0, out=None, n_samples: int = 0) -> "ops.GlmMoments":
+        """Forward, seed, one bnn_laplace_glm_layer per layer, finish (which advances the counter by n_samples)."""
+        la = self.la
+        layers, math_mode = la.layers, _math()[0]
+        last = len(layers) - 1
+        with torch.no_grad():
+            h = self.x
+            for i, d in enumerate(layers):
+                lin = d.linear
+                ops.dense_fwd(h, lin.weight.detach(), lin.bias.detach(), n_samples=1, math_mode=math_mode, relu=d.relu,
+                              drop_p=0.0, layer_id=d.layer_id, seed=state.seed, y_dtype=torch.float32, out=self.acts[i])
+                h = self.acts[i][0]
+            ops.laplace_seed(self.mean, None, "regression", curvature="ggn", sigma=1.0, gy=self.gy, record=self.scratch)
+            for i in range(last, -1, -1):
+                d = layers[i]
+                below = layers[i - 1] if i > 0 else None
+                ops.laplace_glm_layer(self.x if i == 0 else self.acts[i - 1][0], self.gy if i == last else self.g_hidden[i],
+                                      d.linear.weight.detach(), f_w=la.curv[2 * i], f_b=la.curv[2 * i + 1],
+                                      cov_part=self.parts[i], g_x=self.g_hidden[i - 1] if i > 0 else None,
+                                      y=self.acts[i][0] if d.relu else None, gx_mask=below is not None and below.relu,
+                                      precision=tau, precision_device=tau_dev, math_mode=math_mode)
+            return ops.laplace_glm_finish(self.parts, self.mean, la.mode, sigma=sigma, quantiles=quantiles, out=out,
+                                          sample_counter=self.counter if n_samples else None, n_samples=n_samples)
+
+    def sample(self, m: "ops.GlmMoments", samples: int, out=None) -> torch.Tensor:
+        """logits [S, B, C] at the global sample indices counter - S ... counter - 1 (the finish launch advanced the counter)."""
+        with torch.no_grad():
+            return ops.laplace_glm_sample(self.mean, m.chol, samples, seed=state.seed, sample_counter=self.counter, out=out)
+
+
+class GlmPredictiveGraph:
+    """What glm_predictive_graph returns: the static input `.x` ([B, in], the flattened input) and `replay()`, which returns
+    the static Predictive of whatever `.x` holds.  With link 'mc' the sample counter `.counter` lives on the device and the
+    finish launch advances it, so replay k of a graph built at counter c draws the global samples c + (k + 1) S ... (the
+    capture's warm-up run takes c ... c + S - 1), and the host counter is kept in step."""
+
+    def __init__(self, la: "DiagLaplace", x, samples: int, link: str, quantiles, sigma, prior_precision, capture: bool = True):
+        la._check_math()
+        self.la, self.link, self.samples = la, link, int(samples)
+        self.q, self.sigma = la._glm_args(self.samples, link, quantiles), la.sigma if sigma is None else float(sigma)
+        self.tau, self.tau_dev = la._tau(prior_precision, "glm_predictive_graph")
+        B = flat_input(la.mlp, x).shape[0]
+        ch = self._chain = _GlmChain(la, B)
+        ch.stage(x)
+        self.x, self.counter = ch.x, ch.counter
+        self.mc = link == "mc" and la.mode == "classification"
+        self._m = ops.glm_buffers(la.mode, B, ch.C, la.device, len(self.q))
+        self.logits = torch.empty((self.samples, B, ch.C), dtype=torch.float32, device=la.device) if self.mc else None
+        self._pred = ops.predictive_buffers(la.mode, 1, B, ch.C, la.device) if self.mc else None
+        self.result = _first_minibatch(self._pred) if self.mc else la._closed_form(ch.mean, self._m)
+        self.counter.fill_(_word(take_samples(0)))
+        self.graph = None
+        if capture:
+            torch.cuda.synchronize()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._enqueue()                                               # warm-up (also validates the arguments eagerly)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            if self.mc:
+                take_samples(self.samples)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self._enqueue()
+
+    def _enqueue(self):
+        ch = self._chain
+        m = ch.moments(self.tau, self.tau_dev, quantiles=self.q, sigma=self.sigma, out=self._m, n_samples=self.samples if self.mc else 0)
+        if self.mc:
+            ch.sample(m, self.samples, out=self.logits)
+            ops.mc_predictive(self.logits, "classification", out=self._pred)
+
+    @property
+    def moments(self) -> "ops.GlmMoments":
+        """The static cov / var / chol (and closed-form summaries) of the last replay."""
+        return self._m
+
+    def replay(self) -> Predictive:
+        self.la._check_math()
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._enqueue()
+        if self.mc:
+            take_samples(self.samples)                                        # keep the host-side counter in step
+        return self.result
+
+
 class DiagLaplace:
     def __init__(self, mlp, curvature: str = "ggn", sigma: float = 1.0):
         """`mlp`: a trained networks.MLP, or MLP_Dropout with its dropout switched off (mlp.eval()), on the device.
@@ -151,6 +286,7 @@ class DiagLaplace:
         self.math = _math()[0]
         self._eager: Dict[int, _Chain] = {}
         self._graphed: Dict[int, _Chain] = {}
+        self._glm: Dict[int, _GlmChain] = {}
         self._best_index = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._best = torch.zeros(2, dtype=torch.float64, device=self.device)
         self._fitted = False
@@ -228,6 +364,104 @@ class DiagLaplace:
         if not self._fitted:
             raise BnnHipError("DiagLaplace: no prior precision chosen yet; call fit_prior_precision()")
         return float(self._best[1].item())
+
+    # ---- F18: the linearised (GLM) predictive
+    def _tau(self, prior_precision, what: str):
+        """(host tau, device word or None): by default the word fit_prior_precision chose (run with its defaults if it has
+        not been), as network() does."""
+        if prior_precision is None:
+            if not self._fitted:
+                self.fit_prior_precision()
+            return None, self._best[1:2]
+        tau = float(prior_precision)
+        if not 0.0 < tau < float("inf"):
+            raise BnnHipError(f"DiagLaplace.{what}: the prior precision must be positive and finite, got {prior_precision!r}")
+        return tau, None
+
+    def _glm_args(self, samples: int, link: str, quantiles) -> tuple:
+        """The checked quantile levels; every refusal of the GLM interface that needs no device."""
+        if link not in GLM_LINKS:
+            raise BnnHipError(f"DiagLaplace: link must be one of {GLM_LINKS}, got {link!r}")
+        if link == "mc" and int(samples) < 1:
+            raise BnnHipError(f"DiagLaplace: link 'mc' needs samples >= 1, got {samples}")
+        C_out = self.layers[-1].linear.out_features
+        if C_out > L.LAPLACE_GLM_MAX_CLASSES:
+            raise BnnHipError(f"DiagLaplace: the linearised predictive handles at most {L.LAPLACE_GLM_MAX_CLASSES} outputs "
+                              f"(BNN_LAPLACE_GLM_MAX_CLASSES); this network has {C_out}")
+        if self.mode == "classification" and quantiles:
+            raise BnnHipError("DiagLaplace: quantiles are a regression summary")
+        return ops.quantile_levels(quantiles)
+
+    def _glm_chain(self, x) -> _GlmChain:
+        self._check_math()
+        B = flat_input(self.mlp, x).shape[0]
+        ch = self._glm.get(B)
+        if ch is None:
+            ch = self._glm[B] = _GlmChain(self, B)
+        ch.stage(x)
+        return ch
+
+    def _closed_form(self, mean, m) -> Predictive:
+        if self.mode == "classification":
+            return Predictive(probs=m.probs, preds=m.preds, predictive_entropy=m.entropy)
+        return Predictive(mean=mean, variance=m.var, predictive_variance=m.predictive_variance, quantiles=m.quantiles)
+
+    def glm_moments(self, x: torch.Tensor, prior_precision: Optional[float] = None):
+        """(mean [B, C], cov [B, C, C]) of the Gaussian over the outputs of the network linearised at the trained weights,
+        f(x, w) + J(x)(theta - w) with theta ~ N(w, (diag(F) + tau)^-1): mean = the network's output, cov = J diag(s^2) J^T.
+        Defined for any diagonal F, so an empirical-Fisher object is accepted too (the curvature only has to be a diagonal;
+        the GGN is the one the linearisation is the exact Hessian of)."""
+        self._glm_args(0, "probit", None)
+        tau, tau_dev = self._tau(prior_precision, "glm_moments")
+        ch = self._glm_chain(x)
+        m = ch.moments(tau, tau_dev, sigma=self.sigma)
+        return ch.mean.clone(), m.cov
+
+    def glm_predictive(self, x: torch.Tensor, samples: int = 0, *, link: str = "probit", quantiles=None, sigma: Optional[float] = None,
+                       prior_precision: Optional[float] = None, sample_offset: Optional[int] = None) -> Predictive:
+        """The linearised predictive as an ops.Predictive.  Classification, link 'probit': probs = softmax(mean / sqrt(1 +
+        pi / 8 var)) (MacKay), preds and predictive_entropy; expected_entropy and mutual_information are None (no closed
+        form).  Classification, link 'mc': `samples` logit draws mean + chol . eps through bnn_mc_predictive, all five fields.
+        Regression, either link: mean, variance, predictive_variance = variance + sigma^2 and closed-form quantiles; nothing is
+        sampled.  `sigma` defaults to the object's, tau to the word fit_prior_precision chose.  `sample_offset`: the first
+        global sample index of an 'mc' call (by default the next `samples` of the process-wide counter).  An empirical-Fisher
+        object is accepted (see glm_moments)."""
+        q = self._glm_args(samples, link, quantiles)
+        sg = self.sigma if sigma is None else float(sigma)
+        tau, tau_dev = self._tau(prior_precision, "glm_predictive")
+        ch = self._glm_chain(x)
+        mc = link == "mc" and self.mode == "classification"
+        if mc:
+            ch.counter.fill_(_word(take_samples(samples) if sample_offset is None else sample_offset))
+        m = ch.moments(tau, tau_dev, quantiles=q, sigma=sg, n_samples=int(samples) if mc else 0)
+        if not mc:
+            return self._closed_form(ch.mean.clone(), m)
+        return _first_minibatch(ops.mc_predictive(ch.sample(m, int(samples)), "classification"))
+
+    def glm_predictive_graph(self, x: torch.Tensor, samples: int = 0, *, link: str = "probit", quantiles=None,
+                             sigma: Optional[float] = None, prior_precision: Optional[float] = None,
+                             capture: bool = True) -> GlmPredictiveGraph:
+        """glm_predictive for inputs shaped like x, captured once as a hipGraph: `g = la.glm_predictive_graph(x, ...)`, write
+        `g.x`, `g.replay()` -- the same launches as the eager call, so the same bits at the same counter value.  With link
+        'mc' every replay draws fresh samples through the device counter `g.counter`."""
+        return GlmPredictiveGraph(self, x, samples, link, quantiles, sigma, prior_precision, capture=capture)
+
+    def glm_sample(self, x: torch.Tensor, samples: int, *, prior_precision: Optional[float] = None,
+                   sample_offset: Optional[int] = None) -> torch.Tensor:
+        """[samples, B, C] draws of the linearised network's outputs, mean + chol . eps (what link 'mc' and glm_score consume)."""
+        self._glm_args(samples, "mc", None)
+        tau, tau_dev = self._tau(prior_precision, "glm_sample")
+        ch = self._glm_chain(x)
+        ch.counter.fill_(_word(take_samples(samples) if sample_offset is None else sample_offset))
+        m = ch.moments(tau, tau_dev, sigma=self.sigma, n_samples=int(samples))
+        return ch.sample(m, int(samples))
+
+    def glm_score(self, x: torch.Tensor, y: torch.Tensor, samples: int, *, sigma: Optional[float] = None, bins: int = 10,
+                  record=None, prior_precision: Optional[float] = None, sample_offset: Optional[int] = None) -> "ops.Scores":
+        """F12's held-out scores (bnn_mc_score, unchanged) of `samples` draws of the linearised network's outputs, in both
+        modes."""
+        logits = self.glm_sample(x, samples, prior_precision=prior_precision, sample_offset=sample_offset)
+        return ops.mc_score(logits, y, self.mode, sigma=self.sigma if sigma is None else float(sigma), bins=int(bins), record=record)
 
     # ---- the posterior as a network
     def network(self, prior_precision: Optional[float] = None):

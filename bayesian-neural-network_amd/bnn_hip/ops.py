@@ -2841,3 +2841,178 @@ def laplace_posterior(params, curvs, mus, rhos, *, precision=None, precision_dev
             raise BnnHipError(f"laplace_posterior: the prior precision must be positive and finite, got {precision!r}")
         a.precision, a.precision_device = float(precision), None
     L.check(lib.bnn_laplace_posterior(C.byref(a), _stream()), "bnn_laplace_posterior")
+
+
+# ---------------------------------------------------------------------------------------------- F18: the GLM predictive
+GLM_TILE = 64
+
+
+def glm_pairs(classes: int) -> int:
+    """The pairs c <= c' of a covariance row: pair = c' (c' + 1) / 2 + c."""
+    if not 1 <= int(classes) <= L.LAPLACE_GLM_MAX_CLASSES:
+        raise BnnHipError(f"laplace_glm: between 1 and {L.LAPLACE_GLM_MAX_CLASSES} outputs (BNN_LAPLACE_GLM_MAX_CLASSES), got {classes}")
+    return int(classes) * (int(classes) + 1) // 2
+
+
+def glm_tiles(out_features: int) -> int:
+    return (int(out_features) + GLM_TILE - 1) // GLM_TILE
+
+
+def _glm_precision(a, precision, precision_device, what: str):
+    if precision_device is not None:
+        a.precision, a.precision_device = 1.0, _lap_f64(precision_device, "precision_device", 1).data_ptr()
+    else:
+        if precision is None or not 0.0 < float(precision) < math.inf:
+            raise BnnHipError(f"{what}: the prior precision must be positive and finite, got {precision!r}")
+        a.precision, a.precision_device = float(precision), None
+
+
+def laplace_glm_layer(x, gy, w, *, f_w, f_b, cov_part=None, g_x=None, y=None, gx_mask: bool = False, v_out=None,
+                      precision=None, precision_device=None, math_mode: int = L.MATH_F32):
+    """F18 bnn_laplace_glm_layer: one Linear -> [ReLU] group of the linearised predictive.  x [B, in], gy [R, out] (R = B * C,
+    C <= 16), the saved output y [B, out] or None, the curvature (f_w [out, in], f_b [out]) and tau (a host float, or a
+    one-element float64 device tensor); cov_part [ceil(out / 64), B, C (C + 1) / 2] receives the tile partials of
+    sum_o gz_c gz_c' V with V = x^2 . (1 / (f_w + tau))^T + 1 / (f_b + tau); g_x [R, in] = gz w as laplace_layer's;
+    v_out [B, out] = V.  Returns cov_part."""
+    lib = L.load()
+    x = _lap_f32(x, "x")
+    if x.dim() != 2:
+        raise BnnHipError(f"laplace_glm_layer: x must be [batch, in], got {tuple(x.shape)}")
+    B, K = x.shape
+    N = w.shape[0]
+    gy = _lap_f32(gy, "gy")
+    R = gy.shape[0]
+    if gy.dim() != 2 or R % B != 0:
+        raise BnnHipError(f"laplace_glm_layer: gy must be [rows, out] with rows a multiple of the batch {B}, got {tuple(gy.shape)}")
+    P = glm_pairs(R // B)
+    _lap_f32(gy, "gy", (R, N)), _lap_f32(w, "w", (N, K)), _lap_f32(f_w, "f_w", (N, K)), _lap_f32(f_b, "f_b", (N,))
+    _lap_f32(g_x, "g_x", (R, K)), _lap_f32(y, "y", (B, N)), _lap_f32(v_out, "v_out", (B, N))
+    if f_w is None or f_b is None:
+        raise BnnHipError("laplace_glm_layer: the curvature (f_w, f_b) is needed")
+    shape = (glm_tiles(N), B, P)
+    cov_part = torch.empty(shape, dtype=torch.float32, device=x.device) if cov_part is None else _lap_f32(cov_part, "cov_part", shape)
+    a = L.LaplaceGlmLayerArgs()
+    a.struct_bytes = C.sizeof(L.LaplaceGlmLayerArgs)
+    a.batch, a.rows, a.in_features, a.out_features = B, R, K, N
+    a.math, a.gx_mask = _exact_unless_bf16(math_mode), int(bool(gx_mask))
+    _glm_precision(a, precision, precision_device, "laplace_glm_layer")
+    a.x, a.gy, a.y, a.w = x.data_ptr(), gy.data_ptr(), _ptr(y), w.data_ptr()
+    a.f_w, a.f_b, a.g_x, a.cov_part, a.v_out = f_w.data_ptr(), f_b.data_ptr(), _ptr(g_x), cov_part.data_ptr(), _ptr(v_out)
+    L.check(lib.bnn_laplace_glm_layer(C.byref(a), _stream()), "bnn_laplace_glm_layer")
+    return cov_part
+
+
+class GlmMoments(NamedTuple):
+    """What bnn_laplace_glm_finish writes: cov [B, C, C], var [B, C], chol [B, C, C] and the mode's closed-form summaries
+    (classification probs / preds / entropy; regression predictive_variance / quantiles [Q, B, C])."""
+    cov: torch.Tensor
+    var: torch.Tensor
+    chol: torch.Tensor
+    probs: Optional[torch.Tensor] = None
+    preds: Optional[torch.Tensor] = None
+    entropy: Optional[torch.Tensor] = None
+    predictive_variance: Optional[torch.Tensor] = None
+    quantiles: Optional[torch.Tensor] = None
+
+
+def normal_quantiles(levels) -> tuple:
+    """z_q = Phi^-1(q) in fp64 for checked quantile levels; -inf / +inf at 0 / 1."""
+    import statistics
+    nd = statistics.NormalDist()
+    return tuple(-math.inf if q == 0.0 else math.inf if q == 1.0 else nd.inv_cdf(q) for q in quantile_levels(levels))
+
+
+def glm_buffers(mode: str, B: int, Cc: int, device, n_quantiles: int = 0) -> GlmMoments:
+    f = dict(dtype=torch.float32, device=device)
+    base = dict(cov=torch.empty((B, Cc, Cc), **f), var=torch.empty((B, Cc), **f), chol=torch.empty((B, Cc, Cc), **f))
+    if mode == "classification":
+        return GlmMoments(probs=torch.empty((B, Cc), **f), preds=torch.empty(B, dtype=torch.int64, device=device),
+                          entropy=torch.empty(B, **f), **base)
+    if mode == "regression":
+        return GlmMoments(predictive_variance=torch.empty((B, Cc), **f),
+                          quantiles=torch.empty((n_quantiles, B, Cc), **f) if n_quantiles else None, **base)
+    raise Exception("Training mode must be either 'regression' or 'classification'")
+
+
+def laplace_glm_finish(parts, mean, mode: str, *, sigma: float = 1.0, quantiles=(), out: Optional[GlmMoments] = None,
+                       sample_counter=None, n_samples: int = 0) -> GlmMoments:
+    """F18 bnn_laplace_glm_finish: `parts` the cov_part tensors of the layers ([tiles, B, pairs] each, summed in list order),
+    `mean` [B, C] the network's output -> GlmMoments.  `quantiles`: levels in [0, 1] (regression).  `sample_counter`: a uint32
+    (int32 storage) device word that the launch advances by `n_samples`."""
+    lib = L.load()
+    mean = _lap_f32(mean, "mean")
+    if mean.dim() != 2:
+        raise BnnHipError(f"laplace_glm_finish: mean must be [batch, outputs], got {tuple(mean.shape)}")
+    B, Cc = mean.shape
+    P = glm_pairs(Cc)
+    parts = list(parts)
+    if not 1 <= len(parts) <= L.LAPLACE_GLM_MAX_LAYERS:
+        raise BnnHipError(f"laplace_glm_finish: between 1 and {L.LAPLACE_GLM_MAX_LAYERS} layers, got {len(parts)}")
+    if mode not in ("classification", "regression"):
+        raise Exception("Training mode must be either 'regression' or 'classification'")
+    z = normal_quantiles(quantiles) if mode == "regression" else ()
+    if mode == "regression" and not 0.0 < float(sigma) < math.inf:
+        raise BnnHipError(f"laplace_glm_finish: sigma must be positive and finite, got {sigma!r}")
+    if int(n_samples) < 0:
+        raise BnnHipError("laplace_glm_finish: n_samples must be >= 0")
+    if out is None:
+        out = glm_buffers(mode, B, Cc, mean.device, len(z))
+    want = dict(cov=(B, Cc, Cc), var=(B, Cc), chol=(B, Cc, Cc), probs=(B, Cc), preds=(B,), entropy=(B,),
+                predictive_variance=(B, Cc), quantiles=(len(z), B, Cc))
+    for name, t in zip(out._fields, out):
+        if t is None:
+            continue
+        require_device(t)
+        dt = torch.int64 if name == "preds" else torch.float32
+        if tuple(t.shape) != want[name] or t.dtype != dt or not t.is_contiguous():
+            raise BnnHipError(f"laplace_glm_finish: out.{name} must be a contiguous {dt} tensor of shape {want[name]}")
+    if z and out.quantiles is None:
+        raise BnnHipError("laplace_glm_finish: quantile levels need out.quantiles")
+    a = L.LaplaceGlmFinishArgs()
+    a.struct_bytes = C.sizeof(L.LaplaceGlmFinishArgs)
+    a.batch, a.classes, a.n_layers = B, Cc, len(parts)
+    a.mode = L.NLL_CLASSIFICATION if mode == "classification" else L.NLL_REGRESSION
+    a.n_quantiles, a.n_samples, a.sigma = len(z), int(n_samples), float(sigma)
+    for i, v in enumerate(z):
+        a.z[i] = v
+    for i, t in enumerate(parts):
+        t = _lap_f32(t, "cov_part")
+        if t.dim() != 3 or t.shape[0] < 1 or tuple(t.shape[1:]) != (B, P):
+            raise BnnHipError(f"laplace_glm_finish: a cov_part must be [tiles, {B}, {P}], got {tuple(t.shape)}")
+        a.cov_part[i], a.tiles[i] = t.data_ptr(), t.shape[0]
+    a.mean, a.cov, a.var, a.chol = mean.data_ptr(), out.cov.data_ptr(), out.var.data_ptr(), out.chol.data_ptr()
+    if mode == "classification":
+        a.probs, a.preds, a.entropy = _ptr(out.probs), _ptr(out.preds), _ptr(out.entropy)
+    else:
+        a.predictive_variance, a.quantiles = _ptr(out.predictive_variance), _ptr(out.quantiles) if z else None
+    if sample_counter is not None:
+        a.sample_counter = _typed(sample_counter, torch.int32, "sample_counter", 1).data_ptr()
+    L.check(lib.bnn_laplace_glm_finish(C.byref(a), _stream()), "bnn_laplace_glm_finish")
+    return out
+
+
+def laplace_glm_sample(mean, chol, n_samples: int, *, seed: int, sample_base: int = 0, sample_counter=None, out=None):
+    """F18 bnn_laplace_glm_sample: logits [S, B, C] = mean + chol . eps, eps from the Philox stream (5, 1) at the global
+    sample indices sample_base + (*sample_counter - S, when a counter is given) + s."""
+    lib = L.load()
+    mean = _lap_f32(mean, "mean")
+    if mean.dim() != 2:
+        raise BnnHipError(f"laplace_glm_sample: mean must be [batch, outputs], got {tuple(mean.shape)}")
+    B, Cc = mean.shape
+    glm_pairs(Cc)
+    S = int(n_samples)
+    if S < 1:
+        raise BnnHipError(f"laplace_glm_sample: at least one sample, got {n_samples}")
+    _lap_f32(chol, "chol", (B, Cc, Cc))
+    if chol is None:
+        raise BnnHipError("laplace_glm_sample: chol is needed")
+    out = torch.empty((S, B, Cc), dtype=torch.float32, device=mean.device) if out is None else _lap_f32(out, "logits", (S, B, Cc))
+    a = L.LaplaceGlmSampleArgs()
+    a.struct_bytes = C.sizeof(L.LaplaceGlmSampleArgs)
+    a.n_samples, a.batch, a.classes = S, B, Cc
+    a.seed, a.sample_base = int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_base) & 0xFFFFFFFF
+    a.mean, a.chol, a.logits = mean.data_ptr(), chol.data_ptr(), out.data_ptr()
+    if sample_counter is not None:
+        a.sample_counter = _typed(sample_counter, torch.int32, "sample_counter", 1).data_ptr()
+    L.check(lib.bnn_laplace_glm_sample(C.byref(a), _stream()), "bnn_laplace_glm_sample")
+    return out

@@ -10,6 +10,12 @@
 // tile starts from the stored F_w, so a curvature element is ONE chain over every minibatch accumulated so far: no K-split,
 // no float atomics, the same bits whatever the grid.  F_b += colsum(S) rides on the tile column 0 blocks: four strided
 // partial sums per column (the first starting from the stored F_b), added in K6's order.
+//
+// F18 the linearised (GLM) predictive of that posterior: bnn_laplace_glm_layer (the same g_x tiles, through one device function,
+// beside 64 x 64 tiles of V [B, out] = x^2 . (s^2_w)^T + s^2_b with s^2 = 1 / (F + tau) formed while staging, whose epilogue sums
+// gz_c gz_c' V over the tile's columns for every pair c <= c' of a data row: one fixed fmaf chain per partial),
+// bnn_laplace_glm_finish (a thread per data row: the fp64 sum of the partials, cov, var, the Cholesky factor, the probit or
+// the Gaussian summaries) and bnn_laplace_glm_sample (logits = mean + chol . eps on the Philox stream (5, 1)).
 #include <math.h>
 
 #include "bnn_device.h"
@@ -112,27 +118,33 @@ struct LayerParams {
   int vec_x, vec_g, vec_w, vec_gx, vec_fw;
 };
 
+// One 64 x 64 tile of g_x [R, IN] = gz [R, OUT] . W [OUT, IN], masked by the input of data row r mod B: the item of
+// bnn_laplace_layer and of bnn_laplace_glm_layer (P: either kernel's parameters; the same code, so the same bits).
+// A(r, o) = gz, k (= o) contiguous; B(i, o) = W[o, i], i contiguous
+template <typename TX, typename P>
+__device__ __forceinline__ void gx_tile(const P& p, int item, uint4* lds, f32x4 acc[2][2]) {
+  const int tm = item / p.tiles_n, tn = item - tm * p.tiles_n;
+  const GzOpnd A{p.gy, p.y, p.B, p.OUT, p.R, p.vec_g};
+  const Opnd Bo{p.w, nullptr, 1.f, p.IN, p.IN, p.vec_w};
+  gemm_tile<TX, true, false>(A, Bo, tm * kT, tn * kT, p.OUT, lds, acc);
+  tile_epilogue(lds, acc, tm * kT, tn * kT, p.R, p.IN, [&](int row, int col0, int ncol, float o[4]) {
+    if (p.gx_mask) {
+      const long mat = (long)(row % p.B) * p.IN + col0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (c < ncol) o[c] = p.x[mat + c] > 0.f ? o[c] : 0.f;
+    }
+    store_group(p.gx + (long)row * p.IN + col0, o, ncol, p.vec_gx != 0);
+  });
+}
+
 template <typename TX>
 __global__ __launch_bounds__(kThreads) void laplace_layer_kernel(LayerParams p) {
   __shared__ uint4 lds[kLdsUint4];
   f32x4 acc[2][2];
   int item = blockIdx.x;
   if (item < p.tiles_x) {
-    // g_x [R, IN] = gz [R, OUT] . W [OUT, IN]: A(r, o) = gz, k (= o) contiguous; B(i, o) = W[o, i], i contiguous
-    const int tm = item / p.tiles_n, tn = item - tm * p.tiles_n;
-    const GzOpnd A{p.gy, p.y, p.B, p.OUT, p.R, p.vec_g};
-    const Opnd Bo{p.w, nullptr, 1.f, p.IN, p.IN, p.vec_w};
-    gemm_tile<TX, true, false>(A, Bo, tm * kT, tn * kT, p.OUT, lds, acc);
-    // masked by the input of data row r mod B
-    tile_epilogue(lds, acc, tm * kT, tn * kT, p.R, p.IN, [&](int row, int col0, int ncol, float o[4]) {
-      if (p.gx_mask) {
-        const long mat = (long)(row % p.B) * p.IN + col0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (c < ncol) o[c] = p.x[mat + c] > 0.f ? o[c] : 0.f;
-      }
-      store_group(p.gx + (long)row * p.IN + col0, o, ncol, p.vec_gx != 0);
-    });
+    gx_tile<TX>(p, item, lds, acc);
     return;
   }
   item -= p.tiles_x;
@@ -332,6 +344,274 @@ __global__ __launch_bounds__(kThreads) void laplace_posterior_kernel(const Tenso
   }
 }
 
+// ---------------------------------------------------------------------------------------------- F18: the GLM predictive
+// s^2 = fl32(1.0 / ((double)F + tau)): one fp64 add, one fp64 division, rounded once (include/bnn_hip.h F18)
+__device__ __forceinline__ float var_of(float f, double tau) { return (float)(1.0 / ((double)f + tau)); }
+
+// B(o, i) = s^2_w[o, i] from the stored curvature (k = i contiguous); zero beyond the edges, as every operand is
+struct VarOpnd {
+  Opnd o;
+  double tau;
+};
+
+template <bool KC>
+__device__ __forceinline__ void fetch_seg(const VarOpnd& q, int K, int r0, int k0, int s, float v[8]) {
+  static_assert(KC, "F_w is read along its contiguous (in) dimension");
+  fetch_seg<true>(q.o, K, r0, k0, s, v);
+  const int r = r0 + (s >> 2), k = k0 + 8 * (s & 3);
+  const int valid = r < q.o.rows ? min(8, max(0, K - k)) : 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = j < valid ? var_of(v[j], q.tau) : 0.f;
+}
+
+struct GlmLayerParams {
+  const float* x;
+  const float* gy;
+  const float* y;
+  const float* w;
+  const float* fw;
+  const float* fb;
+  float* gx;
+  float* cov_part;
+  float* v_out;
+  double tau;
+  const double* tau_dev;
+  int B, R, C, IN, OUT;
+  int gx_mask;
+  int tiles_x, tiles_n, tiles_o;
+  int vec_x, vec_g, vec_w, vec_gx, vec_fw, vec_v;
+};
+
+template <typename TX>
+__global__ __launch_bounds__(kThreads) void laplace_glm_layer_kernel(GlmLayerParams p) {
+  __shared__ uint4 lds[kLdsUint4];
+  f32x4 acc[2][2];
+  int item = blockIdx.x;
+  if (item < p.tiles_x) {
+    gx_tile<TX>(p, item, lds, acc);
+    return;
+  }
+  item -= p.tiles_x;
+  // V [B, OUT] = x^2 . (s^2_w)^T: A(n, i) = x[n, i]^2, B(o, i) = s^2_w[o, i], both k (= i) contiguous; K = IN
+  const int tm = item / p.tiles_o, to = item - tm * p.tiles_o;
+  const int m0 = tm * kT, n0 = to * kT;
+  const double tau = p.tau_dev ? *p.tau_dev : p.tau;
+  const SqOpnd A{Opnd{p.x, nullptr, 1.f, p.IN, p.B, p.vec_x}};
+  const VarOpnd Bo{Opnd{p.fw, nullptr, 1.f, p.IN, p.OUT, p.vec_fw}, tau};
+  gemm_tile<float, true, true>(A, Bo, m0, n0, p.IN, lds, acc);
+  // + s^2_b; the finished V goes back into the epilogue's LDS tile (a thread rewrites the group it read) for the pair sums
+  float* t = reinterpret_cast<float*>(lds);
+  tile_epilogue(lds, acc, m0, n0, p.B, p.OUT, [&](int row, int col0, int ncol, float o[4]) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c < ncol) {
+        o[c] += var_of(p.fb[col0 + c], tau);
+        t[(row - m0) * kOutLd + (col0 - n0) + c] = o[c];
+      }
+    if (p.v_out) store_group(p.v_out + (long)row * p.OUT + col0, o, ncol, p.vec_v != 0);
+  });
+  __syncthreads();
+  // cov_part[to, n, pair]: one fmaf chain over the tile's columns per (data row, pair c <= c'); consecutive threads share a row
+  const int pairs = p.C * (p.C + 1) / 2, ncol = min(kT, p.OUT - n0);
+#pragma unroll 1
+  for (int q = threadIdx.x; q < kT * pairs; q += kThreads) {
+    const int r = q / pairs, pr = q - r * pairs, n = m0 + r;
+    if (n >= p.B) break;
+    int cb = 0;
+    while ((cb + 1) * (cb + 2) / 2 <= pr) ++cb;
+    const int ca = pr - cb * (cb + 1) / 2;
+    const float* ga = p.gy + ((long)ca * p.B + n) * p.OUT + n0;
+    const float* gb = p.gy + ((long)cb * p.B + n) * p.OUT + n0;
+    const float* yr = p.y ? p.y + (long)n * p.OUT + n0 : nullptr;
+    const float* vr = t + r * kOutLd;
+    float s = 0.f;
+    if (p.vec_g) {
+      // 16-byte loads, four groups in flight (the loop is bound by their latency); the chain keeps its column order
+#pragma unroll 4
+      for (int o = 0; o < ncol; o += 4) {                       // (OUT % 4 == 0: every group is whole)
+        const float4 a4 = *reinterpret_cast<const float4*>(ga + o), b4 = *reinterpret_cast<const float4*>(gb + o);
+        const float4 y4 = yr ? *reinterpret_cast<const float4*>(yr + o) : make_float4(1.f, 1.f, 1.f, 1.f);
+        const float4 v4 = *reinterpret_cast<const float4*>(vr + o);
+        const float av[4] = {a4.x, a4.y, a4.z, a4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
+        const float yv[4] = {y4.x, y4.y, y4.z, y4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float nx = __builtin_fmaf(av[e] * bv[e], vv[e], s);
+          s = yv[e] > 0.f ? nx : s;
+        }
+      }
+    } else {
+#pragma unroll 4
+      for (int o = 0; o < ncol; ++o) {
+        const float g2 = ga[o] * gb[o];
+        const float nx = __builtin_fmaf(g2, vr[o], s);
+        s = (yr && !(yr[o] > 0.f)) ? s : nx;
+      }
+    }
+    p.cov_part[((long)to * p.B + n) * pairs + pr] = s;
+  }
+}
+
+constexpr int kGlmC = BNN_LAPLACE_GLM_MAX_CLASSES;
+constexpr int kGlmPairs = kGlmC * (kGlmC + 1) / 2;
+constexpr int kFinishRows = 8;                                  // data rows per block of bnn_laplace_glm_finish
+
+struct GlmFinishParams {
+  const float* part[BNN_LAPLACE_GLM_MAX_LAYERS];
+  int tiles[BNN_LAPLACE_GLM_MAX_LAYERS];
+  double z[BNN_PREDICTIVE_MAX_QUANTILES];
+  double sigma;
+  const float* mean;
+  float* cov;
+  float* var;
+  float* chol;
+  float* probs;
+  long long* preds;
+  float* entropy;
+  float* pvar;
+  float* quant;
+  uint32_t* counter;
+  int n_layers, B, C, mode, nq, n_samples;
+};
+
+// A block owns kFinishRows data rows.  First every thread sums the partials of its (row, pair) items -- one fixed chain per
+// item, layers in list order, tiles ascending, consecutive threads on consecutive pairs (contiguous loads) -- into the row's
+// fp64 lower triangle in LDS (pair = i (i + 1) / 2 + j, j <= i); then one thread per row does the row's small serial work there.
+__global__ __launch_bounds__(kThreads) void laplace_glm_finish_kernel(GlmFinishParams p) {
+  __shared__ double sh[kFinishRows][kGlmPairs + kGlmC];
+  if (p.counter && blockIdx.x == 0 && threadIdx.x == 0) *p.counter += (uint32_t)p.n_samples;   // no block of this launch reads it
+  const int C = p.C, pairs = C * (C + 1) / 2, row0 = blockIdx.x * kFinishRows;
+#pragma unroll 1
+  for (int q = threadIdx.x; q < kFinishRows * pairs; q += kThreads) {
+    const int r = q / pairs, pr = q - r * pairs;
+    if (row0 + r >= p.B) break;
+    double s = 0.0;
+#pragma unroll 1
+    for (int l = 0; l < p.n_layers; ++l) {
+      const float* src = p.part[l] + (long)(row0 + r) * pairs + pr;
+      const long step = (long)p.B * pairs;
+#pragma unroll 4
+      for (int tl = 0; tl < p.tiles[l]; ++tl) s += (double)src[tl * step];
+    }
+    sh[r][pr] = s;
+  }
+  __syncthreads();
+  const int n = row0 + threadIdx.x;
+  if (threadIdx.x >= kFinishRows || n >= p.B) return;
+  double* a = sh[threadIdx.x];
+  double* vr = a + kGlmPairs;
+  float* cov = p.cov + (long)n * C * C;
+  for (int i = 0; i < C; ++i) {
+    for (int j = 0; j <= i; ++j) {
+      const float v = (float)a[i * (i + 1) / 2 + j];
+      cov[i * C + j] = v;
+      cov[j * C + i] = v;
+    }
+    vr[i] = a[i * (i + 1) / 2 + i];
+    p.var[(long)n * C + i] = (float)vr[i];
+  }
+  // the lower Cholesky factor, in place, column by column; no pivoting (Cov >= min s^2_b I)
+  bool ok = true;
+  for (int j = 0; j < C; ++j) {
+    const int jj = j * (j + 1) / 2;
+    double d = a[jj + j];
+    for (int k = 0; k < j; ++k) d = fma(-a[jj + k], a[jj + k], d);
+    ok = ok && d > 0.0;
+    const double ljj = sqrt(d);
+    a[jj + j] = ljj;
+    for (int i = j + 1; i < C; ++i) {
+      const int ii = i * (i + 1) / 2;
+      double s = a[ii + j];
+      for (int k = 0; k < j; ++k) s = fma(-a[ii + k], a[jj + k], s);
+      a[ii + j] = s / ljj;
+    }
+  }
+  float* chol = p.chol + (long)n * C * C;
+  const float nanf_ = __builtin_nanf("");
+  for (int i = 0; i < C; ++i)
+    for (int j = 0; j < C; ++j) chol[i * C + j] = j > i ? 0.f : (ok ? (float)a[i * (i + 1) / 2 + j] : nanf_);
+  const float* mean = p.mean + (long)n * C;
+  if (p.mode == BNN_NLL_CLASSIFICATION) {
+    if (!p.probs && !p.preds && !p.entropy) return;
+    constexpr double kPi8 = 0.39269908169872415481;             // pi / 8
+    double* tt = a;                                             // (the factor has been written out)
+    double mx = -INFINITY;
+    for (int c = 0; c < C; ++c) {
+      tt[c] = (double)mean[c] / sqrt(1.0 + kPi8 * vr[c]);
+      mx = fmax(mx, tt[c]);
+    }
+    double se = 0.0;
+    for (int c = 0; c < C; ++c) {
+      tt[c] = exp(tt[c] - mx);
+      se += tt[c];
+    }
+    double h = 0.0;
+    float best = 0.f;
+    int bi = 0;
+    for (int c = 0; c < C; ++c) {
+      const double pc = tt[c] / se;
+      h -= pc == 0.0 ? 0.0 : pc * log(pc);
+      const float pf = (float)pc;
+      if (p.probs) p.probs[(long)n * C + c] = pf;
+      if (c == 0 || pf > best) {                                  // the lowest index on ties; a NaN row keeps 0
+        best = pf;
+        bi = c;
+      }
+    }
+    if (p.preds) p.preds[n] = bi;
+    if (p.entropy) p.entropy[n] = (float)h;
+  } else {
+    for (int c = 0; c < C; ++c) {
+      if (p.pvar) p.pvar[(long)n * C + c] = (float)(vr[c] + p.sigma * p.sigma);
+      const double sd = sqrt(vr[c]);
+      for (int q = 0; q < p.nq; ++q) p.quant[((long)q * p.B + n) * C + c] = (float)((double)mean[c] + p.z[q] * sd);
+    }
+  }
+}
+
+// The two N(0, 1) of a Box-Muller pair by the epsilon map's formula (include/bnn_hip.h), evaluated in fp64 from the fp32
+// uniforms and rounded once: this launch is tiny, and its draws then equal the CPU restatement to the last bit or so.
+__device__ __forceinline__ void box_muller_f64(uint32_t ra, uint32_t rb, float& n0, float& n1) {
+  const double u1 = (double)u01(ra), u2 = (double)u01(rb);
+  const double rad = sqrt(-2.0 * log(u1));
+  double sn, cs;
+  sincospi(2.0 * u2, &sn, &cs);
+  n0 = (float)(rad * cs);
+  n1 = (float)(rad * sn);
+}
+
+// one thread = one (sample, data row): its C normals, then one fmaf chain per output
+__global__ __launch_bounds__(kThreads) void laplace_glm_sample_kernel(const float* __restrict__ mean, const float* __restrict__ chol,
+                                                                      float* __restrict__ logits, int S, int B, int C, uint32_t k0,
+                                                                      uint32_t k1, uint32_t sample_base,
+                                                                      const uint32_t* __restrict__ counter) {
+  const long idx = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (idx >= (long)S * B) return;
+  const int s = (int)(idx / B), n = (int)(idx - (long)s * B);
+  const uint32_t g = sample_base + (counter ? *counter - (uint32_t)S : 0u) + (uint32_t)s;
+  const int gpr = (C + 3) >> 2;
+  float z[kGlmC];
+#pragma unroll
+  for (int q = 0; q < kGlmC / 4; ++q) {
+    z[4 * q] = z[4 * q + 1] = z[4 * q + 2] = z[4 * q + 3] = 0.f;
+    if (q < gpr) {
+      const uint4 r = philox4x32<>(make_uint4((uint32_t)(n * gpr + q), g, 5u, 1u), k0, k1);
+      box_muller_f64(r.x, r.y, z[4 * q], z[4 * q + 1]);
+      box_muller_f64(r.z, r.w, z[4 * q + 2], z[4 * q + 3]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < kGlmC; ++c) {
+    if (c < C) {
+      const float* l = chol + ((long)n * C + c) * C;
+      float f = mean[(long)n * C + c];
+#pragma unroll
+      for (int j = 0; j <= c; ++j) f = __builtin_fmaf(l[j], z[j], f);
+      logits[idx * C + c] = f;
+    }
+  }
+}
+
 bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
 
 }  // namespace
@@ -485,6 +765,109 @@ extern "C" int bnn_laplace_posterior(const bnn_laplace_posterior_args* a, void* 
   if (misaligned(a->precision_device, 8)) return BNN_ERR_ALIGN;
   hipLaunchKernelGGL(laplace_posterior_kernel, dim3((unsigned)chunks), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream_), k,
                      a->precision, a->precision_device);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? BNN_OK : (int)err;
+}
+
+extern "C" int bnn_laplace_glm_layer(const bnn_laplace_glm_layer_args* a, void* stream_) {
+  if (!a) return BNN_ERR_NULL;
+  if (a->struct_bytes != sizeof(bnn_laplace_glm_layer_args)) return BNN_ERR_ABI;
+  if (a->batch <= 0 || a->rows <= 0 || a->in_features <= 0 || a->out_features <= 0) return BNN_ERR_SHAPE;
+  if (a->rows % a->batch != 0 || a->rows / a->batch > BNN_LAPLACE_GLM_MAX_CLASSES) return BNN_ERR_SHAPE;
+  if ((long)a->rows * a->in_features > ((long)1 << 31) || (long)a->rows * a->out_features > ((long)1 << 31) ||
+      (long)a->in_features * a->out_features > ((long)1 << 31))
+    return BNN_ERR_SHAPE;
+  if (!a->precision_device && (!(a->precision > 0.0) || !(a->precision < INFINITY))) return BNN_ERR_SHAPE;
+  if (a->math != BNN_MATH_F32 && a->math != BNN_MATH_BF16 && a->math != BNN_MATH_BF16X3) return BNN_ERR_ENUM;
+  if (!a->x || !a->gy || !a->f_w || !a->f_b || !a->cov_part) return BNN_ERR_NULL;
+  if (a->g_x && !a->w) return BNN_ERR_NULL;
+  if (misaligned(a->x, 4) || misaligned(a->gy, 4) || misaligned(a->y, 4) || misaligned(a->w, 4) || misaligned(a->f_w, 4) ||
+      misaligned(a->f_b, 4) || misaligned(a->g_x, 4) || misaligned(a->cov_part, 4) || misaligned(a->v_out, 4) ||
+      misaligned(a->precision_device, 8))
+    return BNN_ERR_ALIGN;
+  GlmLayerParams p;
+  p.x = a->x; p.gy = a->gy; p.y = a->y; p.w = a->w; p.fw = a->f_w; p.fb = a->f_b;
+  p.gx = a->g_x; p.cov_part = a->cov_part; p.v_out = a->v_out;
+  p.tau = a->precision_device ? 1.0 : a->precision;
+  p.tau_dev = a->precision_device;
+  p.B = a->batch; p.R = a->rows; p.C = a->rows / a->batch; p.IN = a->in_features; p.OUT = a->out_features;
+  p.gx_mask = a->gx_mask ? 1 : 0;
+  const int tin = (p.IN + kT - 1) / kT, tout = (p.OUT + kT - 1) / kT, tr = (p.R + kT - 1) / kT, tb = (p.B + kT - 1) / kT;
+  p.tiles_n = tin;
+  p.tiles_o = tout;
+  p.tiles_x = a->g_x ? tr * tin : 0;
+  const long blocks = (long)p.tiles_x + (long)tb * tout;
+  if (blocks > INT32_MAX) return BNN_ERR_SHAPE;
+  p.vec_x = p.IN % 4 == 0 && !misaligned(a->x, 16);
+  p.vec_w = p.IN % 4 == 0 && !misaligned(a->w, 16);
+  p.vec_g = p.OUT % 4 == 0 && !misaligned(a->gy, 16) && !misaligned(a->y, 16);
+  p.vec_gx = p.IN % 4 == 0 && !misaligned(a->g_x, 16);
+  p.vec_fw = p.IN % 4 == 0 && !misaligned(a->f_w, 16);
+  p.vec_v = p.OUT % 4 == 0 && !misaligned(a->v_out, 16);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream_);
+  if (a->math == BNN_MATH_BF16)
+    hipLaunchKernelGGL(laplace_glm_layer_kernel<__bf16>, dim3((unsigned)blocks), dim3(kThreads), 0, st, p);
+  else
+    hipLaunchKernelGGL(laplace_glm_layer_kernel<float>, dim3((unsigned)blocks), dim3(kThreads), 0, st, p);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? BNN_OK : (int)err;
+}
+
+extern "C" int bnn_laplace_glm_finish(const bnn_laplace_glm_finish_args* a, void* stream_) {
+  if (!a) return BNN_ERR_NULL;
+  if (a->struct_bytes != sizeof(bnn_laplace_glm_finish_args)) return BNN_ERR_ABI;
+  if (a->batch <= 0 || a->classes <= 0 || a->classes > BNN_LAPLACE_GLM_MAX_CLASSES) return BNN_ERR_SHAPE;
+  if (a->n_layers <= 0 || a->n_layers > BNN_LAPLACE_GLM_MAX_LAYERS) return BNN_ERR_SHAPE;
+  for (int l = 0; l < a->n_layers; ++l)
+    if (a->tiles[l] <= 0) return BNN_ERR_SHAPE;
+  if (a->n_quantiles < 0 || a->n_quantiles > BNN_PREDICTIVE_MAX_QUANTILES || a->n_samples < 0) return BNN_ERR_SHAPE;
+  if ((long)a->batch * a->classes * a->classes > ((long)1 << 31)) return BNN_ERR_SHAPE;
+  if (a->mode == BNN_NLL_REGRESSION) {
+    if (!(a->sigma > 0.0) || !(a->sigma < INFINITY)) return BNN_ERR_SHAPE;
+    for (int q = 0; q < a->n_quantiles; ++q)
+      if (a->z[q] != a->z[q]) return BNN_ERR_SHAPE;
+  }
+  if (a->mode != BNN_NLL_CLASSIFICATION && a->mode != BNN_NLL_REGRESSION) return BNN_ERR_ENUM;
+  for (int l = 0; l < a->n_layers; ++l)
+    if (!a->cov_part[l]) return BNN_ERR_NULL;
+  if (!a->mean || !a->cov || !a->var || !a->chol) return BNN_ERR_NULL;
+  const int nq = a->mode == BNN_NLL_REGRESSION ? a->n_quantiles : 0;
+  if (nq > 0 && !a->quantiles) return BNN_ERR_NULL;
+  for (int l = 0; l < a->n_layers; ++l)
+    if (misaligned(a->cov_part[l], 4)) return BNN_ERR_ALIGN;
+  if (misaligned(a->mean, 4) || misaligned(a->cov, 4) || misaligned(a->var, 4) || misaligned(a->chol, 4) || misaligned(a->probs, 4) ||
+      misaligned(a->preds, 8) || misaligned(a->entropy, 4) || misaligned(a->predictive_variance, 4) || misaligned(a->quantiles, 4) ||
+      misaligned(a->sample_counter, 4))
+    return BNN_ERR_ALIGN;
+  GlmFinishParams p;
+  for (int l = 0; l < BNN_LAPLACE_GLM_MAX_LAYERS; ++l) {
+    p.part[l] = l < a->n_layers ? a->cov_part[l] : nullptr;
+    p.tiles[l] = l < a->n_layers ? a->tiles[l] : 0;
+  }
+  for (int q = 0; q < BNN_PREDICTIVE_MAX_QUANTILES; ++q) p.z[q] = q < nq ? a->z[q] : 0.0;
+  p.sigma = a->sigma;
+  p.mean = a->mean; p.cov = a->cov; p.var = a->var; p.chol = a->chol;
+  p.probs = a->probs; p.preds = reinterpret_cast<long long*>(a->preds); p.entropy = a->entropy;
+  p.pvar = a->predictive_variance; p.quant = a->quantiles; p.counter = a->sample_counter;
+  p.n_layers = a->n_layers; p.B = a->batch; p.C = a->classes; p.mode = a->mode; p.nq = nq; p.n_samples = a->n_samples;
+  const int blocks = (a->batch + kFinishRows - 1) / kFinishRows;
+  hipLaunchKernelGGL(laplace_glm_finish_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream_), p);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? BNN_OK : (int)err;
+}
+
+extern "C" int bnn_laplace_glm_sample(const bnn_laplace_glm_sample_args* a, void* stream_) {
+  if (!a) return BNN_ERR_NULL;
+  if (a->struct_bytes != sizeof(bnn_laplace_glm_sample_args)) return BNN_ERR_ABI;
+  if (a->n_samples <= 0 || a->batch <= 0 || a->classes <= 0 || a->classes > BNN_LAPLACE_GLM_MAX_CLASSES) return BNN_ERR_SHAPE;
+  if ((long)a->n_samples * a->batch * a->classes > ((long)1 << 31)) return BNN_ERR_SHAPE;
+  if (!a->mean || !a->chol || !a->logits) return BNN_ERR_NULL;
+  if (misaligned(a->mean, 4) || misaligned(a->chol, 4) || misaligned(a->logits, 4) || misaligned(a->sample_counter, 4)) return BNN_ERR_ALIGN;
+  const long threads = (long)a->n_samples * a->batch;
+  const long blocks = (threads + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(laplace_glm_sample_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream_), a->mean,
+                     a->chol, a->logits, a->n_samples, a->batch, a->classes, (uint32_t)(a->seed & 0xFFFFFFFFu), (uint32_t)(a->seed >> 32),
+                     a->sample_base, a->sample_counter);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? BNN_OK : (int)err;
 }

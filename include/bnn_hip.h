@@ -2298,6 +2298,117 @@ int bnn_laplace_evidence(const bnn_laplace_evidence_args* args, void* stream);
 int bnn_laplace_posterior(const bnn_laplace_posterior_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F18  The linearised (GLM) predictive of the F17 posterior (Immer et al. 2021): with theta ~ N(theta*, diag(s^2)),
+ * s^2_p = 1 / (F_p + tau), the output of the network linearised at theta*, f(x, theta*) + J(x)(theta - theta*), is Gaussian
+ * with mean f(x_n, theta*) and covariance J diag(s^2) J^T.  For a chain of Linear -> [ReLU] groups that is, layer by layer,
+ *     Cov[n, c, c'] = sum_l sum_o gz_l[c, n, o] gz_l[c', n, o] V_l[n, o],   V_l[n, o] = sum_i a_l[n, i]^2 s^2_w,l[o, i] + s^2_b,l[o]
+ * a_l the layer's input, gz_l[c, n, :] = d f_c(x_n) / d z_l the deltas of virtual row c * batch + n: the recursion of
+ * bnn_laplace_layer's g_x product started from bnn_laplace_seed in regression mode, BNN_LAPLACE_GGN, sigma = 1, target NULL
+ * (gy[c * batch + n, k] = delta_kc).  Cov >= min_o s^2_b,last[o] I (the last layer's bias term), so it is positive definite
+ * for every finite (F, tau).  No float atomics anywhere: the same inputs give the same bits.
+ *
+ * The variance rule.  s^2 = fl32(1.0 / ((double)F + tau)): the stored fp32 curvature widened, ONE fp64 add of tau (a host
+ * double, or *precision_device = best + 1 of bnn_laplace_evidence), ONE fp64 IEEE division, rounded once to fp32 (RNE).  It
+ * is formed while the operand is staged (weights) or in the epilogue (biases); no variance tensor exists.
+ *
+ * bnn_laplace_glm_layer — one Linear -> [ReLU] group in ONE launch; two item kinds share the grid:
+ *   g_x  (optional; blocks [0, tiles_x)): bnn_laplace_layer's g_x = gz . W tiles, the same device code, the same bits.
+ *   V    [batch, out] = x^2 . (s^2_w)^T, K = in, 64 x 64 tiles on v_mfma_f32_16x16x4_f32 (always exact fp32), x^2 and s^2_w
+ *        formed while staging; then V = fl32(acc + s^2_b[o]).  v_out (optional, [batch, out]): V itself, for tests.
+ *   cov_part[tile_o, n, pair] for the tile's data rows n and the pairs c <= c' (pair = c' (c' + 1) / 2 + c, C (C + 1) / 2 of
+ *        them): s = 0; for o in the tile's columns, ascending: s = fmaf(fl32(gy[c B + n, o] * gy[c' B + n, o]), V[n, o], s),
+ *        the term of a column with y[n, o] <= 0 (y given) LEFT OUT, not multiplied by zero -- so a non-finite V[n, o]
+ *        reaches exactly the rows whose unit o is active.  One fixed chain per partial; [ceil(out / 64), batch, pairs] fp32.
+ *   rows = batch * C, 1 <= C <= BNN_LAPLACE_GLM_MAX_CLASSES.
+ *   Errors, in this order: NULL args; ABI; batch, rows, in, out < 1, rows % batch != 0, C > BNN_LAPLACE_GLM_MAX_CLASSES, a
+ *   matrix over 2^31 elements, a host precision not in (0, inf) without precision_device: BNN_ERR_SHAPE; math: BNN_ERR_ENUM;
+ *   x, gy, f_w, f_b, cov_part, (g_x) w NULL: BNN_ERR_NULL; BNN_ERR_ALIGN (4 bytes; precision_device 8).
+ *
+ * bnn_laplace_glm_finish — a block per 8 data rows: a thread per (row, pair) for the sums, then a thread per row.  In fp64:
+ *   a[pair] = sum over the layers in list order, over each layer's tiles ascending, of cov_part (one fixed chain).  cov [batch, C, C] = fl32(a), symmetric; var [batch, C] its diagonal;
+ *   chol [batch, C, C] the lower Cholesky factor of a, computed in fp64 (no pivoting: see above), rounded once to fp32, zeros
+ *   above the diagonal.  A pivot that is not > 0 (non-finite inputs only) makes the row's whole lower triangle NaN.
+ *   BNN_NLL_CLASSIFICATION: probs = softmax(mean / sqrt(1 + pi / 8 var)) (MacKay's probit approximation; fp64 from a, rounded
+ *   once), preds = argmax of the fp32 probs (int64, the lowest index on ties; 0 for a NaN row), entropy = -sum p log p (fp64
+ *   of the unrounded p).  BNN_NLL_REGRESSION: predictive_variance = var + sigma^2, quantiles [n_quantiles, batch, C] = mean +
+ *   z[q] sqrt(var) with z[q] = Phi^-1(level q) from the host (fp64; -inf / +inf at levels 0 / 1).  sample_counter (optional):
+ *   thread 0 of block 0 adds n_samples; no block of this launch reads it (bnn_dense_fwd's rule).
+ *   Errors, in this order: NULL args; ABI; batch < 1, classes outside [1, BNN_LAPLACE_GLM_MAX_CLASSES], n_layers outside
+ *   [1, BNN_LAPLACE_GLM_MAX_LAYERS], a tiles < 1, n_quantiles outside [0, BNN_PREDICTIVE_MAX_QUANTILES], n_samples < 0, more
+ *   than 2^31 covariance entries, (regression) sigma not in (0, inf) or a NaN z: BNN_ERR_SHAPE; mode: BNN_ERR_ENUM; a
+ *   cov_part, mean, cov, var, chol, (n_quantiles > 0) quantiles NULL: BNN_ERR_NULL; BNN_ERR_ALIGN (4 bytes; preds 8).
+ *
+ * bnn_laplace_glm_sample — logits [n_samples, batch, C]: f[s, n, c] = mean[n, c] + sum_{j <= c} chol[n, c, j] z_j as an fmaf
+ *   chain in j order starting from the mean.  z = eps[s, n, :] from the epsilon generator above on its own stream: counter
+ *   words 2 and 3 are (5, 1) -- every eps counter's word 3 is 0 and the word-3 = 1 streams use words 2 = 0..4, so no existing
+ *   stream moved and BNN_EPS_MAP_VERSION stays 2.  Element (n, j) of global sample g: counter = (n * ceil(C / 4) + (j >> 2),
+ *   g, 5, 1), slot j & 3; g = sample_base + (*sample_counter - n_samples, when a counter is given) + s (uint32 arithmetic).
+ *   A pure function of (seed, g, n, j): the grid and the batch size do not enter.
+ *   Errors, in this order: NULL args; ABI; n_samples, batch < 1, classes outside [1, BNN_LAPLACE_GLM_MAX_CLASSES], more than
+ *   2^31 logits: BNN_ERR_SHAPE; mean, chol, logits NULL: BNN_ERR_NULL; BNN_ERR_ALIGN (4 bytes).
+ * ---------------------------------------------------------------------------------- */
+#define BNN_LAPLACE_GLM_MAX_CLASSES 16
+#define BNN_LAPLACE_GLM_MAX_LAYERS (BNN_LAPLACE_MAX_TENSORS / 2)
+
+typedef struct bnn_laplace_glm_layer_args {
+  uint32_t struct_bytes;
+  int32_t batch, rows, in_features, out_features;
+  int32_t math;             /* bnn_math of the g_x product */
+  int32_t gx_mask;
+  int32_t reserved;
+  double precision;               /* tau, host value; ignored with precision_device */
+  const double* precision_device; /* optional */
+  const float* x;           /* [batch, in] */
+  const float* gy;          /* [rows, out] */
+  const float* y;           /* optional [batch, out] */
+  const float* w;           /* [out, in]; read for g_x only */
+  const float* f_w;         /* [out, in], the curvature (read) */
+  const float* f_b;         /* [out] */
+  float* g_x;               /* optional [rows, in] */
+  float* cov_part;          /* [ceil(out / 64), batch, C (C + 1) / 2] */
+  float* v_out;             /* optional [batch, out] */
+} bnn_laplace_glm_layer_args;
+
+typedef struct bnn_laplace_glm_finish_args {
+  uint32_t struct_bytes;
+  int32_t batch, classes, n_layers;
+  int32_t mode;             /* bnn_nll_mode */
+  int32_t n_quantiles;
+  int32_t n_samples;        /* added to *sample_counter */
+  int32_t reserved;
+  double sigma;             /* the Gaussian likelihood's scale (regression) */
+  double z[BNN_PREDICTIVE_MAX_QUANTILES];                  /* Phi^-1 of the quantile levels */
+  const float* cov_part[BNN_LAPLACE_GLM_MAX_LAYERS];
+  int32_t tiles[BNN_LAPLACE_GLM_MAX_LAYERS];               /* ceil(out / 64) of each layer */
+  const float* mean;        /* [batch, classes]: the network's output */
+  float* cov;               /* [batch, classes, classes] */
+  float* var;               /* [batch, classes] */
+  float* chol;              /* [batch, classes, classes] */
+  float* probs;             /* optional [batch, classes]   (classification) */
+  int64_t* preds;           /* optional [batch] */
+  float* entropy;           /* optional [batch] */
+  float* predictive_variance; /* optional [batch, classes] (regression) */
+  float* quantiles;         /* [n_quantiles, batch, classes] */
+  uint32_t* sample_counter; /* optional device word */
+} bnn_laplace_glm_finish_args;
+
+typedef struct bnn_laplace_glm_sample_args {
+  uint32_t struct_bytes;
+  int32_t n_samples, batch, classes;
+  uint64_t seed;
+  uint32_t sample_base;
+  int32_t reserved;
+  const float* mean;        /* [batch, classes] */
+  const float* chol;        /* [batch, classes, classes] */
+  float* logits;            /* [n_samples, batch, classes] */
+  const uint32_t* sample_counter; /* optional device word */
+} bnn_laplace_glm_sample_args;
+
+int bnn_laplace_glm_layer(const bnn_laplace_glm_layer_args* args, void* stream);
+int bnn_laplace_glm_finish(const bnn_laplace_glm_finish_args* args, void* stream);
+int bnn_laplace_glm_sample(const bnn_laplace_glm_sample_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
