@@ -68,8 +68,6 @@ struct BwdK {
 #define BWD_STAMP_RT(i)
 #endif
 
-// d log p(w) / dw (bnn_prior.h: shared with the sparse backward)
-__device__ __forceinline__ float dlogp(const BwdK& p, float w) { return prior_dlogp(p, w); }
 
 // VEC: K % 4 == 0 and 16-byte aligned rows.  No load sits under per-lane control flow (a load in a
 // divergent branch gets its own basic block and the waits between blocks serialise the batch):
@@ -102,7 +100,7 @@ __global__ __launch_bounds__(256, 3) void bbb_bwd_weights_kernel(const BwdK p) {
   const int k0 = kblk * 64;
   const int n = nblk * 32 + sub * 16 + r;                  // this lane's feature (D column / B-operand column)
   const bool n_ok = n < N;                                 // a sub-tile past N runs on clamped data and stores nothing
-  const int gpr = (K + 3) >> 2;
+  const int gpr = (int)eps_groups_per_row(K);
 
   // Tile i (i = 0..3) of the 64-wide k strip holds the k's congruent to i mod 4: A row r of tile i is
   // k = k0 + 4 r + i, so ONE 16-byte load x[b][k0 + 4r .. +3] feeds all four tiles, and D register
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(256, 3) void bbb_bwd_weights_kernel(const BwdK p) {
       if (n_ok && kb < K) {
         float e[4] = {0.f, 0.f, 0.f, 0.f};
         if (p.eps_mode == BNN_EPS_PHILOX) {
-          philox_normal4((uint32_t)n * (uint32_t)gpr + (uint32_t)(kb >> 2), gs, p.layer_id * 4u, p.k0, p.k1, e);
+          philox_normal4(eps_group((uint32_t)n, kb, (uint32_t)gpr), gs, eps_tensor_id(p.layer_id, kEpsWeight), p.k0, p.k1, e);
         } else if (MEM && p.eps_mode == BNN_EPS_MEMORY) {
 #pragma unroll
           for (int i = 0; i < 4; ++i)
@@ -224,7 +222,7 @@ __global__ __launch_bounds__(256, 3) void bbb_bwd_weights_kernel(const BwdK p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float w = __builtin_fmaf(sg[jr][i], e[i], mu[jr][i]);
-          const float t = tot[i] + glp * dlogp(p, w);
+          const float t = tot[i] + glp * prior_dlogp(p, w);
           G[i][jr] += t;
           H[i][jr] = __builtin_fmaf(t, e[i], H[i][jr]);
         }
@@ -233,14 +231,12 @@ __global__ __launch_bounds__(256, 3) void bbb_bwd_weights_kernel(const BwdK p) {
     if (do_bias) {
       float e = 0.f;
       if (p.eps_mode == BNN_EPS_PHILOX) {
-        float e4[4];
-        philox_normal4((uint32_t)(n >> 2), gs, p.layer_id * 4u + 1u, p.k0, p.k1, e4);
-        e = (n & 3) == 0 ? e4[0] : (n & 3) == 1 ? e4[1] : (n & 3) == 2 ? e4[2] : e4[3];
+        e = eps_bias(n, gs, p.layer_id, p.k0, p.k1);
       } else if (MEM && p.eps_mode == BNN_EPS_MEMORY) {
         e = p.eps_b[(size_t)s * N + n];
       }
       const float bw = __builtin_fmaf(bsg, e, bmu);
-      const float t = colsum + xcs[par][sub][lane] + glp * dlogp(p, bw);
+      const float t = colsum + xcs[par][sub][lane] + glp * prior_dlogp(p, bw);
       Gb += t;
       Hb = __builtin_fmaf(t, e, Hb);
     }
@@ -325,7 +321,7 @@ __device__ __forceinline__ void out_bwd_weight_role(const BwdK& p, float* gzs, f
   const bool e_ok = tid < 64 && en < N && ekb < K;          // K % 4 == 0: a group is whole or absent
   const bool b_ok = blockIdx.x == 0 && tid >= 64 && tid < 64 + N;   // bias: thread 64 + n
   const int bn = min(max(tid - 64, 0), N - 1);
-  const int gpr = (K + 3) >> 2;
+  const int gpr = (int)eps_groups_per_row(K);
   float mu[4] = {0.f, 0.f, 0.f, 0.f}, sg[4] = {1.f, 1.f, 1.f, 1.f}, rh[4] = {0.f, 0.f, 0.f, 0.f};
   if (e_ok) {
     const float4 m4 = *reinterpret_cast<const float4*>(p.w_mu + (size_t)en * K + ekb);
@@ -412,11 +408,11 @@ __device__ __forceinline__ void out_bwd_weight_role(const BwdK& p, float* gzs, f
           for (int i = 0; i < 4; ++i) tot[i] += rd[(g * 16 + en) * 16 + eg * 4 + i];
         }
         float e[4];
-        philox_normal4((uint32_t)en * (uint32_t)gpr + (uint32_t)(ekb >> 2), gs, p.layer_id * 4u, p.k0, p.k1, e);
+        philox_normal4(eps_group((uint32_t)en, ekb, (uint32_t)gpr), gs, eps_tensor_id(p.layer_id, kEpsWeight), p.k0, p.k1, e);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const float w = __builtin_fmaf(sg[i], e[i], mu[i]);
-          const float t = tot[i] + glp * dlogp(p, w);
+          const float t = tot[i] + glp * prior_dlogp(p, w);
           G[i] += t;
           H[i] = __builtin_fmaf(t, e[i], H[i]);
         }
@@ -424,11 +420,9 @@ __device__ __forceinline__ void out_bwd_weight_role(const BwdK& p, float* gzs, f
       if (b_ok) {
         float colsum = 0.f;
         for (int b = 0; b < B; ++b) colsum += gzs[(sp * 128 + b) * 16 + bn];
-        float e4[4];
-        philox_normal4((uint32_t)(bn >> 2), gs, p.layer_id * 4u + 1u, p.k0, p.k1, e4);
-        const float e = (bn & 3) == 0 ? e4[0] : (bn & 3) == 1 ? e4[1] : (bn & 3) == 2 ? e4[2] : e4[3];
+        const float e = eps_bias(bn, gs, p.layer_id, p.k0, p.k1);
         const float bw = __builtin_fmaf(bsg, e, bmu);
-        const float t = colsum + glp * dlogp(p, bw);
+        const float t = colsum + glp * prior_dlogp(p, bw);
         Gb += t;
         Hb = __builtin_fmaf(t, e, Hb);
       }
@@ -546,7 +540,7 @@ extern "C" int bnn_bbb_linear_bwd(const bnn_bbb_bwd_args* a, void* stream_) {
   if (!a->x || !a->gy || !a->w_mu || !a->w_rho || !a->b_mu || !a->b_rho || !a->g_w_mu || !a->g_w_rho || !a->g_b_mu ||
       !a->g_b_rho)
     return BNN_ERR_NULL;
-  if ((unsigned)a->eps_mode > 2u || (unsigned)a->prior.kind > 1u || (unsigned)a->math > 1u) return BNN_ERR_ENUM;
+  if ((unsigned)a->eps_mode > 2u || prior_check(a->prior) == BNN_ERR_ENUM || (unsigned)a->math > 1u) return BNN_ERR_ENUM;
   if (a->eps_mode == BNN_EPS_MEMORY && (!a->eps_w || !a->eps_b)) return BNN_ERR_NULL;
   if (a->relu && !a->y) return BNN_ERR_NULL;
   if (!a->workspace || a->workspace_bytes < bnn_bbb_linear_bwd_workspace_bytes(a->n_samples, a->batch, a->out_features))
@@ -588,7 +582,8 @@ extern "C" int bnn_bbb_linear_bwd(const bnn_bbb_bwd_args* a, void* stream_) {
     k.dbg = v ? reinterpret_cast<unsigned long long*>(strtoull(v, nullptr, 0)) : nullptr;
   }
 #endif
-  if (prior_dlogp_fill(a->prior, k) != BNN_OK) return BNN_ERR_SHAPE;      // bnn_prior.h: shared with the sparse backward
+  if (const int rc = prior_check(a->prior)) return rc;
+  prior_dlogp_fill(a->prior, k);
   if (a->g_x_bf16 && (!a->g_x || (reinterpret_cast<uintptr_t>(a->g_x_bf16) & 15))) return BNN_ERR_ALIGN;
   if (a->w_sampled && a->g_x && a->out_features <= 16 && a->batch <= 256 && (a->in_features & 7) == 0 &&
       a->eps_mode == BNN_EPS_PHILOX && a->math == BNN_MATH_BF16 &&

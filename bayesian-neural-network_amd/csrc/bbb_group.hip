@@ -20,14 +20,9 @@
 // LDS, as F6: x [batch, in], h1, h2 [batch, hidden] (h2 becomes dL/dh2 in place), dL/dh1 [batch, hidden]: 4 x 32 KiB at
 // the limits, plus the per-row vectors.
 #include "mlp_group_common.h"
+#include "bnn_prior.h"
 
 namespace bnn {
-
-struct BgPrior {
-  int kind;
-  float inv_var_p, inv2var_p, c_p;                          // Gaussian: 1 / sigma_p^2, 1 / (2 sigma_p^2), c0 - log sigma_p
-  float pi, c1, c2, a1, a2, inv2var1, inv2var2, invvar1, invvar2;   // mixture: c_i = c0 - log sigma_i, a_i = pi_i / sigma_i
-};
 
 struct BgHyper {
   double beta1, beta2;
@@ -38,7 +33,7 @@ struct BgK {
   const bnn_bbb_group_agent* agents;
   int B, I, H, S, A, max_batches;
   BgHyper hp;
-  BgPrior prior;
+  PriorAll prior;
   float beta[BNN_MLP_GROUP_MAX_BATCHES];
 };
 
@@ -59,30 +54,13 @@ struct BgLayout {
   __host__ __device__ size_t floats() const { return (size_t)4 * P + (size_t)((n[2] + 3) & ~3); }
 };
 
-__device__ __forceinline__ float bg_log_prior(const BgPrior& p, float w) {
-  const float w2 = w * w;
-  if (p.kind == BNN_PRIOR_GAUSS) return __builtin_fmaf(-w2, p.inv2var_p, p.c_p);
-  const float p1 = fast_exp(__builtin_fmaf(-w2, p.inv2var1, p.c1));
-  const float p2 = fast_exp(__builtin_fmaf(-w2, p.inv2var2, p.c2));
-  return fast_log(__builtin_fmaf(p.pi, p1, (1.0f - p.pi) * p2));
-}
-
-// d log prior(w) / dw
-__device__ __forceinline__ float bg_dlog_prior(const BgPrior& p, float w) {
-  if (p.kind == BNN_PRIOR_GAUSS) return -w * p.inv_var_p;
-  const float w2 = w * w;
-  const float n1 = p.a1 * fast_exp(-w2 * p.inv2var1);
-  const float n2 = p.a2 * fast_exp(-w2 * p.inv2var2);
-  return -w * (n1 * p.invvar1 + n2 * p.invvar2) * __builtin_amdgcn_rcpf(n1 + n2);
-}
-
 // One draw of one tensor of logical shape [N, K] (a bias: [1, out]): thread per Philox group (4 consecutive k of a row).
 // wt[k * N + n] = w (the transposed copy), wn[n * K + k] = w when wn; TRAIN: eps kept, and the prior's share of t_s,
 // pt = scale * d log_p / dw, starts (first) or joins the accumulators G, Hh.  stats: log q and log p of the draw are added
 // to the thread's lq, lp in the thread's fixed order.
 template <bool TRAIN>
 __device__ __forceinline__ void bg_sample_tensor(const float* mu, const float* rho, int N, int K, uint32_t tensor_id,
-                                                 uint32_t gsample, uint32_t k0, uint32_t k1, bool zero_eps, const BgPrior& pr,
+                                                 uint32_t gsample, uint32_t k0, uint32_t k1, bool zero_eps, const PriorAll& pr,
                                                  float scale, bool first, bool stats, float* wt, float* wn, float* epso,
                                                  float* G, float* Hh, float& lq, float& lp) {
   const int gpr = (K + 3) >> 2;
@@ -103,7 +81,7 @@ __device__ __forceinline__ void bg_sample_tensor(const float* mu, const float* r
         if (wn) wn[i] = w;
         if (TRAIN) {
           epso[i] = e[slot];
-          const float pt = scale * bg_dlog_prior(pr, w);
+          const float pt = scale * prior_dlogp(pr, w);
           if (first) {
             G[i] = pt;
             Hh[i] = pt * e[slot];
@@ -114,7 +92,7 @@ __device__ __forceinline__ void bg_sample_tensor(const float* mu, const float* r
           if (stats) {
             // log N(w; mu, sigma) with w - mu = sigma eps: c0 - log sigma - eps^2 / 2
             lq += __builtin_fmaf(-0.5f * e[slot], e[slot], kC0 - fast_log(sg));
-            lp += bg_log_prior(pr, w);
+            lp += prior_logp(pr, w);
           }
         }
       }
@@ -125,7 +103,7 @@ __device__ __forceinline__ void bg_sample_tensor(const float* mu, const float* r
 // One draw of the whole network into the workspace.
 template <bool TRAIN>
 __device__ __forceinline__ void bg_sample(const bnn_bbb_group_agent& ag, const BgLayout& L, int I, int H, uint32_t gsample,
-                                          bool zero_eps, const BgPrior& pr, float scale, bool first, bool stats, float& lq,
+                                          bool zero_eps, const PriorAll& pr, float scale, bool first, bool stats, float& lq,
                                           float& lp) {
   const uint32_t k0 = (uint32_t)ag.eps_seed, k1 = (uint32_t)(ag.eps_seed >> 32);
   float* wt = ag.workspace;
@@ -361,11 +339,8 @@ static int check_bbb_group(const bnn_bbb_group_args* a, bool train) {
     if (!(a->beta1 >= 0.0 && a->beta1 < 1.0) || !(a->beta2 >= 0.0 && a->beta2 < 1.0) || !(a->eps >= 0.0) ||
         !(a->weight_decay >= 0.0))
       return BNN_ERR_SHAPE;
-    if ((unsigned)a->prior.kind > 1u) return BNN_ERR_ENUM;
-    if (a->prior.kind == BNN_PRIOR_MIXTURE ? (!(a->prior.sigma1 > 0.f) || !(a->prior.sigma2 > 0.f) || !(a->prior.pi >= 0.f) ||
-                                              !(a->prior.pi <= 1.f))
-                                           : !(a->prior.sigma_p > 0.f))
-      return BNN_ERR_SHAPE;
+    if (const int rc = prior_check(a->prior)) return rc;
+    if (a->prior.kind == BNN_PRIOR_MIXTURE && (!(a->prior.pi >= 0.f) || !(a->prior.pi <= 1.f))) return BNN_ERR_SHAPE;
   } else if (a->n_rows < 1 || a->n_rows > BNN_MLP_GROUP_MAX_BATCH) {
     return BNN_ERR_SHAPE;
   }
@@ -410,27 +385,7 @@ static void bg_fill(BgK& k, const bnn_bbb_group_args* a) {
   k.hp.omb2 = (float)(1.0 - a->beta2);
   k.hp.eps = (float)a->eps;
   k.hp.wd = (float)a->weight_decay;
-  const double c0 = -0.91893853320467274178;
-  BgPrior& o = k.prior;
-  o = BgPrior{};
-  o.kind = a->prior.kind;
-  if (a->prior.kind == BNN_PRIOR_MIXTURE) {
-    const double s1 = a->prior.sigma1, s2 = a->prior.sigma2, pi = a->prior.pi;
-    o.pi = a->prior.pi;
-    o.c1 = (float)(c0 - log(s1));
-    o.c2 = (float)(c0 - log(s2));
-    o.a1 = (float)(pi / s1);
-    o.a2 = (float)((1.0 - pi) / s2);
-    o.inv2var1 = (float)(1.0 / (2.0 * s1 * s1));
-    o.inv2var2 = (float)(1.0 / (2.0 * s2 * s2));
-    o.invvar1 = (float)(1.0 / (s1 * s1));
-    o.invvar2 = (float)(1.0 / (s2 * s2));
-  } else if (a->prior.sigma_p > 0.f) {
-    const double sp = a->prior.sigma_p;
-    o.inv_var_p = (float)(1.0 / (sp * sp));
-    o.inv2var_p = (float)(1.0 / (2.0 * sp * sp));
-    o.c_p = (float)(c0 - log(sp));
-  }
+  k.prior = prior_all_make(a->prior);          // (the forward validates no prior: an unusable one gives zeros it never reads)
   for (int j = 0; j < BNN_MLP_GROUP_MAX_BATCHES; ++j) k.beta[j] = a->beta[j];
 }
 

@@ -73,7 +73,7 @@ struct BbbK {
   const uint32_t* sample_counter;
   int xg;                                 // samples sharing one x row block (x index = s / xg); x_sstride = 0: one x for all
   uint32_t sgrp, sgrp_stride;             // sample groups (bnn_bbb_fwd_args.sample_group): 0 = none
-  float inv2var1, c1, inv2var2, c2, pi;   // mixture: log N(w;0,s_i) = c_i - w^2 * inv2var_i
+  PriorMix mix;                           // mixture prior: the density constants (bnn_prior.h)
   const void* x_lo;                       // BNN_MATH_BF16X3, bf16 x: the low plane of x (strided like x)
   void* y_lo;                             // BNN_MATH_BF16X3, bf16 y: the low plane of y
   const char* w_pieces;                   // K1b2, optional: (mu, sigma) in piece order (bnn_bbb_fwd_args.w_pieces)
@@ -162,17 +162,7 @@ __device__ __forceinline__ void load_xfrag(const char* __restrict__ xs, long off
 // global MC sample index (Philox subsequence) of local sample s
 __device__ __forceinline__ uint32_t global_sample(const BbbK& p, int s) {
   const uint32_t base = p.sample_offset + (p.sample_counter ? *p.sample_counter : 0u);
-  if (p.sgrp == 0u) return base + (uint32_t)s;
-  const uint32_t g = (uint32_t)s / p.sgrp;
-  return base + g * p.sgrp_stride + ((uint32_t)s - g * p.sgrp);
-}
-
-// the mixture density itself (argument of the log), for add_log
-__device__ __forceinline__ float mix_p(const BbbK& p, float w) {
-  const float w2 = w * w;
-  const float p1 = fast_exp(__builtin_fmaf(-w2, p.inv2var1, p.c1));
-  const float p2 = fast_exp(__builtin_fmaf(-w2, p.inv2var2, p.c2));
-  return __builtin_fmaf(p.pi, p1, (1.0f - p.pi) * p2);
+  return eps_global_sample(base, (uint32_t)s, p.sgrp, p.sgrp_stride);
 }
 
 // Sampled bias of feature n for global sample gs (+ its stats); returns b.
@@ -180,9 +170,7 @@ __device__ __forceinline__ float mix_p(const BbbK& p, float w) {
 __device__ __forceinline__ float bias_eps(const BbbK& p, int n, int s, uint32_t gs, bool dump) {
   float e = 0.f;
   if (p.eps_mode == BNN_EPS_PHILOX) {
-    float e4[4];
-    philox_normal4((uint32_t)(n >> 2), gs, p.layer_id * 4u + 1u, p.k0, p.k1, e4);
-    e = (n & 3) == 0 ? e4[0] : (n & 3) == 1 ? e4[1] : (n & 3) == 2 ? e4[2] : e4[3];
+    e = eps_bias(n, gs, p.layer_id, p.k0, p.k1);
   } else if (p.eps_mode == BNN_EPS_MEMORY) {
     e = p.eps_b[(size_t)s * p.N + n];
   }
@@ -196,7 +184,7 @@ __device__ __forceinline__ float sample_bias(const BbbK& p, float bmu, float brh
   const float b = __builtin_fmaf(sig, e, bmu);
   if (do_stats) {
     s_e2 = __builtin_fmaf(e, e, s_e2);
-    s_a = (p.prior_kind == BNN_PRIOR_GAUSS) ? __builtin_fmaf(b, b, s_a) : add_log(s_a, mix_p(p, b));
+    s_a = (p.prior_kind == BNN_PRIOR_GAUSS) ? __builtin_fmaf(b, b, s_a) : add_log(s_a, prior_mix_p(p.mix, b));
     if (do_ls) s_ls = add_log(s_ls, sig);
   }
   return b;
@@ -345,8 +333,8 @@ __device__ __forceinline__ bool bbb_fwd_body(const BbbK& p, const FinPack* fp) {
   const bool do_stats = p.want_stats && mb == 0;
   const bool do_ls = do_stats && (s == 0 || FINAL);
   const bool do_dump = mb == 0;
-  const int gpr = (K + 3) >> 2;
-  const uint32_t wid = p.layer_id * 4u;
+  const int gpr = (int)eps_groups_per_row(K);
+  const uint32_t wid = eps_tensor_id(p.layer_id, kEpsWeight);
   const char* xs = reinterpret_cast<const char*>(p.x) + (size_t)(s / p.xg) * (size_t)p.x_sstride * (XDT == BNN_F32 ? 4 : 2);
   // split-bf16 math (BNN_MATH_BF16X3): bf16 activations are a pair of planes, fp32 activations are split in registers
   constexpr bool X3 = MATH == BNN_MATH_BF16X3;
@@ -484,20 +472,20 @@ __device__ __forceinline__ bool bbb_fwd_body(const BbbK& p, const FinPack* fp) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) e[j] = w[j] = 0.f;
     } else if (TRANS) {
-      const uint32_t gprw = (uint32_t)((p.ldw + 3) >> 2);
+      const uint32_t gprw = eps_groups_per_row(p.ldw);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         e[j] = 0.f;
         if (p.eps_mode == BNN_EPS_PHILOX) {
           float e4[4];
-          philox_normal4((uint32_t)(k + j) * gprw + (uint32_t)(n >> 2), gs, wid, p.k0, p.k1, e4);
-          e[j] = (n & 3) == 0 ? e4[0] : (n & 3) == 1 ? e4[1] : (n & 3) == 2 ? e4[2] : e4[3];
+          philox_normal4(eps_group((uint32_t)(k + j), n, gprw), gs, wid, p.k0, p.k1, e4);
+          e[j] = eps_slot(e4, n);
         } else if (p.eps_mode == BNN_EPS_MEMORY) {
           if (j < valid) e[j] = p.eps_w[((size_t)s * K + k + j) * p.ldw + n];
         }
       }
     } else if (p.eps_mode == BNN_EPS_PHILOX) {
-      const uint32_t g = (uint32_t)n * (uint32_t)gpr + (uint32_t)(k >> 2);
+      const uint32_t g = eps_group((uint32_t)n, k, (uint32_t)gpr);
       philox_normal8(g, gs, wid, p.k0, p.k1, e);
     } else if (p.eps_mode == BNN_EPS_MEMORY) {
       load8<ALIGNED>(p.eps_w + ((size_t)s * N + n) * K + k, valid, e);
@@ -525,7 +513,7 @@ __device__ __forceinline__ bool bbb_fwd_body(const BbbK& p, const FinPack* fp) {
         for (int j = 0; j < 8; ++j) a = __builtin_fmaf(w[j], w[j], a);
       } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) a = (ALIGNED || j < valid) ? add_log(a, mix_p(p, w[j])) : a;
+        for (int j = 0; j < 8; ++j) a = (ALIGNED || j < valid) ? add_log(a, prior_mix_p(p.mix, w[j])) : a;
       }
       if (do_ls) {
 #pragma unroll
@@ -952,8 +940,8 @@ __device__ __forceinline__ void bbb_gemm_body(const BbbK& p, float4 (*xt)[8 * 64
   const bool do_stats = p.want_stats && mb == 0;
   const bool do_ls = do_stats && s == 0;
   const bool do_dump = mb == 0;
-  const int gpr = (K + 3) >> 2;
-  const uint32_t wid = p.layer_id * 4u;
+  const int gpr = (int)eps_groups_per_row(K);
+  const uint32_t wid = eps_tensor_id(p.layer_id, kEpsWeight);
   const __bf16* xs = reinterpret_cast<const __bf16*>(p.x) + (size_t)(s / p.xg) * (size_t)p.x_sstride;
   const int T = (N + 15) >> 4;
 
@@ -1040,7 +1028,7 @@ __device__ __forceinline__ void bbb_gemm_body(const BbbK& p, float4 (*xt)[8 * 64
     float sg[8] = {P.g_lo.x, P.g_lo.y, P.g_lo.z, P.g_lo.w, P.g_hi.x, P.g_hi.y, P.g_hi.z, P.g_hi.w};
     float e[8], w[8];
     if (EPS == BNN_EPS_PHILOX) {
-      const uint32_t g = (uint32_t)n * (uint32_t)gpr + (uint32_t)(k >> 2);
+      const uint32_t g = eps_group((uint32_t)n, k, (uint32_t)gpr);
       philox_normal8(g, gs, wid, p.k0, p.k1, e);
     } else if (EPS == BNN_EPS_MEMORY) {
       load8<true>(p.eps_w + ((size_t)s * N + n) * K + k, lane_ok ? 8 : 0, e);
@@ -1062,7 +1050,7 @@ __device__ __forceinline__ void bbb_gemm_body(const BbbK& p, float4 (*xt)[8 * 64
         for (int j = 0; j < 8; ++j) a = __builtin_fmaf(w[j], w[j], a);
       } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) a = add_log(a, mix_p(p, w[j]));
+        for (int j = 0; j < 8; ++j) a = add_log(a, prior_mix_p(p.mix, w[j]));
       }
       if (do_ls) {
 #pragma unroll
@@ -1328,8 +1316,8 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
   const bool do_stats = p.want_stats && mb == 0 && active;
   const bool do_ls = do_stats && s == 0;
   const bool do_dump = mb == 0 && active;
-  const int gpr = (K + 3) >> 2;
-  const uint32_t wid = p.layer_id * 4u;
+  const int gpr = (int)eps_groups_per_row(K);
+  const uint32_t wid = eps_tensor_id(p.layer_id, kEpsWeight);
   const __bf16* xs = reinterpret_cast<const __bf16*>(p.x) + (size_t)(s / p.xg) * (size_t)p.x_sstride;
   const __bf16* xs_lo = X3 ? reinterpret_cast<const __bf16*>(p.x_lo) + (size_t)(s / p.xg) * (size_t)p.x_sstride : nullptr;
   const int T = (N + 15) >> 4;
@@ -1606,7 +1594,7 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
     }
     if (real) {
       // the Philox counter of the lane's eight weights (an operand of the early x reads below: the generator stays behind them)
-      uint32_t g = (uint32_t)n * (uint32_t)gpr + (uint32_t)(k >> 2);
+      uint32_t g = eps_group((uint32_t)n, k, (uint32_t)gpr);
       // XE: the first half of the pair's x tile (batch tiles 0 .. 3) is requested here, behind the parameter reads and ahead
       // of the generator -- buffer `cur` was complete at the barrier that closed the previous step, so the reads depend on nothing
       // this step computes -- and waited for in front of the first MFMA; LDS returns in order, so the parameter wait counts
@@ -1656,8 +1644,8 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
           a = 0.f;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            a = add_log(a, mix_p(p, w2[j][0]));
-            a = add_log(a, mix_p(p, w2[j][1]));
+            a = add_log(a, prior_mix_p(p.mix, w2[j][0]));
+            a = add_log(a, prior_mix_p(p.mix, w2[j][1]));
           }
         }
         if (st_ls) {
@@ -1922,15 +1910,8 @@ __global__ void bbb_layer_scalars_kernel(const float4* __restrict__ ws, int K, i
   ls = block_sum(ls, scratch);
   if (threadIdx.x == 0) {
     const double cnt = (double)N * K + N;
-    const double c0 = -0.91893853320467274178;
-    if (log_q) log_q[s] = (float)(cnt * c0 - ls - 0.5 * e2);
-    if (log_prior) {
-      if (prior.kind == BNN_PRIOR_GAUSS)
-        log_prior[s] = (float)(cnt * (c0 - log((double)prior.sigma_p)) -
-                               a / (2.0 * (double)prior.sigma_p * (double)prior.sigma_p));
-      else
-        log_prior[s] = (float)a;
-    }
+    if (log_q) log_q[s] = (float)fold_log_q(cnt * kNegLogSqrt2Pi, ls, e2);
+    if (log_prior) log_prior[s] = (float)fold_log_p(prior, cnt, a);
   }
 }
 
@@ -2175,7 +2156,7 @@ static int prepare(const bnn_bbb_fwd_args* a, BbbK& k, bool& al) {
     if (!aligned16(a->x) || !aligned16(a->w_sampled)) return BNN_ERR_ALIGN;
   }
   if ((unsigned)a->x_dtype > 1u || (unsigned)a->y_dtype > 1u || (unsigned)a->math > 2u || (unsigned)a->eps_mode > 2u ||
-      (unsigned)a->prior.kind > 1u || (unsigned)a->form > 4u)
+      prior_check(a->prior) == BNN_ERR_ENUM || (unsigned)a->form > 4u)
     return BNN_ERR_ENUM;
   if ((unsigned)a->x_layout > 1u || (unsigned)a->y_layout > 1u) return BNN_ERR_ENUM;
   if ((a->x_layout && a->x_dtype != BNN_BF16) || (a->y_layout && a->y_dtype != BNN_BF16)) return BNN_ERR_ENUM;
@@ -2226,18 +2207,8 @@ static int prepare(const bnn_bbb_fwd_args* a, BbbK& k, bool& al) {
     k.dbg = v ? reinterpret_cast<unsigned long long*>(strtoull(v, nullptr, 0)) : nullptr;
   }
 #endif
-  const double c0 = -0.91893853320467274178;
-  k.pi = a->prior.pi;
-  if (a->prior.kind == BNN_PRIOR_MIXTURE) {
-    if (!(a->prior.sigma1 > 0.f) || !(a->prior.sigma2 > 0.f)) return BNN_ERR_SHAPE;
-    k.inv2var1 = (float)(1.0 / (2.0 * (double)a->prior.sigma1 * a->prior.sigma1));
-    k.inv2var2 = (float)(1.0 / (2.0 * (double)a->prior.sigma2 * a->prior.sigma2));
-    k.c1 = (float)(c0 - log((double)a->prior.sigma1));
-    k.c2 = (float)(c0 - log((double)a->prior.sigma2));
-  } else {
-    if (a->want_stats && !(a->prior.sigma_p > 0.f)) return BNN_ERR_SHAPE;
-    k.inv2var1 = k.inv2var2 = k.c1 = k.c2 = 0.f;
-  }
+  if (const int rc = prior_check(a->prior, a->want_stats != 0)) return rc;     // sigma_p: read by the statistics fold only
+  k.mix = prior_mix_make(a->prior);
   const int K = a->in_features;
   al = (K % 8 == 0) && aligned16(a->x) && aligned16(a->w_mu) && aligned16(a->w_rho) && (!k.x_lo || aligned16(k.x_lo));
   if (pre) {
@@ -2661,7 +2632,7 @@ extern "C" int bnn_bbb_input_grad_(const bnn_bbb_bwd_args* a, const float* gz, v
   k.k0 = (uint32_t)a->seed; k.k1 = (uint32_t)(a->seed >> 32);
   k.layer_id = a->layer_id; k.sample_offset = a->sample_offset; k.sample_counter = a->sample_counter;
   k.xg = 1; k.sgrp = 0u; k.sgrp_stride = 0u;
-  k.inv2var1 = k.inv2var2 = k.c1 = k.c2 = k.pi = 0.f;
+  k.mix = PriorMix{};
 #ifdef BNN_STAMPS
   k.dbg = nullptr;
 #endif

@@ -3,6 +3,7 @@
 // another layer's sampling as extra blocks (the output layer's weights ride on the launch of the layer before it).
 #pragma once
 #include "bnn_device.h"
+#include "bnn_prior.h"
 #include "../../include/bnn_hip.h"
 #include <math.h>
 
@@ -27,7 +28,7 @@ struct SampleL {
   int T;                // chunks (= statistics entries) per sample; a block = one chunk x one group of kSampleGroup samples
   int bias_per_block;   // block `chunk` also samples biases [chunk * bpb, (chunk + 1) * bpb)
   int prior_kind;
-  float inv2var1, c1, inv2var2, c2, pi;
+  PriorMix mix;
 };
 
 struct SampleK {
@@ -41,28 +42,6 @@ struct SampleK {
   long cast_n;
   int cast_first;          // first block of the cast job (after every layer's blocks)
 };
-
-// the mixture density (argument of the log; accumulated with add_log: explicit contraction, see bnn_device.h)
-struct SampleMix { float inv2var1, c1, inv2var2, c2, pi; };
-__device__ __forceinline__ float sample_mix_p(const SampleMix& L, float w) {
-  const float w2 = w * w;
-  const float p1 = fast_exp(__builtin_fmaf(-w2, L.inv2var1, L.c1));
-  const float p2 = fast_exp(__builtin_fmaf(-w2, L.inv2var2, L.c2));
-  return __builtin_fmaf(L.pi, p1, (1.0f - L.pi) * p2);
-}
-
-// host side: the mixture constants from a bnn_prior (sigma1, sigma2 > 0 checked by the caller); fill_sample below and
-// bnn_sparse_elbo_terms (sparse_train.hip) use it
-inline SampleMix sample_mix_make(const bnn_prior& pr) {
-  const double c0 = -0.91893853320467274178;
-  SampleMix m;
-  m.inv2var1 = (float)(1.0 / (2.0 * (double)pr.sigma1 * pr.sigma1));
-  m.inv2var2 = (float)(1.0 / (2.0 * (double)pr.sigma2 * pr.sigma2));
-  m.c1 = (float)(c0 - log((double)pr.sigma1));
-  m.c2 = (float)(c0 - log((double)pr.sigma2));
-  m.pi = pr.pi;
-  return m;
-}
 
 // One block of the sampling job: `block` = index within the job's own block range, `red` = LDS scratch of
 // >= kSampleRedFloats floats.  Every thread of the block must call it (one barrier inside); threads beyond
@@ -99,12 +78,12 @@ __device__ __forceinline__ void sample_block(const SampleK& p, int block, float*
   // the layer's prior in registers, and ONE branch on its kind per octet: read per weight from the parameter block (the
   // layer index is a run-time value) the kind cost a scalar load, a wait and a branch for each of the 16 weights of a sample
   const bool gauss = L.prior_kind == BNN_PRIOR_GAUSS;      // block-uniform
-  const SampleMix mix = {L.inv2var1, L.c1, L.inv2var2, L.c2, L.pi};
+  const PriorMix mix = L.mix;
   const int opr = K >> 3;                                  // octets per row
   const long total = (long)N * opr;
   const uint32_t gs_base = p.sample_offset + (p.sample_counter ? *p.sample_counter : 0u);
-  const uint32_t gpr = (uint32_t)(K >> 2);
-  const uint32_t wid = L.layer_id * 4u;
+  const uint32_t gpr = (uint32_t)(K >> 2);                 // K % 8 == 0: eps_groups_per_row(K) without its round-up
+  const uint32_t layer_id = L.layer_id, wid = eps_tensor_id(layer_id, kEpsWeight);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool active = (int)threadIdx.x < kSampleThreads;
   if (!active) {                                          // whole waves (kSampleThreads is a multiple of 64): a wider block's
@@ -160,15 +139,15 @@ __device__ __forceinline__ void sample_block(const SampleK& p, int block, float*
 #pragma unroll 1
   for (int si = 0; si < ns; ++si) {
     const int s = s0 + si;
-    uint32_t gs = gs_base;
-    if (p.sgrp == 0u) gs += (uint32_t)s;
+    uint32_t gs = gs_base;                                 // eps_global_sample's value, in the spelling this kernel was built with: s % sgrp
+    if (p.sgrp == 0u) gs += (uint32_t)s;                   // compiles to a second division sequence, and the kernel's device code is held fixed
     else gs += ((uint32_t)s / p.sgrp) * p.sgrp_stride + (uint32_t)s % p.sgrp;
     const bool do_ls = s == 0;
     float s_e2 = 0.f, s_a = 0.f, s_ls = 0.f;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const bool ok = o[u] < total;
-      const uint32_t g = (uint32_t)n[u] * gpr + (uint32_t)(k[u] >> 2);
+      const uint32_t g = eps_group((uint32_t)n[u], k[u], gpr);
       float e[8];
       philox_normal4(g, gs, wid, p.k0, p.k1, e);
       philox_normal4(g + 1u, gs, wid, p.k0, p.k1, e + 4);
@@ -183,7 +162,7 @@ __device__ __forceinline__ void sample_block(const SampleK& p, int block, float*
         for (int j = 0; j < 8; ++j) a = __builtin_fmaf(w[j], w[j], a);
       } else {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) a = add_log(a, sample_mix_p(mix, w[j]));
+        for (int j = 0; j < 8; ++j) a = add_log(a, prior_mix_p(mix, w[j]));
       }
       s_e2 += ok ? e2 : 0.f;
       s_a += ok ? a : 0.f;
@@ -196,13 +175,11 @@ __device__ __forceinline__ void sample_block(const SampleK& p, int block, float*
       }
     }
     if (has_bias) {
-      float e4[4];
-      philox_normal4((uint32_t)(bn >> 2), gs, wid + 1u, p.k0, p.k1, e4);
-      const float e = (bn & 3) == 0 ? e4[0] : (bn & 3) == 1 ? e4[1] : (bn & 3) == 2 ? e4[2] : e4[3];
+      const float e = eps_bias(bn, gs, layer_id, p.k0, p.k1);
       const float b = __builtin_fmaf(bsg, e, bmu);
       L.b_out[(size_t)s * N + bn] = b;
       s_e2 = __builtin_fmaf(e, e, s_e2);
-      s_a = gauss ? __builtin_fmaf(b, b, s_a) : add_log(s_a, sample_mix_p(mix, b));
+      s_a = gauss ? __builtin_fmaf(b, b, s_a) : add_log(s_a, prior_mix_p(mix, b));
       if (do_ls) s_ls = add_log(s_ls, bsg);
     }
     const float a0 = wave_sum(s_e2), a1 = wave_sum(s_a), a2 = wave_sum(s_ls);
@@ -247,12 +224,11 @@ static inline int fill_sample(const bnn_bbb_sample_args* a, bnn::SampleK& k, lon
   if (a->struct_bytes != sizeof(bnn_bbb_sample_args)) return BNN_ERR_ABI;
   if (a->n_layers <= 0 || a->n_layers > BNN_SAMPLE_MAX_LAYERS || a->n_samples <= 0) return BNN_ERR_SHAPE;
   blocks = 0;
-  const double c0 = -0.91893853320467274178;
   for (int i = 0; i < a->n_layers; ++i) {
     const bnn_bbb_sample_layer& l = a->layer[i];
     if (l.in_features <= 0 || l.out_features <= 0 || (l.in_features & 7)) return BNN_ERR_SHAPE;
     if (!l.w_mu || !l.w_rho || !l.b_mu || !l.b_rho || !l.w_out || !l.b_out || !l.workspace) return BNN_ERR_NULL;
-    if ((unsigned)l.prior.kind > 1u) return BNN_ERR_ENUM;
+    if (prior_check(l.prior) == BNN_ERR_ENUM) return BNN_ERR_ENUM;
     const uintptr_t al = reinterpret_cast<uintptr_t>(l.w_mu) | reinterpret_cast<uintptr_t>(l.w_rho) |
                          reinterpret_cast<uintptr_t>(l.w_out) | reinterpret_cast<uintptr_t>(l.workspace);
     if (al & 15) return BNN_ERR_ALIGN;
@@ -266,16 +242,9 @@ static inline int fill_sample(const bnn_bbb_sample_args* a, bnn::SampleK& k, lon
     o.T = sample_chunks(l.in_features, l.out_features);
     o.bias_per_block = (l.out_features + o.T - 1) / o.T;
     if (o.bias_per_block > kSampleThreads) return BNN_ERR_SHAPE;     // in_features < 8 per 256 outputs: not a layer shape
+    if (const int rc = prior_check(l.prior)) return rc;
     o.prior_kind = l.prior.kind;
-    o.pi = l.prior.pi;
-    if (l.prior.kind == BNN_PRIOR_MIXTURE) {
-      if (!(l.prior.sigma1 > 0.f) || !(l.prior.sigma2 > 0.f)) return BNN_ERR_SHAPE;
-      const bnn::SampleMix m = bnn::sample_mix_make(l.prior);
-      o.inv2var1 = m.inv2var1; o.inv2var2 = m.inv2var2; o.c1 = m.c1; o.c2 = m.c2;
-    } else {
-      if (!(l.prior.sigma_p > 0.f)) return BNN_ERR_SHAPE;
-      o.inv2var1 = o.inv2var2 = o.c1 = o.c2 = 0.f;
-    }
+    o.mix = prior_mix_make(l.prior);
     blocks += (long)o.T * ((a->n_samples + kSampleGroup - 1) / kSampleGroup);
     if (blocks > 0x3fffffff) return BNN_ERR_SHAPE;
   }

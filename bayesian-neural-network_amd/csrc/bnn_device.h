@@ -13,7 +13,8 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
 constexpr int kWave = 64;
-constexpr float kC0 = -0.918938533204672742f;  // -log(sqrt(2 pi)), networks.py:46
+constexpr double kNegLogSqrt2Pi = -0.91893853320467274178;   // -log(sqrt(2 pi)), networks.py:46: the one definition
+constexpr float kC0 = (float)kNegLogSqrt2Pi;
 constexpr float kLn2 = 0.693147180559945309f;
 constexpr float kLog2e = 1.442695040888963407f;
 
@@ -64,6 +65,44 @@ __device__ __forceinline__ void philox_normal4(uint32_t group, uint32_t gsample,
   const uint4 r = philox4x32<>(make_uint4(group, gsample, tensor_id, 0u), k0, k1);
   box_muller(r.x, r.y, out[0], out[1]);
   box_muller(r.z, r.w, out[2], out[3]);
+}
+
+// ---------------------------------------------------------------------------- epsilon map
+// The device statement of the epsilon map of include/bnn_hip.h: which Philox draw belongs to which weight, bias or
+// activation.  Every forward and its backward go through these, so they cannot disagree.
+constexpr uint32_t kEpsWeight = 0u, kEpsBias = 1u, kEpsLrAct = 2u, kEpsDropout = 3u;   // tensor kinds
+__host__ __device__ __forceinline__ constexpr uint32_t eps_tensor_id(uint32_t layer_id, uint32_t kind) { return 4u * layer_id + kind; }
+// groups of four per row of a [rows, cols] tensor; the group of element (row, col); the same for a caller that walks
+// groups and holds the group's own column gcol = col >> 2
+__device__ __forceinline__ uint32_t eps_groups_per_row(int cols) { return (uint32_t)((cols + 3) >> 2); }
+__device__ __forceinline__ uint32_t eps_group_at(uint32_t row, uint32_t gcol, uint32_t groups_per_row) {
+  return row * groups_per_row + gcol;
+}
+template <class C>
+__device__ __forceinline__ uint32_t eps_group(uint32_t row, C col, uint32_t groups_per_row) {
+  return row * groups_per_row + (uint32_t)(col >> 2);
+}
+// element `col`'s value among its group's four (a select over four values: spelled over e4[] itself the arms are loads
+// under branches, and the compiler then sinks parts of Box-Muller into them differently from site to site)
+template <class C>
+__device__ __forceinline__ float eps_slot(float e0, float e1, float e2, float e3, C col) {
+  return (col & 3) == 0 ? e0 : (col & 3) == 1 ? e1 : (col & 3) == 2 ? e2 : e3;
+}
+template <class C>
+__device__ __forceinline__ float eps_slot(const float e4[4], C col) { return eps_slot(e4[0], e4[1], e4[2], e4[3], col); }
+// the draw of bias n (a [1, N] tensor) for global sample gs
+template <class C>
+__device__ __forceinline__ float eps_bias(C n, uint32_t gs, uint32_t layer_id, uint32_t k0, uint32_t k1) {
+  float e4[4];
+  philox_normal4((uint32_t)(n >> 2), gs, eps_tensor_id(layer_id, kEpsBias), k0, k1, e4);
+  return eps_slot(e4, n);
+}
+// global sample index (Philox subsequence) of local sample s; base = sample_offset + the device counter.  Sample
+// groups (sgrp != 0): group g = s / sgrp starts at base + g * sgrp_stride.
+__device__ __forceinline__ uint32_t eps_global_sample(uint32_t base, uint32_t s, uint32_t sgrp, uint32_t sgrp_stride) {
+  if (sgrp == 0u) return base + s;
+  const uint32_t g = s / sgrp;
+  return base + g * sgrp_stride + (s - g * sgrp);
 }
 
 // Two consecutive epsilon groups (`group`, `group + 1`: the 8 weights a lane of the block forms holds per k-step) with

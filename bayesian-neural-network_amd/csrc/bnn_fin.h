@@ -6,6 +6,7 @@
 // bnn_finalize_args.scratch (fin_scratch).
 #pragma once
 #include "bnn_device.h"
+#include "bnn_prior.h"
 #include "bnn_nll_row.h"
 #include "../../include/bnn_hip.h"
 #include <math.h>
@@ -79,7 +80,7 @@ static inline int make_fin(const bnn_finalize_args* a, FinK& k, FinC& cst) {
   if (!a) return BNN_ERR_NULL;
   if (a->struct_bytes != sizeof(bnn_finalize_args)) return BNN_ERR_ABI;
   if (a->n_layers < 0 || a->n_layers > 8 || a->n_samples <= 0 || a->n_samples > 65535) return BNN_ERR_SHAPE;
-  if ((unsigned)a->prior.kind > 1u || (unsigned)a->nll_mode > 1u) return BNN_ERR_ENUM;
+  if (prior_check(a->prior) == BNN_ERR_ENUM || (unsigned)a->nll_mode > 1u) return BNN_ERR_ENUM;
   for (int l = 0; l < 8; ++l) {
     k.ws[l] = l < a->n_layers ? reinterpret_cast<const float*>(a->layer_workspace[l]) : nullptr;
     k.lin[l] = l < a->n_layers ? a->layer_in[l] : 0;
@@ -90,7 +91,7 @@ static inline int make_fin(const bnn_finalize_args* a, FinK& k, FinC& cst) {
       if (k.lin[l] <= 0 || k.lout[l] <= 0) return BNN_ERR_SHAPE;
     }
   }
-  if (a->n_layers > 0 && !(a->prior.kind == BNN_PRIOR_MIXTURE) && !(a->prior.sigma_p > 0.f)) return BNN_ERR_SHAPE;
+  if (a->n_layers > 0 && a->prior.kind != BNN_PRIOR_MIXTURE && prior_check(a->prior) != BNN_OK) return BNN_ERR_SHAPE;
   if (a->group_samples < 0 || (a->group_samples > 0 && a->n_samples % a->group_samples != 0)) return BNN_ERR_SHAPE;
   if (a->target_per_group && a->group_samples <= 0) return BNN_ERR_SHAPE;
   if (a->nll) {
@@ -106,18 +107,16 @@ static inline int make_fin(const bnn_finalize_args* a, FinK& k, FinC& cst) {
   k.nll_partial = nullptr; k.nll_rb = 0;
   k.tgt_stride = a->target_per_group
                      ? (a->nll_mode == BNN_NLL_CLASSIFICATION ? (long)a->batch : (long)a->batch * a->classes) : 0;
-  const double c0 = -0.91893853320467274178;
-  const double sp = (a->prior.kind == BNN_PRIOR_MIXTURE) ? 1.0 : (double)a->prior.sigma_p;
   for (int l = 0; l < 8; ++l) cst.cnt_c0[l] = cst.lp_const[l] = cst.kl_const[l] = 0.0;
   for (int l = 0; l < a->n_layers; ++l) {
-    const double cnt = (double)a->layer_out[l] * a->layer_in[l] + a->layer_out[l];
-    cst.cnt_c0[l] = cnt * c0;
-    cst.lp_const[l] = cnt * (c0 - log(sp));
-    cst.kl_const[l] = 0.5 * (2.0 * cnt * log(sp) - cnt);
+    const PriorFold f = prior_fold_make(a->prior, (double)a->layer_out[l] * a->layer_in[l] + a->layer_out[l]);
+    cst.cnt_c0[l] = f.cnt_c0;
+    cst.lp_const[l] = f.lp_const;
+    cst.kl_const[l] = f.kl_const;
   }
-  cst.inv2var = 1.0 / (2.0 * sp * sp);
+  cst.inv2var = prior_fold_make(a->prior, 0.0).inv2var;
   const double ns = a->nll_sigma > 0.f ? (double)a->nll_sigma : 1.0;
-  cst.reg_const = log(ns) - c0;
+  cst.reg_const = log(ns) - kNegLogSqrt2Pi;
   cst.reg_inv2var = 1.0 / (2.0 * ns * ns);
   return BNN_OK;
 }
@@ -357,8 +356,8 @@ __device__ __forceinline__ void fin_sample(const FinK& p, const FinC& cst, int s
       if (p.local_reparam) {
         a_tot += (float)(cst.kl_const[l] - r0 + (r1 + r2) * cst.inv2var);
       } else {
-        const double lq = cst.cnt_c0[l] - r2 - 0.5 * r0;
-        const double lp = (p.prior.kind == BNN_PRIOR_GAUSS) ? cst.lp_const[l] - r1 * cst.inv2var : r1;
+        const double lq = fold_log_q(cst.cnt_c0[l], r2, r0);
+        const double lp = fold_log_p(p.prior.kind, cst.lp_const[l], cst.inv2var, r1);
         a_tot += (float)lp;
         b_tot += (float)lq;
       }

@@ -16,7 +16,6 @@
 //                        through LDS, rows in ascending (s, n) order: no atomics, one summation order per shape.
 #include "bnn_device.h"
 #include "bnn_prior.h"
-#include "bbb_sample_body.h"
 #include <type_traits>
 
 namespace bnn {
@@ -25,6 +24,7 @@ namespace {
 constexpr int kFlThreads = 256;
 constexpr uint32_t kSignWord3 = 2u;      // counter word 3 of the sign stream (eps streams: 0; bandit / epoch / acquire / BatchBALD: 1)
 
+// eps_global_sample's value (bnn_device.h) as these kernels were built: s % sgrp is a second division sequence, kept with their device code
 __device__ __forceinline__ uint32_t fl_gsample(uint32_t base, uint32_t s, uint32_t sgrp, uint32_t stride) {
   return sgrp == 0u ? base + s : base + (s / sgrp) * stride + s % sgrp;
 }
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(kFlThreads) void flipout_signs_kernel(bnn_flipout_s
   const uint32_t smp = (uint32_t)(i / per);
   const long rem = i - (long)smp * per;
   const uint32_t row = (uint32_t)(rem / a.cols), col = (uint32_t)(rem - (long)row * a.cols);
-  const uint32_t m = sign_mask(a.row_offset + row, (uint32_t)a.cols, col, a.sample_offset + smp, 4u * a.layer_id + (uint32_t)a.kind,
+  const uint32_t m = sign_mask(a.row_offset + row, (uint32_t)a.cols, col, a.sample_offset + smp, eps_tensor_id(a.layer_id, (uint32_t)a.kind),
                                (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
   a.out[i] = m ? (int8_t)-1 : (int8_t)1;
 }
@@ -67,7 +67,7 @@ struct PrepK {
   int eps_mode, want_stats, gauss;
   uint32_t layer_id, sample_offset, sgrp, sgrp_stride, k0, k1;
   const uint32_t* sample_counter;
-  SampleMix mix;
+  PriorMix mix;
 };
 
 __global__ __launch_bounds__(kFlThreads) void flipout_prepare_kernel(PrepK p) {
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(kFlThreads) void flipout_prepare_kernel(PrepK p) {
       if (is_w && p.mu_bf16) p.mu_bf16[off + j] = (__bf16)mu[j];
     }
   const float ls_wave = p.want_stats ? wave_sum(s_ls) : 0.f;
-  const uint32_t tid = 4u * p.layer_id + (is_w ? 0u : 1u);
+  const uint32_t tid = eps_tensor_id(p.layer_id, is_w ? kEpsWeight : kEpsBias);
   const long entries = (long)gridDim.x * (kFlThreads / 64);
 #pragma unroll 1
   for (int d = 0; d < p.D; ++d) {
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kFlThreads) void flipout_prepare_kernel(PrepK p) {
       if (j >= cnt) continue;
       const float w = __builtin_fmaf(sg[j], e[j], mu[j]);
       s_e2 = __builtin_fmaf(e[j], e[j], s_e2);
-      s_a = p.gauss ? __builtin_fmaf(w, w, s_a) : add_log(s_a, sample_mix_p(p.mix, w));
+      s_a = p.gauss ? __builtin_fmaf(w, w, s_a) : add_log(s_a, prior_mix_p(p.mix, w));
       const size_t o = (size_t)d * per + off + j;
       if (is_w) {
         const float dl = __fmul_rn(sg[j], e[j]);
@@ -172,8 +172,8 @@ __global__ __launch_bounds__(kFlThreads) void flipout_fold_kernel(const float* _
     __syncthreads();
   }
   if (t == 0) {
-    log_q[d] = (float)(cnt_c0 - red[2][0] - 0.5 * red[0][0]);
-    log_prior[d] = (float)(gauss ? lp_const - red[1][0] * inv2var : red[1][0]);
+    log_q[d] = (float)fold_log_q(cnt_c0, red[2][0], red[0][0]);
+    log_prior[d] = (float)fold_log_p(gauss ? BNN_PRIOR_GAUSS : BNN_PRIOR_MIXTURE, lp_const, inv2var, red[1][0]);
   }
 }
 
@@ -260,7 +260,7 @@ __global__ __launch_bounds__(kFlThreads) void flipout_fwd_kernel(FwdK p) {
     __syncthreads();                                                  // the previous sample's epilogue has read sS
     if (!p.zero && tid < kFwdRows) {
       const uint4 w = sign_words(p.row_offset + (uint32_t)(n0 + tid), (uint32_t)((N + 127) >> 7), (uint32_t)(o_blk >> 7), gs,
-                                 4u * p.layer_id + 1u, p.k0, p.k1);
+                                 eps_tensor_id(p.layer_id, kEpsBias), p.k0, p.k1);
       uint32_t* o = sS + tid * 4;
       o[0] = w.x; o[1] = w.y; o[2] = w.z; o[3] = w.w;
     }
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(kFlThreads) void flipout_fwd_kernel(FwdK p) {
     for (int k0 = 0; k0 < K; k0 += 32) {
       // (every thread is past the previous k-step's staging, the only reader of sR: its words may be replaced here)
       if (!p.zero && (k0 & 127) == 0 && tid < kFwdRows) {
-        const uint4 w = sign_words(p.row_offset + (uint32_t)(n0 + tid), (uint32_t)p.g128, (uint32_t)(k0 >> 7), gs, 4u * p.layer_id, p.k0, p.k1);
+        const uint4 w = sign_words(p.row_offset + (uint32_t)(n0 + tid), (uint32_t)p.g128, (uint32_t)(k0 >> 7), gs, eps_tensor_id(p.layer_id, kEpsWeight), p.k0, p.k1);
         uint32_t* o = sR + tid * 4;
         o[0] = w.x; o[1] = w.y; o[2] = w.z; o[3] = w.w;
       }
@@ -373,13 +373,13 @@ __global__ __launch_bounds__(kFlThreads) void flipout_bwd_flip_kernel(BwdK p) {
     float g = p.gy[i];
     if (p.relu && !(p.y[i] > 0.f)) g = 0.f;
     p.gz[i] = g;
-    p.gzs[i] = flip(g, sign_mask(p.row_offset + n, (uint32_t)p.N, o, fl_gsample(base, s, p.sgrp, p.sgrp_stride), 4u * p.layer_id + 1u,
+    p.gzs[i] = flip(g, sign_mask(p.row_offset + n, (uint32_t)p.N, o, fl_gsample(base, s, p.sgrp, p.sgrp_stride), eps_tensor_id(p.layer_id, kEpsBias),
                                  p.k0, p.k1));
   } else {
     const long j = i - e1, sn = j / p.K;
     const uint32_t k = (uint32_t)(j - sn * p.K), s = (uint32_t)(sn / p.B), n = (uint32_t)(sn - (long)s * p.B);
     const float v = p.x[p.x_per_sample ? j : (long)n * p.K + k];
-    p.xr[j] = flip(v, sign_mask(p.row_offset + n, (uint32_t)p.K, k, fl_gsample(base, s, p.sgrp, p.sgrp_stride), 4u * p.layer_id, p.k0, p.k1));
+    p.xr[j] = flip(v, sign_mask(p.row_offset + n, (uint32_t)p.K, k, fl_gsample(base, s, p.sgrp, p.sgrp_stride), eps_tensor_id(p.layer_id, kEpsWeight), p.k0, p.k1));
   }
 }
 
@@ -490,17 +490,13 @@ __global__ __launch_bounds__(256) void flipout_bwd_x_kernel(BwdK p) {
   if (n < B && k < K) {
     const uint32_t base = p.sample_offset + (p.sample_counter ? *p.sample_counter : 0u);
     const uint32_t m = sign_mask(p.row_offset + (uint32_t)n, (uint32_t)K, (uint32_t)k, fl_gsample(base, (uint32_t)s, p.sgrp, p.sgrp_stride),
-                                 4u * p.layer_id, p.k0, p.k1);
+                                 eps_tensor_id(p.layer_id, kEpsWeight), p.k0, p.k1);
     p.g_x[((size_t)s * B + n) * K + k] = a1 + flip(a2, m);
   }
 }
 
 bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
 bool bad_features(int v) { return v < 1 || v > BNN_FLIPOUT_MAX_FEATURES; }
-bool bad_prior_scale(const bnn_prior& pr) {
-  if (pr.kind == BNN_PRIOR_MIXTURE) return !(pr.sigma1 > 0.f) || !(pr.sigma2 > 0.f);
-  return !(pr.sigma_p > 0.f);
-}
 long prepare_blocks(int K, int N) {
   const long items = (long)N * ((K + 3) >> 2) + ((N + 3) >> 2);
   return (items + kFlThreads - 1) / kFlThreads;
@@ -537,8 +533,8 @@ extern "C" int bnn_flipout_prepare(const bnn_flipout_prepare_args* a, void* stre
   if (a->n_samples < 1 || a->n_draws < 1 || a->n_samples % a->n_draws != 0 || bad_features(a->in_features) ||
       bad_features(a->out_features))
     return BNN_ERR_SHAPE;
-  if ((unsigned)a->prior.kind <= 1u && a->want_stats && bad_prior_scale(a->prior)) return BNN_ERR_SHAPE;
-  if ((unsigned)a->eps_mode > 2u || (a->math != BNN_MATH_F32 && a->math != BNN_MATH_BF16) || (unsigned)a->prior.kind > 1u)
+  if (a->want_stats && prior_check(a->prior) == BNN_ERR_SHAPE) return BNN_ERR_SHAPE;
+  if ((unsigned)a->eps_mode > 2u || (a->math != BNN_MATH_F32 && a->math != BNN_MATH_BF16) || prior_check(a->prior) == BNN_ERR_ENUM)
     return BNN_ERR_ENUM;
   const bool bf16 = a->math == BNN_MATH_BF16, mem = a->eps_mode == BNN_EPS_MEMORY;
   if (!a->w_mu || !a->w_rho || !a->b_mu || !a->b_rho || !a->delta || !a->b_draw || (mem && (!a->eps_w || !a->eps_b)) ||
@@ -563,16 +559,14 @@ extern "C" int bnn_flipout_prepare(const bnn_flipout_prepare_args* a, void* stre
   k.layer_id = a->layer_id; k.sample_offset = a->sample_offset; k.sgrp = a->sample_group; k.sgrp_stride = a->sample_group_stride;
   k.k0 = (uint32_t)a->seed; k.k1 = (uint32_t)(a->seed >> 32);
   k.sample_counter = a->sample_counter;
-  k.mix = SampleMix{0.f, 0.f, 0.f, 0.f, 0.f};
-  if (a->want_stats && a->prior.kind == BNN_PRIOR_MIXTURE) k.mix = sample_mix_make(a->prior);
+  k.mix = PriorMix{};
+  if (a->want_stats && a->prior.kind == BNN_PRIOR_MIXTURE) k.mix = prior_mix_make(a->prior);
   const long blocks = prepare_blocks(a->in_features, a->out_features);
   hipLaunchKernelGGL(flipout_prepare_kernel, dim3((unsigned)blocks), dim3(kFlThreads), 0, stream, k);
   if (a->want_stats) {
-    const double c0 = -0.91893853320467274178;
-    const double cnt = (double)a->out_features * a->in_features + a->out_features;
-    const double sp = k.gauss ? (double)a->prior.sigma_p : 1.0;
+    const PriorFold f = prior_fold_make(a->prior, (double)a->out_features * a->in_features + a->out_features);
     hipLaunchKernelGGL(flipout_fold_kernel, dim3((unsigned)a->n_draws), dim3(kFlThreads), 0, stream, k.part, blocks * (kFlThreads / 64),
-                       k.gauss, cnt * c0, cnt * (c0 - log(sp)), 1.0 / (2.0 * sp * sp), a->log_prior, a->log_q);
+                       k.gauss, f.cnt_c0, f.lp_const, f.inv2var, a->log_prior, a->log_q);
   }
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? BNN_OK : (int)err;
@@ -637,8 +631,7 @@ extern "C" int bnn_flipout_bwd(const bnn_flipout_bwd_args* a, void* stream_) {
   if (a->n_samples < 1 || a->n_draws < 1 || a->batch < 1 || a->n_samples % a->n_draws != 0 || bad_features(a->in_features) ||
       bad_features(a->out_features) || (unsigned)a->x_per_sample > 1u || a->n_samples > 65535)
     return BNN_ERR_SHAPE;
-  if ((unsigned)a->prior.kind <= 1u && bad_prior_scale(a->prior)) return BNN_ERR_SHAPE;
-  if ((unsigned)a->prior.kind > 1u) return BNN_ERR_ENUM;
+  if (const int rc = prior_check(a->prior)) return rc;
   if (!a->x || !a->gy || !a->w_mu || !a->w_rho || !a->b_mu || !a->b_rho || !a->eps_w || !a->eps_b || !a->g_w_mu || !a->g_w_rho ||
       !a->g_b_mu || !a->g_b_rho || (a->relu && !a->y))
     return BNN_ERR_NULL;
@@ -649,7 +642,7 @@ extern "C" int bnn_flipout_bwd(const bnn_flipout_bwd_args* a, void* stream_) {
   for (const void* q : ptrs)
     if (misaligned(q, 4)) return BNN_ERR_ALIGN;
   BwdK k;
-  if (prior_dlogp_fill(a->prior, k) != BNN_OK) return BNN_ERR_SHAPE;
+  prior_dlogp_fill(a->prior, k);
   k.x = a->x; k.gy = a->gy; k.y = a->y; k.w_mu = a->w_mu; k.w_rho = a->w_rho; k.b_mu = a->b_mu; k.b_rho = a->b_rho;
   k.eps_w = a->eps_w; k.eps_b = a->eps_b; k.glp = a->g_log_prior; k.glq = a->g_log_q;
   k.g_w_mu = a->g_w_mu; k.g_w_rho = a->g_w_rho; k.g_b_mu = a->g_b_mu; k.g_b_rho = a->g_b_rho; k.g_x = a->g_x;

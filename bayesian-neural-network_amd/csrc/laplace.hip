@@ -181,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void laplace_layer_kernel(LayerParams p) 
     });
 }
 
-constexpr double kHalfLog2Pi = 0.91893853320467274178;
+constexpr double kHalfLog2Pi = -kNegLogSqrt2Pi;
 
 // one block; thread t owns data rows t, t + 256, ...; virtual row r = c B + n
 __global__ __launch_bounds__(kThreads) void laplace_seed_kernel(const float* __restrict__ z, const void* __restrict__ target, int B,

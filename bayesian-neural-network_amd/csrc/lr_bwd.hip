@@ -58,7 +58,7 @@ __global__ void lr_bwd_prep_kernel(const float* __restrict__ gy, const float* __
                                    int B, int N, int relu, int eps_mode, uint32_t k0, uint32_t k1, uint32_t layer_id,
                                    uint32_t sample_offset, const uint32_t* sample_counter) {
   if (sample_counter) sample_offset += *sample_counter;
-  const int gpr = (N + 3) >> 2;
+  const int gpr = (N + 3) >> 2;      // eps_groups_per_row(N), as this kernel was built
   const bool vec = (N & 3) == 0;
   const long total = (long)S * B * gpr;
   for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
@@ -93,7 +93,7 @@ __global__ void lr_bwd_prep_kernel(const float* __restrict__ gy, const float* __
       }
     }
     if (eps_mode == BNN_EPS_PHILOX)
-      philox_normal4((uint32_t)b * (uint32_t)gpr + (uint32_t)g, sample_offset + (uint32_t)s, layer_id * 4u + 2u, k0, k1, e4);
+      philox_normal4((uint32_t)b * (uint32_t)gpr + (uint32_t)g, sample_offset + (uint32_t)s, eps_tensor_id(layer_id, kEpsLrAct), k0, k1, e4);   // eps_group_at(b, g, gpr)
     float gz4[4], h4[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256, 3) void lr_bwd_weights_kernel(const LrBwdK p) 
         float e0 = 0.f, e1 = 0.f;
         if (p.eps_mode == BNN_EPS_PHILOX) {
           float e4[4];
-          philox_normal4((uint32_t)(na >> 2), sample_base + (uint32_t)s, p.layer_id * 4u + 1u, p.k0, p.k1, e4);
+          philox_normal4((uint32_t)(na >> 2), sample_base + (uint32_t)s, eps_tensor_id(p.layer_id, kEpsBias), p.k0, p.k1, e4);
           e0 = (na & 2) ? e4[2] : e4[0];                  // na is even: (na, na + 1) sit in one group of 4
           e1 = (na & 2) ? e4[3] : e4[1];
         } else if (p.eps_mode == BNN_EPS_MEMORY) {
@@ -540,7 +540,7 @@ __device__ __forceinline__ void lr_out_rows(const LrBwdK& p, const LrOutBwd& o, 
   // gz / h of rows b0 .. b0 + nrows - 1 of sample s into LDS as [row][16] (features padded with zeros); a thread takes
   // one (row, group of 4 features)
   const int N = p.N, B = p.B;
-  const int gpr = (N + 3) >> 2;
+  const int gpr = (N + 3) >> 2;      // eps_groups_per_row(N), as this kernel was built
   for (int i = threadIdx.x; i < nrows * 4; i += blockDim.x) {
     const int r = i >> 2, g = i & 3;
     const int b = b0 + r;
@@ -548,7 +548,7 @@ __device__ __forceinline__ void lr_out_rows(const LrBwdK& p, const LrOutBwd& o, 
     if (b < B && g < gpr) {
       const size_t row = ((size_t)s * B + b) * N;
       float e4[4];
-      philox_normal4((uint32_t)b * (uint32_t)gpr + (uint32_t)g, gs, p.layer_id * 4u + 2u, p.k0, p.k1, e4);
+      philox_normal4(eps_group_at((uint32_t)b, (uint32_t)g, (uint32_t)gpr), gs, eps_tensor_id(p.layer_id, kEpsLrAct), p.k0, p.k1, e4);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int n = g * 4 + j;
@@ -622,9 +622,7 @@ __device__ __forceinline__ void lr_out_weight_role(const LrBwdK& p, const LrOutB
       for (int sp = 0; sp < SP && s0 + sp < S; ++sp) {
         float cs = 0.f;
         for (int b = 0; b < B; ++b) cs += gzs[(sp * 128 + b) * 16 + tid];
-        float e4[4];
-        philox_normal4((uint32_t)(tid >> 2), sample_base + (uint32_t)(s0 + sp), p.layer_id * 4u + 1u, p.k0, p.k1, e4);
-        const float e = (tid & 3) == 0 ? e4[0] : (tid & 3) == 1 ? e4[1] : (tid & 3) == 2 ? e4[2] : e4[3];
+        const float e = eps_bias(tid, sample_base + (uint32_t)(s0 + sp), p.layer_id, p.k0, p.k1);
         Gb += cs;
         Hb = __builtin_fmaf(cs, e, Hb);
       }

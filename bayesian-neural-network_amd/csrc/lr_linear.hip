@@ -77,9 +77,7 @@ struct LrK {
 // global MC sample index (Philox subsequence) of local sample s
 __device__ __forceinline__ uint32_t lr_global_sample(const LrK& p, int s) {
   const uint32_t base = p.sample_offset + (p.sample_counter ? *p.sample_counter : 0u);
-  if (p.sgrp == 0u) return base + (uint32_t)s;
-  const uint32_t g = (uint32_t)s / p.sgrp;
-  return base + g * p.sgrp_stride + ((uint32_t)s - g * p.sgrp);
+  return eps_global_sample(base, (uint32_t)s, p.sgrp, p.sgrp_stride);
 }
 
 #ifdef BNN_STAMPS
@@ -102,7 +100,7 @@ __device__ __forceinline__ void lr_epilogue_item(const LrK& p, int s, uint32_t g
                                                  const float* bias4, const float* eps_pre = nullptr) {
   const int N = p.N, B = p.B;
   const bool vec_ok = (N & 3) == 0;
-  const int gprN = (N + 3) >> 2;
+  const int gprN = (int)eps_groups_per_row(N);
   const size_t yoff = ((size_t)s * B + brow) * N + nb;
   float e4[4] = {0.f, 0.f, 0.f, 0.f};
   if (p.eps_mode == BNN_EPS_PHILOX) {
@@ -110,7 +108,7 @@ __device__ __forceinline__ void lr_epilogue_item(const LrK& p, int s, uint32_t g
 #pragma unroll
       for (int i = 0; i < 4; ++i) e4[i] = eps_pre[i];
     } else {
-      philox_normal4((uint32_t)brow * (uint32_t)gprN + (uint32_t)(nb >> 2), gs, p.layer_id * 4u + 2u, p.k0, p.k1, e4);
+      philox_normal4(eps_group((uint32_t)brow, nb, (uint32_t)gprN), gs, eps_tensor_id(p.layer_id, kEpsLrAct), p.k0, p.k1, e4);
     }
   } else if (p.eps_mode == BNN_EPS_MEMORY) {
 #pragma unroll
@@ -230,9 +228,7 @@ __device__ __forceinline__ void lr_fwd_body(const LrK& p) {
     bmu_pre = p.b_mu[n];
     bsig_pre = softplus(p.b_rho[n]);
     if (p.eps_mode == BNN_EPS_PHILOX) {
-      float e4[4];
-      philox_normal4((uint32_t)(n >> 2), gs, p.layer_id * 4u + 1u, p.k0, p.k1, e4);
-      beps_pre = (n & 3) == 0 ? e4[0] : (n & 3) == 1 ? e4[1] : (n & 3) == 2 ? e4[2] : e4[3];
+      beps_pre = eps_bias(n, gs, p.layer_id, p.k0, p.k1);
     } else if (p.eps_mode == BNN_EPS_MEMORY) {
       beps_pre = p.eps_b[(size_t)s * N + n];
     }
@@ -676,9 +672,7 @@ __global__ __launch_bounds__(512) void lr_fwd_kslice_kernel(const LrK p) {
   if (p.eps_mode == BNN_EPS_MEMORY) beps_mem = p.eps_b[(size_t)s * N + min(n0 + (lane & 31), N - 1)];
   if (bias_lane && p.eps_mode == BNN_EPS_PHILOX) {
     const int n = n0 + lane;
-    float e4[4];
-    philox_normal4((uint32_t)(n >> 2), gs, p.layer_id * 4u + 1u, p.k0, p.k1, e4);
-    beps_phx = (n & 3) == 0 ? e4[0] : (n & 3) == 1 ? e4[1] : (n & 3) == 2 ? e4[2] : e4[3];
+    beps_phx = eps_bias(n, gs, p.layer_id, p.k0, p.k1);
   }
 #pragma unroll
   for (int u = 0; u < PG; ++u) {                               // the arithmetic starts HERE: issued loads stay ahead of it
@@ -747,9 +741,7 @@ __global__ __launch_bounds__(512) void lr_fwd_kslice_kernel(const LrK p) {
         if (spread && se % KSL != ks) continue;                // (spread: the samples whose epilogue runs in this block)
         float be = 0.f;
         if (p.eps_mode == BNN_EPS_PHILOX) {
-          float e4[4];
-          philox_normal4((uint32_t)(n >> 2), gs + (uint32_t)se, p.layer_id * 4u + 1u, p.k0, p.k1, e4);   // (no sample groups here)
-          be = (n & 3) == 0 ? e4[0] : (n & 3) == 1 ? e4[1] : (n & 3) == 2 ? e4[2] : e4[3];
+          be = eps_bias(n, gs + (uint32_t)se, p.layer_id, p.k0, p.k1);   // (no sample groups here)
         } else if (p.eps_mode == BNN_EPS_MEMORY) {
           be = p.eps_b[(size_t)se * N + n];
         }
@@ -846,12 +838,12 @@ __global__ __launch_bounds__(512) void lr_fwd_kslice_kernel(const LrK p) {
   // activation noise of the lane's two output items (drawn by whoever runs the epilogue; the last arriver draws it while
   // the other slices' tiles are in flight)
   const int brow = m0 + wave * 16 + r;
-  const int gprN = (N + 3) >> 2;
+  const int gprN = (int)eps_groups_per_row(N);
   float eps_pre[2][4];
   auto draw_eps = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int ft = 0; ft < 2; ++ft)
-      philox_normal4((uint32_t)brow * (uint32_t)gprN + (uint32_t)((n0 + ft * 16 + q * 4) >> 2), gs, p.layer_id * 4u + 2u, p.k0, p.k1, eps_pre[ft]);
+      philox_normal4(eps_group((uint32_t)brow, n0 + ft * 16 + q * 4, (uint32_t)gprN), gs, eps_tensor_id(p.layer_id, kEpsLrAct), p.k0, p.k1, eps_pre[ft]);
   };
   // ---- hand-off between the slices of the unit
   if (KSL > 1) {
@@ -1212,9 +1204,7 @@ __global__ __launch_bounds__(NW * 64, PREP ? 4 : 3) void lr_fwd_gemm_kernel(cons
     bmu_pre = p.b_mu[n];
     bsig_pre = softplus(p.b_rho[n]);
     if (p.eps_mode == BNN_EPS_PHILOX) {
-      float e4[4];
-      philox_normal4((uint32_t)(n >> 2), gs, p.layer_id * 4u + 1u, p.k0, p.k1, e4);
-      beps_pre = (n & 3) == 0 ? e4[0] : (n & 3) == 1 ? e4[1] : (n & 3) == 2 ? e4[2] : e4[3];
+      beps_pre = eps_bias(n, gs, p.layer_id, p.k0, p.k1);
     } else if (p.eps_mode == BNN_EPS_MEMORY) {
       beps_pre = p.eps_b[(size_t)s * N + n];
     }
@@ -1444,7 +1434,7 @@ __global__ __launch_bounds__(NW * 64, PREP ? 4 : 3) void lr_fwd_gemm_kernel(cons
   __syncthreads();
   const int nb = tile * 16 + q * 4;
   const bool vec_ok = (N & 3) == 0;
-  const int gprN = (N + 3) >> 2;
+  const int gprN = (int)eps_groups_per_row(N);
   if (nb < N) {
     float bq[4];
 #pragma unroll
@@ -1464,7 +1454,7 @@ __global__ __launch_bounds__(NW * 64, PREP ? 4 : 3) void lr_fwd_gemm_kernel(cons
 #else
         if (p.eps_mode == BNN_EPS_PHILOX) {
 #endif
-          philox_normal4((uint32_t)brow * (uint32_t)gprN + (uint32_t)(nb >> 2), gs, p.layer_id * 4u + 2u, p.k0, p.k1, e4);
+          philox_normal4(eps_group((uint32_t)brow, nb, (uint32_t)gprN), gs, eps_tensor_id(p.layer_id, kEpsLrAct), p.k0, p.k1, e4);
         } else if (p.eps_mode == BNN_EPS_MEMORY) {
 #pragma unroll
           for (int i = 0; i < 4; ++i)
@@ -1591,8 +1581,8 @@ __global__ __launch_bounds__(256) void lr_final_rows_kernel(const LrRows p, cons
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int K = p.K, N = p.N, B = p.B;
   float* const mine = p.parts + (size_t)s * 16;
-  uint32_t gs = p.sample_offset + (p.sample_counter ? *p.sample_counter : 0u);
-  if (p.sgrp == 0u) gs += (uint32_t)s;
+  uint32_t gs = p.sample_offset + (p.sample_counter ? *p.sample_counter : 0u);   // eps_global_sample's value in this kernel's own
+  if (p.sgrp == 0u) gs += (uint32_t)s;                                           // spelling (see bbb_sample_body.h)
   else gs += ((uint32_t)s / p.sgrp) * p.sgrp_stride + (uint32_t)s % p.sgrp;
   const bool vec4 = !((reinterpret_cast<uintptr_t>(p.w_mu) | reinterpret_cast<uintptr_t>(p.w_rho)) & 15);
   float pub0 = 0.f;
@@ -1804,10 +1794,10 @@ __global__ __launch_bounds__(256) void lr_final_rows_kernel(const LrRows p, cons
         v += red_v[wv][lane];
       }
       const int brow = rb * 16 + r;
-      const int gprN = (N + 3) >> 2;
+      const int gprN = (int)eps_groups_per_row(N);
       float ea[4], eb[4];
-      philox_normal4((uint32_t)min(brow, B - 1) * (uint32_t)gprN + (uint32_t)q, gs, p.layer_id * 4u + 2u, p.k0, p.k1, ea);
-      philox_normal4((uint32_t)q, gs, p.layer_id * 4u + 1u, p.k0, p.k1, eb);
+      philox_normal4(eps_group_at((uint32_t)min(brow, B - 1), (uint32_t)q, (uint32_t)gprN), gs, eps_tensor_id(p.layer_id, kEpsLrAct), p.k0, p.k1, ea);
+      philox_normal4((uint32_t)q, gs, eps_tensor_id(p.layer_id, kEpsBias), p.k0, p.k1, eb);   // the whole group q: biases 4 q .. 4 q + 3
       float o4[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {

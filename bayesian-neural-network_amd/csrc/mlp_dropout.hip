@@ -220,7 +220,7 @@ __global__ __launch_bounds__(kThreads) void dense_fwd_kernel(DenseParams p) {
       const int sm = p.x_shared ? s : row / p.B, brow = p.x_shared ? row : row - sm * p.B;
       float o[4];
       if (p.drop) {
-        const uint4 rr = philox4x32<>(make_uint4((uint32_t)brow * gpr + ((uint32_t)col0 >> 2), base + (uint32_t)sm, p.tensor_id, 0u),
+        const uint4 rr = philox4x32<>(make_uint4(eps_group((uint32_t)brow, (uint32_t)col0, gpr), base + (uint32_t)sm, p.tensor_id, 0u),
                                       p.k0, p.k1);
         o[0] = rr.x >= p.thr ? v[0] * p.scale : 0.f;
         o[1] = rr.y >= p.thr ? v[1] * p.scale : 0.f;
@@ -377,7 +377,7 @@ extern "C" int bnn_dense_fwd(const bnn_dense_fwd_args* a, void* stream_) {
   p.vec_y = a->out_features % 4 == 0 && !misaligned(a->y, 4 * yb);
   p.k0 = (uint32_t)a->seed;
   p.k1 = (uint32_t)(a->seed >> 32);
-  p.tensor_id = 4u * (uint32_t)a->layer_id + 3u;
+  p.tensor_id = eps_tensor_id((uint32_t)a->layer_id, kEpsDropout);
   p.sample_base = a->sample_offset;
   p.inc = a->sample_counter_inc;
   p.counter = a->sample_counter;
@@ -418,7 +418,7 @@ extern "C" int bnn_dropout_mask(float* mask, uint64_t seed, uint32_t layer_id, u
   long nb = (total + 255) / 256;
   if (nb > 4096) nb = 4096;
   hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream_), mask,
-                     (uint32_t)seed, (uint32_t)(seed >> 32), 4u * layer_id + 3u, sample_offset, n_samples, rows, cols, thr, scale);
+                     (uint32_t)seed, (uint32_t)(seed >> 32), eps_tensor_id(layer_id, kEpsDropout), sample_offset, n_samples, rows, cols, thr, scale);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? BNN_OK : (int)err;
 }

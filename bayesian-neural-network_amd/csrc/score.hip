@@ -25,7 +25,7 @@ constexpr int kRowsPerWave = 8;
 constexpr int kRowsPerBlock = kScoreWaves * kRowsPerWave;
 constexpr int kHeadWords = 8;
 constexpr int kMaxWords = kHeadWords + 3 * BNN_SCORE_MAX_BINS;
-constexpr double kHalfLog2Pi = 0.91893853320467274178;
+constexpr double kHalfLog2Pi = -kNegLogSqrt2Pi;
 constexpr double kInvSqrt2 = 0.70710678118654752440;
 
 struct ScoreK {

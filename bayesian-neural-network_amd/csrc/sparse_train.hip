@@ -25,7 +25,6 @@
 //   L1 read rate stage B, as in the forward.
 #include "bnn_device.h"
 #include "bnn_prior.h"
-#include "bbb_sample_body.h"      // sample_mix_p: the log-prior term of the dense sampling kernel K1s
 #include "../../include/bnn_hip.h"
 #include <math.h>
 
@@ -38,6 +37,8 @@ constexpr int kWaveEntries = 16;       // entries per wave of the weight-gradien
 constexpr int kGxChunk = 512;          // entries per stage of the input-gradient kernel: 2 x 512 x 8 bytes of LDS
 constexpr int kMaxCG = 32;
 
+// eps_slot's value (bnn_device.h) with the loads left under the branches, where the compiler sinks the Box-Muller half a thread
+// does not need: with eps_slot's select over four values the captured sparse step measured 0.5 - 1 % slower, so this form stays
 __device__ __forceinline__ float pick4(const float n4[4], int slot) {
   return slot == 0 ? n4[0] : slot == 1 ? n4[1] : slot == 2 ? n4[2] : n4[3];
 }
@@ -72,7 +73,7 @@ struct TermsK {
   uint32_t k0, k1, sample_offset;
   const uint32_t* sample_counter;
   int prior_kind;
-  SampleMix mix;
+  PriorMix mix;
   double lp_const, inv2var;                  // Gaussian: c0 - log sigma_p, 1 / (2 sigma_p^2)
   float4* part;                              // [S][total_blocks]: (sum eps^2, sum w^2 | log mixture, sum log sigma, kept biases)
   float* log_prior;
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(kTermThreads) void sparse_terms_kernel(const TermsK
   if (local < L.entry_blocks) {
     const int nnz = min(L.nnz, L.row_ptr[L.out]);
     const int span0 = local * kTermSpan, span1 = min(span0 + kTermSpan, nnz);
-    const uint32_t gpr = (uint32_t)((L.in + 3) >> 2);
+    const uint32_t gpr = eps_groups_per_row(L.in);
     for (int j = span0 + (int)threadIdx.x; j < span1; j += kTermThreads) {
       const int c = (int)L.col[j];
       const int o = row_of(L.row_ptr, L.out, j);
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kTermThreads) void sparse_terms_kernel(const TermsK
       const bool follower = j > span0 && j - 1 >= row_lo && ((int)L.col[j - 1] >> 2) == (c >> 2);
       if (follower) continue;
       float n4[4];
-      philox_normal4((uint32_t)o * gpr + (uint32_t)(c >> 2), gs, 4u * L.layer_id, p.k0, p.k1, n4);
+      philox_normal4((uint32_t)o * gpr + (uint32_t)(c >> 2), gs, eps_tensor_id(L.layer_id, kEpsWeight), p.k0, p.k1, n4);   // eps_group(o, c, gpr)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int jq = j + q;
@@ -115,20 +116,20 @@ __global__ __launch_bounds__(kTermThreads) void sparse_terms_kernel(const TermsK
         const float sg = L.sigma[jq];
         const float w = __builtin_fmaf(sg, ev, L.mu[jq]);
         e2 = __builtin_fmaf(ev, ev, e2);
-        a = gauss ? __builtin_fmaf(w, w, a) : add_log(a, sample_mix_p(p.mix, w));
+        a = gauss ? __builtin_fmaf(w, w, a) : add_log(a, prior_mix_p(p.mix, w));
         if (do_ls) ls = add_log(ls, sg);
       }
     }
   } else {
     const int o = (local - L.entry_blocks) * kTermThreads + (int)threadIdx.x;
     if (o < L.out && L.b_keep[o]) {
-      float n4[4];
-      philox_normal4((uint32_t)(o >> 2), gs, 4u * L.layer_id + 1u, p.k0, p.k1, n4);
+      float n4[4];                                                     // eps_bias, with pick4
+      philox_normal4((uint32_t)(o >> 2), gs, eps_tensor_id(L.layer_id, kEpsBias), p.k0, p.k1, n4);
       const float ev = pick4(n4, o & 3);
       const float sg = L.b_sigma[o];
       const float w = __builtin_fmaf(sg, ev, L.b_mu[o]);
       e2 = __builtin_fmaf(ev, ev, e2);
-      a = gauss ? __builtin_fmaf(w, w, a) : add_log(a, sample_mix_p(p.mix, w));
+      a = gauss ? __builtin_fmaf(w, w, a) : add_log(a, prior_mix_p(p.mix, w));
       if (do_ls) ls = add_log(ls, sg);
       cnt = 1.f;
     }
@@ -154,7 +155,6 @@ __global__ __launch_bounds__(kTermThreads) void sparse_terms_kernel(const TermsK
 __global__ __launch_bounds__(kTermThreads) void sparse_terms_fold_kernel(const TermsK p) {
   __shared__ double sh[kTermThreads][4];
   const int s = blockIdx.x, t = threadIdx.x;
-  const double c0 = -0.91893853320467274178;
   float a_tot = 0.f, b_tot = 0.f;
   for (int l = 0; l < p.n_layers; ++l) {
     const TermsL& L = p.L[l];
@@ -175,7 +175,8 @@ __global__ __launch_bounds__(kTermThreads) void sparse_terms_fold_kernel(const T
     }
     if (t == 0) {
       const double cnt = (double)min(L.nnz, L.row_ptr[L.out]) + sh[0][3];
-      const double lq = cnt * c0 - sh[0][2] - 0.5 * sh[0][0];
+      const double lq = fold_log_q(cnt * kNegLogSqrt2Pi, sh[0][2], sh[0][0]);
+      // fold_log_p's value, the count applied under the branch as this kernel was built (it counts the survivors itself)
       const double lp = p.prior_kind == BNN_PRIOR_GAUSS ? cnt * p.lp_const - sh[0][1] * p.inv2var : sh[0][1];
       a_tot += (float)lp;
       b_tot += (float)lq;
@@ -265,8 +266,8 @@ __global__ __launch_bounds__(256) void sparse_bwd_weights_kernel(const BwdS p) {
     const float bsg = softplus(brh);
     float G = 0.f, H = 0.f;
     for (int sb = 0; sb < S; sb += 64) {
-      float n4[4];
-      philox_normal4((uint32_t)(o >> 2), gs0 + (uint32_t)(sb + lane), 4u * p.layer_id + 1u, p.k0, p.k1, n4);   // lane = sample
+      float n4[4];                                                     // eps_bias, with pick4; lane = sample
+      philox_normal4((uint32_t)(o >> 2), gs0 + (uint32_t)(sb + lane), eps_tensor_id(p.layer_id, kEpsBias), p.k0, p.k1, n4);
       const float el = pick4(n4, o & 3);
       const int ns = min(64, S - sb);
       for (int si = 0; si < ns; ++si) {
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(256) void sparse_bwd_weights_kernel(const BwdS p) {
   if (e >= e_end) return;                                               // wave-uniform
   int o = row_of(p.row_ptr, out, e);
   int row_end = p.row_ptr[o + 1];
-  const uint32_t gpr = (uint32_t)((in + 3) >> 2);
+  const uint32_t gpr = eps_groups_per_row(in);
   while (e < e_end) {
     while (row_end <= e && o + 1 < out) {                               // rows that end here (empty ones among them)
       ++o;
@@ -322,7 +323,7 @@ __global__ __launch_bounds__(256) void sparse_bwd_weights_kernel(const BwdS p) {
     float G[4] = {0.f, 0.f, 0.f, 0.f}, H[4] = {0.f, 0.f, 0.f, 0.f};
     for (int sb = 0; sb < S; sb += 64) {
       float n4[4];
-      philox_normal4((uint32_t)o * gpr + (uint32_t)(cc[0] >> 2), gs0 + (uint32_t)(sb + lane), 4u * p.layer_id, p.k0, p.k1, n4);
+      philox_normal4(eps_group((uint32_t)o, cc[0], gpr), gs0 + (uint32_t)(sb + lane), eps_tensor_id(p.layer_id, kEpsWeight), p.k0, p.k1, n4);
       const int ns = min(64, S - sb);
       for (int si = 0; si < ns; ++si) {
         const int s = sb + si;
@@ -383,7 +384,7 @@ __global__ __launch_bounds__(256) void sparse_bwd_input_kernel(const BwdS p, int
   const float* __restrict__ gzp = p.gz + (size_t)s * out * rows;
   const float* __restrict__ xp = p.x + (size_t)(p.x_per_sample > 0 ? s / p.x_per_sample : 0) * in * rows;
   float* __restrict__ gxp = p.gx + (size_t)s * in * rows;
-  const uint32_t gpr = (uint32_t)((in + 3) >> 2);
+  const uint32_t gpr = eps_groups_per_row(in);
   auto emit = [&](int cl, float acc) {
     if (live) {
       const size_t at = (size_t)(c0 + cl) * rows + r;
@@ -405,7 +406,7 @@ __global__ __launch_bounds__(256) void sparse_bwd_input_kernel(const BwdS p, int
       const int pm = min(max(p.perm[k], 0), nnz - 1);
       const int c = c0 + row_of(s_cp, nc, k);
       float n4[4];
-      philox_normal4((uint32_t)o * gpr + (uint32_t)(c >> 2), gs, 4u * p.layer_id, p.k0, p.k1, n4);
+      philox_normal4(eps_group((uint32_t)o, c, gpr), gs, eps_tensor_id(p.layer_id, kEpsWeight), p.k0, p.k1, n4);
       se[e].w = __builtin_fmaf(softplus(p.rho[pm]), pick4(n4, c & 3), p.mu[pm]);
       se[e].o = o;
     }
@@ -487,9 +488,7 @@ extern "C" int bnn_sparse_elbo_terms(const bnn_sparse_elbo_args* a, void* stream
     nnzs[l] = y.nnz;
     outs[l] = y.out_features;
   }
-  if ((unsigned)a->prior.kind > 1u) return BNN_ERR_ENUM;
-  if (a->prior.kind == BNN_PRIOR_MIXTURE ? (!(a->prior.sigma1 > 0.f) || !(a->prior.sigma2 > 0.f)) : !(a->prior.sigma_p > 0.f))
-    return BNN_ERR_SHAPE;
+  if (const int rc = prior_check(a->prior)) return rc;
   if (!a->log_prior || !a->log_q) return BNN_ERR_NULL;
   for (int l = 0; l < a->n_layers; ++l) {
     const bnn_sparse_elbo_layer& y = a->layer[l];
@@ -525,16 +524,12 @@ extern "C" int bnn_sparse_elbo_terms(const bnn_sparse_elbo_args* a, void* stream
   k.k0 = (uint32_t)a->seed; k.k1 = (uint32_t)(a->seed >> 32);
   k.sample_offset = a->sample_offset; k.sample_counter = a->sample_counter;
   k.prior_kind = a->prior.kind;
-  const double c0 = -0.91893853320467274178;
-  k.mix.pi = a->prior.pi;
-  k.mix.inv2var1 = k.mix.inv2var2 = k.mix.c1 = k.mix.c2 = 0.f;
+  k.mix = prior_mix_make(a->prior);
   k.lp_const = 0; k.inv2var = 0;
-  if (a->prior.kind == BNN_PRIOR_MIXTURE) {
-    k.mix = sample_mix_make(a->prior);                                   // bbb_sample_body.h: the dense sampling kernel's
-  } else {                                                               // K4's (bnn_fin.h)
-    const double sp = a->prior.sigma_p;
-    k.lp_const = c0 - log(sp);
-    k.inv2var = 1.0 / (2.0 * sp * sp);
+  if (a->prior.kind == BNN_PRIOR_GAUSS) {
+    const PriorFold f = prior_fold_make(a->prior, 1.0);                  // per element: the kernel knows the count
+    k.lp_const = f.lp_const;
+    k.inv2var = f.inv2var;
   }
   k.part = reinterpret_cast<float4*>(a->workspace);
   k.log_prior = a->log_prior; k.log_q = a->log_q;
@@ -561,9 +556,9 @@ extern "C" int bnn_sparse_bwd(const bnn_sparse_bwd_args* a, void* stream_) {
   const int bdim = 64 * waves;
   const long batch_blocks = (a->rows + bdim - 1) / bdim;
   if (a->g_x && batch_blocks > 65535) return BNN_ERR_SHAPE;             // the input gradient's grid: 256 rows per block
-  if ((unsigned)a->prior.kind > 1u) return BNN_ERR_ENUM;
+  if (const int rc = prior_check(a->prior)) return rc;
   BwdS k;
-  if (prior_dlogp_fill(a->prior, k) != BNN_OK) return BNN_ERR_SHAPE;
+  prior_dlogp_fill(a->prior, k);
   if (!a->row_ptr || !a->col || !a->mu_val || !a->rho_val || !a->b_mu || !a->b_rho || !a->b_keep || !a->x || !a->gy ||
       !a->g_mu_val || !a->g_rho_val || !a->g_b_mu || !a->g_b_rho)
     return BNN_ERR_NULL;

@@ -38,7 +38,9 @@
  *       u(r) = fma((float)r, 2^-32, 2^-33)                  in (0,1]
  *       slot 0,1 = sqrt(-2 ln u(r0)) * {cos, sin}(2 pi u(r1)); slot 2,3 likewise from r2,r3
  *       eps[row, col] = slot (col & 3)
- *   oracle/bnn_oracle.py:philox_normal restates this on the CPU.
+ *   oracle/bnn_oracle.py:philox_normal restates this on the CPU.  On the device the map is stated once, next to the generator
+ *   in csrc/bnn_device.h: kEpsWeight .. kEpsDropout, eps_tensor_id, eps_groups_per_row, eps_group, eps_slot, eps_bias,
+ *   eps_global_sample; every kernel's forward and backward call those.
  *   Kind 3: the MC-dropout uniform of the activations that leave Linear layer l (an MLP_Dropout's nn.Dropout after the
  *   ReLU of Linear l), logical shape [batch, features], same counter layout, t = 4*l + 3:
  *       (r0,r1,r2,r3) = Philox4x32-R((group, g, 4*l + 3, 0), key)
