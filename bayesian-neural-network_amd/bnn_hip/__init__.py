@@ -15,10 +15,14 @@
 `laplace`    DiagLaplace: a diagonal Laplace posterior for a trained MLP / MLP_Dropout, Fisher accumulation on the device, the prior
              precision by the marginal likelihood, the result a BayesianNetwork (F17)
 `diagnostics` PosteriorStats: weight / sigma / SNR / posterior-sample histograms of a model in one device pass (F11)
+`sgmcmc`     FusedSGMCMC / WeightBank: SGLD / SGHMC in the optimiser's place of K6's captured step, the samples filed into a
+             device-resident bank of weight sets that predicts as an ensemble, one launch per layer for all members (F19)
 """
 from .runtime import get_math, manual_seed, set_host_eps, set_math, shard_samples  # noqa: F401
 from ._lib import BnnHipError  # noqa: F401
 from .active import ActiveLearner, ActivePool  # noqa: F401
 from .laplace import DiagLaplace  # noqa: F401
+from .sgmcmc import FusedSGMCMC, WeightBank  # noqa: F401
 
-__all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError", "ActiveLearner", "ActivePool", "DiagLaplace"]
+__all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError", "ActiveLearner", "ActivePool", "DiagLaplace",
+           "FusedSGMCMC", "WeightBank"]

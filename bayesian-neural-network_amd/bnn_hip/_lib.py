@@ -47,6 +47,7 @@ EXPORTS = (
     "bnn_flipout_prepare_workspace_bytes", "bnn_flipout_bwd_workspace_bytes",
     "bnn_laplace_seed", "bnn_laplace_layer", "bnn_laplace_evidence", "bnn_laplace_posterior", "bnn_laplace_evidence_workspace_bytes",
     "bnn_laplace_glm_layer", "bnn_laplace_glm_finish", "bnn_laplace_glm_sample",
+    "bnn_sgmcmc_noise", "bnn_sgmcmc_step", "bnn_bank_fwd",
 )
 
 
@@ -577,6 +578,29 @@ class LaplaceGlmSampleArgs(C.Structure):
                 ("mean", C.c_void_p), ("chol", C.c_void_p), ("logits", C.c_void_p), ("sample_counter", C.c_void_p)]
 
 
+SGMCMC_MAX_TENSORS = 16
+SGMCMC_TABLE_COLS = 4
+
+
+class SgmcmcArgs(C.Structure):
+    """bnn_sgmcmc_args (include/bnn_hip.h F19): one SGLD / SGHMC step over every parameter tensor"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_tensors", C.c_int32), ("param", C.c_void_p * SGMCMC_MAX_TENSORS),
+                ("grad", C.c_void_p * SGMCMC_MAX_TENSORS), ("momentum", C.c_void_p * SGMCMC_MAX_TENSORS),
+                ("noise", C.c_void_p * SGMCMC_MAX_TENSORS), ("numel", C.c_int64 * SGMCMC_MAX_TENSORS),
+                ("grad_scale", C.c_float), ("tau", C.c_float), ("eps_mode", C.c_int32), ("table_rows", C.c_int32),
+                ("table", C.c_void_p), ("seed", C.c_uint64), ("step", C.c_void_p), ("collected", C.c_void_p),
+                ("ticket", C.c_void_p), ("burn_in", C.c_uint32), ("capacity", C.c_int32), ("bank", C.c_void_p)]
+
+
+class BankFwdArgs(C.Structure):
+    """bnn_bank_fwd_args (include/bnn_hip.h F19): one Linear -> [ReLU] layer for the members of a weight bank"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("members", C.c_int32), ("first", C.c_int32), ("batch", C.c_int32),
+                ("in_features", C.c_int32), ("out_features", C.c_int32), ("x_shared", C.c_int32), ("relu", C.c_int32),
+                ("x", C.c_void_p), ("x_dtype", C.c_int32), ("math", C.c_int32), ("w", C.c_void_p), ("b", C.c_void_p),
+                ("w_stride", C.c_int64), ("b_stride", C.c_int64), ("y", C.c_void_p), ("y_dtype", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 HIST_MAX_JOBS = 16
 HIST_MAX_EDGES = 2048
 HIST_CHUNK = 8192
@@ -909,6 +933,11 @@ def _load_real():
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     lib.bnn_laplace_evidence_workspace_bytes.restype = C.c_size_t
     lib.bnn_laplace_evidence_workspace_bytes.argtypes = [C.POINTER(LaplaceEvidenceArgs)]
+    lib.bnn_sgmcmc_noise.restype = C.c_int
+    lib.bnn_sgmcmc_noise.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int64, C.c_void_p]
+    for name, cls in (("bnn_sgmcmc_step", SgmcmcArgs), ("bnn_bank_fwd", BankFwdArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

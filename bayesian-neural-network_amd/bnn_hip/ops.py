@@ -3016,3 +3016,118 @@ def laplace_glm_sample(mean, chol, n_samples: int, *, seed: int, sample_base: in
         a.sample_counter = _typed(sample_counter, torch.int32, "sample_counter", 1).data_ptr()
     L.check(lib.bnn_laplace_glm_sample(C.byref(a), _stream()), "bnn_laplace_glm_sample")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- F19 SG-MCMC
+def sgmcmc_noise(seed: int, tensor: int, step: int, numel: int, device) -> torch.Tensor:
+    """F19 bnn_sgmcmc_noise: the SG-MCMC noise stream of parameter tensor `tensor` at chain step `step`, materialised:
+    float32[numel] (counter (i >> 2, step, tensor, 3), slot i & 3)."""
+    lib = L.load()
+    if torch.device(device).type != "cuda":
+        raise BnnHipError("bnn_hip.sgmcmc_noise needs a ROCm device")
+    if not 0 <= int(tensor) < L.SGMCMC_MAX_TENSORS or int(numel) < 1:
+        raise BnnHipError(f"sgmcmc_noise: tensor must lie in [0, {L.SGMCMC_MAX_TENSORS}) and numel be >= 1")
+    out = torch.empty(int(numel), dtype=torch.float32, device=device)
+    L.check(lib.bnn_sgmcmc_noise(out.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tensor), int(step) & 0xFFFFFFFF, int(numel),
+                                 _stream()), "bnn_sgmcmc_noise")
+    return out
+
+
+def bank_layout(numels: Sequence[int]) -> tuple:
+    """(offsets, stride) of a weight bank's member: every tensor starts at a multiple of 64 elements."""
+    offs, tot = [], 0
+    for n in numels:
+        offs.append(tot)
+        tot += (int(n) + 63) // 64 * 64
+    return tuple(offs), tot
+
+
+def sgmcmc_step(params, grads, *, table: torch.Tensor, step: torch.Tensor, ticket: torch.Tensor, grad_scale: float, tau: float,
+                eps_mode: int = L.EPS_PHILOX, seed: int = 0, momenta=None, noise=None, burn_in: int = 0, collected=None,
+                bank: Optional[torch.Tensor] = None):
+    """F19 bnn_sgmcmc_step: one SGLD (momenta None) / SGHMC step over lists of fp32 tensors in one launch.  `table`: device
+    float32 [L, 4] rows (a, b, c, collect flag); `step`, `collected`: one-element int32 device words (read as uint32), `ticket`
+    16 zeroed int32 words; `noise`: one tensor per parameter (EPS_MEMORY).  `bank`: float32 [capacity, stride] with the
+    stride of bank_layout -- the step files its result into member collected % capacity when its table row says so."""
+    lib = L.load()
+    n = len(params)
+    if not 1 <= n <= L.SGMCMC_MAX_TENSORS:
+        raise BnnHipError(f"sgmcmc_step: between 1 and {L.SGMCMC_MAX_TENSORS} parameter tensors, got {n}")
+    if len(grads) != n or (momenta is not None and len(momenta) != n) or (eps_mode == L.EPS_MEMORY and (noise is None or len(noise) != n)):
+        raise BnnHipError("sgmcmc_step: one gradient (momentum, noise) tensor per parameter")
+    require_device(table, step, ticket, collected, bank)
+    if table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != L.SGMCMC_TABLE_COLS or not table.is_contiguous() or \
+            table.shape[0] < 1:
+        raise BnnHipError(f"sgmcmc_step: table must be a contiguous float32 [L, {L.SGMCMC_TABLE_COLS}] tensor")
+    _typed(step, torch.int32, "step", 1)
+    _typed(ticket, torch.int32, "ticket", 16)
+    a = L.SgmcmcArgs()
+    a.struct_bytes = C.sizeof(L.SgmcmcArgs)
+    a.n_tensors = n
+    keep = [table, step, ticket, collected, bank]
+    for j in range(n):
+        ts = [params[j], grads[j]] + ([momenta[j]] if momenta is not None else []) + ([noise[j]] if eps_mode == L.EPS_MEMORY else [])
+        for t in ts:
+            require_device(t)
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != params[j].numel():
+                raise BnnHipError("sgmcmc_step: parameters, gradients, momenta and noise must be contiguous float32 of one size")
+        keep += ts
+        a.param[j], a.grad[j], a.numel[j] = params[j].data_ptr(), grads[j].data_ptr(), params[j].numel()
+        if momenta is not None:
+            a.momentum[j] = momenta[j].data_ptr()
+        if eps_mode == L.EPS_MEMORY:
+            a.noise[j] = noise[j].data_ptr()
+    a.grad_scale, a.tau, a.eps_mode = float(grad_scale), float(tau), int(eps_mode)
+    a.table_rows, a.table = table.shape[0], table.data_ptr()
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.step, a.ticket, a.burn_in = step.data_ptr(), ticket.data_ptr(), int(burn_in) & 0xFFFFFFFF
+    if bank is not None:
+        stride = bank_layout([p.numel() for p in params])[1]
+        if bank.dtype != torch.float32 or bank.dim() != 2 or bank.shape[1] != stride or not bank.is_contiguous() or bank.shape[0] < 1:
+            raise BnnHipError(f"sgmcmc_step: the bank must be a contiguous float32 [capacity, {stride}] tensor")
+        if collected is None:
+            raise BnnHipError("sgmcmc_step: a bank needs its `collected` word")
+        a.collected = _typed(collected, torch.int32, "collected", 1).data_ptr()
+        a.bank, a.capacity = bank.data_ptr(), bank.shape[0]
+    a._keep = keep
+    L.check(lib.bnn_sgmcmc_step(C.byref(a), _stream()), "bnn_sgmcmc_step")
+
+
+def bank_fwd(x: torch.Tensor, bank: torch.Tensor, w_off: int, b_off: Optional[int], *, out_features: int, members: int,
+             first: int = 0, relu: bool = False, math_mode: int = L.MATH_F32, y_dtype=torch.float32, out=None) -> torch.Tensor:
+    """F19 bnn_bank_fwd: y[j] = act(x[j or shared] . W[first + j]^T + b[first + j]) for `members` members of `bank` (float32
+    [capacity, stride]) in one launch; member m's [out, in] weights start at bank[m, w_off], its bias at bank[m, b_off] (None:
+    no bias).  x [B, in] (shared) or [members, B, in]; returns [members, B, out] of y_dtype.  Bit-equal per member to
+    dense_fwd(x_j, W_m, b_m, n_samples=1, drop_p=0)."""
+    lib = L.load()
+    require_device(x, bank, out)
+    M, first, N = int(members), int(first), int(out_features)
+    if bank.dtype != torch.float32 or bank.dim() != 2 or not bank.is_contiguous():
+        raise BnnHipError("bank_fwd: the bank must be a contiguous float32 [capacity, stride] tensor")
+    if M < 1 or first < 0 or first + M > bank.shape[0]:
+        raise BnnHipError(f"bank_fwd: members [{first}, {first + M}) lie outside the bank's {bank.shape[0]} slots")
+    if x.dim() == 2:
+        shared, B, K = 1, x.shape[0], x.shape[1]
+    elif x.dim() == 3 and x.shape[0] == M:
+        shared, B, K = 0, x.shape[1], x.shape[2]
+    else:
+        raise BnnHipError(f"bank_fwd: x must be [batch, in] or [{M}, batch, in], got {tuple(x.shape)}")
+    stride = bank.shape[1]
+    if N < 1 or w_off < 0 or w_off + N * K > stride or (b_off is not None and (b_off < 0 or b_off + N > stride)):
+        raise BnnHipError("bank_fwd: the layer's weights / bias lie outside a member")
+    x = x if x.is_contiguous() else x.contiguous()
+    if out is None:
+        out = torch.empty((M, B, N), dtype=y_dtype, device=x.device)
+    elif tuple(out.shape) != (M, B, N) or not out.is_contiguous():
+        raise BnnHipError(f"bank_fwd: out must be a contiguous [{M}, {B}, {N}] tensor")
+    a = L.BankFwdArgs()
+    a.struct_bytes = C.sizeof(L.BankFwdArgs)
+    a.members, a.first, a.batch, a.in_features, a.out_features = M, first, B, K, N
+    a.x_shared, a.relu, a.x, a.x_dtype, a.math = shared, int(bool(relu)), x.data_ptr(), _dt(x), int(math_mode)
+    a.w, a.w_stride = bank.data_ptr() + 4 * int(w_off), stride
+    if b_off is not None:
+        a.b, a.b_stride = bank.data_ptr() + 4 * int(b_off), stride
+    a.y, a.y_dtype = out.data_ptr(), _dt(out)
+    a._keep = (x, bank, out)
+    L.check(lib.bnn_bank_fwd(C.byref(a), _stream()), "bnn_bank_fwd")
+    return out

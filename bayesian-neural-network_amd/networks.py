@@ -29,6 +29,7 @@ from bnn_hip import dense_train as _dense_train
 from bnn_hip import mcdropout as _mcdropout
 from bnn_hip import flipout as _flipout
 from bnn_hip import laplace as _laplace
+from bnn_hip import sgmcmc as _sgmcmc
 from bnn_hip.functional import BBBLinearFn as _BBBLinearFn
 from bnn_hip.functional import LayerCall as _LayerCall
 from bnn_hip.functional import LRLinearFn as _LRLinearFn
@@ -416,6 +417,21 @@ class _PlainMLP(nn.Module):
         la.fit_prior_precision(); bnn = la.network()` gives a BayesianNetwork centred on these weights.  MLP_Dropout: with
         the dropout off (mlp.eval())."""
         return _laplace.DiagLaplace(self, **kw)
+
+    def weight_bank(self, capacity):
+        """Extension (not in the reference): an empty bnn_hip.sgmcmc.WeightBank of `capacity` weight sets of this network on
+        the device -- where a deep ensemble puts its members (`bank.push(mlp)` after training each) and predicts from them
+        (`bank.predictive(x)`, `bank.score(x, y)`, `bank.evaluate(loader)`): one launch per layer for all members."""
+        return _sgmcmc.WeightBank(self, int(capacity))
+
+    def sgmcmc(self, lr=1e-3, *, capacity=30, **kw):
+        """Extension (not in the reference): `(sampler, bank)` wired together -- a bnn_hip.sgmcmc.FusedSGMCMC over this
+        network's parameters (SGLD; `friction=alpha` for SGHMC; `cycle_length` for the cyclical schedule; `dataset_size`
+        and `batch_size` are required) that files every `thin`-th step after `burn_in` into a WeightBank of `capacity`
+        members.  `step = mlp.graphed_train_step(sampler, x, y)` then samples as it trains; the documented target is MLP
+        (an MLP_Dropout's dropout is more gradient noise, and its members predict with the dropout off)."""
+        bank = _sgmcmc.WeightBank(self, int(capacity))
+        return _sgmcmc.FusedSGMCMC(self.parameters(), lr, bank=bank, **kw), bank
 
 
 class MLP(_PlainMLP):

@@ -2411,6 +2411,96 @@ int bnn_laplace_glm_finish(const bnn_laplace_glm_finish_args* args, void* stream
 int bnn_laplace_glm_sample(const bnn_laplace_glm_sample_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F19  stochastic-gradient MCMC for MLP / MLP_Dropout (not in the reference: SGLD, Welling & Teh 2011; SGHMC, Chen et al. 2014;
+ * the cyclical schedule of Zhang et al. 2020) and a device-resident bank of weight snapshots that predicts as an ensemble.
+ *
+ * The SG-MCMC noise stream.  Element i of parameter tensor t (its index in the launch's tensor list, 0 ..
+ *   BNN_SGMCMC_MAX_TENSORS - 1) at chain step k:
+ *       counter = (i >> 2, k, t, 3), key = (seed_lo, seed_hi), slot i & 3 by the map's Box-Muller (top of this file)
+ *   Counter word 3 = 3: every epsilon stream has word 3 = 0, the bandit / epoch / acquisition / BatchBALD / GLM streams word
+ *   3 = 1 and Flipout's signs word 3 = 2, so no existing stream moved and BNN_EPS_MAP_VERSION stays 2.  A pure function of
+ *   (seed, k, t, i): the other tensors of the launch and the grid do not enter.
+ * bnn_sgmcmc_noise — the stream materialised, out[i] for i < numel (for tests; the sampler never reads it).
+ *   Errors: out NULL: BNN_ERR_NULL; numel outside [1, 2^34] or tensor >= BNN_SGMCMC_MAX_TENSORS: BNN_ERR_SHAPE; BNN_ERR_ALIGN.
+ *
+ * bnn_sgmcmc_step — one sampler step over up to BNN_SGMCMC_MAX_TENSORS fp32 tensors in ONE launch.  With k the value of the
+ *   device word *step before the launch and (a, b, c, flag) = table[k % table_rows], every element does, in fp32 with the
+ *   fused multiply-adds written out,
+ *       g  = fma(grad_scale, grad, tau * p)        grad: of the SUM loss over the minibatch; grad_scale = N_data / batch
+ *       v' = fma(c, eps, fma(-a, g, b * v))        v = 0 and v' not stored when momentum[0] == NULL
+ *       p' = p + v'
+ *   SGLD is the table a = lr / 2, b = 0, c = sqrt(lr T) without momentum; SGHMC a = lr, b = 1 - alpha, c = sqrt(2 alpha lr T).
+ *   The host builds the table in fp64 and rounds once; no transcendental of the rule runs on the device.  eps by eps_mode:
+ *   BNN_EPS_PHILOX the stream above at step k, BNN_EPS_MEMORY noise[t][i], BNN_EPS_ZERO 0.
+ *   Every block reads *step before its update; the block that arrives last stores k + 1 (the ticketed hand-off of
+ *   bnn_adam_step; ticket: 16 zeroed uint32 words, left zeroed).  No tick launch, no float atomics.
+ *   The bank (optional): fp32 [capacity, stride], stride = sum_t round_up(numel[t], 64); element i of tensor t of member m at
+ *   bank[m * stride + off_t + i], off_t = sum_{u < t} round_up(numel[u], 64).  When k >= burn_in and flag != 0 every thread
+ *   also stores p' into member *collected % capacity (*collected read before the update), and the last block advances
+ *   *collected with *step: a ring that overwrites its oldest member; the padding words are never written.
+ *   Errors, in this order: NULL args; ABI; n_tensors outside [1, BNN_SGMCMC_MAX_TENSORS], table_rows < 1, (bank) capacity < 1, a
+ *   numel outside [1, 2^34]: BNN_ERR_SHAPE; eps_mode: BNN_ERR_ENUM; table, step, ticket, (bank) collected, a param, a grad, a
+ *   momentum when momentum[0] is given (or one given when it is not), (BNN_EPS_MEMORY) a noise NULL: BNN_ERR_NULL; BNN_ERR_ALIGN
+ *   (tensors, table and bank 16 bytes, words 4).
+ *
+ * bnn_bank_fwd — one Linear -> [ReLU] layer for `members` members of a bank in ONE launch:
+ *       y[j] = act(x[j or shared] . W[first + j]^T + b[first + j]),   j < members
+ *   W[m] = w + m * w_stride ([out, in] fp32), b[m] = b + m * b_stride (fp32 [out]; b may be NULL); x [batch, in] shared by the
+ *   members (x_shared = 1: layer 1) or [members, batch, in]; y [members, batch, out].  x and y fp32 or bf16 by bnn_dense_fwd's
+ *   rules (bf16 only in BNN_MATH_BF16).  One block owns a 64 x 64 tile of ONE member's batch x out problem; a row tile never
+ *   straddles two members.  An output element is bnn_dense_fwd's chain: 32-wide k stages in order, v_mfma_f32_16x16x32_bf16
+ *   per stage in bf16 math, eight v_mfma_f32_16x16x4_f32 in exact-fp32 math, accumulators from zero, then + b, then max(., 0)
+ *   -- member j's output is bit-equal to bnn_dense_fwd on (x[j], W[first + j], b[first + j]) with n_samples = 1, drop_p = 0.
+ *   Members outside [first, first + members) are not read.
+ *   Errors, in this order: NULL args; ABI; members, batch, in_features, out_features < 1, first < 0, a negative stride, more
+ *   than 2^30 tiles: BNN_ERR_SHAPE; math, dtypes, bf16 activations outside BNN_MATH_BF16: BNN_ERR_ENUM; x, w, y NULL:
+ *   BNN_ERR_NULL; BNN_ERR_ALIGN (element size).
+ * ---------------------------------------------------------------------------------- */
+#define BNN_SGMCMC_MAX_TENSORS 16
+#define BNN_SGMCMC_TABLE_COLS 4           /* a, b, c, collect flag */
+
+typedef struct bnn_sgmcmc_args {
+  uint32_t struct_bytes;
+  int32_t n_tensors;
+  float* param[BNN_SGMCMC_MAX_TENSORS];
+  const float* grad[BNN_SGMCMC_MAX_TENSORS];
+  float* momentum[BNN_SGMCMC_MAX_TENSORS];       /* all NULL: no momentum buffer (SGLD) */
+  const float* noise[BNN_SGMCMC_MAX_TENSORS];    /* BNN_EPS_MEMORY */
+  int64_t numel[BNN_SGMCMC_MAX_TENSORS];
+  float grad_scale, tau;
+  int32_t eps_mode;         /* bnn_eps_mode */
+  int32_t table_rows;       /* L */
+  const float* table;       /* device [L, BNN_SGMCMC_TABLE_COLS] */
+  uint64_t seed;
+  uint32_t* step;           /* device word k */
+  uint32_t* collected;      /* device word; with a bank */
+  uint32_t* ticket;         /* 16 device words, zero between launches */
+  uint32_t burn_in;
+  int32_t capacity;         /* members of the bank */
+  float* bank;              /* optional [capacity, stride] */
+} bnn_sgmcmc_args;
+
+typedef struct bnn_bank_fwd_args {
+  uint32_t struct_bytes;
+  int32_t members, first, batch, in_features, out_features;
+  int32_t x_shared;         /* 1: x [batch,in] for all members; 0: x [members,batch,in] */
+  int32_t relu;
+  const void* x;
+  int32_t x_dtype;          /* bnn_dtype */
+  int32_t math;             /* bnn_math */
+  const float* w;           /* member m's [out,in] at w + m * w_stride */
+  const float* b;           /* member m's [out] at b + m * b_stride, or NULL */
+  int64_t w_stride, b_stride;
+  void* y;                  /* [members,batch,out] */
+  int32_t y_dtype;          /* bnn_dtype */
+  int32_t reserved;
+} bnn_bank_fwd_args;
+
+int bnn_sgmcmc_noise(float* out, uint64_t seed, uint32_t tensor, uint32_t step, int64_t numel, void* stream);
+int bnn_sgmcmc_step(const bnn_sgmcmc_args* args, void* stream);
+int bnn_bank_fwd(const bnn_bank_fwd_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
