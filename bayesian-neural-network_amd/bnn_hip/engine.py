@@ -679,15 +679,20 @@ class GraphedElbo:
                 self.ws[i] = ops.sample_workspace(S, k_i, n_i, dev)
         # Piece-order activations (ops.pieces_activation): layer i's input is in piece order exactly when layer i
         # launches the pair block GEMM (K1b2) in bf16 math and its producer can write the layout -- the prepare launch's cast for
-        # the first layer, a K1b2 launch for a later one.  The last layer's input stays row-major (K1c / K1r read it).  The
+        # the first layer, a K1b2 launch for a later one.  The output layer's input is in piece order when the last hidden layer
+        # launches K1b2 and the output layer runs as the one-launch form K1c (_k1c_final), whose fragment loads have the piece's lane
+        # geometry; every other output-layer form (K1r, the two-launch form) reads row-major activations.  The
         # buffers keep their places (x16, bufs[i]) and carry the layout themselves, so whoever hands them to ops.bbb_plan /
-        # ops.bbb_linear_fwd launches the form the evaluation runs.
+        # ops.bbb_linear_fwd / ops.bbb_final_fwd launches the form the evaluation runs.
         self.k1b2 = self._k1b2_layers() if state.pieces else [False] * nl
+        self.k1c = self._k1c_final()
         for i in range(nl - 1):
             if self.k1b2[i] and i == 0 and self.x16 is not None:
                 self.x16 = ops.pieces_activation(self.x.shape, dev)
             elif self.k1b2[i] and i > 0 and self.k1b2[i - 1]:
                 self.bufs[i - 1] = ops.pieces_activation(self.bufs[i - 1].shape, dev)
+        if nl >= 2 and self.k1b2[nl - 2] and self.k1c and state.final_pieces:
+            self.bufs[nl - 2] = ops.pieces_activation(self.bufs[nl - 2].shape, dev)
         # ... and the (mu, sigma) of those layers once more in piece order, written by the prepare launch of every evaluation (mu
         # changes between evaluations); the buffer rides on the layer's sigma tensor (ops.param_pieces)
         self.wpieces = [ops.param_pieces(sp.in_out[1], sp.in_out[0], dev) if (k and state.param_pieces) else None
@@ -834,6 +839,17 @@ class GraphedElbo:
                 res[i] = plan["form"] == L.FORM_GEMM and plan["waves"] == 8
             h = self.bufs[i]
         return res
+
+    def _k1c_final(self):
+        """Does the output layer run as ONE launch that samples, multiplies and finalizes (K1c)?  The conditions of
+        bnn_bbb_final_fwd for that form, at the arguments _enqueue hands it: more pairs than the row-split form takes, one
+        16-feature tile, one 128-row batch block, 16-byte fragments, no form preference.  (Where the library decided otherwise it
+        would refuse a piece-order x with BNN_ERR_ENUM in the warm-up evaluation: nothing runs on a misread buffer.)"""
+        last = len(self.specs) - 1
+        k_last, n_last = self.specs[last].in_out
+        return (not self.lr and self.math == L.MATH_BF16 and not self.rows and not self.lib[last] and
+                self._common_kw(last)["form"] == L.FORM_AUTO and self.n_local > FINAL_ROWS_MAX_SAMPLES and
+                n_last <= 16 and self.x.shape[-2] <= 128 and k_last % 8 == 0)
 
     def _sample_layer(self, i, grp):
         """K1s of layer i into its static buffers (on the current stream)."""

@@ -77,7 +77,8 @@ def pieces_activation(shape, device) -> torch.Tensor:
     """A zeroed bf16 activation buffer in PIECE ORDER (include/bnn_hip.h, bnn_layout) for the logical tensor `shape` =
     [batch, features] or [rows, batch, features]: [rows * ceil(batch / 128)][ceil(features / 32)][8 batch tiles][64 lanes][8].
     The layout travels with the tensor OBJECT (its `bnn_pieces` attribute holds the logical shape): bbb_linear_fwd / bbb_plan /
-    eval_prepare read it from the `x`, `out` and `cast_out` they are handed, every other entry point refuses such a tensor.
+    bbb_final_fwd (its x, where the output layer runs as one launch) / eval_prepare read it from the `x`, `out` and `cast_out` they
+    are handed, every other entry point refuses such a tensor.
     Pad positions are never written by a launch, so the buffer is zeroed once, here."""
     shape = tuple(int(d) for d in shape)
     if len(shape) not in (2, 3) or min(shape) < 1:
@@ -118,7 +119,7 @@ def _x3(x: torch.Tensor, n_samples: int, pieces_ok: bool = False):
     shape = pieces_shape(x)
     if shape is not None:
         if not pieces_ok:
-            raise BnnHipError("a piece-order activation buffer (ops.pieces_activation) is read by bbb_linear_fwd only")
+            raise BnnHipError("a piece-order activation buffer (ops.pieces_activation) is read by bbb_linear_fwd / bbb_final_fwd only")
         if len(shape) == 3 and n_samples % shape[0]:
             raise BnnHipError(f"x has {shape[0]} row blocks, which does not divide {n_samples} samples")
         return x, shape[-2], shape[-1], (n_samples // shape[0] if len(shape) == 3 else 0)

@@ -14,6 +14,7 @@ arguments (networks.py:50, :92, :142), so build-side settings live here and in e
   BNN_HIP_PIECES 1 (default) | 0: keep the operands of the pair-block-GEMM layers of a captured evaluation row-major
                  (engine.GraphedElbo; the same bits either way -- the switch is there to compare the two);
   BNN_HIP_PARAM_PIECES 1 (default) | 0: the same for the (mu, sigma) copy alone
+  BNN_HIP_FINAL_PIECES 1 (default) | 0: the same for the hand-over of the last hidden layer to the output layer (K1b2 -> K1c) alone
 """
 from __future__ import annotations
 
@@ -37,6 +38,7 @@ class _State:
                                     # the forms with each other through it)
         self.pieces = os.environ.get("BNN_HIP_PIECES", "1") != "0"   # piece-order activations between K1b2 layers (engine.GraphedElbo)
         self.param_pieces = self.pieces and os.environ.get("BNN_HIP_PARAM_PIECES", "1") != "0"   # ... and their (mu, sigma)
+        self.final_pieces = self.pieces and os.environ.get("BNN_HIP_FINAL_PIECES", "1") != "0"   # ... and the output layer's x (K1c)
         self.device_counter = None  # device int32[1] added to every layer's sample index at run time
                                     # (set while a training step is captured as a hipGraph: train.py)
 

@@ -306,9 +306,16 @@ struct FinPack : FinTail {   // the tail's block + K1c's K-slice stage
 // MT: 16-row batch tiles per block (8 = 128 rows).  The matmul-only forms use 2: without generator work a block's
 // cost is the x it pulls through its CU's L1 (all of K for its rows), so four times the blocks each ingest a quarter;
 // with sampling fused every batch block would redo the tile's sampling, hence 8 there.
-template <int MATH, int XDT, int R, bool ALIGNED, bool FINAL, bool TRANS = false, bool PRE = false, int MT = 8, bool WT = false>
+// XTL (K1c only: FINAL, bf16 x, bf16 math): x in PIECE ORDER (include/bnn_hip.h, bnn_layout) -- the B fragment of (k-step t, batch
+// tile m) is lane-linear, one contiguous 1 KiB run per wave load, where the row-major fragment is sixteen 64-byte row segments at
+// a 2 K byte stride (20 lines touched for 8 of payload, all through the one CU the pair's block sits on).  Same values in the
+// same lanes: same bits.
+template <int MATH, int XDT, int R, bool ALIGNED, bool FINAL, bool TRANS = false, bool PRE = false, int MT = 8, bool WT = false,
+          bool XTL = false>
 __device__ __forceinline__ bool bbb_fwd_body(const BbbK& p, const FinPack* fp) {
   constexpr int F = 16 / R;
+  static_assert(!XTL || (FINAL && R == 1 && ALIGNED && MT == 8 && XDT == BNN_BF16 && MATH == BNN_MATH_BF16),
+                "piece-order x: the fused output layer in bf16 math");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int r = lane & 15, q = lane >> 4;
@@ -410,6 +417,12 @@ __device__ __forceinline__ bool bbb_fwd_body(const BbbK& p, const FinPack* fp) {
     auto stage = [&](int ch) {
 #pragma unroll
       for (int mm = 0; mm < MC; ++mm) {
+        if constexpr (XTL) {
+          // the lane's chunk of piece (t, m): no row or k clamp -- the batch edge and the k tail are ZEROS in memory (x_sstride
+          // counts the padded elements of a row block), and the weights of lanes past K are zeroed below (valid <= 0)
+          xraw[mm] = *reinterpret_cast<const float4*>(xs + ((size_t)((t * 8 + ch * MC + mm) * 64 + lane)) * 16);
+          continue;
+        }
         const int row = m0 + (ch * MC + mm) * 16 + r;
 #pragma unroll
         for (int cc = 0; cc < R; ++cc) {
@@ -746,9 +759,9 @@ __global__ __launch_bounds__(768) void bbb_fwd_kernel(const BbbK p) {
   bbb_fwd_body<MATH, XDT, R, ALIGNED, false>(p, nullptr);
 }
 
-template <int MATH, int XDT>
+template <int MATH, int XDT, bool XTL = false>
 __global__ __launch_bounds__(768) void bbb_fwd_final_kernel(const BbbK p, const FinPack fp) {
-  bbb_fwd_body<MATH, XDT, 1, true, true>(p, &fp);
+  bbb_fwd_body<MATH, XDT, 1, true, true, false, false, 8, false, XTL>(p, &fp);
 }
 
 // K1a carrying an independent sampling job (bnn_bbb_fwd_args.rider) as extra blocks behind its own (whose count the
@@ -2259,8 +2272,8 @@ static int bbb_linear_fwd_impl(const bnn_bbb_fwd_args* a, void* stream_, bool no
   BbbPlan pl{};
   rc = bbb_plan(a, al, pl, grad_mask == nullptr);    // the masked input-gradient epilogue belongs to the tile form
   if (rc != BNN_OK) return rc;
-  // piece-order operands: the pair block GEMM in bf16 math reads and writes them and nothing else does -- any other plan would
-  // misread the buffer
+  // piece-order operands: of this entry point's plans the pair block GEMM in bf16 math reads and writes them and nothing else does --
+  // any other plan would misread the buffer (bnn_bbb_final_fwd's one-launch form reads a piece-order x too)
   if ((a->x_layout || a->y_layout || a->w_pieces) && !(pl.form == BNN_FORM_GEMM && pl.pairs > 1 && a->math == BNN_MATH_BF16))
     return BNN_ERR_ENUM;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -2464,7 +2477,10 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
   bool al = false;
   int rc = prepare(a, k, al);
   if (rc != BNN_OK) return rc;
-  if (a->x_layout || a->y_layout || a->w_pieces) return BNN_ERR_ENUM;     // the output-layer forms read row-major operands
+  // piece-order operands: the one-launch form (K1c) reads a piece-order x in bf16 math (prepare: bf16, 16-byte aligned); every
+  // other output-layer form reads row-major operands, and none writes a piece-order y or takes parameter pieces
+  const bool x_pieces = a->x_layout == BNN_LAYOUT_PIECES;
+  if (a->y_layout || a->w_pieces || (x_pieces && (a->w_sampled || a->math != BNN_MATH_BF16))) return BNN_ERR_ENUM;
   FinPack fp;
   rc = make_fin(f, fp.k, fp.c);
   if (rc != BNN_OK) return rc;
@@ -2521,6 +2537,7 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
                     f->classes == a->out_features && f->batch == a->batch && a->y_dtype == BNN_F32 &&
                     (a->n_samples == 1 || a->n_samples > kFinalTicketMaxSamples || f->ticket != nullptr) && !(a->log_prior || a->log_q) &&
                     a->form == BNN_FORM_AUTO;
+  if (x_pieces && !fuse) return BNN_ERR_ENUM;           // (the two-launch form would misread the buffer)
   if (!fuse) {
     rc = bnn_bbb_linear_fwd(a, stream_);
     if (rc != BNN_OK) return rc;
@@ -2536,6 +2553,7 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
   fp.ticket = tail_kernel ? nullptr : f->ticket;
   const int K = a->in_features;
   const int ssteps = (K + 31) / 32;
+  if (x_pieces) k.x_sstride = a->x_per_sample ? (long)ssteps * 4096 : 0;     // one 128-row block of ssteps pieces-of-8 per x row block
   // K-range slices per sample: one k-step per wave where the scratch allows it (<= 12 waves per
   // block), so the last layer's latency chain is one step long instead of ceil(ssteps/12).
   int KS = (ssteps + 11) / 12;
@@ -2571,7 +2589,11 @@ extern "C" int bnn_bbb_final_fwd(const bnn_bbb_fwd_args* a, const bnn_finalize_a
     if (err == hipSuccess)                                                                     \
       hipLaunchKernelGGL((bbb_fwd_final_kernel<MATH, XDT>), grid, block, lds, stream, k, fp);  \
   } while (0)
-  if (a->math == BNN_MATH_BF16) {
+  if (x_pieces) {
+    err = allow_big_lds(bbb_fwd_final_kernel<BNN_MATH_BF16, BNN_BF16, true>, lds);
+    if (err == hipSuccess)
+      hipLaunchKernelGGL((bbb_fwd_final_kernel<BNN_MATH_BF16, BNN_BF16, true>), grid, block, lds, stream, k, fp);
+  } else if (a->math == BNN_MATH_BF16) {
     if (a->x_dtype == BNN_F32) BNN_FIN(BNN_MATH_BF16, BNN_F32); else BNN_FIN(BNN_MATH_BF16, BNN_BF16);
   } else if (a->math == BNN_MATH_BF16X3) {
     if (a->x_dtype == BNN_F32) BNN_FIN(BNN_MATH_BF16X3, BNN_F32); else BNN_FIN(BNN_MATH_BF16X3, BNN_BF16);

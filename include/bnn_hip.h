@@ -182,9 +182,12 @@ struct bnn_bbb_sample_args;
  *     [row][batch block of 128][k-step t = feature / 32][batch tile m (8)][lane (64)][8 bf16]
  * lane (r = lane & 15, q = lane >> 4) of piece (t, m) holds x[128 * block + 16 * m + r][32 * t + 8 * q .. + 7].  Features are padded to
  * a multiple of 32 and batch rows to a multiple of 128 with ZEROS -- rows * ceil(batch / 128) * ceil(features / 32) * 8192 bytes in
- * all, 16-byte aligned: the caller allocates the buffer zeroed and no launch writes a pad position.  Only that plan reads or writes the layout: every other
- * launch handed a BNN_LAYOUT_PIECES operand returns BNN_ERR_ENUM (the plan itself, bnn_bbb_plan, does not depend on the layouts);
- * the split-bf16 form of the plan refuses it too (its operands are plane pairs). */
+ * all, 16-byte aligned: the caller allocates the buffer zeroed and no launch writes a pad position.  That plan reads and writes the layout,
+ * and the one-launch output layer of bnn_bbb_final_fwd (one 16-feature tile, batch <= 128, bf16 math, sampling in the launch) READS
+ * it as its x -- the lane geometry of its fragments is the piece's; every other launch handed a BNN_LAYOUT_PIECES operand returns
+ * BNN_ERR_ENUM -- bnn_bbb_final_fwd for a piece-order y or w_pieces, over pre-sampled weights, in fp32 or split-bf16 math and wherever
+ * it would run as two launches -- (the plan itself, bnn_bbb_plan, does not depend on the layouts); the split-bf16 form of the plan
+ * refuses it too (its operands are plane pairs). */
 typedef enum bnn_layout { BNN_LAYOUT_ROWS = 0, BNN_LAYOUT_PIECES = 1 } bnn_layout;
 
 typedef struct bnn_bbb_fwd_args {

@@ -26,7 +26,7 @@ from isa_loop_mix import classify                       # noqa: E402
 
 CSRC = os.path.join(REPO, "bayesian-neural-network_amd", "csrc")
 KERNELS = {   # key -> (source file, mangled-name substring, family of bench.KERNEL_SOURCES)
-    "bbb_fwd_gemm2_kernel<4,2,philox>": ("bbb_linear.hip", "bbb_fwd_gemm2_kernelILi4ELi2ELi0ELi2ELb0ELi5E", "bbb"),   # the form the headline's layer 2 runs: x and parameters in piece order
+    "bbb_fwd_gemm2_kernel<4,2,philox>": ("bbb_linear.hip", "bbb_fwd_gemm2_kernelILi4ELi2ELi0ELi2ELb0ELi7E", "bbb"),   # the form the headline's layers run: x, y and parameters in piece order
     "bbb_fwd_gemm2_kernel<4,2,philox,x3>": ("bbb_linear.hip", "bbb_fwd_gemm2_kernelILi4ELi2ELi0ELi2ELb1E", "bbb"),
     "bbb_fwd_gemm_kernel<4,true,philox>": ("bbb_linear.hip", "bbb_fwd_gemm_kernelILi4ELb1ELi0", "bbb"),
     "bbb_fwd_gemm_kernel<4,false,philox>": ("bbb_linear.hip", "bbb_fwd_gemm_kernelILi4ELb0ELi0", "bbb"),
