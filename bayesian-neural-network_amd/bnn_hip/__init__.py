@@ -8,6 +8,7 @@
 `optim`      FusedAdam / FusedSGD: torch.optim.Adam's / SGD's update in one launch (F2, K6)
 `train`      GraphedTrainStep: zero_grad -> sample_elbo -> backward -> Adam as one hipGraph
 `dense_train` GraphedDenseTrainStep: the same for MLP / MLP_Dropout (forward, loss, backward, SGD / Adam) (K6)
+`capture`    what every captured object shares: the optimiser's sample counter, warm-up and its undo, side-stream capture
 `synth`      synthetic inputs with the reference's distributions (numpy only)
 `active`     ActivePool / ActiveLearner: pool scoring, top-k acquisition and training on the labelled subset (F10); BatchBALD batches
              chosen jointly (joint_probs / acquire_batchbald, F15)

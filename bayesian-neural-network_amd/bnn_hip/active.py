@@ -22,6 +22,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .capture import word32
 from .epoch import DeviceDataset, DeviceLoader, EpochRunner, fill_rows
 from .ops import BnnHipError
 from .runtime import state, take_samples
@@ -242,8 +243,7 @@ class ActivePool:
                     a, b = g0 * B, min(N, (g0 + G) * B)
                     ev = self._evaluator(net, G, B, samples)
                     self._fill(ev.x.view(G * B, d), a, b)
-                    c = state.counter                                   # where a predictive call made now would start
-                    ev.counter.fill_(c - (1 << 32) if c >= (1 << 31) else c)
+                    ev.counter.fill_(word32(state.counter))             # where a predictive call made now would start
                     ev.replay()
                     take(ev._pred, a, b)
             else:

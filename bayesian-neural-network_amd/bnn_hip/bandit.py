@@ -27,9 +27,10 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .capture import capture_on_side_stream
 from .ops import BnnHipError
 from .optim import FusedAdam
-from .runtime import state, take_samples
+from .runtime import state
 
 
 class RewardTable(NamedTuple):
@@ -189,7 +190,7 @@ class BNNBandit:
         self.capture = capture
         self.calls_decide = self.calls_replay = None
         self.g_decide = self.g_replay = None
-        self.train._sync_counter()
+        self.train._shared.sync()
         mirror = self.train._shared["mirror"]
         if capture == "calls":
             with L.recording() as calls:
@@ -204,16 +205,7 @@ class BNNBandit:
         torch.cuda.synchronize()
         self._reset_words(mirror)
         if capture is True:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self.g_decide = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.g_decide, stream=side):
-                    self._decide()
-                self.g_replay = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.g_replay, stream=side):
-                    self._replay()
-            torch.cuda.current_stream().wait_stream(side)
+            self.g_decide, self.g_replay = capture_on_side_stream(self._decide, self._replay)
         elif capture not in ("calls", False):
             raise BnnHipError(f"BNNBandit: capture must be True, 'calls' or False, got {capture!r}")
         torch.cuda.synchronize()
@@ -222,7 +214,7 @@ class BNNBandit:
         self.step_word.zero_()
         self._counts.zero_()
         self.regrets.zero_()
-        self.train._set_counter(mirror)
+        self.train._shared.set(mirror)
 
     def _decide(self):
         """bnn_bandit_rows -> forward of the A rows -> bnn_bandit_act, on the current stream."""
@@ -258,32 +250,28 @@ class BNNBandit:
             raise BnnHipError("BNNBandit: sample sharding is not supported")
         t = self.t
         thompson = self.policy == "thompson"
+        counter = self.train._shared
         if thompson:
-            self.train._sync_counter()
+            counter.sync()
         if self.g_decide is not None:
             self.g_decide.replay()
             if thompson:
-                self._advance_mirror()
+                counter.advance(self.dec_samples)
             self.g_replay.replay()
         elif self.calls_decide is not None:
             self._run_calls(self.calls_decide)
             if thompson:
-                self._advance_mirror()
+                counter.advance(self.dec_samples)
             self._run_calls(self.calls_replay)
         else:
             self._decide()
             if thompson:
-                self._advance_mirror()
+                counter.advance(self.dec_samples)
             self._replay()
         for j in range(n_batches(t, self.batch_size, self.buffer_size)):
             self.loss_info = self.train.step(self.slab[j], self.targets[j], beta(j, self.num_batches))
         self.scheduler.step()
         self.t = t + 1
-
-    def _advance_mirror(self):
-        take_samples(self.dec_samples)
-        sh = self.train._shared
-        sh["mirror"] = (sh["mirror"] + self.dec_samples) & 0xFFFFFFFF
 
     def update(self, mushroom: Optional[int] = None):
         """One bandit step (base_bandit.py:75-84 + the training of bandits.py:43-51 + main.py:103's scheduler.step()) on
@@ -481,13 +469,7 @@ class GreedyBanditGroup:
         self._counts.zero_()
         self.regrets.zero_()
         if capture:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, stream=side):
-                    self._enqueue()
-            torch.cuda.current_stream().wait_stream(side)
+            self.graph = capture_on_side_stream(self._enqueue)
         torch.cuda.synchronize()
 
     def _enqueue(self, train: bool = True):
@@ -790,13 +772,7 @@ class BNNBanditGroup:
         self.regrets.zero_()
         self.sample_counter.zero_()
         if capture is True:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, stream=side):
-                    self._enqueue()
-            torch.cuda.current_stream().wait_stream(side)
+            self.graph = capture_on_side_stream(self._enqueue)
         torch.cuda.synchronize()
 
     def _enqueue(self, train: bool = True):

@@ -15,10 +15,11 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .capture import SampleCounter, grad_bucket, snapshot, warm_up
 from .mcdropout import _math, flat_input, layers_of
 from .ops import BnnHipError
 from .optim import FusedAdam, FusedSGD, _sgd_supported
-from .runtime import state, take_samples
+from .runtime import state
 from .sgmcmc import FusedSGMCMC
 
 LOSSES = ("cross_entropy", "mse")
@@ -71,11 +72,7 @@ class GraphedDenseTrainStep:
         in_opt = {id(p) for g in optimizer.param_groups for p in g["params"]}
         if any(id(p) not in in_opt for p in self.params):
             raise BnnHipError("GraphedDenseTrainStep: the optimiser must hold every parameter of the network")
-        offs, tot = [], 0
-        for p in self.params:
-            offs.append(tot)
-            tot += (p.numel() + 63) // 64 * 64
-        self.bucket = torch.zeros(tot, dtype=torch.float32, device=dev)
+        self.bucket, offs = grad_bucket(self.params, dev)
         self.grad_views = [self.bucket[o:o + p.numel()].view(p.shape) for o, p in zip(offs, self.params)]
         self._grad_of = dict(zip(map(id, self.params), self.grad_views))
 
@@ -86,20 +83,22 @@ class GraphedDenseTrainStep:
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.scales = [ops.dropout_params(d.p)[1] for d in self.layers]
 
-        # ONE device sample counter per optimiser, shared by every step object built on it (the 128-row and the 96-row
-        # last batch of an MNIST epoch): a step draws global sample index base + counter, the output layer's forward
-        # advances it, and the host's counter is kept in step (take_samples), so later evaluations draw past it
-        sh = getattr(optimizer, "_sample_words", None)
-        if sh is None or sh["counter"].device != dev:
-            sh = optimizer._sample_words = dict(counter=torch.zeros(1, dtype=torch.int32, device=dev), base=take_samples(0),
-                                                mirror=0)
-        self._shared = sh
+        # the optimiser's shared device sample counter (capture.SampleCounter): a step draws global sample index
+        # base + counter, the output layer's forward advances it, and the host's counter is kept in step, so later
+        # evaluations draw past it
+        sh = self._shared = SampleCounter.of(optimizer, dev)
         self.counter, self.base = sh["counter"], sh["base"]
-        self._sync_counter()
+        sh.sync()
 
         self.graph = None
         if capture:
-            self._warm_up()
+            # one real step on a side stream (allocator pools, the optimiser's lazily created state and device words), then
+            # its effects undone: parameters, optimiser state, device step / learning-rate words, sample counter
+            restore, mirror = snapshot(optimizer), sh["mirror"]
+            warm_up(self._enqueue, sync_first=True)
+            restore()
+            sh.set(mirror)
+            torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):
                 self._enqueue()
@@ -135,62 +134,6 @@ class GraphedDenseTrainStep:
         for p, g in zip(self.params, self.grad_views):
             p.grad = g
 
-    # ---- the sample counter (as train.GraphedTrainStep keeps it)
-    def _set_counter(self, value: int):
-        value &= 0xFFFFFFFF
-        self.counter.fill_(value - (1 << 32) if value >= (1 << 31) else value)     # the kernels add it as a uint32
-        self._shared["mirror"] = value
-
-    def _sync_counter(self):
-        """Before a step: the device counter must equal the host's count of indices drawn since `base` (evaluations
-        between steps draw from the host counter); one small fill when they differ, nothing otherwise."""
-        want = (state.counter - self.base) & 0xFFFFFFFF
-        if want != self._shared["mirror"]:
-            self._set_counter(want)
-
-    def _warm_up(self):
-        """One real step on a side stream (allocator pools, the optimiser's lazily created state and device words),
-        then its effects undone: parameters, optimiser state, device step / learning-rate words, sample counter."""
-        opt = self.opt
-        params = [p for g in opt.param_groups for p in g["params"]]
-        saved_p = [p.detach().clone() for p in params]
-        had_state = {p for p in params if p in opt.state and len(opt.state[p])}
-        saved_state = {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in opt.state[p].items()} for p in had_state}
-        saved_dev = {gi: [w.clone() if torch.is_tensor(w) else w for w in d] for gi, d in opt._dev.items()}
-        mirror, host_counter = self._shared["mirror"], state.counter
-        torch.cuda.synchronize()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._enqueue()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        state.counter = host_counter
-        with torch.no_grad():
-            for p, q in zip(params, saved_p):
-                p.copy_(q)
-            for p in params:
-                st = opt.state.get(p)
-                if not st:
-                    continue
-                if p in had_state:
-                    for k, v in saved_state[p].items():
-                        st[k].copy_(v) if torch.is_tensor(st.get(k)) and torch.is_tensor(v) else st.__setitem__(k, v)
-                else:                            # the warm-up created it: back to a fresh optimiser's values
-                    for k, v in st.items():
-                        if torch.is_tensor(v):
-                            v.zero_()
-        for gi, d in opt._dev.items():
-            if gi in saved_dev:
-                for w, s in zip(d, saved_dev[gi]):
-                    if torch.is_tensor(w):
-                        w.copy_(s)
-            elif isinstance(opt, FusedAdam):     # created by the warm-up: start from the host-side step
-                steps = [int(saved_state[p]["step"]) for p in opt.param_groups[gi]["params"] if p in saved_state]
-                d[0].fill_(max(steps) if steps else 0)
-        self._set_counter(mirror)
-        torch.cuda.synchronize()
-
     # ---- the public step
     def step(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """One optimiser step on minibatch (x, y); returns the static 0-dim loss tensor (the reference's loss_info: read
@@ -210,12 +153,11 @@ class GraphedDenseTrainStep:
         """The step on whatever the static buffers (x, y) hold -- step() after its staging; a caller that stages them on
         the device itself (epoch.EpochRunner) calls this.  Same bookkeeping, same return value."""
         self.opt.sync_lr()
-        self._sync_counter()
+        self._shared.sync()
         if self.graph is not None:
             self._attach_grads()
             self.graph.replay()
         else:
             self._enqueue()
-        take_samples(1)
-        self._shared["mirror"] = (self._shared["mirror"] + 1) & 0xFFFFFFFF
+        self._shared.advance(1)
         return self.loss

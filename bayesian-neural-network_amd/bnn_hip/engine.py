@@ -13,6 +13,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .capture import capture_on_side_stream
 from .functional import AllReduceSumFn, BBBLinearFn, ElboFn, LayerCall, LRLinearFn, NetCall, NLLFn
 from .ops import Predictive
 from .runtime import state, take_samples
@@ -726,14 +727,7 @@ class GraphedElbo:
             self._enqueue()                      # warm-up (also validates arguments eagerly)
             take_samples(self.total_samples)
             torch.cuda.synchronize()
-            side = self.stream if self.stream is not None else torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side):
-                    self._eager()
-            torch.cuda.current_stream().wait_stream(side)
-            self.graph = g
+            self.graph = capture_on_side_stream(self._eager, stream=self.stream)
 
     def _enqueue(self):
         """One evaluation of all local (minibatch, MC sample) pairs."""

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .capture import word32
 from .ops import BnnHipError
 from .runtime import state
 
@@ -303,8 +304,7 @@ def score(net, loader, samples: int, *, sigma: float = 1.0, bins: int = 10, chun
                 yv[:b - a].copy_(ds.y[a:b])
                 if G * B > b - a:
                     yv[b - a:].zero_()                  # padding: a valid label for the chain's own NLL; never scored
-                c = state.counter                      # where a per-minibatch loop started now would draw
-                ev.counter.fill_(c - (1 << 32) if c >= (1 << 31) else c)
+                ev.counter.fill_(word32(state.counter))     # where a per-minibatch loop started now would draw
                 ev.replay()
         else:
             dropout = isinstance(net, networks.MLP_Dropout) and samples > 0

@@ -24,6 +24,7 @@ from torch import nn
 
 from . import _lib as L
 from . import ops
+from .capture import warm_up, word32
 from .mcdropout import _math, flat_input, layers_of
 from .engine import _first_minibatch
 from .ops import BnnHipError, Predictive
@@ -87,13 +88,7 @@ class _Chain:
         """One warm-up run on a side stream (allocator pools), its accumulation undone, then the capture."""
         la = self.la
         saved = [t.clone() for t in la.curv] + [la.record.clone()]
-        torch.cuda.synchronize()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self.enqueue()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+        warm_up(self.enqueue, sync_first=True)
         for t, s in zip(la.curv + [la.record], saved):
             t.copy_(s)
         self.graph = torch.cuda.CUDAGraph()
@@ -127,12 +122,6 @@ class LaplaceStep:
 
 
 GLM_LINKS = ("probit", "mc")
-
-
-def _word(v: int) -> int:
-    """A uint32 sample index as the int32 a torch word stores."""
-    v = int(v) & 0xFFFFFFFF
-    return v - (1 << 32) if v >= 1 << 31 else v
 
 
 class _GlmChain:
@@ -216,16 +205,10 @@ class GlmPredictiveGraph:
         self.logits = torch.empty((self.samples, B, ch.C), dtype=torch.float32, device=la.device) if self.mc else None
         self._pred = ops.predictive_buffers(la.mode, 1, B, ch.C, la.device) if self.mc else None
         self.result = _first_minibatch(self._pred) if self.mc else la._closed_form(ch.mean, self._m)
-        self.counter.fill_(_word(take_samples(0)))
+        self.counter.fill_(word32(take_samples(0)))
         self.graph = None
         if capture:
-            torch.cuda.synchronize()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                self._enqueue()                                               # warm-up (also validates the arguments eagerly)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
+            warm_up(self._enqueue, sync_first=True)                           # (also validates the arguments eagerly)
             if self.mc:
                 take_samples(self.samples)
             self.graph = torch.cuda.CUDAGraph()
@@ -432,7 +415,7 @@ class DiagLaplace:
         ch = self._glm_chain(x)
         mc = link == "mc" and self.mode == "classification"
         if mc:
-            ch.counter.fill_(_word(take_samples(samples) if sample_offset is None else sample_offset))
+            ch.counter.fill_(word32(take_samples(samples) if sample_offset is None else sample_offset))
         m = ch.moments(tau, tau_dev, quantiles=q, sigma=sg, n_samples=int(samples) if mc else 0)
         if not mc:
             return self._closed_form(ch.mean.clone(), m)
@@ -452,7 +435,7 @@ class DiagLaplace:
         self._glm_args(samples, "mc", None)
         tau, tau_dev = self._tau(prior_precision, "glm_sample")
         ch = self._glm_chain(x)
-        ch.counter.fill_(_word(take_samples(samples) if sample_offset is None else sample_offset))
+        ch.counter.fill_(word32(take_samples(samples) if sample_offset is None else sample_offset))
         m = ch.moments(tau, tau_dev, sigma=self.sigma, n_samples=int(samples))
         return ch.sample(m, int(samples))
 

@@ -13,6 +13,7 @@ from torch import nn
 
 from . import _lib as L
 from . import ops
+from .capture import capture_on_side_stream
 from .engine import _first_minibatch, dist_info
 from .ops import BnnHipError, Predictive
 from .runtime import state, take_samples
@@ -186,14 +187,8 @@ class GraphedDropoutPredictive:
                 self._enqueue()                  # warm-up (also validates the arguments eagerly)
             take_samples(S)
             torch.cuda.synchronize()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side):
-                    self._enqueue()
-            torch.cuda.current_stream().wait_stream(side)
-            self.graph = g
+            with torch.no_grad():
+                self.graph = capture_on_side_stream(self._enqueue)
 
     def _enqueue(self):
         logits = run_chain(self.layers, self.x, self.samples, sample_offset=0, counter=self.counter, bufs=self.bufs)

@@ -18,6 +18,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .capture import capture_on_side_stream, word32
 from .engine import _first_minibatch
 from .mcdropout import _math, _summary_args, flat_input, layers_of
 from .ops import BnnHipError, Predictive
@@ -73,8 +74,7 @@ def build_table(lr: float, *, temperature: float = 1.0, friction: Optional[float
 
 def _word(value: int, device) -> torch.Tensor:
     """A uint32 device word held as int32[1] (the kernels read it unsigned)."""
-    value &= 0xFFFFFFFF
-    return torch.tensor([value - (1 << 32) if value >= (1 << 31) else value], dtype=torch.int32, device=device)
+    return torch.tensor([word32(value)], dtype=torch.int32, device=device)
 
 
 def _read_word(w: torch.Tensor) -> int:
@@ -82,8 +82,7 @@ def _read_word(w: torch.Tensor) -> int:
 
 
 def _set_word(w: torch.Tensor, value: int):
-    value &= 0xFFFFFFFF
-    w.fill_(value - (1 << 32) if value >= (1 << 31) else value)
+    w.fill_(word32(value))
 
 
 # ---------------------------------------------------------------------------------------------------- the bank
@@ -265,14 +264,8 @@ class GraphedBankPredictive:
             with torch.no_grad():
                 self._enqueue()                  # warm-up (also validates the arguments eagerly)
             torch.cuda.synchronize()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, stream=side):
-                    self._enqueue()
-            torch.cuda.current_stream().wait_stream(side)
-            self.graph = g
+            with torch.no_grad():
+                self.graph = capture_on_side_stream(self._enqueue)
 
     def _enqueue(self):
         logits = self.bank._chain(self.x, self.members, self.first, bufs=self.bufs)
@@ -292,7 +285,7 @@ class GraphedBankPredictive:
 
 
 # ---------------------------------------------------------------------------------------------------- the sampler
-# _dev[gi]: the entries a captured step holds the address of (dense_train's warm-up saves and restores the tensors)
+# _dev[gi]: the entries a captured step holds the address of (capture.snapshot saves and restores them around a warm-up)
 _STEP, _COLLECTED, _TICKET, _TABLE, _LR = range(5)
 
 

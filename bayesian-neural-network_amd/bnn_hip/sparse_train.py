@@ -17,8 +17,9 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .capture import SampleCounter, grad_bucket, snapshot, warm_up
 from .optim import FusedAdam
-from .runtime import state, take_samples
+from .runtime import state
 
 
 def csc_view(row_ptr: torch.Tensor, col: torch.Tensor, nnz: int, in_features: int):
@@ -74,21 +75,14 @@ class SparseTrainStep:
         self.x16 = None                                        # exact fp32 throughout: no bf16 copy of the minibatch
         self.rows = rows = self.x.shape[0]
         self.beta = torch.zeros((), dtype=torch.float32, device=dev)
-        sh = getattr(optimizer, "_sample_words", None)
-        if sh is None or sh["counter"].device != dev:
-            sh = optimizer._sample_words = dict(counter=torch.zeros(1, dtype=torch.int32, device=dev), base=take_samples(0), mirror=0)
-        self._shared = sh
+        sh = self._shared = SampleCounter.of(optimizer, dev)
         self.counter, self.base = sh["counter"], sh["base"]
         self.keep = [k.to(torch.uint8).contiguous() for k in keeps]            # owned by the step
         self.csc = [csc_view(c.row_ptr, c.col, c.nnz, c.fin) if i > 0 else (None, None, None) for i, c in enumerate(layers)]
 
         # ---- parameters and the flat gradient bucket (each slice 256-byte aligned); p.grad are views of it
         self.params = cn.parameters()
-        offs, tot = [], 0
-        for p in self.params:
-            offs.append(tot)
-            tot += (max(p.numel(), 1) + 63) // 64 * 64
-        self.bucket = torch.zeros(tot, dtype=torch.float32, device=dev)
+        self.bucket, offs = grad_bucket(self.params, dev, never_empty=True)
         self.grad_views = [self.bucket[o:o + p.numel()] for o, p in zip(offs, self.params)]
         self._grad_store = [self.bucket[o:o + max(p.numel(), 1)] for o, p in zip(offs, self.params)]   # (never an empty tensor)
         for p, g in zip(self.params, self.grad_views):
@@ -125,45 +119,13 @@ class SparseTrainStep:
             raise ops.BnnHipError("SparseTrainStep: y must be contiguous int64 labels (classification) or float32 targets (regression)")
         self._rnd = rnd
         self._build_bwd()
-        self._sync_counter()
+        sh.sync()
 
-        # ---- warm-up on a side stream, then undo its effects (as train.GraphedTrainStep does)
-        params = [p for g in optimizer.param_groups for p in g["params"]]
-        saved_p = [p.detach().clone() for p in params]
-        saved_sig = [(c.sigma_val.clone(), c.b_sigma.clone()) for c in layers]
-        saved_state = {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in optimizer.state[p].items()}
-                       for p in params if p in optimizer.state and len(optimizer.state[p])}
-        saved_dev_step = {gi: d[0].clone() for gi, d in getattr(optimizer, "_dev", {}).items()}
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        host_counter = state.counter
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self._one_step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        state.counter = host_counter
-        with torch.no_grad():
-            for p, q in zip(params, saved_p):
-                p.copy_(q)
-            for c, (sv, bs) in zip(layers, saved_sig):
-                c.sigma_val.copy_(sv)
-                c.b_sigma.copy_(bs)
-            for p in params:
-                st = optimizer.state[p]
-                if p in saved_state:
-                    for k, v in saved_state[p].items():
-                        st[k].copy_(v) if torch.is_tensor(v) else st.__setitem__(k, v)
-                elif "exp_avg" in st:
-                    st["exp_avg"].zero_()
-                    st["exp_avg_sq"].zero_()
-        for gi in getattr(optimizer, "_dev", {}):
-            if gi in saved_dev_step:
-                optimizer._dev[gi][0].copy_(saved_dev_step[gi])
-            else:
-                steps = [int(saved_state[p]["step"]) for p in optimizer.param_groups[gi]["params"] if p in saved_state]
-                optimizer._dev[gi][0].fill_(max(steps) if steps else 0)
-        self._set_counter(sh["mirror"])
+        # ---- warm-up on a side stream, then undo its effects (the sigmas are the refresh launch's outputs)
+        restore, mirror = snapshot(optimizer, extra=[t for c in layers for t in (c.sigma_val, c.b_sigma)]), sh["mirror"]
+        warm_up(self._one_step, max(1, warmup))
+        restore()
+        sh.set(mirror)
         torch.cuda.synchronize()
 
         # ---- capture
@@ -225,17 +187,7 @@ class SparseTrainStep:
         self._update()
         return out
 
-    # ------------------------------------------------------------------------------------------------ bookkeeping
-    def _set_counter(self, value: int):
-        value &= 0xFFFFFFFF
-        self.counter.fill_(value - (1 << 32) if value >= (1 << 31) else value)
-        self._shared["mirror"] = value
-
-    def _sync_counter(self):
-        want = (state.counter - self.base) & 0xFFFFFFFF
-        if want != self._shared["mirror"]:
-            self._set_counter(want)
-
+    # ------------------------------------------------------------------------------------------------ the public step
     def step(self, x: torch.Tensor, y: torch.Tensor, beta: float):
         """One optimiser step on minibatch (x, y) with KL weight beta.  Returns (loss, mean log p, mean log q, nll): static
         tensors, read them before the next call."""
@@ -252,18 +204,16 @@ class SparseTrainStep:
     def replay(self):
         """The step on whatever the static buffers (x, y, beta) hold."""
         self.opt.sync_lr()
-        self._sync_counter()
+        self._shared.sync()
         self.graph.replay()
-        take_samples(self.samples)
-        self._shared["mirror"] = (self._shared["mirror"] + self.samples) & 0xFFFFFFFF
+        self._shared.advance(self.samples)
         return self.out
 
     def eager(self):
         """The same launches issued one by one instead of replayed (bit for bit the replay's results): for tests and
         debugging.  Same bookkeeping as replay()."""
         self.opt.sync_lr()
-        self._sync_counter()
+        self._shared.sync()
         out = self._one_step()
-        take_samples(self.samples)
-        self._shared["mirror"] = (self._shared["mirror"] + self.samples) & 0xFFFFFFFF
+        self._shared.advance(self.samples)
         return out

@@ -23,8 +23,9 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .capture import SampleCounter, grad_bucket, snapshot, warm_up
 from .optim import FusedAdam
-from .runtime import state, take_samples
+from .runtime import state
 
 
 # BBB, bf16 math, hand-chained step: sample every layer's weights ONCE per step in one streaming launch
@@ -81,13 +82,9 @@ class GraphedTrainStep:
         self.x16 = (self.x.to(torch.bfloat16) if (TRAIN_BF16_FORWARD_INPUTS and not autograd and state.math == L.MATH_BF16 and
                                                   x.dtype == torch.float32) else None)
         self.beta = torch.zeros((), dtype=torch.float32, device=dev)
-        # ONE device MC-sample counter per optimiser, shared by every step object built on it (full batches and the 96-row
-        # last MNIST batch are two objects on one net): a step draws global sample index base + counter (+ rank * S), the
-        # counter advances inside Adam's launch, so alternating objects never replay an index.  `mirror` is the host's copy.
-        sh = getattr(optimizer, "_sample_words", None)
-        if sh is None or sh["counter"].device != dev:
-            sh = optimizer._sample_words = dict(counter=torch.zeros(1, dtype=torch.int32, device=dev), base=take_samples(0), mirror=0)
-        self._shared = sh
+        # the optimiser's shared device MC-sample counter (capture.SampleCounter): a step draws global sample index
+        # base + counter (+ rank * S), the counter advances inside Adam's launch
+        sh = self._shared = SampleCounter.of(optimizer, dev)
         self.counter, self.base = sh["counter"], sh["base"]
         self.fin_ticket = torch.zeros(1, dtype=torch.int32, device=dev)   # lets the samples be finalized in parallel
         self.fin_scratch = ops.final_scratch(self.samples, dev)   # hand-off words of the row-split / K-sliced output layer
@@ -95,14 +92,10 @@ class GraphedTrainStep:
         self._lr_rider_bufs, self._lr_rider_job = None, None      # the output layer's prepared operands + KL workspace (bnn_lr_rider)
         # one flat gradient bucket (each slice 256-byte aligned); p.grad are views of it
         self.params = [p for sp in net._specs() for p in (sp.m.weight_mu, sp.m.weight_rho, sp.m.bias_mu, sp.m.bias_rho)]
-        offs, tot = [], 0
-        for p in self.params:
-            offs.append(tot)
-            tot += (p.numel() + 63) // 64 * 64
-        self.bucket = torch.zeros(tot, dtype=torch.float32, device=dev)
+        self.bucket, offs = grad_bucket(self.params, dev)
         self.grad_views = [self.bucket[o:o + p.numel()].view(p.shape) for o, p in zip(offs, self.params)]
         self.bucket_cut = offs[4] if len(offs) > 4 else 0      # first element of layer 1's gradients (layer 0 = 4 tensors)
-        self.bucket16 = torch.zeros(tot, dtype=torch.bfloat16, device=dev) if self.grad16 else None
+        self.bucket16 = torch.zeros_like(self.bucket, dtype=torch.bfloat16) if self.grad16 else None
         self.grad16_of = ({p: self.bucket16[o:o + p.numel()].view(p.shape) for o, p in zip(offs, self.params)}
                           if self.grad16 else None)
         self._elbo = net.sample_elbo_lr if net.local_reparam else net.sample_elbo
@@ -119,44 +112,16 @@ class GraphedTrainStep:
             self.wsamp_t = [torch.empty((S, sp.in_out[0], sp.in_out[1]), dtype=torch.bfloat16, device=dev)
                             if (TRAIN_TRANSPOSED_INPUT_GRAD and 0 < i < len(specs) - 1 and sp.in_out[1] % 8 == 0) else None
                             for i, sp in enumerate(specs)]
-        self._sync_counter()              # indices other code drew since the last step (evaluations) are skipped, not reused
+        sh.sync()                         # indices other code drew since the last step (evaluations) are skipped, not reused
 
-        # ---- warm-up on a side stream (allocator pools, lazy inits), then undo its effects
-        params = [p for g in optimizer.param_groups for p in g["params"]]
-        saved_p = [p.detach().clone() for p in params]
-        saved_state = {p: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in optimizer.state[p].items()}
-                       for p in params if p in optimizer.state and len(optimizer.state[p])}
-        # a capturable FusedAdam counts its steps in device words (state[p]["step"] is not written during training):
-        # snapshot them, so that a step object built on an already trained optimiser (another batch shape, a
-        # re-capture) leaves the bias-correction step where it was
-        saved_dev_step = {gi: d[0].clone() for gi, d in getattr(optimizer, "_dev", {}).items()}
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        host_counter = state.counter
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self._one_step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        state.counter = host_counter
-        with torch.no_grad():
-            for p, q in zip(params, saved_p):
-                p.copy_(q)
-            for p in params:
-                st = optimizer.state[p]
-                if p in saved_state:
-                    for k, v in saved_state[p].items():
-                        st[k].copy_(v) if torch.is_tensor(v) else st.__setitem__(k, v)
-                else:
-                    st["exp_avg"].zero_()
-                    st["exp_avg_sq"].zero_()
-        for gi in getattr(optimizer, "_dev", {}):
-            if gi in saved_dev_step:
-                optimizer._dev[gi][0].copy_(saved_dev_step[gi])
-            else:                                        # the warm-up created the device words: start from the host-side step
-                steps = [int(saved_state[p]["step"]) for p in optimizer.param_groups[gi]["params"] if p in saved_state]
-                optimizer._dev[gi][0].fill_(max(steps) if steps else 0)
-        self._set_counter(sh["mirror"])    # the warm-up's steps advanced it
+        # ---- warm-up on a side stream (allocator pools, lazy inits), then undo its effects.  A capturable FusedAdam counts
+        # its steps in device words (state[p]["step"] is not written during training): they are part of the snapshot, so that
+        # a step object built on an already trained optimiser (another batch shape, a re-capture) leaves the bias-correction
+        # step where it was
+        restore, mirror = snapshot(optimizer), sh["mirror"]
+        warm_up(self._one_step, max(1, warmup))
+        restore()
+        sh.set(mirror)                     # the warm-up's steps advanced it
         torch.cuda.synchronize()
 
         # ---- capture
@@ -358,18 +323,6 @@ class GraphedTrainStep:
         sp.m.weight_mu.grad, sp.m.weight_rho.grad, sp.m.bias_mu.grad, sp.m.bias_rho.grad = grads[:4]
         self._bwd_g = grads[4]
 
-    def _set_counter(self, value: int):
-        value &= 0xFFFFFFFF
-        self.counter.fill_(value - (1 << 32) if value >= (1 << 31) else value)     # the kernels add it as a uint32
-        self._shared["mirror"] = value
-
-    def _sync_counter(self):
-        """Before a step: the device counter must equal the host's count of indices drawn since `base` (eager evaluations
-        between steps draw from the host counter); one small fill when they differ, nothing otherwise."""
-        want = (state.counter - self.base) & 0xFFFFFFFF
-        if want != self._shared["mirror"]:
-            self._set_counter(want)
-
     def _update(self):
         with torch.no_grad():
             # the step's MC-sample counter advances inside Adam's launch (after the backward re-read it); set per call:
@@ -433,7 +386,7 @@ class GraphedTrainStep:
         """The step on whatever the static buffers (x, x16, y, beta) hold -- step() after its staging; a caller that stages
         them on the device itself (epoch.EpochRunner) calls this.  Same bookkeeping, same return value."""
         self.opt.sync_lr()
-        self._sync_counter()
+        self._shared.sync()
         self.graph.replay()
         if self.dp:
             w_hi = self._allreduce_upper()              # beside ...
@@ -442,8 +395,7 @@ class GraphedTrainStep:
             w_hi.wait()
             w_lo.wait()
             self.graph_update.replay()
-        take_samples(self.samples * self.world)
-        self._shared["mirror"] = (self._shared["mirror"] + self.samples * self.world) & 0xFFFFFFFF
+        self._shared.advance(self.samples * self.world)
         return self.out
 
 

@@ -226,6 +226,28 @@ def test_building_the_step_leaves_model_and_optimiser_unchanged(dev, kind):
     assert int(opt._sample_words["counter"].item()) == mirror
 
 
+@pytest.mark.parametrize("kind", ["sgd", "adam"])
+def test_a_step_built_after_an_lr_change_trains_at_the_new_rate(dev, kind):
+    """The second object's warm-up step is the first launch to see the halved rate: undoing it must not leave the device
+    word at the old rate with the new one taken for written.  Against the same launches issued eagerly (no warm-up)."""
+    def run(capture):
+        bnn_hip.set_math("f32")
+        bnn_hip.manual_seed(SEED, 300)
+        mlp = _mlp(dev, 8, 16, 4, "classification", False, seed=11)
+        opt = _opt(kind, mlp, lr=1e-2)
+        x, y = _batch(dev, mlp, 8)
+        mlp.graphed_train_step(opt, x, y, capture=capture).step(x, y)
+        opt.param_groups[0]["lr"] = 5e-3
+        before = [p.detach().clone() for p in mlp.parameters()]
+        mlp.graphed_train_step(opt, x[:5], y[:5], capture=capture).step(x[:5], y[:5])
+        return before, [p.detach().clone() for p in mlp.parameters()]
+
+    start_g, graphed = run(True)
+    start_e, eager = run(False)
+    for s, t, a, b in zip(start_g, start_e, graphed, eager):
+        assert torch.equal(s, t) and torch.equal(a, b) and not torch.equal(a, s)
+
+
 def _ref_torch_loop(mlp, opt, x, y, masks):
     """The reference's train_step body on stock torch modules; masks (one per dropout layer) stand in for nn.Dropout."""
     opt.zero_grad()

@@ -620,6 +620,45 @@ def test_graphed_train_step_equals_eager_steps(local_reparam, autograd):
             assert float((a - b).abs().max()) <= 2e-5 * float(a.abs().max()), k
 
 
+def test_a_step_built_after_an_lr_change_trains_at_the_new_rate():
+    """A second GraphedTrainStep built after param_groups[0]['lr'] was halved and before any replay: its warm-up is the first
+    launch to see the new rate, and undoing the warm-up must leave the learning-rate word and its 'last written' a pair.
+    The replay's update, bit for bit, is an eager FusedAdam step at the halved rate from the same parameters, moments and
+    step count on the same gradients."""
+    import networks
+    from bnn_hip.optim import FusedAdam
+    from bnn_hip.train import GraphedTrainStep
+    dev = torch.device("cuda:0")
+    bnn_hip.set_math("f32")
+    bnn_hip.manual_seed(99, counter=40)
+    mp = dict(input_shape=8, classes=4, batch_size=8, hidden_units=16, mode="classification", mu_init=[-0.2, 0.2],
+              rho_init=[-5, -4], prior_init=[1.0], mixture_prior=False, local_reparam=False)
+    torch.manual_seed(3)
+    net = networks.BayesianNetwork(mp).to(dev).train()
+    rs = np.random.RandomState(4)
+    x = torch.from_numpy(rs.uniform(0, 1, (8, 1, 1, 8)).astype(np.float32)).to(dev)
+    y = torch.from_numpy(rs.randint(0, 4, 8)).to(dev)
+    opt = FusedAdam(net.parameters(), lr=1e-2, capturable=True)
+    GraphedTrainStep(net, opt, x, y, 2).step(x, y, 0.1)
+    opt.param_groups[0]["lr"] = 5e-3
+    second = GraphedTrainStep(net, opt, x[:5], y[:5], 2)
+    params = list(net.parameters())
+    start = [(p.detach().clone(), opt.state[p]["exp_avg"].clone(), opt.state[p]["exp_avg_sq"].clone()) for p in params]
+    assert opt.device_step() == 1
+    second.step(x[:5], y[:5], 0.1)
+    assert opt.device_step() == 2
+    twins = [torch.nn.Parameter(p0.clone()) for p0, _, _ in start]
+    ref = FusedAdam(twins, lr=5e-3, capturable=True)
+    for q, p, (_, m, v) in zip(twins, params, start):
+        ref.state[q] = dict(step=1, exp_avg=m.clone(), exp_avg_sq=v.clone())
+        q.grad = p.grad.clone()
+    ref.step()
+    assert ref.device_step() == 2
+    for q, p, (p0, _, _) in zip(twins, params, start):
+        assert torch.equal(q.detach(), p.detach()) and not torch.equal(p.detach(), p0)
+        assert torch.equal(ref.state[q]["exp_avg"], opt.state[p]["exp_avg"])
+
+
 def test_out_of_range_label_poisons_loss_and_gradient():
     """A label outside [0, classes) must not train silently on a wrong loss (nn.CrossEntropyLoss, reference
     networks.py:186, raises): the NLL and the row's logit gradient come out NaN."""

@@ -49,9 +49,9 @@ def device_loop():
         e = ev[k]
         b.indices[b.t].fill_(int(i))
         e[0].record()
-        b.train._sync_counter()
+        b.train._shared.sync()
         b.g_decide.replay()
-        b._advance_mirror() if POLICY == "thompson" else None
+        b.train._shared.advance(b.dec_samples) if POLICY == "thompson" else None
         e[1].record()
         b.g_replay.replay()
         e[2].record()
