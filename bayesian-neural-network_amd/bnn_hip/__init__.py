@@ -18,12 +18,15 @@
 `diagnostics` PosteriorStats: weight / sigma / SNR / posterior-sample histograms of a model in one device pass (F11)
 `sgmcmc`     FusedSGMCMC / WeightBank: SGLD / SGHMC in the optimiser's place of K6's captured step, the samples filed into a
              device-resident bank of weight sets that predicts as an ensemble, one launch per layer for all members (F19)
+`kfac`       KronLaplace: the Kronecker-factored (KFAC) Laplace posterior -- factor accumulation, evidence, GLM predictive and
+             matrix-normal weight draws into a WeightBank, in the Kronecker eigenbasis (F20)
 """
 from .runtime import get_math, manual_seed, set_host_eps, set_math, shard_samples  # noqa: F401
 from ._lib import BnnHipError  # noqa: F401
 from .active import ActiveLearner, ActivePool  # noqa: F401
 from .laplace import DiagLaplace  # noqa: F401
 from .sgmcmc import FusedSGMCMC, WeightBank  # noqa: F401
+from .kfac import KronLaplace  # noqa: F401
 
 __all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError", "ActiveLearner", "ActivePool", "DiagLaplace",
-           "FusedSGMCMC", "WeightBank"]
+           "FusedSGMCMC", "WeightBank", "KronLaplace"]

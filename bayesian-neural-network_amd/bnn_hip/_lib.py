@@ -48,6 +48,8 @@ EXPORTS = (
     "bnn_laplace_seed", "bnn_laplace_layer", "bnn_laplace_evidence", "bnn_laplace_posterior", "bnn_laplace_evidence_workspace_bytes",
     "bnn_laplace_glm_layer", "bnn_laplace_glm_finish", "bnn_laplace_glm_sample",
     "bnn_sgmcmc_noise", "bnn_sgmcmc_step", "bnn_bank_fwd",
+    "bnn_kfac_layer", "bnn_kfac_evidence", "bnn_kfac_evidence_workspace_bytes", "bnn_kfac_glm_rotate", "bnn_kfac_glm_var",
+    "bnn_kfac_sample", "bnn_kfac_sample_workspace_bytes",
 )
 
 
@@ -578,6 +580,55 @@ class LaplaceGlmSampleArgs(C.Structure):
                 ("mean", C.c_void_p), ("chol", C.c_void_p), ("logits", C.c_void_p), ("sample_counter", C.c_void_p)]
 
 
+class KfacLayerArgs(C.Structure):
+    """bnn_kfac_layer_args (include/bnn_hip.h F20)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("batch", C.c_int32), ("rows", C.c_int32), ("in_features", C.c_int32),
+                ("out_features", C.c_int32), ("math", C.c_int32), ("gx_mask", C.c_int32), ("reserved", C.c_int32),
+                ("x", C.c_void_p), ("gy", C.c_void_p), ("y", C.c_void_p), ("w", C.c_void_p),
+                ("a", C.c_void_p), ("s", C.c_void_p), ("g", C.c_void_p), ("g_x", C.c_void_p)]
+
+
+class KfacEvidenceArgs(C.Structure):
+    """bnn_kfac_evidence_args (include/bnn_hip.h F20)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_layers", C.c_int32), ("n_precisions", C.c_int32), ("reserved", C.c_int32),
+                ("weight", C.c_void_p * LAPLACE_GLM_MAX_LAYERS), ("bias", C.c_void_p * LAPLACE_GLM_MAX_LAYERS),
+                ("lambda_a", C.c_void_p * LAPLACE_GLM_MAX_LAYERS), ("lambda_g", C.c_void_p * LAPLACE_GLM_MAX_LAYERS),
+                ("in_features", C.c_int32 * LAPLACE_GLM_MAX_LAYERS), ("out_features", C.c_int32 * LAPLACE_GLM_MAX_LAYERS),
+                ("precision", C.c_double * LAPLACE_MAX_PRECISIONS),
+                ("record", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("log_evidence", C.c_void_p), ("best_index", C.c_void_p), ("best", C.c_void_p)]
+
+
+class KfacGlmRotateArgs(C.Structure):
+    """bnn_kfac_glm_rotate_args (include/bnn_hip.h F20)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("batch", C.c_int32), ("rows", C.c_int32), ("in_features", C.c_int32),
+                ("out_features", C.c_int32), ("math", C.c_int32), ("gx_mask", C.c_int32), ("reserved", C.c_int32),
+                ("x", C.c_void_p), ("gy", C.c_void_p), ("y", C.c_void_p), ("w", C.c_void_p),
+                ("q_a", C.c_void_p), ("q_g", C.c_void_p), ("at", C.c_void_p), ("gt", C.c_void_p), ("g_x", C.c_void_p)]
+
+
+class KfacGlmVarArgs(C.Structure):
+    """bnn_kfac_glm_var_args (include/bnn_hip.h F20)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("batch", C.c_int32), ("rows", C.c_int32), ("in_features", C.c_int32),
+                ("out_features", C.c_int32), ("reserved", C.c_int32 * 3),
+                ("precision", C.c_double), ("precision_device", C.c_void_p),
+                ("at", C.c_void_p), ("gt", C.c_void_p), ("lambda_a", C.c_void_p), ("lambda_g", C.c_void_p),
+                ("cov_part", C.c_void_p), ("v_out", C.c_void_p)]
+
+
+class KfacSampleArgs(C.Structure):
+    """bnn_kfac_sample_args (include/bnn_hip.h F20)"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("members", C.c_int32), ("first", C.c_int32), ("in_features", C.c_int32),
+                ("out_features", C.c_int32), ("layer", C.c_uint32), ("sample_base", C.c_uint32), ("reserved", C.c_int32),
+                ("seed", C.c_uint64), ("precision", C.c_double), ("precision_device", C.c_void_p),
+                ("w", C.c_void_p), ("b", C.c_void_p), ("q_a", C.c_void_p), ("q_g", C.c_void_p),
+                ("lambda_a", C.c_void_p), ("lambda_g", C.c_void_p), ("bank", C.c_void_p),
+                ("bank_stride", C.c_int64), ("w_offset", C.c_int64), ("b_offset", C.c_int64),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+KFAC_NOISE_WORD3 = 4
+
 SGMCMC_MAX_TENSORS = 16
 SGMCMC_TABLE_COLS = 4
 
@@ -938,6 +989,15 @@ def _load_real():
     for name, cls in (("bnn_sgmcmc_step", SgmcmcArgs), ("bnn_bank_fwd", BankFwdArgs)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    for name, cls in (("bnn_kfac_layer", KfacLayerArgs), ("bnn_kfac_evidence", KfacEvidenceArgs),
+                      ("bnn_kfac_glm_rotate", KfacGlmRotateArgs), ("bnn_kfac_glm_var", KfacGlmVarArgs),
+                      ("bnn_kfac_sample", KfacSampleArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    lib.bnn_kfac_evidence_workspace_bytes.restype = C.c_size_t
+    lib.bnn_kfac_evidence_workspace_bytes.argtypes = [C.POINTER(KfacEvidenceArgs)]
+    lib.bnn_kfac_sample_workspace_bytes.restype = C.c_size_t
+    lib.bnn_kfac_sample_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     v = lib.bnn_version()
     if v != ABI_VERSION:
         raise BnnHipError(f"libbnn_hip.so ABI version {v} != binding version {ABI_VERSION}")

@@ -36,7 +36,7 @@ DEFAULT_PRECISIONS = np.logspace(-4, 4, 33)
 class _Chain:
     """The static buffers of one minibatch shape and the launches over them."""
 
-    def __init__(self, la: "DiagLaplace", B: int):
+    def __init__(self, la: "LaplaceBase", B: int):
         self.la, self.B = la, B
         dev, layers = la.device, la.layers
         C_out = layers[-1].linear.out_features
@@ -54,7 +54,7 @@ class _Chain:
         xf = flat_input(la.mlp, x)
         ops.require_device(y)
         if xf.numel() != self.x.numel() or y.numel() != self.y.numel() or y.dtype != self.y.dtype:
-            raise BnnHipError(f"DiagLaplace: a minibatch of {self.B} rows needs x of {self.x.numel()} float32 elements and "
+            raise BnnHipError(f"{_who(la)}: a minibatch of {self.B} rows needs x of {self.x.numel()} float32 elements and "
                               f"y of {self.y.numel()} {self.y.dtype} elements")
         if xf.is_contiguous() and y.is_contiguous():
             ops.stage_inputs(xf, self.x, y, self.y)                           # one launch instead of two
@@ -78,23 +78,22 @@ class _Chain:
             for i in range(last, -1, -1):
                 d = layers[i]
                 below = layers[i - 1] if i > 0 else None
-                ops.laplace_layer(self.x if i == 0 else self.acts[i - 1][0], self.gy if i == last else self.g_hidden[i],
-                                  d.linear.weight.detach(), f_w=la.curv[2 * i], f_b=la.curv[2 * i + 1],
-                                  g_x=self.g_hidden[i - 1] if i > 0 else None,
-                                  y=self.acts[i][0] if d.relu else None, gx_mask=below is not None and below.relu,
-                                  math_mode=math_mode)
+                la._curvature_launch(i, self.x if i == 0 else self.acts[i - 1][0], self.gy if i == last else self.g_hidden[i],
+                                     g_x=self.g_hidden[i - 1] if i > 0 else None,
+                                     y=self.acts[i][0] if d.relu else None, gx_mask=below is not None and below.relu,
+                                     math_mode=math_mode)
 
     def capture(self):
         """One warm-up run on a side stream (allocator pools), its accumulation undone, then the capture."""
         la = self.la
-        saved = [t.clone() for t in la.curv] + [la.record.clone()]
+        saved = [t.clone() for t in la._accumulated()]
         warm_up(self.enqueue, sync_first=True)
-        for t, s in zip(la.curv + [la.record], saved):
+        for t, s in zip(la._accumulated(), saved):
             t.copy_(s)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.enqueue()
-        for t, s in zip(la.curv + [la.record], saved):                        # (capturing launches nothing; kept for safety)
+        for t, s in zip(la._accumulated(), saved):                            # (capturing launches nothing; kept for safety)
             t.copy_(s)
 
     def run(self):
@@ -119,6 +118,7 @@ class LaplaceStep:
         """The accumulation of whatever the static buffers (x, y) hold."""
         self._chain.la._check_math()
         self._chain.run()
+        self._chain.la._invalidate()
 
 
 GLM_LINKS = ("probit", "mc")
@@ -130,7 +130,7 @@ class _GlmChain:
     a scratch record, never into la.record), bnn_laplace_glm_layer per layer top down, bnn_laplace_glm_finish, and for
     link 'mc' bnn_laplace_glm_sample (+ bnn_mc_predictive).  No parallel branches."""
 
-    def __init__(self, la: "DiagLaplace", B: int):
+    def __init__(self, la: "LaplaceBase", B: int):
         self.la, self.B = la, B
         dev, layers = la.device, la.layers
         C_out = layers[-1].linear.out_features
@@ -142,13 +142,14 @@ class _GlmChain:
         self.gy = torch.empty((self.R, C_out), **f32)
         self.g_hidden = [torch.empty((self.R, d.linear.out_features), **f32) for d in layers[:-1]]
         self.parts = [torch.empty((ops.glm_tiles(d.linear.out_features), B, P), **f32) for d in layers]
+        la._glm_buffers(self)
         self.scratch = torch.zeros(L.LAPLACE_RECORD_DOUBLES, dtype=torch.float64, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def stage(self, x: torch.Tensor):
         xf = flat_input(self.la.mlp, x)
         if xf.numel() != self.x.numel():
-            raise BnnHipError(f"DiagLaplace: a batch of {self.B} rows needs x of {self.x.numel()} float32 elements")
+            raise BnnHipError(f"{_who(self.la)}: a batch of {self.B} rows needs x of {self.x.numel()} float32 elements")
         self.x.copy_(xf.reshape(self.x.shape), non_blocking=True)
 
     @property
@@ -156,7 +157,7 @@ class _GlmChain:
         return self.acts[-1][0]
 
     def moments(self, tau, tau_dev, *, quantiles=(), sigma: float = 1.0, out=None, n_samples: int = 0) -> "ops.GlmMoments":
-        """Forward, seed, one bnn_laplace_glm_layer per layer, finish (which advances the counter by n_samples)."""
+        """Forward, seed, the posterior's variance launches per layer, finish (which advances the counter by n_samples)."""
         la = self.la
         layers, math_mode = la.layers, _math()[0]
         last = len(layers) - 1
@@ -171,11 +172,10 @@ class _GlmChain:
             for i in range(last, -1, -1):
                 d = layers[i]
                 below = layers[i - 1] if i > 0 else None
-                ops.laplace_glm_layer(self.x if i == 0 else self.acts[i - 1][0], self.gy if i == last else self.g_hidden[i],
-                                      d.linear.weight.detach(), f_w=la.curv[2 * i], f_b=la.curv[2 * i + 1],
-                                      cov_part=self.parts[i], g_x=self.g_hidden[i - 1] if i > 0 else None,
-                                      y=self.acts[i][0] if d.relu else None, gx_mask=below is not None and below.relu,
-                                      precision=tau, precision_device=tau_dev, math_mode=math_mode)
+                la._glm_launch(self, i, self.x if i == 0 else self.acts[i - 1][0], self.gy if i == last else self.g_hidden[i],
+                               g_x=self.g_hidden[i - 1] if i > 0 else None,
+                               y=self.acts[i][0] if d.relu else None, gx_mask=below is not None and below.relu,
+                               precision=tau, precision_device=tau_dev, math_mode=math_mode)
             return ops.laplace_glm_finish(self.parts, self.mean, la.mode, sigma=sigma, quantiles=quantiles, out=out,
                                           sample_counter=self.counter if n_samples else None, n_samples=n_samples)
 
@@ -191,8 +191,9 @@ class GlmPredictiveGraph:
     finish launch advances it, so replay k of a graph built at counter c draws the global samples c + (k + 1) S ... (the
     capture's warm-up run takes c ... c + S - 1), and the host counter is kept in step."""
 
-    def __init__(self, la: "DiagLaplace", x, samples: int, link: str, quantiles, sigma, prior_precision, capture: bool = True):
+    def __init__(self, la: "LaplaceBase", x, samples: int, link: str, quantiles, sigma, prior_precision, capture: bool = True):
         la._check_math()
+        la._glm_ready()
         self.la, self.link, self.samples = la, link, int(samples)
         self.q, self.sigma = la._glm_args(self.samples, link, quantiles), la.sigma if sigma is None else float(sigma)
         self.tau, self.tau_dev = la._tau(prior_precision, "glm_predictive_graph")
@@ -229,6 +230,7 @@ class GlmPredictiveGraph:
 
     def replay(self) -> Predictive:
         self.la._check_math()
+        self.la._glm_ready()
         if self.graph is not None:
             self.graph.replay()
         else:
@@ -238,33 +240,44 @@ class GlmPredictiveGraph:
         return self.result
 
 
-class DiagLaplace:
+def _who(obj) -> str:
+    """The posterior's class name for a message (a bare stand-in object in a test has its own)."""
+    return type(obj).__name__
+
+
+class LaplaceBase:
+    """What every Laplace posterior of an MLP here shares: the refusals, the accumulation chain (forward, seed, one curvature
+    launch per layer top down; eager or captured), the record, the prior precision chosen by the evidence and the linearised
+    (GLM) predictive's interface.  A structure (DiagLaplace; kfac.KronLaplace) supplies its accumulated tensors
+    (_allocate, _accumulated), its layer launches (_curvature_launch, _glm_launch, _glm_buffers) and its evidence (_evidence)."""
+
     def __init__(self, mlp, curvature: str = "ggn", sigma: float = 1.0):
         """`mlp`: a trained networks.MLP, or MLP_Dropout with its dropout switched off (mlp.eval()), on the device.
         `curvature`: 'ggn' (the exact generalised Gauss-Newton / Fisher of the likelihood: C back-propagations per row) or
         'empirical' (squared gradients of the observed labels' log-likelihood: one).  `sigma`: the scale of the Gaussian
         likelihood (regression)."""
+        name = _who(self)
         if curvature not in ops.LAPLACE_CURVATURES:
-            raise BnnHipError(f"DiagLaplace: curvature must be one of {tuple(ops.LAPLACE_CURVATURES)}, got {curvature!r}")
+            raise BnnHipError(f"{name}: curvature must be one of {tuple(ops.LAPLACE_CURVATURES)}, got {curvature!r}")
         if not 0.0 < float(sigma) < float("inf"):
-            raise BnnHipError(f"DiagLaplace: sigma must be positive and finite, got {sigma!r}")
+            raise BnnHipError(f"{name}: sigma must be positive and finite, got {sigma!r}")
         if mlp.mode not in ("classification", "regression"):
-            raise BnnHipError(f"DiagLaplace: unknown mode {mlp.mode!r}")
+            raise BnnHipError(f"{name}: unknown mode {mlp.mode!r}")
         for m in mlp.modules():
             if isinstance(m, nn.Dropout) and m.p > 0 and m.training:
-                raise BnnHipError("DiagLaplace: the network's dropout is on; the Laplace approximation is taken at the "
+                raise BnnHipError(f"{name}: the network's dropout is on; the Laplace approximation is taken at the "
                                   "deterministic trained network -- call mlp.eval() first")
         self.layers = layers_of(mlp)
         if any(d.linear.bias is None for d in self.layers):
-            raise BnnHipError("DiagLaplace: every Linear needs a bias (BayesianLinear has one)")
+            raise BnnHipError(f"{name}: every Linear needs a bias (BayesianLinear has one)")
         if state.shard_samples:
-            raise BnnHipError("DiagLaplace: MC-sample sharding is not supported; switch it off")
+            raise BnnHipError(f"{name}: MC-sample sharding is not supported; switch it off")
         self.mlp, self.mode, self.curvature, self.sigma = mlp, mlp.mode, curvature, float(sigma)
         self.params = [t.detach() for d in self.layers for t in (d.linear.weight, d.linear.bias)]
         if len(self.params) > L.LAPLACE_MAX_TENSORS:
-            raise BnnHipError(f"DiagLaplace: at most {L.LAPLACE_MAX_TENSORS // 2} layers")
+            raise BnnHipError(f"{name}: at most {L.LAPLACE_MAX_TENSORS // 2} layers")
         self.device = self.params[0].device
-        self.curv = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self._allocate()
         self.record = torch.zeros(L.LAPLACE_RECORD_DOUBLES, dtype=torch.float64, device=self.device)
         self.math = _math()[0]
         self._eager: Dict[int, _Chain] = {}
@@ -276,15 +289,24 @@ class DiagLaplace:
 
     def _check_math(self):
         if _math()[0] != self.math:
-            raise BnnHipError("DiagLaplace: the math mode changed since this object was built (a captured chain bakes it in)")
+            raise BnnHipError(f"{_who(self)}: the math mode changed since this object was built (a captured chain bakes it in)")
+
+    def _invalidate(self):
+        """Called after every accumulation and reset: whatever a structure derives from the accumulated tensors is stale."""
+
+    def _glm_ready(self):
+        """Called before the GLM launches, eager or replayed: bring what they read up to date with the accumulated tensors."""
+
+    def _glm_buffers(self, chain: "_GlmChain"):
+        """Per-chain buffers of the structure's GLM launches (none by default)."""
 
     # ---- accumulation
     def reset(self):
         """Zero the curvature and the record (and forget a chosen prior precision)."""
-        for t in self.curv:
+        for t in self._accumulated():
             t.zero_()
-        self.record.zero_()
         self._fitted = False
+        self._invalidate()
 
     def accumulate(self, x: torch.Tensor, y: torch.Tensor):
         """Add one minibatch: forward, seed, one curvature launch per layer (eager launches)."""
@@ -296,6 +318,7 @@ class DiagLaplace:
         ch.stage(x, y)
         ch.enqueue()
         self._fitted = False
+        self._invalidate()
 
     def accumulate_graph(self, x: torch.Tensor, y: torch.Tensor) -> LaplaceStep:
         """The chain for minibatches shaped like (x, y), captured once as a hipGraph: `s = la.accumulate_graph(x, y)`, then
@@ -330,10 +353,6 @@ class DiagLaplace:
                                    torch.zeros(2, dtype=torch.float64, device=self.device))
         return out
 
-    def _evidence(self, precisions, best_index, best):
-        taus = [float(t) for t in np.asarray(precisions, dtype=np.float64).reshape(-1)]
-        return ops.laplace_evidence(self.params, self.curv, taus, record=self.record, best_index=best_index, best=best)
-
     def fit_prior_precision(self, precisions: Sequence[float] = DEFAULT_PRECISIONS) -> torch.Tensor:
         """Choose the candidate of the largest evidence (the lowest index on ties).  The choice stays on the device
         (network() takes it from there); `.prior_precision` reads it.  Returns the log evidences [G] (device)."""
@@ -345,7 +364,7 @@ class DiagLaplace:
     def prior_precision(self) -> float:
         """The precision fit_prior_precision chose (one device read)."""
         if not self._fitted:
-            raise BnnHipError("DiagLaplace: no prior precision chosen yet; call fit_prior_precision()")
+            raise BnnHipError(f"{_who(self)}: no prior precision chosen yet; call fit_prior_precision()")
         return float(self._best[1].item())
 
     # ---- F18: the linearised (GLM) predictive
@@ -358,25 +377,26 @@ class DiagLaplace:
             return None, self._best[1:2]
         tau = float(prior_precision)
         if not 0.0 < tau < float("inf"):
-            raise BnnHipError(f"DiagLaplace.{what}: the prior precision must be positive and finite, got {prior_precision!r}")
+            raise BnnHipError(f"{_who(self)}.{what}: the prior precision must be positive and finite, got {prior_precision!r}")
         return tau, None
 
     def _glm_args(self, samples: int, link: str, quantiles) -> tuple:
         """The checked quantile levels; every refusal of the GLM interface that needs no device."""
         if link not in GLM_LINKS:
-            raise BnnHipError(f"DiagLaplace: link must be one of {GLM_LINKS}, got {link!r}")
+            raise BnnHipError(f"{_who(self)}: link must be one of {GLM_LINKS}, got {link!r}")
         if link == "mc" and int(samples) < 1:
-            raise BnnHipError(f"DiagLaplace: link 'mc' needs samples >= 1, got {samples}")
+            raise BnnHipError(f"{_who(self)}: link 'mc' needs samples >= 1, got {samples}")
         C_out = self.layers[-1].linear.out_features
         if C_out > L.LAPLACE_GLM_MAX_CLASSES:
-            raise BnnHipError(f"DiagLaplace: the linearised predictive handles at most {L.LAPLACE_GLM_MAX_CLASSES} outputs "
+            raise BnnHipError(f"{_who(self)}: the linearised predictive handles at most {L.LAPLACE_GLM_MAX_CLASSES} outputs "
                               f"(BNN_LAPLACE_GLM_MAX_CLASSES); this network has {C_out}")
         if self.mode == "classification" and quantiles:
-            raise BnnHipError("DiagLaplace: quantiles are a regression summary")
+            raise BnnHipError(f"{_who(self)}: quantiles are a regression summary")
         return ops.quantile_levels(quantiles)
 
     def _glm_chain(self, x) -> _GlmChain:
         self._check_math()
+        self._glm_ready()
         B = flat_input(self.mlp, x).shape[0]
         ch = self._glm.get(B)
         if ch is None:
@@ -391,9 +411,10 @@ class DiagLaplace:
 
     def glm_moments(self, x: torch.Tensor, prior_precision: Optional[float] = None):
         """(mean [B, C], cov [B, C, C]) of the Gaussian over the outputs of the network linearised at the trained weights,
-        f(x, w) + J(x)(theta - w) with theta ~ N(w, (diag(F) + tau)^-1): mean = the network's output, cov = J diag(s^2) J^T.
-        Defined for any diagonal F, so an empirical-Fisher object is accepted too (the curvature only has to be a diagonal;
-        the GGN is the one the linearisation is the exact Hessian of)."""
+        f(x, w) + J(x)(theta - w) with theta ~ N(w, (diag(F) + tau)^-1): mean = the network's output, cov = J diag(s^2) J^T
+        (KronLaplace: theta ~ N(w, (H + tau)^-1) with its Kronecker-factored H, cov = J (H + tau)^-1 J^T).
+        Defined for any such curvature, so an empirical-Fisher object is accepted too (the GGN is the one the linearisation
+        is the exact Hessian of)."""
         self._glm_args(0, "probit", None)
         tau, tau_dev = self._tau(prior_precision, "glm_moments")
         ch = self._glm_chain(x)
@@ -445,6 +466,29 @@ class DiagLaplace:
         modes."""
         logits = self.glm_sample(x, samples, prior_precision=prior_precision, sample_offset=sample_offset)
         return ops.mc_score(logits, y, self.mode, sigma=self.sigma if sigma is None else float(sigma), bins=int(bins), record=record)
+
+
+class DiagLaplace(LaplaceBase):
+    """The diagonal structure: curv[2 l], curv[2 l + 1] the curvature diagonals of layer l's weight and bias."""
+
+    def _allocate(self):
+        self.curv = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+
+    def _accumulated(self):
+        return self.curv + [self.record]
+
+    def _curvature_launch(self, i, x, gy, *, g_x, y, gx_mask, math_mode):
+        ops.laplace_layer(x, gy, self.layers[i].linear.weight.detach(), f_w=self.curv[2 * i], f_b=self.curv[2 * i + 1], g_x=g_x,
+                          y=y, gx_mask=gx_mask, math_mode=math_mode)
+
+    def _evidence(self, precisions, best_index, best):
+        taus = [float(t) for t in np.asarray(precisions, dtype=np.float64).reshape(-1)]
+        return ops.laplace_evidence(self.params, self.curv, taus, record=self.record, best_index=best_index, best=best)
+
+    def _glm_launch(self, chain, i, x, gy, *, g_x, y, gx_mask, precision, precision_device, math_mode):
+        ops.laplace_glm_layer(x, gy, self.layers[i].linear.weight.detach(), f_w=self.curv[2 * i], f_b=self.curv[2 * i + 1],
+                              cov_part=chain.parts[i], g_x=g_x, y=y, gx_mask=gx_mask, precision=precision,
+                              precision_device=precision_device, math_mode=math_mode)
 
     # ---- the posterior as a network
     def network(self, prior_precision: Optional[float] = None):

@@ -3132,3 +3132,157 @@ def bank_fwd(x: torch.Tensor, bank: torch.Tensor, w_off: int, b_off: Optional[in
     a._keep = (x, bank, out)
     L.check(lib.bnn_bank_fwd(C.byref(a), _stream()), "bnn_bank_fwd")
     return out
+
+
+# ------------------------------------------------------------------------------------- F20: Kronecker-factored Laplace
+def _kfac_rows(x, gy, w, what: str):
+    """(B, R, in, out) of a layer call's x [B, in], gy [R, out], w [out, in]."""
+    x = _lap_f32(x, "x")
+    if x.dim() != 2:
+        raise BnnHipError(f"{what}: x must be [batch, in], got {tuple(x.shape)}")
+    B, K = x.shape
+    N = w.shape[0]
+    gy = _lap_f32(gy, "gy")
+    if gy.dim() != 2 or gy.shape[0] % B != 0:
+        raise BnnHipError(f"{what}: gy must be [rows, out] with rows a multiple of the batch {B}, got {tuple(gy.shape)}")
+    R = gy.shape[0]
+    _lap_f32(gy, "gy", (R, N)), _lap_f32(w, "w", (N, K))
+    return B, R, K, N
+
+
+def kfac_layer(x, gy, w, *, a, s, g, g_x=None, y=None, gx_mask: bool = False, math_mode: int = L.MATH_F32):
+    """F20 bnn_kfac_layer: one Linear -> [ReLU] group.  x [B, in], gy [R, out] (R a multiple of B), the saved output
+    y [B, out] (gz = y > 0 ? gy : 0) or None; a [in, in] += x^T x, s [in] += colsum(x), g [out, out] += gz^T gz (exact fp32,
+    bit-symmetric); g_x [R, in] = gz w as laplace_layer's (the same bits)."""
+    lib = L.load()
+    B, R, K, N = _kfac_rows(x, gy, w, "kfac_layer")
+    if a is None or s is None or g is None:
+        raise BnnHipError("kfac_layer: the factors (a, s, g) are needed")
+    _lap_f32(a, "a", (K, K)), _lap_f32(s, "s", (K,)), _lap_f32(g, "g", (N, N))
+    _lap_f32(g_x, "g_x", (R, K)), _lap_f32(y, "y", (B, N))
+    k = L.KfacLayerArgs()
+    k.struct_bytes = C.sizeof(L.KfacLayerArgs)
+    k.batch, k.rows, k.in_features, k.out_features = B, R, K, N
+    k.math, k.gx_mask = _exact_unless_bf16(math_mode), int(bool(gx_mask))
+    k.x, k.gy, k.y, k.w = x.data_ptr(), gy.data_ptr(), _ptr(y), w.data_ptr()
+    k.a, k.s, k.g, k.g_x = a.data_ptr(), s.data_ptr(), g.data_ptr(), _ptr(g_x)
+    L.check(lib.bnn_kfac_layer(C.byref(k), _stream()), "bnn_kfac_layer")
+
+
+def kfac_evidence(weights, biases, lambdas_a, lambdas_g, precisions, *, record, log_evidence=None, best_index=None, best=None,
+                  workspace=None):
+    """F20 bnn_kfac_evidence: the Laplace log marginal likelihood in the Kronecker eigenbasis at every candidate prior precision
+    (host floats) -> (log_evidence float64 [G], best_index int32 [1], best float64 [2] = (maximum, its precision)).  Per layer
+    the weight [out, in], the bias [out] and the float64 eigenvalues lambda_a [in + 1], lambda_g [out].  Nothing is read back."""
+    lib = L.load()
+    taus = [float(t) for t in precisions]
+    G, n = len(taus), len(weights)
+    if not 1 <= G <= L.LAPLACE_MAX_PRECISIONS:
+        raise BnnHipError(f"kfac_evidence: between 1 and {L.LAPLACE_MAX_PRECISIONS} candidate precisions, got {G}")
+    if not all(0.0 < t < math.inf for t in taus):
+        raise BnnHipError("kfac_evidence: prior precisions must be positive and finite")
+    if not 1 <= n <= L.LAPLACE_GLM_MAX_LAYERS or not len(biases) == len(lambdas_a) == len(lambdas_g) == n:
+        raise BnnHipError(f"kfac_evidence: between 1 and {L.LAPLACE_GLM_MAX_LAYERS} layers, each with weight, bias and two eigenvalue vectors")
+    a = L.KfacEvidenceArgs()
+    a.struct_bytes = C.sizeof(L.KfacEvidenceArgs)
+    a.n_layers, a.n_precisions = n, G
+    for l, (w, b, la, lg) in enumerate(zip(weights, biases, lambdas_a, lambdas_g)):
+        _lap_f32(w, "weight")
+        N, K = w.shape
+        _lap_f32(b, "bias", (N,)), _lap_f64(la, "lambda_a", K + 1), _lap_f64(lg, "lambda_g", N)
+        a.weight[l], a.bias[l], a.lambda_a[l], a.lambda_g[l] = w.data_ptr(), b.data_ptr(), la.data_ptr(), lg.data_ptr()
+        a.in_features[l], a.out_features[l] = K, N
+    for g, t in enumerate(taus):
+        a.precision[g] = t
+    dev = weights[0].device
+    need = lib.bnn_kfac_evidence_workspace_bytes(C.byref(a))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    log_evidence = torch.empty(G, dtype=torch.float64, device=dev) if log_evidence is None else _lap_f64(log_evidence, "log_evidence", G)
+    best_index = torch.zeros(1, dtype=torch.int32, device=dev) if best_index is None else _typed(best_index, torch.int32, "best_index", 1)
+    best = torch.zeros(2, dtype=torch.float64, device=dev) if best is None else _lap_f64(best, "best", 2)
+    a.record = _lap_f64(record, "record", L.LAPLACE_RECORD_DOUBLES).data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a.log_evidence, a.best_index, a.best = log_evidence.data_ptr(), best_index.data_ptr(), best.data_ptr()
+    L.check(lib.bnn_kfac_evidence(C.byref(a), _stream()), "bnn_kfac_evidence")
+    return log_evidence, best_index, best
+
+
+def kfac_glm_rotate(x, gy, w, *, q_a, q_g, at=None, gt=None, g_x=None, y=None, gx_mask: bool = False, math_mode: int = L.MATH_F32):
+    """F20 bnn_kfac_glm_rotate: at [B, in + 1] = [x | 1] q_a, gt [R, out] = gz q_g (exact fp32; eigenvectors in columns) and
+    g_x [R, in] = gz w as laplace_layer's, in one launch.  Returns (at, gt)."""
+    lib = L.load()
+    B, R, K, N = _kfac_rows(x, gy, w, "kfac_glm_rotate")
+    glm_pairs(R // B)
+    if q_a is None or q_g is None:
+        raise BnnHipError("kfac_glm_rotate: the eigenvectors (q_a, q_g) are needed")
+    _lap_f32(q_a, "q_a", (K + 1, K + 1)), _lap_f32(q_g, "q_g", (N, N)), _lap_f32(g_x, "g_x", (R, K)), _lap_f32(y, "y", (B, N))
+    at = torch.empty((B, K + 1), dtype=torch.float32, device=x.device) if at is None else _lap_f32(at, "at", (B, K + 1))
+    gt = torch.empty((R, N), dtype=torch.float32, device=x.device) if gt is None else _lap_f32(gt, "gt", (R, N))
+    a = L.KfacGlmRotateArgs()
+    a.struct_bytes = C.sizeof(L.KfacGlmRotateArgs)
+    a.batch, a.rows, a.in_features, a.out_features = B, R, K, N
+    a.math, a.gx_mask = _exact_unless_bf16(math_mode), int(bool(gx_mask))
+    a.x, a.gy, a.y, a.w = x.data_ptr(), gy.data_ptr(), _ptr(y), w.data_ptr()
+    a.q_a, a.q_g, a.at, a.gt, a.g_x = q_a.data_ptr(), q_g.data_ptr(), at.data_ptr(), gt.data_ptr(), _ptr(g_x)
+    L.check(lib.bnn_kfac_glm_rotate(C.byref(a), _stream()), "bnn_kfac_glm_rotate")
+    return at, gt
+
+
+def kfac_glm_var(at, gt, lambda_a, lambda_g, *, cov_part=None, v_out=None, precision=None, precision_device=None):
+    """F20 bnn_kfac_glm_var: V [B, out] = at^2 . D^T with D_ji = 1 / (lambda_g[j] lambda_a[i] + tau) formed while staging, and
+    the tile partials of sum_j gt_c gt_c' V into cov_part [ceil(out / 64), B, C (C + 1) / 2] (laplace_glm_finish's layout).
+    at [B, in + 1], gt [B * C, out] float32; the eigenvalues float64; tau a host float or a one-element float64 device tensor."""
+    lib = L.load()
+    at, gt = _lap_f32(at, "at"), _lap_f32(gt, "gt")
+    if at.dim() != 2 or gt.dim() != 2 or at.shape[1] < 2 or gt.shape[0] % at.shape[0] != 0:
+        raise BnnHipError(f"kfac_glm_var: at must be [batch, in + 1] and gt [batch * C, out], got {tuple(at.shape)}, {tuple(gt.shape)}")
+    B, K1 = at.shape
+    R, N = gt.shape
+    P = glm_pairs(R // B)
+    _lap_f64(lambda_a, "lambda_a", K1), _lap_f64(lambda_g, "lambda_g", N), _lap_f32(v_out, "v_out", (B, N))
+    shape = (glm_tiles(N), B, P)
+    cov_part = torch.empty(shape, dtype=torch.float32, device=at.device) if cov_part is None else _lap_f32(cov_part, "cov_part", shape)
+    a = L.KfacGlmVarArgs()
+    a.struct_bytes = C.sizeof(L.KfacGlmVarArgs)
+    a.batch, a.rows, a.in_features, a.out_features = B, R, K1 - 1, N
+    _glm_precision(a, precision, precision_device, "kfac_glm_var")
+    a.at, a.gt, a.lambda_a, a.lambda_g = at.data_ptr(), gt.data_ptr(), lambda_a.data_ptr(), lambda_g.data_ptr()
+    a.cov_part, a.v_out = cov_part.data_ptr(), _ptr(v_out)
+    L.check(lib.bnn_kfac_glm_var(C.byref(a), _stream()), "bnn_kfac_glm_var")
+    return cov_part
+
+
+def kfac_sample(w, b, q_a, q_g, lambda_a, lambda_g, bank: torch.Tensor, w_off: int, b_off: int, *, members: int, first: int = 0,
+                layer: int, seed: int, sample_base: int = 0, precision=None, precision_device=None, workspace=None):
+    """F20 bnn_kfac_sample: `members` matrix-normal draws Wbar + q_g (E o Sigma) q_a^T of one layer into slots first ... of
+    `bank` (float32 [capacity, stride]; the weight at bank[m, w_off], the bias at bank[m, b_off]), two launches.  The noise of
+    draw m is the Philox stream (e >> 2, sample_base + m, layer, 4), slot e & 3.  Returns the workspace (reusable)."""
+    lib = L.load()
+    require_device(bank, workspace)
+    _lap_f32(w, "w")
+    N, K = w.shape
+    _lap_f32(b, "b", (N,)), _lap_f32(q_a, "q_a", (K + 1, K + 1)), _lap_f32(q_g, "q_g", (N, N))
+    _lap_f64(lambda_a, "lambda_a", K + 1), _lap_f64(lambda_g, "lambda_g", N)
+    M, first = int(members), int(first)
+    if bank.dtype != torch.float32 or bank.dim() != 2 or not bank.is_contiguous():
+        raise BnnHipError("kfac_sample: the bank must be a contiguous float32 [capacity, stride] tensor")
+    if M < 1 or first < 0 or first + M > bank.shape[0]:
+        raise BnnHipError(f"kfac_sample: members [{first}, {first + M}) lie outside the bank's {bank.shape[0]} slots")
+    stride = bank.shape[1]
+    if w_off < 0 or w_off + N * K > stride or b_off < 0 or b_off + N > stride:
+        raise BnnHipError("kfac_sample: the layer's weights / bias lie outside a member")
+    need = lib.bnn_kfac_sample_workspace_bytes(M, K, N)
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=bank.device)
+    a = L.KfacSampleArgs()
+    a.struct_bytes = C.sizeof(L.KfacSampleArgs)
+    a.members, a.first, a.in_features, a.out_features = M, first, K, N
+    a.layer, a.sample_base, a.seed = int(layer) & 0xFFFFFFFF, int(sample_base) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF
+    _glm_precision(a, precision, precision_device, "kfac_sample")
+    a.w, a.b, a.q_a, a.q_g = w.data_ptr(), b.data_ptr(), q_a.data_ptr(), q_g.data_ptr()
+    a.lambda_a, a.lambda_g = lambda_a.data_ptr(), lambda_g.data_ptr()
+    a.bank, a.bank_stride, a.w_offset, a.b_offset = bank.data_ptr(), stride, int(w_off), int(b_off)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    L.check(lib.bnn_kfac_sample(C.byref(a), _stream()), "bnn_kfac_sample")
+    return workspace

@@ -29,6 +29,7 @@ from bnn_hip import dense_train as _dense_train
 from bnn_hip import mcdropout as _mcdropout
 from bnn_hip import flipout as _flipout
 from bnn_hip import laplace as _laplace
+from bnn_hip import kfac as _kfac
 from bnn_hip import sgmcmc as _sgmcmc
 from bnn_hip.functional import BBBLinearFn as _BBBLinearFn
 from bnn_hip.functional import LayerCall as _LayerCall
@@ -411,12 +412,17 @@ class _PlainMLP(nn.Module):
         Dropout is always on (train mode), with fresh masks every step (bnn_hip.dense_train.GraphedDenseTrainStep)."""
         return _dense_train.GraphedDenseTrainStep(self, optimizer, x, y, **kw)
 
-    def laplace(self, **kw):
+    def laplace(self, structure="diag", **kw):
         """Extension (not in the reference): a bnn_hip.laplace.DiagLaplace on this trained network -- the diagonal Laplace
         posterior (keywords: curvature 'ggn' | 'empirical', sigma).  `la = mlp.laplace(); la.fit(loader);
         la.fit_prior_precision(); bnn = la.network()` gives a BayesianNetwork centred on these weights.  MLP_Dropout: with
-        the dropout off (mlp.eval())."""
-        return _laplace.DiagLaplace(self, **kw)
+        the dropout off (mlp.eval()).  structure='kron': a bnn_hip.kfac.KronLaplace instead, the Kronecker-factored posterior
+        (correlated inside a layer; the same keywords; `la.sample_bank(members)` in network()'s place)."""
+        if structure == "diag":
+            return _laplace.DiagLaplace(self, **kw)
+        if structure == "kron":
+            return _kfac.KronLaplace(self, **kw)
+        raise _laplace.BnnHipError(f"laplace: structure must be 'diag' or 'kron', got {structure!r}")
 
     def weight_bank(self, capacity):
         """Extension (not in the reference): an empty bnn_hip.sgmcmc.WeightBank of `capacity` weight sets of this network on

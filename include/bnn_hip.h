@@ -2504,6 +2504,175 @@ int bnn_sgmcmc_step(const bnn_sgmcmc_args* args, void* stream);
 int bnn_bank_fwd(const bnn_bank_fwd_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F20  Kronecker-factored (KFAC) Laplace posterior of MLP / MLP_Dropout (Martens & Grosse 2015; Ritter et al. 2018; Immer et
+ * al. 2021): the posterior family that keeps the correlations inside a layer.  Per layer, weight W [out, in] and bias b taken
+ * jointly as Wbar = [W | b] [out, in + 1], abar_n = [a_n ; 1] the homogeneous input of data row n, gz the masked deltas of the
+ * virtual rows (F17's, seeded by bnn_laplace_seed: r = c * batch + n), summed over every accumulated minibatch:
+ *     A = sum_n a_n a_n^T [in, in],   s = sum_n a_n [in],   G = sum_r gz_r gz_r^T [out, out],   N = record[1] (data rows)
+ *     Abar = [[A, s], [s^T, N]],      H ~= (Abar (x) G) / N                    (exact for N = 1)
+ * Once per fit (on the host side of the ABI: an fp64 symmetric eigendecomposition): Abar / N = Q_A diag(lA) Q_A^T,
+ * G = Q_G diag(lG) Q_G^T, eigenvalues below 0 set to 0.  In that basis the posterior is diagonal with precisions
+ * d_ji = lG_j lA_i + tau.  No float atomics anywhere: the same inputs give the same bits.
+ *
+ * bnn_kfac_layer — bnn_laplace_layer with the diagonal product replaced by the factors; one Linear -> [ReLU] group in ONE
+ *   launch, three item kinds sharing the grid:
+ *   gz   = gy [rows, out] (y == NULL), or y[r mod batch, o] > 0 ? gy : 0, formed while staging
+ *   a   += x^T x   [in, in],  K = batch;   g += gz^T gz  [out, out],  K = rows: 64 x 64 tiles on v_mfma_f32_16x16x4_f32, always
+ *          exact fp32, the accumulator INITIALISED FROM THE STORED FACTOR (one fixed chain per element over every minibatch; no
+ *          K-split).  Only tiles with tn <= tm are computed; each is written to both halves from the same registers (a
+ *          diagonal tile writes its lower triangle to both), so a factor is bit-symmetric.
+ *   s   += colsum(x) [in]: four strided partial sums per column, the first starting from the stored s, added in
+ *          bnn_dense_bwd's order.
+ *   g_x  = gz . W [rows, in] (optional), times (x[r mod batch, i] > 0) when gx_mask: bnn_laplace_layer's device code, so its
+ *          bits; BNN_MATH_BF16 rounds gz and W to bf16, other modes are exact fp32.
+ *   Any shape >= 1; every load is bounded by the shape; 4-byte aligned pointers, 16-byte loads / stores where rows and bases
+ *   allow.
+ *   Errors, in this order: NULL args; ABI; batch, rows, in, out < 1, rows % batch != 0, a matrix over 2^31 elements:
+ *   BNN_ERR_SHAPE; math: BNN_ERR_ENUM; x, gy, a, s, g, (g_x) w NULL: BNN_ERR_NULL; BNN_ERR_ALIGN.
+ *
+ * bnn_kfac_evidence — log_evidence[g] = loglik - tau_g |w|^2 / 2 + P log(tau_g) / 2 - 1/2 sum_l sum_ji log(lG_j lA_i + tau_g)
+ *   for up to BNN_LAPLACE_MAX_PRECISIONS candidates over up to BNN_LAPLACE_GLM_MAX_LAYERS layers; P = sum_l out (in + 1),
+ *   loglik = record[0], |w|^2 from the parameters.  fp64 throughout, bnn_laplace_evidence's two stages: a block sums one
+ *   BNN_LAPLACE_CHUNK of one layer's [out, in + 1] grid (element e: j = e / (in + 1), i = e mod (in + 1), the parameter
+ *   beside it W[j, i] or b[j]; thread t the elements t, t + 256, ...; then a fixed tree), one final block sums the blocks and
+ *   writes log_evidence, *best_index (the lowest index on ties), best[0] the maximum, best[1] its precision -- device words;
+ *   nothing is read back.  Workspace: bnn_kfac_evidence_workspace_bytes(args) (0 for arguments the call would refuse).
+ *   Errors, in this order: NULL args; ABI; n_layers outside [1, BNN_LAPLACE_GLM_MAX_LAYERS], n_precisions outside
+ *   [1, BNN_LAPLACE_MAX_PRECISIONS], an in / out < 1, a precision not in (0, inf): BNN_ERR_SHAPE; a weight / bias / lambda,
+ *   record, log_evidence NULL: BNN_ERR_NULL; workspace NULL or short: BNN_ERR_WORKSPACE; BNN_ERR_ALIGN (fp64 words 8 bytes).
+ *
+ * The GLM covariance of data row n is cov[c, c'] = sum_l sum_j gt_cj gt_c'j V_nj with gt = g Q_G (g the Jacobian deltas of
+ * output c, seeded as F18 does), at = abar Q_A and V_nj = sum_i at_ni^2 / (lG_j lA_i + tau): two launches per layer, then
+ * bnn_laplace_glm_finish / bnn_laplace_glm_sample unchanged.
+ *
+ * bnn_kfac_glm_rotate — ONE launch, three item kinds: g_x tiles (as above, the math mode's), at [batch, in + 1] = abar . Q_A
+ *   (K = in + 1; the homogeneous 1 is appended while staging, no padded copy of x exists) and gt [rows, out] = gz . Q_G
+ *   (K = out).  The rotations are always exact fp32 (a bf16 eigenvector matrix is not orthogonal to better than 4e-3).
+ *   q_a [in + 1, in + 1], q_g [out, out]: eigenvectors in columns.  rows = batch * C, C <= BNN_LAPLACE_GLM_MAX_CLASSES.
+ *   Errors, in this order: NULL args; ABI; a dimension < 1, rows % batch != 0, more than BNN_LAPLACE_GLM_MAX_CLASSES virtual
+ *   rows per data row, a matrix over 2^31 elements: BNN_ERR_SHAPE; math: BNN_ERR_ENUM; x, gy, q_a, q_g, at, gt, (g_x) w NULL:
+ *   BNN_ERR_NULL; BNN_ERR_ALIGN.
+ *
+ * bnn_kfac_glm_var — ONE launch: 64 x 64 tiles of V [batch, out] = at^2 . D^T (K = in + 1, exact fp32), D_ji =
+ *   fl32(1.0 / (lG_j lA_i + tau)) formed while staging from the two fp64 eigenvalue vectors: one fp64 fma, one fp64 division,
+ *   rounded once.  tau = *precision_device or `precision`.  The epilogue sums gt_c gt_c' V over the tile's columns for every
+ *   pair c <= c' of a data row, one fixed fmaf chain per partial: cov_part [ceil(out / 64), batch, C (C + 1) / 2] in the layout
+ *   bnn_laplace_glm_finish reads (pair = c' (c' + 1) / 2 + c).  v_out (optional, [batch, out]): V itself, for tests.
+ *   Errors, in this order: NULL args; ABI; a dimension < 1, rows % batch != 0, more than BNN_LAPLACE_GLM_MAX_CLASSES virtual
+ *   rows per data row, a matrix over 2^31 elements, a host precision not in (0, inf): BNN_ERR_SHAPE; at, gt, lambda_a,
+ *   lambda_g, cov_part NULL: BNN_ERR_NULL; BNN_ERR_ALIGN (fp64 words 8 bytes).
+ *
+ * bnn_kfac_sample — matrix-normal weight draws of one layer for `members` bank members, TWO launches:
+ *   T_m    = (E_m o Sigma) . Q_A^T [out, in + 1] (K = in + 1), Sigma_ji = fl32((lG_j lA_i + tau)^-1/2) formed in fp64 and the
+ *            noise formed while staging: element e = j (in + 1) + i of Wbar draws from the Philox counter (e >> 2, global sample
+ *            index sample_base + m, layer, 4), key = seed, slot e & 3, through the epsilon map's Box-Muller (counter word 3:
+ *            0 .. 3 are taken -- the epsilon streams, the bandit / epoch / acquisition / GLM streams, Flipout's signs and
+ *            SG-MCMC's noise).  BNN_EPS_MAP_VERSION stays 2: a new stream, no old one moves.
+ *   Wbar_m = Wbar + Q_G . T_m (K = out); the epilogue writes the weight columns to bank[(first + m) bank_stride + w_offset +
+ *            j in + i] and the bias column to bank[(first + m) bank_stride + b_offset + j]: WeightBank's member layout.
+ *   Always exact fp32.  Workspace: bnn_kfac_sample_workspace_bytes(members, in, out) = members out (in + 1) floats (0 for
+ *   arguments the call would refuse) -- bounded by the chunk of members a call draws.
+ *   Errors, in this order: NULL args; ABI; members, in, out < 1, first or a bank offset < 0, a matrix over 2^31 elements, a
+ *   host precision not in (0, inf): BNN_ERR_SHAPE; w, b, q_a, q_g, lambda_a, lambda_g, bank NULL: BNN_ERR_NULL; workspace NULL
+ *   or short: BNN_ERR_WORKSPACE; BNN_ERR_ALIGN (fp64 words 8 bytes).
+ * ---------------------------------------------------------------------------------- */
+typedef struct bnn_kfac_layer_args {
+  uint32_t struct_bytes;
+  int32_t batch, rows, in_features, out_features;
+  int32_t math;             /* bnn_math of the g_x product */
+  int32_t gx_mask;
+  int32_t reserved;
+  const float* x;           /* [batch, in] */
+  const float* gy;          /* [rows, out] */
+  const float* y;           /* optional [batch, out] */
+  const float* w;           /* [out, in]; read for g_x only */
+  float* a;                 /* [in, in], accumulated */
+  float* s;                 /* [in], accumulated */
+  float* g;                 /* [out, out], accumulated */
+  float* g_x;               /* optional [rows, in] */
+} bnn_kfac_layer_args;
+
+typedef struct bnn_kfac_evidence_args {
+  uint32_t struct_bytes;
+  int32_t n_layers, n_precisions;
+  int32_t reserved;
+  const float* weight[BNN_LAPLACE_GLM_MAX_LAYERS];     /* [out, in] */
+  const float* bias[BNN_LAPLACE_GLM_MAX_LAYERS];       /* [out] */
+  const double* lambda_a[BNN_LAPLACE_GLM_MAX_LAYERS];  /* [in + 1] */
+  const double* lambda_g[BNN_LAPLACE_GLM_MAX_LAYERS];  /* [out] */
+  int32_t in_features[BNN_LAPLACE_GLM_MAX_LAYERS], out_features[BNN_LAPLACE_GLM_MAX_LAYERS];
+  double precision[BNN_LAPLACE_MAX_PRECISIONS];
+  const double* record;
+  void* workspace;
+  size_t workspace_bytes;
+  double* log_evidence;     /* [n_precisions] */
+  int32_t* best_index;      /* optional device word */
+  double* best;             /* optional [2]: the maximum, its precision */
+} bnn_kfac_evidence_args;
+
+typedef struct bnn_kfac_glm_rotate_args {
+  uint32_t struct_bytes;
+  int32_t batch, rows, in_features, out_features;
+  int32_t math;             /* bnn_math of the g_x product */
+  int32_t gx_mask;
+  int32_t reserved;
+  const float* x;           /* [batch, in] */
+  const float* gy;          /* [rows, out] */
+  const float* y;           /* optional [batch, out] */
+  const float* w;           /* [out, in]; read for g_x only */
+  const float* q_a;         /* [in + 1, in + 1] */
+  const float* q_g;         /* [out, out] */
+  float* at;                /* [batch, in + 1] */
+  float* gt;                /* [rows, out] */
+  float* g_x;               /* optional [rows, in] */
+} bnn_kfac_glm_rotate_args;
+
+typedef struct bnn_kfac_glm_var_args {
+  uint32_t struct_bytes;
+  int32_t batch, rows, in_features, out_features;
+  int32_t reserved[3];
+  double precision;               /* host value; ignored with precision_device */
+  const double* precision_device; /* optional */
+  const float* at;          /* [batch, in + 1] */
+  const float* gt;          /* [rows, out] */
+  const double* lambda_a;   /* [in + 1] */
+  const double* lambda_g;   /* [out] */
+  float* cov_part;          /* [ceil(out / 64), batch, C (C + 1) / 2] */
+  float* v_out;             /* optional [batch, out] */
+} bnn_kfac_glm_var_args;
+
+typedef struct bnn_kfac_sample_args {
+  uint32_t struct_bytes;
+  int32_t members;          /* draws of this call */
+  int32_t first;            /* the bank slot of the first of them */
+  int32_t in_features, out_features;
+  uint32_t layer;           /* counter word 2 */
+  uint32_t sample_base;     /* the global sample index of the first draw */
+  int32_t reserved;
+  uint64_t seed;
+  double precision;               /* host value; ignored with precision_device */
+  const double* precision_device; /* optional */
+  const float* w;           /* [out, in] */
+  const float* b;           /* [out] */
+  const float* q_a;         /* [in + 1, in + 1] */
+  const float* q_g;         /* [out, out] */
+  const double* lambda_a;   /* [in + 1] */
+  const double* lambda_g;   /* [out] */
+  float* bank;              /* member m's weight at bank[m * bank_stride + w_offset ...], its bias at ... + b_offset */
+  int64_t bank_stride, w_offset, b_offset;
+  void* workspace;          /* T of the call's members */
+  size_t workspace_bytes;
+} bnn_kfac_sample_args;
+
+size_t bnn_kfac_evidence_workspace_bytes(const bnn_kfac_evidence_args* args);
+size_t bnn_kfac_sample_workspace_bytes(int32_t members, int32_t in_features, int32_t out_features);
+int bnn_kfac_sample(const bnn_kfac_sample_args* args, void* stream);
+int bnn_kfac_layer(const bnn_kfac_layer_args* args, void* stream);
+int bnn_kfac_evidence(const bnn_kfac_evidence_args* args, void* stream);
+int bnn_kfac_glm_rotate(const bnn_kfac_glm_rotate_args* args, void* stream);
+int bnn_kfac_glm_var(const bnn_kfac_glm_var_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
