@@ -20,6 +20,8 @@
              device-resident bank of weight sets that predicts as an ensemble, one launch per layer for all members (F19)
 `kfac`       KronLaplace: the Kronecker-factored (KFAC) Laplace posterior -- factor accumulation, evidence, GLM predictive and
              matrix-normal weight draws into a WeightBank, in the Kronecker eigenbasis (F20)
+`ensemble`   DeepEnsemble / EnsembleTrainStep: a deep ensemble trained in place in a WeightBank, every member per launch, one
+             captured training step whatever the number of members (F21)
 """
 from .runtime import get_math, manual_seed, set_host_eps, set_math, shard_samples  # noqa: F401
 from ._lib import BnnHipError  # noqa: F401
@@ -27,6 +29,7 @@ from .active import ActiveLearner, ActivePool  # noqa: F401
 from .laplace import DiagLaplace  # noqa: F401
 from .sgmcmc import FusedSGMCMC, WeightBank  # noqa: F401
 from .kfac import KronLaplace  # noqa: F401
+from .ensemble import DeepEnsemble, EnsembleTrainStep  # noqa: F401
 
 __all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError", "ActiveLearner", "ActivePool", "DiagLaplace",
-           "FusedSGMCMC", "WeightBank", "KronLaplace"]
+           "FusedSGMCMC", "WeightBank", "KronLaplace", "DeepEnsemble", "EnsembleTrainStep"]

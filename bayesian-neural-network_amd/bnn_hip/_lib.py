@@ -50,6 +50,7 @@ EXPORTS = (
     "bnn_sgmcmc_noise", "bnn_sgmcmc_step", "bnn_bank_fwd",
     "bnn_kfac_layer", "bnn_kfac_evidence", "bnn_kfac_evidence_workspace_bytes", "bnn_kfac_glm_rotate", "bnn_kfac_glm_var",
     "bnn_kfac_sample", "bnn_kfac_sample_workspace_bytes",
+    "bnn_ens_fwd", "bnn_ens_loss", "bnn_ens_bwd",
 )
 
 
@@ -652,6 +653,33 @@ class BankFwdArgs(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class EnsFwdArgs(C.Structure):
+    """bnn_ens_fwd_args (include/bnn_hip.h F21): the training forward of one layer for the members of a weight bank"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("members", C.c_int32), ("first", C.c_int32), ("batch", C.c_int32),
+                ("in_features", C.c_int32), ("out_features", C.c_int32), ("x_shared", C.c_int32), ("relu", C.c_int32),
+                ("math", C.c_int32), ("layer_id", C.c_int32), ("x", C.c_void_p), ("w", C.c_void_p), ("b", C.c_void_p),
+                ("w_stride", C.c_int64), ("b_stride", C.c_int64), ("drop_p", C.c_double), ("seed", C.c_uint64),
+                ("sample_offset", C.c_uint32), ("sample_counter_inc", C.c_uint32), ("sample_counter", C.c_void_p),
+                ("y", C.c_void_p)]
+
+
+class EnsLossArgs(C.Structure):
+    """bnn_ens_loss_args (include/bnn_hip.h F21): bnn_dense_loss for every member, one block each"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("members", C.c_int32), ("batch", C.c_int32), ("classes", C.c_int32),
+                ("loss_mode", C.c_int32), ("target_shared", C.c_int32), ("grad_scale", C.c_float), ("reserved", C.c_int32),
+                ("logits", C.c_void_p), ("target", C.c_void_p), ("loss", C.c_void_p), ("g_logits", C.c_void_p)]
+
+
+class EnsBwdArgs(C.Structure):
+    """bnn_ens_bwd_args (include/bnn_hip.h F21): bnn_dense_bwd for every member in one launch"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("members", C.c_int32), ("first", C.c_int32), ("batch", C.c_int32),
+                ("in_features", C.c_int32), ("out_features", C.c_int32), ("x_shared", C.c_int32), ("math", C.c_int32),
+                ("gx_mask", C.c_int32), ("y_scale", C.c_float), ("gx_scale", C.c_float), ("reserved", C.c_int32),
+                ("x", C.c_void_p), ("gy", C.c_void_p), ("y", C.c_void_p), ("w", C.c_void_p),
+                ("w_stride", C.c_int64), ("g_stride", C.c_int64), ("g_w", C.c_void_p), ("g_b", C.c_void_p),
+                ("g_x", C.c_void_p)]
+
+
 HIST_MAX_JOBS = 16
 HIST_MAX_EDGES = 2048
 HIST_CHUNK = 8192
@@ -992,6 +1020,9 @@ def _load_real():
     for name, cls in (("bnn_kfac_layer", KfacLayerArgs), ("bnn_kfac_evidence", KfacEvidenceArgs),
                       ("bnn_kfac_glm_rotate", KfacGlmRotateArgs), ("bnn_kfac_glm_var", KfacGlmVarArgs),
                       ("bnn_kfac_sample", KfacSampleArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    for name, cls in (("bnn_ens_fwd", EnsFwdArgs), ("bnn_ens_loss", EnsLossArgs), ("bnn_ens_bwd", EnsBwdArgs)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     lib.bnn_kfac_evidence_workspace_bytes.restype = C.c_size_t

@@ -182,53 +182,69 @@ def fill_rows(dataset: DeviceDataset, dst: torch.Tensor, a: int, b: int):
 
 
 class EpochRunner:
-    """One epoch of the reference's train_step on a train.GraphedTrainStep or a dense_train.GraphedDenseTrainStep:
+    """One epoch of the reference's train_step on a train.GraphedTrainStep, a dense_train.GraphedDenseTrainStep or an
+    ensemble.EnsembleTrainStep built on a shared minibatch:
     run_epoch() = one bnn_epoch_permutation, then M x (bnn_epoch_stage into the step's own x, x16, y and beta, the step's
     replay()).  The step keeps its bookkeeping (learning-rate words, MC-sample counter and its host mirror, data-parallel
-    all-reduces) exactly as step() does, so evaluations between epochs draw past the indices used."""
+    all-reduces) exactly as step() does, so evaluations between epochs draw past the indices used.  An ensemble's losses
+    (one per member: more than bnn_epoch_stage's loss words) are filed by one device copy after each replay instead."""
 
     def __init__(self, step, loader: DeviceLoader):
         from .dense_train import GraphedDenseTrainStep
+        from .ensemble import EnsembleTrainStep
         self.step, self.loader = step, loader
-        self.dense = isinstance(step, GraphedDenseTrainStep)
+        self.ensemble = isinstance(step, EnsembleTrainStep)
+        if self.ensemble and step.per_member:
+            raise BnnHipError("EpochRunner: an EnsembleTrainStep must be built on a shared minibatch ([batch, ...])")
+        self.dense = isinstance(step, GraphedDenseTrainStep) or self.ensemble
         ds, B = loader.dataset, loader.batch_size
         d = ds.x.shape[1]
         if not step.x.is_contiguous() or step.x.numel() != B * d or step.x.dtype != torch.float32:
             raise BnnHipError(f"EpochRunner: the step was built on another minibatch shape than [{B}, {d}]")
         if step.y.dtype != ds.y.dtype or not step.y.is_contiguous() or step.y.numel() != B * (ds.y.shape[1] if ds.y.dim() == 2 else 1):
             raise BnnHipError("EpochRunner: the step's targets do not match the data set's")
-        if self.dense:
+        if self.ensemble:
+            self._out = ()                                              # step.loss [members], copied row by row
+            self._beta = None
+        elif self.dense:
             self._out = (step.loss,)
             self._beta = None
         else:
             self._out = tuple(step.out)
             self._beta = torch.from_numpy(beta_table(len(loader))).to(ds.device)
         self._loss_src = [o.reshape(1) for o in self._out]              # views of the step's static outputs
-        self.loss_cols = len(self._out)
+        self.loss_cols = step.members if self.ensemble else len(self._out)
         self._args = {}
 
     def _stage_args(self, shuffled: bool, history: torch.Tensor) -> L.EpochStageArgs:
         a = self._args.get(shuffled)
         if a is None:
-            kw = dict(x_bf16_out=getattr(self.step, "x16", None), loss_src=self._loss_src, loss_history=history)
+            kw = dict(x_bf16_out=getattr(self.step, "x16", None))
+            if not self.ensemble:
+                kw.update(loss_src=self._loss_src, loss_history=history)
             if self._beta is not None:
                 kw.update(beta_table=self._beta, beta=self.step.beta.reshape(1))
             a = self._args[shuffled] = self.loader.stage_args(self.step.x, self.step.y, shuffled, **kw)
-        a.loss_history = history.data_ptr()                             # a fresh [M, k] per epoch, the block re-used
+        if not self.ensemble:
+            a.loss_history = history.data_ptr()                         # a fresh [M, k] per epoch, the block re-used
         return a
 
     def run_epoch(self, order=None) -> torch.Tensor:
         """Returns the per-minibatch loss tuples as one device tensor [M, k] (k = 4 BBB, 3 local reparameterisation, 1
-        MLP): row M-1 is the reference's loss_info, its first entry the epoch_loss.  No host synchronisation."""
+        MLP, the members of an ensemble): row M-1 is the reference's loss_info, its first entry the epoch_loss.  No host
+        synchronisation."""
         ld, M = self.loader, len(self.loader)
         perm = ld.begin_epoch(order)
         hist = torch.empty((M, self.loss_cols), dtype=torch.float32, device=ld.dataset.device)
         a = self._stage_args(perm is not None, hist)
         step = self.step
-        for _ in range(M):
+        for j in range(M):
             ops.epoch_stage(a)                   # files minibatch j-1's loss words, stages minibatch j
             step.replay()
-        hist[M - 1].copy_(torch.cat(self._loss_src))
+            if self.ensemble:
+                hist[j].copy_(step.loss)
+        if not self.ensemble:
+            hist[M - 1].copy_(torch.cat(self._loss_src))
         ld.end_epoch()
         return hist
 

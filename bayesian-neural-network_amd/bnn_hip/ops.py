@@ -3134,6 +3134,134 @@ def bank_fwd(x: torch.Tensor, bank: torch.Tensor, w_off: int, b_off: Optional[in
     return out
 
 
+# ------------------------------------------------------------------------------------- F21: training a deep ensemble
+def _ens_bank(bank: torch.Tensor, members: int, first: int, what: str) -> int:
+    """Checks `bank` (float32 [capacity, stride], contiguous, on the device) and the member span; returns the stride."""
+    require_device(bank)
+    if bank.dtype != torch.float32 or bank.dim() != 2 or not bank.is_contiguous():
+        raise BnnHipError(f"{what}: the bank must be a contiguous float32 [capacity, stride] tensor")
+    if members < 1 or first < 0 or first + members > bank.shape[0]:
+        raise BnnHipError(f"{what}: members [{first}, {first + members}) lie outside the bank's {bank.shape[0]} slots")
+    return int(bank.shape[1])
+
+
+def _ens_act(t: Optional[torch.Tensor], shape: tuple, what: str):
+    if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
+        raise BnnHipError(f"{what}: expected a contiguous float32 tensor of shape {shape}, got {tuple(t.shape)} {t.dtype}")
+
+
+def ens_fwd(x: torch.Tensor, bank: torch.Tensor, w_off: int, b_off: Optional[int], *, out_features: int, members: int,
+            first: int = 0, relu: bool = False, drop_p: float = 0.0, layer_id: int = 0, seed: int = 0, sample_offset: int = 0,
+            sample_counter=None, sample_counter_inc: int = 0, math_mode: int = L.MATH_F32, out=None) -> torch.Tensor:
+    """F21 bnn_ens_fwd: y[j] = drop_j(act(x[j or shared] . W[first + j]^T + b[first + j])) for `members` members of `bank` in one
+    launch, fp32 in and out; the kind-3 mask of `layer_id` at global sample index sample_offset + *sample_counter + j.  x
+    [B, in] (shared) or [members, B, in]; returns [members, B, out].  Bit-equal per member to dense_fwd(x_j, W, b, n_samples=1)
+    at that index."""
+    lib = L.load()
+    M, first, N = int(members), int(first), int(out_features)
+    stride = _ens_bank(bank, M, first, "ens_fwd")
+    require_device(x, out, sample_counter)
+    dropout_params(drop_p)
+    if x.dim() == 2:
+        shared, B, K = 1, x.shape[0], x.shape[1]
+    elif x.dim() == 3 and x.shape[0] == M:
+        shared, B, K = 0, x.shape[1], x.shape[2]
+    else:
+        raise BnnHipError(f"ens_fwd: x must be [batch, in] or [{M}, batch, in], got {tuple(x.shape)}")
+    _ens_act(x, tuple(x.shape), "ens_fwd")
+    if N < 1 or w_off < 0 or w_off + N * K > stride or (b_off is not None and (b_off < 0 or b_off + N > stride)):
+        raise BnnHipError("ens_fwd: the layer's weights / bias lie outside a member")
+    if out is None:
+        out = torch.empty((M, B, N), dtype=torch.float32, device=x.device)
+    _ens_act(out, (M, B, N), "ens_fwd")
+    if sample_counter is not None and (sample_counter.dtype != torch.int32 or sample_counter.numel() != 1):
+        raise BnnHipError("ens_fwd: sample_counter must be a one-element int32 device tensor")
+    a = L.EnsFwdArgs()
+    a.struct_bytes = C.sizeof(L.EnsFwdArgs)
+    a.members, a.first, a.batch, a.in_features, a.out_features = M, first, B, K, N
+    a.x_shared, a.relu, a.math, a.layer_id = shared, int(bool(relu)), _exact_unless_bf16(int(math_mode)), int(layer_id)
+    a.x, a.w, a.w_stride = x.data_ptr(), bank.data_ptr() + 4 * int(w_off), stride
+    if b_off is not None:
+        a.b, a.b_stride = bank.data_ptr() + 4 * int(b_off), stride
+    a.drop_p, a.seed, a.sample_offset = float(drop_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset) & 0xFFFFFFFF
+    a.sample_counter, a.sample_counter_inc = _ptr(sample_counter), int(sample_counter_inc)
+    a.y = out.data_ptr()
+    a._keep = (x, bank, out, sample_counter)
+    L.check(lib.bnn_ens_fwd(C.byref(a), _stream()), "bnn_ens_fwd")
+    return out
+
+
+def ens_loss(logits: torch.Tensor, target: torch.Tensor, mode: str, *, grad_scale: float = 1.0, loss=None, g_logits=None):
+    """F21 bnn_ens_loss: (loss [M], g_logits [M, B, C]) of dense_loss per member of logits [M, B, C], one launch.  target:
+    one for all members (int64 [B] / float32 of B * C elements) or one per member (M times as many elements)."""
+    lib = L.load()
+    require_device(logits, target, loss, g_logits)
+    if logits.dim() != 3:
+        raise BnnHipError(f"ens_loss: logits must be [members, batch, classes], got {tuple(logits.shape)}")
+    _ens_act(logits, tuple(logits.shape), "ens_loss")
+    M, B, Cc = logits.shape
+    if mode == "classification":
+        lm, per, dt = L.NLL_CLASSIFICATION, B, torch.int64
+    elif mode == "regression":
+        lm, per, dt = L.NLL_REGRESSION, B * Cc, torch.float32
+    else:
+        raise BnnHipError(f"ens_loss: unknown mode {mode!r}")
+    if target.dtype != dt or target.numel() not in (per, M * per) or not target.is_contiguous():
+        raise BnnHipError(f"ens_loss: {mode} targets must be contiguous {dt} with {per} (shared) or {M * per} elements")
+    shared = int(target.numel() == per)
+    if loss is None:
+        loss = torch.empty((M,), dtype=torch.float32, device=logits.device)
+    _ens_act(loss, (M,), "ens_loss")
+    if g_logits is None:
+        g_logits = torch.empty_like(logits)
+    _ens_act(g_logits, (M, B, Cc), "ens_loss")
+    a = L.EnsLossArgs()
+    a.struct_bytes = C.sizeof(L.EnsLossArgs)
+    a.members, a.batch, a.classes, a.loss_mode, a.target_shared = M, B, Cc, lm, shared
+    a.grad_scale = float(grad_scale)
+    a.logits, a.target, a.loss, a.g_logits = logits.data_ptr(), target.data_ptr(), loss.data_ptr(), g_logits.data_ptr()
+    L.check(lib.bnn_ens_loss(C.byref(a), _stream()), "bnn_ens_loss")
+    return loss, g_logits
+
+
+def ens_bwd(x: torch.Tensor, gy: torch.Tensor, bank: torch.Tensor, w_off: int, bucket: torch.Tensor, b_off: Optional[int] = None,
+            *, first: int = 0, g_x=None, y=None, y_scale: float = 1.0, gx_mask: bool = False, gx_scale: float = 1.0,
+            math_mode: int = L.MATH_F32):
+    """F21 bnn_ens_bwd: dense_bwd for every member in one launch.  gy [M, B, out]; x [B, in] (shared) or [M, B, in]; member
+    first + j's weights at bank[first + j, w_off]; its gradients go to bucket[j, w_off] ([out, in]) and bucket[j, b_off]
+    ([out]; None: no bias gradient), `bucket` float32 [M, stride] in the bank's layout; g_x (optional) [M, B, in]."""
+    lib = L.load()
+    if gy.dim() != 3:
+        raise BnnHipError(f"ens_bwd: gy must be [members, batch, out], got {tuple(gy.shape)}")
+    M, B, N = gy.shape
+    first = int(first)
+    stride = _ens_bank(bank, M, first, "ens_bwd")
+    require_device(x, gy, bucket, g_x, y)
+    if x.dim() == 2 and x.shape[0] == B:
+        shared, K = 1, x.shape[1]
+    elif x.dim() == 3 and x.shape[0] == M and x.shape[1] == B:
+        shared, K = 0, x.shape[2]
+    else:
+        raise BnnHipError(f"ens_bwd: x must be [{B}, in] or [{M}, {B}, in], got {tuple(x.shape)}")
+    for t, shp in ((x, tuple(x.shape)), (gy, (M, B, N)), (y, (M, B, N)), (g_x, (M, B, K)), (bucket, (M, stride))):
+        _ens_act(t, shp, "ens_bwd")
+    if w_off < 0 or w_off + N * K > stride or (b_off is not None and (b_off < 0 or b_off + N > stride)):
+        raise BnnHipError("ens_bwd: the layer's weights / bias lie outside a member")
+    a = L.EnsBwdArgs()
+    a.struct_bytes = C.sizeof(L.EnsBwdArgs)
+    a.members, a.first, a.batch, a.in_features, a.out_features = M, first, B, K, N
+    a.x_shared, a.math, a.gx_mask = shared, _exact_unless_bf16(int(math_mode)), int(bool(gx_mask))
+    a.y_scale, a.gx_scale = float(y_scale), float(gx_scale)
+    a.x, a.gy, a.y = x.data_ptr(), gy.data_ptr(), _ptr(y)
+    a.w, a.w_stride, a.g_stride = bank.data_ptr() + 4 * int(w_off), stride, stride
+    a.g_w = bucket.data_ptr() + 4 * int(w_off)
+    if b_off is not None:
+        a.g_b = bucket.data_ptr() + 4 * int(b_off)
+    a.g_x = _ptr(g_x)
+    a._keep = (x, gy, y, bank, bucket, g_x)
+    L.check(lib.bnn_ens_bwd(C.byref(a), _stream()), "bnn_ens_bwd")
+
+
 # ------------------------------------------------------------------------------------- F20: Kronecker-factored Laplace
 def _kfac_rows(x, gy, w, what: str):
     """(B, R, in, out) of a layer call's x [B, in], gy [R, out], w [out, in]."""

@@ -39,4 +39,35 @@ __device__ __forceinline__ void nll_row_grad(const float* row, int C, int mode, 
   }
 }
 
+// bnn_dense_loss's row loop (dense_train.hip; one block per member in bnn_ens_loss, ensemble.hip): thread t of THREADS owns rows
+// t, t + THREADS, ... of z [B, C]; writes their gradient rows g (times gs) and returns the thread's partial of the SUM loss
+// (cross_entropy / mse_loss, reduction='sum'), which the caller adds up in a fixed-order tree.
+template <int THREADS>
+__device__ __forceinline__ float dense_loss_rows(const float* __restrict__ z, const void* __restrict__ target, int B, int C, int mode,
+                                                 float gs, float* __restrict__ g) {
+  float acc = 0.f;
+#pragma unroll 1
+  for (int b = threadIdx.x; b < B; b += THREADS) {
+    const float* row = z + (long)b * C;
+    float* grow = g + (long)b * C;
+    if (mode == BNN_NLL_CLASSIFICATION) {
+      const long long tc = reinterpret_cast<const long long*>(target)[b];
+      const bool ok = tc >= 0 && tc < C;
+      float mx, se;
+      row_max_sumexp(row, C, mx, se);
+      // an out-of-range label: NaN loss and row gradient, and z[label] is never read
+      acc += ok ? (mx + logf(se)) - row[ok ? tc : 0] : __builtin_nanf("");
+      softmax_row_grad(row, C, tc, mx, se, gs, grow);
+    } else {
+      const float* tg = reinterpret_cast<const float*>(target) + (long)b * C;
+      for (int c = 0; c < C; ++c) {
+        const float d = row[c] - tg[c];
+        acc = __builtin_fmaf(d, d, acc);
+        grow[c] = 2.f * d * gs;
+      }
+    }
+  }
+  return acc;
+}
+
 }  // namespace bnn

@@ -7,6 +7,8 @@
 // optionally masked on load), or a caller's own (laplace.hip: squares and sums of squares formed on load).
 #pragma once
 
+#include <math.h>
+
 #include "bnn_device.h"
 
 namespace bnn {
@@ -222,6 +224,16 @@ __device__ __forceinline__ void col_sum4(uint4* lds, int m0, int cols, int N, co
   part[g * 64 + c] = s;
   __syncthreads();
   if (threadIdx.x < 64 && o < cols && out) out[o] = ((part[c] + part[64 + c]) + part[128 + c]) + part[192 + c];
+}
+
+// The kind-3 dropout map's threshold and scale (K5's forward and the ensemble's training forward): thr = min(floor(p 2^32),
+// 2^32 - 1), scale = (float)(1 / (1 - p)) in fp64; false unless 0 <= p < 1 (NaN fails)
+inline bool drop_params(double p, uint32_t& thr, float& scale) {
+  if (!(p >= 0.0 && p < 1.0)) return false;
+  const double t = floor(p * 4294967296.0);
+  thr = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+  scale = (float)(1.0 / (1.0 - p));
+  return true;
 }
 
 }  // namespace

@@ -81,29 +81,7 @@ __global__ __launch_bounds__(kThreads) void dense_loss_kernel(const float* __res
                                                               int C, int mode, float gs, float* __restrict__ loss,
                                                               float* __restrict__ g) {
   __shared__ float part[kThreads];
-  float acc = 0.f;
-#pragma unroll 1
-  for (int b = threadIdx.x; b < B; b += kThreads) {
-    const float* row = z + (long)b * C;
-    float* grow = g + (long)b * C;
-    if (mode == BNN_NLL_CLASSIFICATION) {
-      const long long tc = reinterpret_cast<const long long*>(target)[b];
-      const bool ok = tc >= 0 && tc < C;
-      float mx, se;
-      row_max_sumexp(row, C, mx, se);
-      // an out-of-range label: NaN loss and row gradient, and z[label] is never read
-      acc += ok ? (mx + logf(se)) - row[ok ? tc : 0] : __builtin_nanf("");
-      softmax_row_grad(row, C, tc, mx, se, gs, grow);
-    } else {
-      const float* tg = reinterpret_cast<const float*>(target) + (long)b * C;
-      for (int c = 0; c < C; ++c) {
-        const float d = row[c] - tg[c];
-        acc = __builtin_fmaf(d, d, acc);
-        grow[c] = 2.f * d * gs;
-      }
-    }
-  }
-  const float total = tree_sum<kThreads>(acc, part);
+  const float total = tree_sum<kThreads>(dense_loss_rows<kThreads>(z, target, B, C, mode, gs, g), part);
   if (threadIdx.x == 0) *loss = total;
 }
 

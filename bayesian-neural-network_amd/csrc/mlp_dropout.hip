@@ -258,15 +258,6 @@ __global__ void dropout_mask_kernel(float* __restrict__ mask, uint32_t k0, uint3
   }
 }
 
-// thr = min(floor(p 2^32), 2^32 - 1), scale = (float)(1 / (1 - p)) in fp64; false unless 0 <= p < 1 (NaN fails)
-bool drop_params(double p, uint32_t& thr, float& scale) {
-  if (!(p >= 0.0 && p < 1.0)) return false;
-  const double t = floor(p * 4294967296.0);
-  thr = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
-  scale = (float)(1.0 / (1.0 - p));
-  return true;
-}
-
 bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
 
 // Argument checks and the launch geometry of bnn_dense_fwd (a pure function of the arguments' values and alignment).

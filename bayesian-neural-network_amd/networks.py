@@ -31,6 +31,7 @@ from bnn_hip import flipout as _flipout
 from bnn_hip import laplace as _laplace
 from bnn_hip import kfac as _kfac
 from bnn_hip import sgmcmc as _sgmcmc
+from bnn_hip import ensemble as _ensemble
 from bnn_hip.functional import BBBLinearFn as _BBBLinearFn
 from bnn_hip.functional import LayerCall as _LayerCall
 from bnn_hip.functional import LRLinearFn as _LRLinearFn
@@ -429,6 +430,14 @@ class _PlainMLP(nn.Module):
         the device -- where a deep ensemble puts its members (`bank.push(mlp)` after training each) and predicts from them
         (`bank.predictive(x)`, `bank.score(x, y)`, `bank.evaluate(loader)`): one launch per layer for all members."""
         return _sgmcmc.WeightBank(self, int(capacity))
+
+    def ensemble(self, members, seeds=None):
+        """Extension (not in the reference): a bnn_hip.ensemble.DeepEnsemble of `members` weight sets of this network, trained
+        in place in a WeightBank, every member per launch -- `ens = mlp.ensemble(5, seeds=range(5))` (member j re-initialised
+        by reset_parameters() under seed j; this network is left untouched), `opt = FusedSGD(ens.parameters(), lr,
+        capturable=True)`, `step = ens.graphed_train_step(opt, x, y)`, `losses = step.step(x, y)` ([members]), then
+        `ens.bank.predictive(x)`.  Without seeds, push the members yourself (`ens.bank.push(net)`)."""
+        return _ensemble.DeepEnsemble(self, int(members), seeds)
 
     def sgmcmc(self, lr=1e-3, *, capacity=30, **kw):
         """Extension (not in the reference): `(sampler, bank)` wired together -- a bnn_hip.sgmcmc.FusedSGMCMC over this

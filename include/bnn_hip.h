@@ -2673,6 +2673,102 @@ int bnn_kfac_glm_rotate(const bnn_kfac_glm_rotate_args* args, void* stream);
 int bnn_kfac_glm_var(const bnn_kfac_glm_var_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F21  Training a deep ensemble (Lakshminarayanan et al. 2017; not in the reference): one K6 training step of ALL `members`
+ * members of an F19 weight bank as a fixed chain of launches -- bnn_ens_fwd per layer, bnn_ens_loss, bnn_ens_bwd per layer,
+ * then ONE bnn_sgd_step / bnn_adam_step over the bank buffer and the gradient bucket taken as flat tensors of
+ * members * stride elements -- whatever `members` is.  Member j's tensor lives at base + (first + j) * stride (the bank:
+ * bnn_bank_fwd_args' w / w_stride) or base + j * stride (the gradient bucket [members, stride] in the bank's layout; its padding
+ * words are never written).  All three sit on the 64 x 64 tile core of bnn_dense_bwd and bnn_bank_fwd; a block owns one tile of
+ * ONE member, work items are dealt to the XCDs in contiguous ranges of the (member, tile) list.  Every activation is fp32.
+ *
+ * bnn_ens_fwd — the training forward of one Linear -> [ReLU] -> [Dropout] group for all members:
+ *       y[j] = drop_j(act(x[j or shared] . W[first + j]^T + b[first + j])),   j < members
+ *   x fp32 [batch, in] shared by the members (x_shared = 1) or [members, batch, in]; y fp32 [members, batch, out].  The kind-3
+ *   mask of layer layer_id (K5's map) at global sample index sample_offset + *sample_counter + j; drop_p = 0 applies none.
+ *   sample_counter_inc is added to *sample_counter by the launch and only allowed with drop_p == 0 (K5's rule: a launch that
+ *   increments reads no counter); the output layer's launch of a captured step passes `members`.  Math as bnn_dense_fwd
+ *   (BNN_MATH_BF16: operands rounded to bf16 while staged; BNN_MATH_F32 / BNN_MATH_BF16X3: exact fp32).  Member j's output is
+ *   bit-equal to bnn_dense_fwd on (x[j], W[first + j], b[first + j]) with n_samples = 1 and sample_offset = that index.
+ *   Errors, in this order: NULL args; ABI; members, batch, in_features, out_features < 1, first < 0, layer_id < 0, a negative
+ *   stride, drop_p outside [0, 1), sample_counter_inc with drop_p != 0, more than 2^30 tiles: BNN_ERR_SHAPE; math: BNN_ERR_ENUM;
+ *   x, w, y NULL, sample_counter NULL with sample_counter_inc: BNN_ERR_NULL; a pointer not 4-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_ens_loss — bnn_dense_loss for every member, ONE block per member (the same row loop and fixed-order tree: bit-equal
+ *   per member): loss[j] and g_logits[j] of logits[j] [batch, classes] against target (target_shared = 1: one int64 [batch] /
+ *   fp32 [batch, classes] for all members; 0: [members, ...]).  An out-of-range label makes THAT member's loss and its row's
+ *   gradient NaN, reads nothing out of range and leaves the other members untouched.
+ *   Errors, in this order: NULL args; ABI; members, batch, classes < 1, batch * classes > 2^31: BNN_ERR_SHAPE; loss_mode:
+ *   BNN_ERR_ENUM; logits, target, loss, g_logits NULL: BNN_ERR_NULL; logits / loss / g_logits / fp32 targets not 4-byte, int64
+ *   targets not 8-byte aligned: BNN_ERR_ALIGN.
+ *
+ * bnn_ens_bwd — bnn_dense_bwd for every member in ONE launch over (member, tile): per member the input-gradient tiles
+ *   g_x[j] = gz[j] . W[first + j] (optional; the long-K items, ahead of the member's weight-gradient items), g_w[j] = gz[j]^T .
+ *   x[j or shared] and g_b[j] = colsum(gz[j]); gz formed on load from gy[j] and (optionally) the saved output y[j], the g_x
+ *   mask read off x[j] (the layer below's saved output) -- bnn_dense_bwd's rules and math.  g_w / g_b are member j's tensors at
+ *   g_w + j * g_stride / g_b + j * g_stride.  No float atomics, no K-split: every output element is bnn_dense_bwd's fixed
+ *   chain, so member j's g_w, g_b and g_x are bit-equal to bnn_dense_bwd on that member's operands whatever `members` and
+ *   the grid order.
+ *   Errors, in this order: NULL args; ABI; members, batch, in_features, out_features < 1, first < 0, a negative stride, a
+ *   product of two dimensions above 2^31, more than 2^30 work items: BNN_ERR_SHAPE; math: BNN_ERR_ENUM; x, gy, w, g_w NULL:
+ *   BNN_ERR_NULL; a pointer not 4-byte aligned: BNN_ERR_ALIGN.
+ * ---------------------------------------------------------------------------------- */
+typedef struct bnn_ens_fwd_args {
+  uint32_t struct_bytes;
+  int32_t members, first, batch, in_features, out_features;
+  int32_t x_shared;         /* 1: x [batch,in] for all members; 0: x [members,batch,in] */
+  int32_t relu;
+  int32_t math;             /* bnn_math */
+  int32_t layer_id;         /* >= 0: the mask's tensor id is 4 * layer_id + 3 */
+  const float* x;
+  const float* w;           /* member m's [out,in] at w + m * w_stride */
+  const float* b;           /* member m's [out] at b + m * b_stride, or NULL */
+  int64_t w_stride, b_stride;
+  double drop_p;            /* in [0, 1) */
+  uint64_t seed;
+  uint32_t sample_offset;
+  uint32_t sample_counter_inc;
+  uint32_t* sample_counter; /* optional DEVICE word */
+  float* y;                 /* [members,batch,out] */
+} bnn_ens_fwd_args;
+
+typedef struct bnn_ens_loss_args {
+  uint32_t struct_bytes;
+  int32_t members, batch, classes;
+  int32_t loss_mode;        /* bnn_nll_mode */
+  int32_t target_shared;    /* 1: one target for all members; 0: a target per member */
+  float grad_scale;
+  int32_t reserved;
+  const float* logits;      /* [members, batch, classes] */
+  const void* target;       /* int64 [(members,) batch] or fp32 [(members,) batch, classes] */
+  float* loss;              /* [members] (unscaled) */
+  float* g_logits;          /* [members, batch, classes] */
+} bnn_ens_loss_args;
+
+typedef struct bnn_ens_bwd_args {
+  uint32_t struct_bytes;
+  int32_t members, first, batch, in_features, out_features;
+  int32_t x_shared;         /* 1: x [batch,in] for all members; 0: x [members,batch,in] */
+  int32_t math;             /* bnn_math of the g_x product */
+  int32_t gx_mask;
+  float y_scale;
+  float gx_scale;
+  int32_t reserved;
+  const float* x;
+  const float* gy;          /* [members,batch,out] */
+  const float* y;           /* optional [members,batch,out] */
+  const float* w;           /* member m's [out,in] at w + m * w_stride */
+  int64_t w_stride;
+  int64_t g_stride;         /* of g_w and g_b */
+  float* g_w;               /* member j's [out,in] at g_w + j * g_stride */
+  float* g_b;               /* optional: member j's [out] at g_b + j * g_stride */
+  float* g_x;               /* optional [members,batch,in] */
+} bnn_ens_bwd_args;
+
+int bnn_ens_fwd(const bnn_ens_fwd_args* args, void* stream);
+int bnn_ens_loss(const bnn_ens_loss_args* args, void* stream);
+int bnn_ens_bwd(const bnn_ens_bwd_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
