@@ -1294,6 +1294,13 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
 #else
   constexpr bool X_EARLY = !X3 && (BNN_K1B2_STEP_PARTS & 2);
 #endif
+  // the last steps of a piece-order launch (-DBNN_K1B2_TAIL_PARTS=<bits>, for measurement like the knob above): bit 0 = the last
+  // whole step and the K-tail step on the straight-line bodies too, bit 1 = the half-width generator in a K-tail step of <= 16 k
+#ifndef BNN_K1B2_TAIL_PARTS
+#define BNN_K1B2_TAIL_PARTS 3
+#endif
+  constexpr bool TAIL_FORMS = STEP_FORMS && XTL && WTL && EPS == BNN_EPS_PHILOX && (BNN_K1B2_TAIL_PARTS & 1);
+  constexpr bool TAIL_HALF = TAIL_FORMS && (BNN_K1B2_TAIL_PARTS & 2);
   constexpr int WPW = 4 / SB;                 // parameter pieces (of a tile's four) each of the SB waves of a tile brings
   constexpr int XPW = 8 / NF;                 // x pieces (batch tiles of its pair) each of the NF waves of a pair brings
   constexpr int XT = X3 ? 1024 : 512;         // float4s of one pair's x tile (X3: the hi plane's 8 pieces, then the lo plane's)
@@ -1550,16 +1557,23 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
   // wave-uniform conditions of a step come to.  0 = generic: prior kind, epsilon dump and statistics tested in the step, as
   // every launch ran it before (mixture prior, epsilon dump, epsilon from memory or zero, X3, every masked step);
   // 1 / 2 / 3 = Gaussian prior, no epsilon dump, {no statistics, statistics, statistics + sum of log sigma}: nothing to test.
-  // FAST (compile-time): step t + 1 exists and its 32 k lie inside K -- its pieces are requested with stage_fast, no test.
-  auto step = [&, &mfma_phase = mfma_phase](int t, int cur, auto full_, auto body_, auto fast_) __attribute__((always_inline)) {
+  // FAST (compile-time): step t + 1 exists and its pieces are whole in memory -- its 32 k inside K, or (piece-order operands) a
+  // K tail zero-padded there -- so they are requested with stage_fast, no test.
+  // LAST (compile-time; piece-order operands, a wave whose tile is full, BODY 1 .. 3): the launch's last step, nothing to stage.
+  // 1 = its 32 k inside K (FULL); 2 = the K-tail step, whose pads are exact zeros in both operands' pieces: the weights and the
+  // bf16 pack need no mask, the sums of eps^2 and of log sigma keep theirs; 3 = 2 with the half-width generator (tail <= 16 k).
+  auto step = [&, &mfma_phase = mfma_phase](int t, int cur, auto full_, auto body_, auto fast_, auto last_) __attribute__((always_inline)) {
     constexpr bool FULL = decltype(full_)::value;
     constexpr int BODY = decltype(body_)::value;
     constexpr bool FAST = decltype(fast_)::value;
-    static_assert(!BODY || (FULL && !X3 && EPS == BNN_EPS_PHILOX), "step bodies: maskless bf16 steps of the on-chip generator");
+    constexpr int LAST = decltype(last_)::value;
+    constexpr bool PADZ = LAST >= 2;
+    static_assert(!BODY || ((FULL || PADZ) && !X3 && EPS == BNN_EPS_PHILOX), "step bodies: bf16 steps of the on-chip generator without weight masks");
     static_assert(!FAST || (FULL && !X3), "unconditional staging: the maskless bf16 loop");
+    static_assert(!LAST || (BODY && !FAST && XTL && WTL && FULL == (LAST == 1)), "last-step forms: straight-line bodies of a piece-order launch");
     const int k = t * 32 + q * 8;
-    const bool lane_ok = FULL || (n_ok && k < K);
-    const bool real = FULL || !phantom;                          // wave-uniform
+    const bool lane_ok = FULL || ((PADZ || n_ok) && k < K);
+    const bool real = FULL || PADZ || !phantom;                  // wave-uniform
     // (the early x reads go with the straight-line bodies: across the generic body's branches the compiler lays blocks out of
     // line, and tools/lint_hand_loads.py follows a load to its wait in textual order; with the bodies taken out, the maskless step)
     constexpr bool XE = X_EARLY && (BODY != 0 || (!STEP_FORMS && FULL));
@@ -1569,7 +1583,7 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
     const bool st_ls = BODY ? BODY == 3 : do_ls;
     K2_T(st0);
     // the buffer staged here was last read in step t - 1 (barrier since)
-    const bool staged = FAST || t + 1 < ksteps;                  // block-uniform
+    const bool staged = !LAST && (FAST || t + 1 < ksteps);       // block-uniform
 #ifdef BNN_TUNE
     // tuning build only (wrong results; tools/k1b_ablate.py): BNN_TUNE_K1B bit 0 = no barrier, 1 = no waits, 3 = no DMA (the LDS
     // reads of the parameters stay: stale bytes, the same vector work), 4 = no x reads, 5 = no MFMAs
@@ -1607,7 +1621,8 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
     }
     if (real) {
       // the Philox counter of the lane's eight weights (an operand of the early x reads below: the generator stays behind them)
-      uint32_t g = eps_group((uint32_t)n, k, (uint32_t)gpr);
+      // (LAST == 3: lane L + 32, whose own 8 k are padding four groups further on, takes lane L's counter -- philox_normal8_lower_half)
+      uint32_t g = eps_group((uint32_t)n, LAST == 3 ? k - (q >> 1) * 16 : k, (uint32_t)gpr);
       // XE: the first half of the pair's x tile (batch tiles 0 .. 3) is requested here, behind the parameter reads and ahead
       // of the generator -- buffer `cur` was complete at the barrier that closed the previous step, so the reads depend on nothing
       // this step computes -- and waited for in front of the first MFMA; LDS returns in order, so the parameter wait counts
@@ -1629,7 +1644,9 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
       const f32x2 mu2[4] = {{m_lo[0], m_lo[1]}, {m_lo[2], m_lo[3]}, {m_hi[0], m_hi[1]}, {m_hi[2], m_hi[3]}};
       const f32x2 sg2[4] = {{g_lo[0], g_lo[1]}, {g_lo[2], g_lo[3]}, {g_hi[0], g_hi[1]}, {g_hi[2], g_hi[3]}};
       float e[8];
-      if (EPS == BNN_EPS_PHILOX) {
+      if (EPS == BNN_EPS_PHILOX && LAST == 3) {
+        philox_normal8_lower_half<>(g, q >= 2, gs, wid, p.k0, p.k1, e);
+      } else if (EPS == BNN_EPS_PHILOX) {
         uint4 pa_, pb_;
         philox_pair<>(g, gs, wid, p.k0, p.k1, pa_, pb_);
         box_muller8(pa_, pb_, e);
@@ -1669,8 +1686,11 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
           }
         }
         const float e2 = e2v[0] + e2v[1];
+        // (PADZ: no mask on s_a -- a padded weight is fma(+0, eps, +0) = +0 for every finite eps, and a sum of squares is never
+        // -0, so adding its square changes no bit; a padded sigma's log is -inf and the pad lanes' eps are real draws, so the other
+        // two sums keep the mask)
         s_e2 += lane_ok ? e2 : 0.f;
-        s_a += lane_ok ? a : 0.f;
+        s_a += (PADZ || lane_ok) ? a : 0.f;
         s_ls += lane_ok ? ls : 0.f;
       }
       bf16x8 wa, wl = {};
@@ -1692,15 +1712,38 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
       } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          wa[2 * j] = lane_ok ? (__bf16)w2[j][0] : (__bf16)0.f;
-          wa[2 * j + 1] = lane_ok ? (__bf16)w2[j][1] : (__bf16)0.f;
+          wa[2 * j] = (PADZ || lane_ok) ? (__bf16)w2[j][0] : (__bf16)0.f;     // (PADZ: the padded w is +0 already)
+          wa[2 * j + 1] = (PADZ || lane_ok) ? (__bf16)w2[j][1] : (__bf16)0.f;
         }
       }
 #ifdef BNN_STAMPS
       asm volatile("" :: "v"(wa));
 #endif
       K2_T(st2);
-      if (XE) {
+      if (XE && LAST != 0) {
+        // A last-step form is straight-line code between the loops and the epilogue, and there the register allocator gives the
+        // step's MFMAs a SECOND set of accumulator registers (the move into the epilogue's registers comes for free).  In the
+        // loops' order -- all eight x fragments in registers before the first MFMA -- both sets and both halves of the x tile
+        // are alive at once: 109 VGPRs for the kernel where the loops take 102.  So here the first half's MFMAs are ISSUED ahead
+        // of the second half's reads, whose registers are then the ones the first four accumulators left; the matrix pipe works
+        // on the four while the reads are under way, as it does in the loops.  (The early reads landed long ago: lgkmcnt(0).)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xe0), "+v"(xe1), "+v"(xe2), "+v"(xe3));
+        __builtin_amdgcn_sched_barrier(0);     // (statistics and pack stay above: their operands die here)
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xe0), acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xe1), acc[1], 0, 0, 0);
+        acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xe2), acc[2], 0, 0, 0);
+        acc[3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xe3), acc[3], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        f32x4 xl0, xl1, xl2, xl3;
+        asm volatile("ds_read_b128 %0, %4 offset:4096\n\tds_read_b128 %1, %4 offset:5120\n\tds_read_b128 %2, %4 offset:6144\n\tds_read_b128 %3, %4 offset:7168"
+                     : "=&v"(xl0), "=&v"(xl1), "=&v"(xl2), "=&v"(xl3) : "v"(xa), "v"(wa));
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xl0), "+v"(xl1), "+v"(xl2), "+v"(xl3));
+        acc[4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xl0), acc[4], 0, 0, 0);
+        acc[5] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xl1), acc[5], 0, 0, 0);
+        acc[6] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xl2), acc[6], 0, 0, 0);
+        acc[7] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, __builtin_bit_cast(bf16x8, xl3), acc[7], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+      } else if (XE) {
         // the second half of the x tile goes out once the generator's registers are free; the first half (requested at the top
         // of the step) has landed when at most these four reads are outstanding, and its four MFMAs run under their round trip
         f32x4 xl0, xl1, xl2, xl3;
@@ -1749,8 +1792,9 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
     const int full_steps = tile_full ? (K >> 5) : 0;            // steps whose 32 k are all inside K
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
-    constexpr std::integral_constant<int, 0> generic{};
+    constexpr std::integral_constant<int, 0> generic{}, l_none{};
     int t = 0, cur = 0;
+    int last_body = 0;                                          // (TAIL_FORMS) the body of a wave whose last step takes a last-step form
     if constexpr (STEP_FORMS) {
       // The wave's step body, chosen ONCE (every condition is launch- or wave-uniform and constant over the loop).  The maskless
       // loop ends one step early: each of its steps requests a step whose 32 k lie inside K (stage_fast, nothing to test), and the
@@ -1758,10 +1802,23 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
       // per step -- with all its masks true it gives the bits of the maskless body.
       // BARRIER INVARIANT (stated in `step`): every body passes the one barrier of a step exactly once per step, on every path, and
       // the loops below run `ksteps` steps in all, whichever body a wave takes: t counts 0 .. ksteps - 1 through both of them.
+      // PIECE-ORDER operands (TAIL_FORMS), a wave with a full tile and a body 1 .. 3: ALL its steps are straight-line.  The K tail
+      // and the edges are zero-padded in memory, so the tail step's pieces are requested like any other's (stage_fast) and the
+      // maskless loop runs up to the last step, ksteps - 1 steps; `last_body` then hands that one step to the last-step forms
+      // behind the loops.  A phantom wave or one with a partial tile keeps the generic masked steps (tile_full
+      // is false); a launch with row-major operands or split-bf16 math has no such code.
       const int fast_steps = full_steps - 1;
       auto run = [&](auto body_) __attribute__((always_inline)) {
+        constexpr int BODY = decltype(body_)::value;
+        int loop_steps = fast_steps;
+        if constexpr (TAIL_FORMS && BODY != 0) {
+          if (tile_full) {                                        // wave-uniform
+            loop_steps = ksteps - 1;
+            last_body = BODY;
+          }
+        }
 #pragma nounroll
-        for (; t < fast_steps; ++t, cur ^= 1) step(t, cur, yes, body_, yes);
+        for (; t < loop_steps; ++t, cur ^= 1) step(t, cur, yes, body_, yes, l_none);
       };
       if constexpr (EPS != BNN_EPS_PHILOX) {
         run(generic);
@@ -1772,12 +1829,32 @@ __global__ __launch_bounds__(NF * SB * 64, 4) void bbb_fwd_gemm2_kernel(const Bb
         else if (do_stats) run(std::integral_constant<int, 2>{});
         else run(std::integral_constant<int, 1>{});
       }
+      // The one step such a wave has left (last_body != 0), in its last-step form: whole (K % 32 == 0), the K tail, or the K tail
+      // with the half-width generator.
+      // BARRIER INVARIANT, restated: the loop above ran ksteps - 1 steps and exactly one form follows, each of them one `step` with
+      // its one barrier, so the wave passes `ksteps` barriers like the block's other waves (generic, phantom) and leaves
+      // t == ksteps: the masked loop below runs no step for it.
+      if constexpr (TAIL_FORMS) {
+        if (last_body != 0) {                                     // wave-uniform
+          auto last = [&](auto body_) __attribute__((always_inline)) {
+            const int ktail = K & 31;                             // launch-uniform
+            if (ktail == 0) step(t, cur, yes, body_, no, std::integral_constant<int, 1>{});
+            else if (TAIL_HALF && ktail <= 16) { if constexpr (TAIL_HALF) step(t, cur, no, body_, no, std::integral_constant<int, 3>{}); }
+            else step(t, cur, no, body_, no, std::integral_constant<int, 2>{});
+          };
+          if (last_body == 3) last(std::integral_constant<int, 3>{});
+          else if (last_body == 2) last(std::integral_constant<int, 2>{});
+          else last(std::integral_constant<int, 1>{});
+          ++t;
+          cur ^= 1;
+        }
+      }
     } else {
 #pragma nounroll
-      for (; t < full_steps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, yes, generic, no);
+      for (; t < full_steps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, yes, generic, no, l_none);
     }
 #pragma nounroll
-    for (; t < ksteps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, no, generic, no);
+    for (; t < ksteps; ++t, cur = (cur + 1 == NB ? 0 : cur + 1)) step(t, cur, no, generic, no, l_none);
   }
 
 #ifdef BNN_STAMPS

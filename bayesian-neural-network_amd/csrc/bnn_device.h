@@ -165,6 +165,37 @@ __device__ __forceinline__ void philox_normal8(uint32_t group, uint32_t gsample,
   box_muller8(a, b, out);
 }
 
+// philox_normal8 for a wave whose lanes 32 .. 63 hold nothing real (the block forms' K-tail step of at most 16 k: lane L + 32's
+// weights are padding): ONE Philox call and two Box-Muller pairs per lane instead of two and four.  Lane L < 32 draws group
+// `group` -- out[0 .. 3] -- and lane L + 32, handed the SAME `group` value as lane L, draws group + 1, the counter of lane L's
+// second group (same sample, tensor id and key); its four normals move down into lane L's out[4 .. 7], one
+// v_permlane32_swap_b32 per register.  That instruction exchanges lanes 32 .. 63 of its first operand with lanes 0 .. 31 of its
+// second and leaves the other two halves alone; the builtin returns {first, second} as they stand afterwards, so with both
+// operands the lane's own normal, element 1 holds in lane L what lane L + 32 computed (and in lane L + 32 its own value).
+// Epsilon is a pure function of (group, sample, tensor, key) and every operation below is the one box_muller8 applies to the
+// same element, so lanes 0 .. 31 hold the bits of philox_normal8(group, ...); lanes 32 .. 63 hold finite values of no meaning.
+template <int ROUNDS = BNN_PHILOX_ROUNDS>
+__device__ __forceinline__ void philox_normal8_lower_half(uint32_t group, bool upper, uint32_t gsample, uint32_t tensor_id,
+                                                          uint32_t k0, uint32_t k1, float out[8]) {
+  typedef __attribute__((ext_vector_type(2))) float f32x2;
+  const uint4 c = philox4x32<ROUNDS>(make_uint4(group + (upper ? 1u : 0u), gsample, tensor_id, 0u), k0, k1);
+  const f32x2 us = {2.3283064365386963e-10f, 2.3283064365386963e-10f}, uo = {1.1641532182693481e-10f, 1.1641532182693481e-10f};
+  const f32x2 u01v = __builtin_elementwise_fma(f32x2{(float)c.x, (float)c.y}, us, uo);
+  const f32x2 u23v = __builtin_elementwise_fma(f32x2{(float)c.z, (float)c.w}, us, uo);
+  const f32x2 l = {__builtin_amdgcn_logf(u01v[0]), __builtin_amdgcn_logf(u23v[0])};
+  const f32x2 v = l * f32x2{-2.0f * kLn2, -2.0f * kLn2};
+  const float rad0 = __builtin_amdgcn_sqrtf(v[0]), rad1 = __builtin_amdgcn_sqrtf(v[1]);
+  out[0] = rad0 * __builtin_amdgcn_cosf(u01v[1]);
+  out[1] = rad0 * __builtin_amdgcn_sinf(u01v[1]);
+  out[2] = rad1 * __builtin_amdgcn_cosf(u23v[1]);
+  out[3] = rad1 * __builtin_amdgcn_sinf(u23v[1]);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t own = __float_as_uint(out[i]);
+    out[4 + i] = __uint_as_float(__builtin_amdgcn_permlane32_swap(own, own, false, false)[1]);
+  }
+}
+
 // ---------------------------------------------------------------------------- math
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * kLog2e); }
 __device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * kLn2; }
