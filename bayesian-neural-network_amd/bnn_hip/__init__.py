@@ -22,14 +22,18 @@
              matrix-normal weight draws into a WeightBank, in the Kronecker eigenbasis (F20)
 `ensemble`   DeepEnsemble / EnsembleTrainStep: a deep ensemble trained in place in a WeightBank, every member per launch, one
              captured training step whatever the number of members (F21)
+`swag`       FusedSWAG / SwagPosterior: SGD with momentum in the optimiser's place of K6's captured step that also collects SWAG's
+             moments, the SWA point estimate, SWAG-Diagonal as a BayesianNetwork and low-rank draws into a WeightBank (F22)
 """
 from .runtime import get_math, manual_seed, set_host_eps, set_math, shard_samples  # noqa: F401
 from ._lib import BnnHipError  # noqa: F401
 from .active import ActiveLearner, ActivePool  # noqa: F401
 from .laplace import DiagLaplace  # noqa: F401
 from .sgmcmc import FusedSGMCMC, WeightBank  # noqa: F401
+from .swag import FusedSWAG, SwagPosterior  # noqa: F401
 from .kfac import KronLaplace  # noqa: F401
 from .ensemble import DeepEnsemble, EnsembleTrainStep  # noqa: F401
 
 __all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError", "ActiveLearner", "ActivePool", "DiagLaplace",
-           "FusedSGMCMC", "WeightBank", "KronLaplace", "DeepEnsemble", "EnsembleTrainStep"]
+           "FusedSGMCMC", "WeightBank", "KronLaplace", "DeepEnsemble", "EnsembleTrainStep",
+           "FusedSWAG", "SwagPosterior"]

@@ -51,6 +51,7 @@ EXPORTS = (
     "bnn_kfac_layer", "bnn_kfac_evidence", "bnn_kfac_evidence_workspace_bytes", "bnn_kfac_glm_rotate", "bnn_kfac_glm_var",
     "bnn_kfac_sample", "bnn_kfac_sample_workspace_bytes",
     "bnn_ens_fwd", "bnn_ens_loss", "bnn_ens_bwd",
+    "bnn_swag_step", "bnn_swag_sample",
 )
 
 
@@ -680,6 +681,31 @@ class EnsBwdArgs(C.Structure):
                 ("g_x", C.c_void_p)]
 
 
+SWAG_MAX_RANK = 32
+SWAG_MAX_MEMBERS = 64
+SWAG_NOISE_WORD3 = 5
+
+
+class SwagStepArgs(C.Structure):
+    """bnn_swag_step_args (include/bnn_hip.h F22): one SGD step that also folds the iterate into SWAG's moments"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_tensors", C.c_int32), ("param", C.c_void_p * SGMCMC_MAX_TENSORS),
+                ("grad", C.c_void_p * SGMCMC_MAX_TENSORS), ("momentum", C.c_void_p * SGMCMC_MAX_TENSORS),
+                ("numel", C.c_int64 * SGMCMC_MAX_TENSORS), ("lr", C.c_double), ("momentum_factor", C.c_double),
+                ("weight_decay", C.c_double), ("lr_device", C.c_void_p), ("start", C.c_uint32), ("every", C.c_uint32),
+                ("rank", C.c_int32), ("reserved", C.c_int32), ("mean", C.c_void_p), ("m2", C.c_void_p), ("dev", C.c_void_p),
+                ("step", C.c_void_p), ("count", C.c_void_p), ("ticket", C.c_void_p)]
+
+
+class SwagSampleArgs(C.Structure):
+    """bnn_swag_sample_args (include/bnn_hip.h F22): draws from the SWAG Gaussian into members of a weight bank"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_tensors", C.c_int32), ("numel", C.c_int64 * SGMCMC_MAX_TENSORS),
+                ("rank", C.c_int32), ("members", C.c_int32), ("first", C.c_int32), ("capacity", C.c_int32),
+                ("low_rank", C.c_int32), ("eps_mode", C.c_int32), ("c_d", C.c_float), ("var_clamp", C.c_float),
+                ("c_lr", C.c_float * (SWAG_MAX_RANK + 1)), ("sample_base", C.c_uint32), ("seed", C.c_uint64),
+                ("mean", C.c_void_p), ("m2", C.c_void_p), ("dev", C.c_void_p), ("count", C.c_void_p), ("z1", C.c_void_p),
+                ("z2", C.c_void_p), ("bank", C.c_void_p)]
+
+
 HIST_MAX_JOBS = 16
 HIST_MAX_EDGES = 2048
 HIST_CHUNK = 8192
@@ -1023,6 +1049,9 @@ def _load_real():
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     for name, cls in (("bnn_ens_fwd", EnsFwdArgs), ("bnn_ens_loss", EnsLossArgs), ("bnn_ens_bwd", EnsBwdArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    for name, cls in (("bnn_swag_step", SwagStepArgs), ("bnn_swag_sample", SwagSampleArgs)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     lib.bnn_kfac_evidence_workspace_bytes.restype = C.c_size_t

@@ -21,6 +21,7 @@ from .ops import BnnHipError
 from .optim import FusedAdam, FusedSGD, _sgd_supported
 from .runtime import state
 from .sgmcmc import FusedSGMCMC
+from .swag import FusedSWAG
 
 LOSSES = ("cross_entropy", "mse")
 
@@ -29,14 +30,14 @@ class GraphedDenseTrainStep:
     def __init__(self, mlp, optimizer, x: torch.Tensor, y: torch.Tensor, loss=None, capture: bool = True):
         """`x`, `y`: an example minibatch (the shape and dtype of every later one): classification x [B, 1, h, w] with
         int64 labels [B], regression x [B, in] with float32 targets of B * out elements.  `optimizer`: FusedSGD,
-        FusedAdam or sgmcmc.FusedSGMCMC (the sampler in the optimiser's place) with capturable=True over the network's
-        parameters.  `loss`: 'cross_entropy' or 'mse' (sum reduction),
+        FusedAdam, sgmcmc.FusedSGMCMC (the sampler in the optimiser's place) or swag.FusedSWAG (SGD that also collects SWAG's
+        moments) with capturable=True over the network's parameters.  `loss`: 'cross_entropy' or 'mse' (sum reduction),
         by default the reference's for mlp.mode.  `capture=False`: the same launches, run eagerly on every step.
 
         Building the step runs one real warm-up step and then restores the parameters, the optimiser state and the
         sample counter, so the model and the optimiser are left as they were."""
-        if not isinstance(optimizer, (FusedSGD, FusedAdam, FusedSGMCMC)):
-            raise BnnHipError("GraphedDenseTrainStep needs FusedSGD, FusedAdam or FusedSGMCMC (capturable=True)")
+        if not isinstance(optimizer, (FusedSGD, FusedAdam, FusedSGMCMC, FusedSWAG)):
+            raise BnnHipError("GraphedDenseTrainStep needs FusedSGD, FusedAdam, FusedSGMCMC or FusedSWAG (capturable=True)")
         if not all(g.get("capturable") for g in optimizer.param_groups):
             raise BnnHipError("GraphedDenseTrainStep needs a capturable optimiser (capturable=True)")
         if isinstance(optimizer, FusedSGD):

@@ -3094,6 +3094,131 @@ def sgmcmc_step(params, grads, *, table: torch.Tensor, step: torch.Tensor, ticke
     L.check(lib.bnn_sgmcmc_step(C.byref(a), _stream()), "bnn_sgmcmc_step")
 
 
+# ---------------------------------------------------------------------------------------------------------------- F22 SWAG
+def swag_collects(step: int, start: int, every: int) -> bool:
+    """bnn_swag_step's predicate on the uint32 step word: k >= start and (k - start + 1) % every == 0."""
+    k, start = int(step) & 0xFFFFFFFF, int(start) & 0xFFFFFFFF
+    return k >= start and (k - start + 1) % int(every) == 0
+
+
+def swag_coefficients(scale: float, low_rank: bool = True) -> tuple:
+    """(c_d, c_lr) of bnn_swag_sample, formed in fp64 and rounded once: c_d = sqrt(scale / 2) with the low-rank term and
+    sqrt(scale) without; c_lr[e] = sqrt(scale / (2 (e - 1))) for e = 2 .. SWAG_MAX_RANK, c_lr[0] = c_lr[1] = 0 (all 0
+    without the low-rank term)."""
+    import numpy as np
+    scale = float(scale)
+    if not 0.0 <= scale < float("inf"):
+        raise BnnHipError(f"swag: scale must be finite and >= 0, got {scale!r}")
+    c_lr = np.zeros(L.SWAG_MAX_RANK + 1, dtype=np.float64)
+    if low_rank:
+        e = np.arange(2, L.SWAG_MAX_RANK + 1, dtype=np.float64)
+        c_lr[2:] = np.sqrt(scale / (2.0 * (e - 1.0)))
+    return float(np.float32(math.sqrt(scale / 2.0 if low_rank else scale))), c_lr.astype(np.float32)
+
+
+def _swag_moments(name, numels, mean, m2, dev, rank):
+    stride = bank_layout(numels)[1]
+    require_device(mean, m2, dev)
+    for t, nm in ((mean, "mean"), (m2, "m2")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (stride,):
+            raise BnnHipError(f"{name}: {nm} must be a contiguous float32 [{stride}] tensor (the bank's layout)")
+    if rank > 0 and (dev is None or dev.dtype != torch.float32 or not dev.is_contiguous() or tuple(dev.shape) != (rank, stride)):
+        raise BnnHipError(f"{name}: dev must be a contiguous float32 [{rank}, {stride}] tensor")
+    return stride
+
+
+def swag_step(params, grads, *, lr: float, momentum: float = 0.0, weight_decay: float = 0.0, lr_device=None, momenta=None,
+              start: int = 0, every: int = 1, mean: torch.Tensor, m2: torch.Tensor, dev: Optional[torch.Tensor],
+              step: torch.Tensor, count: torch.Tensor, ticket: torch.Tensor):
+    """F22 bnn_swag_step: one torch.optim.SGD step (momenta None: no momentum buffer) over lists of fp32 tensors in one
+    launch; when the step word k has k >= start and (k - start + 1) % every == 0 the launch also folds the new iterate into
+    `mean`, `m2` (Welford) and row count % rank of `dev` ([rank, stride]; None: rank 0).  `step`, `count`: one-element int32
+    device words (read as uint32), `ticket` 16 zeroed int32 words."""
+    lib = L.load()
+    n = len(params)
+    if not 1 <= n <= L.SGMCMC_MAX_TENSORS:
+        raise BnnHipError(f"swag_step: between 1 and {L.SGMCMC_MAX_TENSORS} parameter tensors, got {n}")
+    if len(grads) != n or (momenta is not None and len(momenta) != n):
+        raise BnnHipError("swag_step: one gradient (momentum) tensor per parameter")
+    rank = 0 if dev is None else int(dev.shape[0])
+    if rank > L.SWAG_MAX_RANK or int(every) < 1 or int(start) < 0:
+        raise BnnHipError(f"swag_step: rank <= {L.SWAG_MAX_RANK}, every >= 1 and start >= 0 are required")
+    require_device(step, count, ticket, lr_device)
+    _swag_moments("swag_step", [p.numel() for p in params], mean, m2, dev, rank)
+    a = L.SwagStepArgs()
+    a.struct_bytes = C.sizeof(L.SwagStepArgs)
+    a.n_tensors = n
+    keep = [mean, m2, dev, step, count, ticket, lr_device]
+    for j in range(n):
+        ts = [params[j], grads[j]] + ([momenta[j]] if momenta is not None else [])
+        for t in ts:
+            require_device(t)
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != params[j].numel():
+                raise BnnHipError("swag_step: parameters, gradients and momenta must be contiguous float32 of one size")
+        keep += ts
+        a.param[j], a.grad[j], a.numel[j] = params[j].data_ptr(), grads[j].data_ptr(), params[j].numel()
+        if momenta is not None:
+            a.momentum[j] = momenta[j].data_ptr()
+    a.lr, a.momentum_factor, a.weight_decay, a.lr_device = float(lr), float(momentum), float(weight_decay), _ptr(lr_device)
+    a.start, a.every, a.rank = int(start) & 0xFFFFFFFF, int(every), rank
+    a.mean, a.m2, a.dev = mean.data_ptr(), m2.data_ptr(), _ptr(dev)
+    a.step = _typed(step, torch.int32, "step", 1).data_ptr()
+    a.count = _typed(count, torch.int32, "count", 1).data_ptr()
+    a.ticket = _typed(ticket, torch.int32, "ticket", 16).data_ptr()
+    a._keep = keep
+    L.check(lib.bnn_swag_step(C.byref(a), _stream()), "bnn_swag_step")
+
+
+def swag_sample(numels: Sequence[int], mean: torch.Tensor, m2: torch.Tensor, dev: Optional[torch.Tensor], count: torch.Tensor,
+                bank: torch.Tensor, *, members: int, first: int = 0, scale: float = 1.0, low_rank: bool = True,
+                var_clamp: float = 1e-30, eps_mode: int = L.EPS_PHILOX, seed: int = 0, sample_base: int = 0, z1=None, z2=None):
+    """F22 bnn_swag_sample: members first .. first + members - 1 of `bank` (float32 [capacity, stride]) drawn from the SWAG
+    Gaussian in one launch, members <= SWAG_MAX_MEMBERS: theta = mean + c_d sqrt(max(m2 / n, var_clamp)) z1 [+ c_lr[Keff]
+    sum_j dev[j] z2[j]], n = the device word `count`, Keff = min(n, rank).  Draw j of the launch is global draw
+    sample_base + j of the seed's streams.  EPS_MEMORY: z1 [members, stride], z2 [members, rank]."""
+    lib = L.load()
+    numels = [int(v) for v in numels]
+    if not 1 <= len(numels) <= L.SGMCMC_MAX_TENSORS:
+        raise BnnHipError(f"swag_sample: between 1 and {L.SGMCMC_MAX_TENSORS} parameter tensors, got {len(numels)}")
+    rank = 0 if dev is None else int(dev.shape[0])
+    m, first = int(members), int(first)
+    if low_rank and rank == 0:
+        raise BnnHipError("swag_sample: the low-rank term needs deviation rows (rank >= 1); pass low_rank=False for SWAG-Diagonal")
+    if rank > L.SWAG_MAX_RANK or not 1 <= m <= L.SWAG_MAX_MEMBERS or not float(var_clamp) >= 0.0:
+        raise BnnHipError(f"swag_sample: rank <= {L.SWAG_MAX_RANK}, 1 <= members <= {L.SWAG_MAX_MEMBERS} and var_clamp >= 0 are required")
+    stride = _swag_moments("swag_sample", numels, mean, m2, dev, rank)
+    require_device(count, bank, z1, z2)
+    if bank.dtype != torch.float32 or bank.dim() != 2 or bank.shape[1] != stride or not bank.is_contiguous():
+        raise BnnHipError(f"swag_sample: the bank must be a contiguous float32 [capacity, {stride}] tensor")
+    if first < 0 or first + m > bank.shape[0]:
+        raise BnnHipError(f"swag_sample: members [{first}, {first + m}) outside the bank's {bank.shape[0]}")
+    a = L.SwagSampleArgs()
+    a.struct_bytes = C.sizeof(L.SwagSampleArgs)
+    a.n_tensors = len(numels)
+    for j, v in enumerate(numels):
+        a.numel[j] = v
+    a.rank, a.members, a.first, a.capacity = rank, m, first, bank.shape[0]
+    a.low_rank, a.eps_mode = 1 if low_rank else 0, int(eps_mode)
+    c_d, c_lr = swag_coefficients(scale, bool(low_rank))
+    a.c_d, a.var_clamp = c_d, float(var_clamp)
+    for e in range(L.SWAG_MAX_RANK + 1):
+        a.c_lr[e] = float(c_lr[e])
+    a.sample_base, a.seed = int(sample_base) & 0xFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.mean, a.m2, a.dev = mean.data_ptr(), m2.data_ptr(), _ptr(dev) if low_rank else None
+    a.count, a.bank = _typed(count, torch.int32, "count", 1).data_ptr(), bank.data_ptr()
+    if eps_mode == L.EPS_MEMORY:
+        if z1 is None or z1.dtype != torch.float32 or not z1.is_contiguous() or tuple(z1.shape) != (m, stride):
+            raise BnnHipError(f"swag_sample: z1 must be a contiguous float32 [{m}, {stride}] tensor")
+        a.z1 = z1.data_ptr()
+        if low_rank:
+            if z2 is None or z2.dtype != torch.float32 or not z2.is_contiguous() or tuple(z2.shape) != (m, rank):
+                raise BnnHipError(f"swag_sample: z2 must be a contiguous float32 [{m}, {rank}] tensor")
+            a.z2 = z2.data_ptr()
+    a._keep = [mean, m2, dev, count, bank, z1, z2]
+    L.check(lib.bnn_swag_sample(C.byref(a), _stream()), "bnn_swag_sample")
+    return bank
+
+
 def bank_fwd(x: torch.Tensor, bank: torch.Tensor, w_off: int, b_off: Optional[int], *, out_features: int, members: int,
              first: int = 0, relu: bool = False, math_mode: int = L.MATH_F32, y_dtype=torch.float32, out=None) -> torch.Tensor:
     """F19 bnn_bank_fwd: y[j] = act(x[j or shared] . W[first + j]^T + b[first + j]) for `members` members of `bank` (float32

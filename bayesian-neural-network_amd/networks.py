@@ -31,6 +31,7 @@ from bnn_hip import flipout as _flipout
 from bnn_hip import laplace as _laplace
 from bnn_hip import kfac as _kfac
 from bnn_hip import sgmcmc as _sgmcmc
+from bnn_hip import swag as _swag
 from bnn_hip import ensemble as _ensemble
 from bnn_hip.functional import BBBLinearFn as _BBBLinearFn
 from bnn_hip.functional import LayerCall as _LayerCall
@@ -447,6 +448,15 @@ class _PlainMLP(nn.Module):
         (an MLP_Dropout's dropout is more gradient noise, and its members predict with the dropout off)."""
         bank = _sgmcmc.WeightBank(self, int(capacity))
         return _sgmcmc.FusedSGMCMC(self.parameters(), lr, bank=bank, **kw), bank
+
+    def swag(self, lr=1e-3, *, rank=20, **kw):
+        """Extension (not in the reference): `(opt, swag)` wired together -- a bnn_hip.swag.FusedSWAG over this network's
+        parameters (torch.optim.SGD's momentum and weight_decay; `start`, `every`: which optimiser steps are collected) and
+        the bnn_hip.swag.SwagPosterior it fills (`rank` deviation rows; 0: SWAG-Diagonal only).  `step =
+        mlp.graphed_train_step(opt, x, y)` then fits the posterior as it trains; afterwards `swag.swa()` is the SWA point
+        estimate, `swag.network()` SWAG-Diagonal as a BayesianNetwork and `swag.sample_bank(30).predictive(x)` full SWAG."""
+        post = _swag.SwagPosterior(self, rank=int(rank))
+        return _swag.FusedSWAG(self.parameters(), lr, swag=post, **kw), post
 
 
 class MLP(_PlainMLP):

@@ -2769,6 +2769,100 @@ int bnn_ens_loss(const bnn_ens_loss_args* args, void* stream);
 int bnn_ens_bwd(const bnn_ens_bwd_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F22  SWAG for MLP / MLP_Dropout (Maddox et al. 2019, "A Simple Baseline for Bayesian Uncertainty in Deep Learning"; not in
+ * the reference): a Gaussian with a diagonal-plus-low-rank covariance fitted to the iterates of plain SGD.  The tensor list is
+ * F19's: up to BNN_SGMCMC_MAX_TENSORS fp32 tensors; the moments (mean [stride], m2 [stride], dev [rank, stride]) hold element i
+ * of tensor t at off_t + i, off_t = sum_{u < t} round_up(numel[u], 64), stride = sum_t round_up(numel[t], 64) -- the layout of
+ * one member of an F19 bank.  Padding words are never written.
+ *
+ * bnn_swag_step — one SGD step (torch.optim.SGD, dampening 0, no nesterov; the momentum buffer starts at 0) over all tensors in
+ *   ONE launch that also folds the new iterate into the moments when the step collects.  With k = *step and n = *count, both
+ *   read before the update, every element does, in fp32 with the fused multiply-adds written out,
+ *       g' = weight_decay != 0 ? fma(weight_decay, p, g) : g
+ *       u  = momentum[0] != NULL ? (v' = fma(momentum_factor, v, g')) : g'
+ *       p' = fma(-lr, u, p)                              lr: *lr_device when given
+ *   (without momentum buffers p' is bnn_sgd_step's bits), and when k >= start && (k - start + 1) % every == 0, with
+ *   r = 1 / (float)(n + 1) correctly rounded,
+ *       d = p' - mean;   mean' = fma(d, r, mean);   m2' = fma(d, p' - mean', m2);   dev[n % rank][i] = p' - mean'   (rank > 0)
+ *   Welford's update: m2 / n is the population variance of the collected iterates without the cancellation of
+ *   mean(theta^2) - mean(theta)^2; the deviation uses the updated mean, as the paper's does.  rank = 0: no dev (SWAG-Diagonal).
+ *   Every block reads *step and *count before its update; the block that arrives last stores k + 1 and, on a collecting step,
+ *   n + 1 (the ticketed hand-off of bnn_adam_step; ticket: 16 zeroed uint32 words, left zeroed).  No float atomics, no tick
+ *   launch.
+ *   Errors, in this order: NULL args; ABI; n_tensors outside [1, BNN_SGMCMC_MAX_TENSORS], rank outside [0, BNN_SWAG_MAX_RANK],
+ *   every < 1, a negative or NaN lr / momentum_factor / weight_decay, a numel outside [1, 2^34]: BNN_ERR_SHAPE; step, count,
+ *   ticket, mean, m2, (rank > 0) dev, a param, a grad, a momentum when momentum[0] is given (or one given when it is not) NULL:
+ *   BNN_ERR_NULL; BNN_ERR_ALIGN (tensors, mean, m2 and dev 16 bytes, words 4).
+ *
+ * bnn_swag_sample — members first .. first + members - 1 of a bank [capacity, stride] in ONE launch, members <=
+ *   BNN_SWAG_MAX_MEMBERS.  With n = *count, Keff = low_rank ? min(n, rank) : 0 and q = sample_base + member index within the
+ *   launch, every element does
+ *       s     = sqrt(max(m2 * (1 / (float)n), var_clamp))            correctly rounded sqrt and reciprocal (n = 0: 1 / n := 0)
+ *       theta = fma(c_d * s, z1, mean)
+ *       acc   = 0;  for j = 0 .. Keff - 1 ascending:  acc = fma(dev[j][i], z2[q][j], acc)
+ *       theta = fma(c_lr[Keff], acc, theta)                          low_rank only
+ *   The host forms c_d (sqrt(scale / 2) with the low-rank term, sqrt(scale) without) and c_lr[e] = sqrt(scale / (2 (e - 1))),
+ *   c_lr[0] = c_lr[1] = 0, in fp64 and rounds them once: no transcendental of the rule beyond the one sqrt runs on the device.
+ *   The noise, by eps_mode.  BNN_EPS_PHILOX: counter word 3 = 5 (0 eps, 1 bandit / epoch / acquisition / BatchBALD / GLM, 2
+ *   Flipout, 3 SG-MCMC, 4 KFAC: no existing stream moved, BNN_EPS_MAP_VERSION stays 2), key = (seed_lo, seed_hi), the map's
+ *   Box-Muller: z1 of element i of tensor t from counter (i >> 2, q, t, 5) slot i & 3, z2[q][j] from counter
+ *   (j >> 2, q, BNN_SGMCMC_MAX_TENSORS, 5) slot j & 3 -- pure functions of (seed, q, t, i) and (seed, q, j); the launch's other
+ *   members, the grid and rank do not enter.  BNN_EPS_MEMORY: z1 [members, stride] in the bank's layout and z2 [members, rank]
+ *   (low_rank).  BNN_EPS_ZERO: every member is the mean's bits.
+ *   Members outside [first, first + members) and the padding words are not written.
+ *   Errors, in this order: NULL args; ABI; n_tensors outside [1, BNN_SGMCMC_MAX_TENSORS], rank outside [0, BNN_SWAG_MAX_RANK],
+ *   members outside [1, BNN_SWAG_MAX_MEMBERS], first < 0, capacity < 1, first + members > capacity, low_rank with rank 0, a
+ *   negative or NaN var_clamp, a numel outside [1, 2^34]: BNN_ERR_SHAPE; eps_mode: BNN_ERR_ENUM; mean, m2, count, bank,
+ *   (low_rank) dev, (BNN_EPS_MEMORY) z1, (BNN_EPS_MEMORY and low_rank) z2 NULL: BNN_ERR_NULL; BNN_ERR_ALIGN (mean, m2, dev, bank
+ *   and z1 16 bytes, count and z2 4).
+ * ---------------------------------------------------------------------------------- */
+#define BNN_SWAG_MAX_RANK 32
+#define BNN_SWAG_MAX_MEMBERS 64           /* per launch */
+
+typedef struct bnn_swag_step_args {
+  uint32_t struct_bytes;
+  int32_t n_tensors;
+  float* param[BNN_SGMCMC_MAX_TENSORS];
+  const float* grad[BNN_SGMCMC_MAX_TENSORS];
+  float* momentum[BNN_SGMCMC_MAX_TENSORS];       /* all NULL: no momentum buffer */
+  int64_t numel[BNN_SGMCMC_MAX_TENSORS];
+  double lr, momentum_factor, weight_decay;
+  const float* lr_device;   /* optional device float: overrides lr */
+  uint32_t start, every;    /* collect when k >= start && (k - start + 1) % every == 0 */
+  int32_t rank;             /* K: rows of dev */
+  int32_t reserved;
+  float* mean;              /* [stride] */
+  float* m2;                /* [stride] */
+  float* dev;               /* [rank, stride]; unread when rank == 0 */
+  uint32_t* step;           /* device word k */
+  uint32_t* count;          /* device word n */
+  uint32_t* ticket;         /* 16 device words, zero between launches */
+} bnn_swag_step_args;
+
+typedef struct bnn_swag_sample_args {
+  uint32_t struct_bytes;
+  int32_t n_tensors;
+  int64_t numel[BNN_SGMCMC_MAX_TENSORS];
+  int32_t rank, members, first, capacity;
+  int32_t low_rank;         /* 1: full SWAG; 0: SWAG-Diagonal */
+  int32_t eps_mode;         /* bnn_eps_mode */
+  float c_d, var_clamp;
+  float c_lr[BNN_SWAG_MAX_RANK + 1];             /* indexed by Keff */
+  uint32_t sample_base;
+  uint64_t seed;
+  const float* mean;
+  const float* m2;
+  const float* dev;         /* low_rank */
+  const uint32_t* count;    /* device word n */
+  const float* z1;          /* BNN_EPS_MEMORY: [members, stride] */
+  const float* z2;          /* BNN_EPS_MEMORY and low_rank: [members, rank] */
+  float* bank;              /* [capacity, stride] */
+} bnn_swag_sample_args;
+
+int bnn_swag_step(const bnn_swag_step_args* args, void* stream);
+int bnn_swag_sample(const bnn_swag_sample_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
