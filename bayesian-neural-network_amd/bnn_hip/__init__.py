@@ -24,6 +24,8 @@
              captured training step whatever the number of members (F21)
 `swag`       FusedSWAG / SwagPosterior: SGD with momentum in the optimiser's place of K6's captured step that also collects SWAG's
              moments, the SWA point estimate, SWAG-Diagonal as a BayesianNetwork and low-rank draws into a WeightBank (F22)
+`svgd`       SteinTransform: SVGD / kde-WGD repulsive ensembles -- the members of a DeepEnsemble coupled through an RBF kernel, the
+             gradient bucket rewritten into the Stein direction by three launches inside EnsembleTrainStep (F23)
 """
 from .runtime import get_math, manual_seed, set_host_eps, set_math, shard_samples  # noqa: F401
 from ._lib import BnnHipError  # noqa: F401
@@ -33,7 +35,8 @@ from .sgmcmc import FusedSGMCMC, WeightBank  # noqa: F401
 from .swag import FusedSWAG, SwagPosterior  # noqa: F401
 from .kfac import KronLaplace  # noqa: F401
 from .ensemble import DeepEnsemble, EnsembleTrainStep  # noqa: F401
+from .svgd import SteinTransform  # noqa: F401
 
 __all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError", "ActiveLearner", "ActivePool", "DiagLaplace",
            "FusedSGMCMC", "WeightBank", "KronLaplace", "DeepEnsemble", "EnsembleTrainStep",
-           "FusedSWAG", "SwagPosterior"]
+           "FusedSWAG", "SwagPosterior", "SteinTransform"]

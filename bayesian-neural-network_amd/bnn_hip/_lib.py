@@ -52,6 +52,7 @@ EXPORTS = (
     "bnn_kfac_sample", "bnn_kfac_sample_workspace_bytes",
     "bnn_ens_fwd", "bnn_ens_loss", "bnn_ens_bwd",
     "bnn_swag_step", "bnn_swag_sample",
+    "bnn_svgd_chunks", "bnn_svgd_dist", "bnn_svgd_coef", "bnn_svgd_direction",
 )
 
 
@@ -706,6 +707,37 @@ class SwagSampleArgs(C.Structure):
                 ("z2", C.c_void_p), ("bank", C.c_void_p)]
 
 
+SVGD_MAX_MEMBERS = 64
+SVGD_CHUNK = 4096
+SVGD_CHAIN = 129
+SVGD_SVGD, SVGD_WGD = 0, 1
+
+
+def svgd_record_doubles(members: int) -> int:
+    """BNN_SVGD_RECORD_DOUBLES(members): D2 [M, M], med, h, r [M]"""
+    m = int(members)
+    return m * m + m + 2
+
+
+class SvgdDistArgs(C.Structure):
+    """bnn_svgd_dist_args (include/bnn_hip.h F23): per-chunk sums of squared differences of every pair of bank members"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("members", C.c_int32), ("stride", C.c_int64), ("bank", C.c_void_p),
+                ("partials", C.c_void_p)]
+
+
+class SvgdCoefArgs(C.Structure):
+    """bnn_svgd_coef_args (include/bnn_hip.h F23): D2, median, bandwidth, kernel matrix and [A | B] in one fp64 block"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("members", C.c_int32), ("chunks", C.c_int32), ("method", C.c_int32),
+                ("grad_scale", C.c_double), ("tau", C.c_double), ("bandwidth", C.c_double), ("partials", C.c_void_p),
+                ("coef", C.c_void_p), ("record", C.c_void_p)]
+
+
+class SvgdDirectionArgs(C.Structure):
+    """bnn_svgd_direction_args (include/bnn_hip.h F23): bucket <- [A | B] . [bucket ; bank] in place"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("members", C.c_int32), ("stride", C.c_int64), ("coef", C.c_void_p),
+                ("bank", C.c_void_p), ("bucket", C.c_void_p)]
+
+
 HIST_MAX_JOBS = 16
 HIST_MAX_EDGES = 2048
 HIST_CHUNK = 8192
@@ -1054,6 +1086,11 @@ def _load_real():
     for name, cls in (("bnn_swag_step", SwagStepArgs), ("bnn_swag_sample", SwagSampleArgs)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    for name, cls in (("bnn_svgd_dist", SvgdDistArgs), ("bnn_svgd_coef", SvgdCoefArgs), ("bnn_svgd_direction", SvgdDirectionArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    lib.bnn_svgd_chunks.restype = C.c_int32
+    lib.bnn_svgd_chunks.argtypes = [C.c_int64]
     lib.bnn_kfac_evidence_workspace_bytes.restype = C.c_size_t
     lib.bnn_kfac_evidence_workspace_bytes.argtypes = [C.POINTER(KfacEvidenceArgs)]
     lib.bnn_kfac_sample_workspace_bytes.restype = C.c_size_t

@@ -9,7 +9,8 @@ buffer, flat.  `EnsembleTrainStep` is dense_train.GraphedDenseTrainStep for all 
   layer, top down (gradients into a bucket [M, stride] in the bank's layout)  ->  bnn_sgd_step / bnn_adam_step over the two
   flat tensors.
 
-Three layers: 3 + 1 + 3 + 1 = 8 launches whatever M, captured once.  The step works in place on the bank's buffer: after any
+Three layers: 3 + 1 + 3 + 1 = 8 launches whatever M, captured once (11 with a svgd.SteinTransform, F23, which rewrites the bucket
+into the SVGD / kde-WGD direction ahead of the optimiser's launch).  The step works in place on the bank's buffer: after any
 number of steps bank.predictive(x) is the ensemble's predictive with nothing copied.  Per member every launch is bit-equal to
 the single-network launch of K6, so M = 1 is a plain GraphedDenseTrainStep and member j of an M-member step t equals an
 independent K6 step whose sample counter stands at base + M t + j."""
@@ -77,15 +78,27 @@ class DeepEnsemble:
         """In place: the buffer keeps its address (the parameter, a captured step and a captured predictive hold it)."""
         self.bank.load_state_dict(sd)
 
-    def graphed_train_step(self, optimizer, x, y, loss=None, capture: bool = True) -> "EnsembleTrainStep":
-        return EnsembleTrainStep(self, optimizer, x, y, loss=loss, capture=capture)
+    def graphed_train_step(self, optimizer, x, y, loss=None, capture: bool = True, transform=None) -> "EnsembleTrainStep":
+        return EnsembleTrainStep(self, optimizer, x, y, loss=loss, capture=capture, transform=transform)
+
+    def svgd(self, *, dataset_size, batch_size, prior_precision: float = 1.0, temperature: float = 1.0, method: str = "svgd",
+             bandwidth=None):
+        """A svgd.SteinTransform over this ensemble's members (F23): pass it as `transform=` to graphed_train_step and the
+        members are trained as SVGD particles (method="svgd") or as a kde-WGD repulsive ensemble ("wgd") instead of
+        independently.  The prior enters through `prior_precision`: build the optimiser with weight_decay = 0."""
+        from .svgd import SteinTransform
+        return SteinTransform(self, dataset_size=dataset_size, batch_size=batch_size, prior_precision=prior_precision,
+                              temperature=temperature, method=method, bandwidth=bandwidth)
 
 
 class EnsembleTrainStep:
-    def __init__(self, ens: DeepEnsemble, optimizer, x: torch.Tensor, y: torch.Tensor, loss=None, capture: bool = True):
+    def __init__(self, ens: DeepEnsemble, optimizer, x: torch.Tensor, y: torch.Tensor, loss=None, capture: bool = True,
+                 transform=None):
         """`x`, `y`: an example minibatch -- the single network's shapes ([B, ...]: one minibatch shared by all members) or
         with a leading member dimension ([M, B, ...]: a minibatch per member); y follows x.  `optimizer`: FusedSGD or
         FusedAdam with capturable=True built on ens.parameters().  `loss`, `capture`: as GraphedDenseTrainStep.
+        `transform`: a svgd.SteinTransform of this ensemble (ens.svgd(...)): its three launches rewrite the gradient bucket
+        between the last bnn_ens_bwd and the optimiser's launch (11 launches instead of 8); None: independent members.
 
         Building the step runs one real warm-up step and then restores the bank, the optimiser state and the sample
         counter."""
@@ -119,7 +132,9 @@ class EnsembleTrainStep:
         if ens.bank.count() != M:
             raise BnnHipError(f"EnsembleTrainStep: the bank holds {ens.bank.count()} of {M} members; push the rest first "
                               "(ens.bank.push(net)) or give seeds")
-        self.ens, self.bank, self.opt, self.members = ens, ens.bank, optimizer, M
+        if transform is not None and (getattr(transform, "ens", None) is not ens or not callable(getattr(transform, "enqueue", None))):
+            raise BnnHipError("EnsembleTrainStep: the transform must be built on this ensemble (ens.svgd(...))")
+        self.ens, self.bank, self.opt, self.members, self.transform = ens, ens.bank, optimizer, M, transform
         self.loss_mode = "classification" if loss == "cross_entropy" else "regression"
         self.per_member = x.dim() == (5 if mlp.mode == "classification" else 3)
         if self.per_member:
@@ -149,7 +164,7 @@ class EnsembleTrainStep:
         self.g_hidden = [torch.empty((M, B, d.linear.out_features), dtype=torch.float32, device=dev) for d in self.layers[:-1]]
         self.loss = torch.zeros((M,), dtype=torch.float32, device=dev)
         self.scales = [ops.dropout_params(d.p)[1] for d in self.layers]
-        self.launches = 2 * len(self.layers) + 2
+        self.launches = 2 * len(self.layers) + 2 + (transform.launches if transform is not None else 0)
 
         sh = self._shared = SampleCounter.of(optimizer, dev)
         self.counter, self.base = sh["counter"], sh["base"]
@@ -185,6 +200,8 @@ class EnsembleTrainStep:
                             bank.buffer, bank._w_off[i], self.bucket, bank._b_off[i],
                             g_x=self.g_hidden[i - 1] if i > 0 else None, gx_mask=below is not None and below.relu,
                             gx_scale=self.scales[i - 1] if i > 0 else 1.0, math_mode=self.math)
+            if self.transform is not None:
+                self.transform.enqueue(self.bank, self.bucket)
         self.ens._param.grad = self._grad
         if isinstance(self.opt, FusedAdam):
             self.opt._bump = None                # the sample counter advances in the forward, not in Adam's launch

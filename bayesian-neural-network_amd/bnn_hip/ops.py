@@ -3219,6 +3219,87 @@ def swag_sample(numels: Sequence[int], mean: torch.Tensor, m2: torch.Tensor, dev
     return bank
 
 
+# ------------------------------------------------------------------------------------- F23: SVGD / repulsive ensembles
+def svgd_chunks(stride: int) -> int:
+    """bnn_svgd_chunks: rows of bnn_svgd_dist's partials for a bank of this stride (whole 64-column tiles per chunk, at most
+    SVGD_CHUNK columns, about 512 chunks of a smaller bank)."""
+    n = int(L.load().bnn_svgd_chunks(int(stride)))
+    if n < 1:
+        raise BnnHipError(f"svgd_chunks: the stride must be a multiple of 64 in [64, 2^34], got {stride}")
+    return n
+
+
+def _svgd_rows(t: torch.Tensor, members: int, what: str, name: str) -> int:
+    """`t` as the first `members` rows of a contiguous float32 [rows, stride] tensor; returns the stride."""
+    if not 1 <= members <= L.SVGD_MAX_MEMBERS:
+        raise BnnHipError(f"{what}: between 1 and {L.SVGD_MAX_MEMBERS} members, got {members}")
+    require_device(t)
+    if t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.shape[0] < members or t.shape[1] < 64 or t.shape[1] % 64:
+        raise BnnHipError(f"{what}: {name} must be a contiguous float32 [>= {members}, stride] tensor, stride a multiple of 64, "
+                          f"got {tuple(t.shape)} {t.dtype}")
+    return int(t.shape[1])
+
+
+def _svgd_flat(t: torch.Tensor, dtype, numel: int, what: str, name: str) -> torch.Tensor:
+    require_device(t)
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < numel:
+        raise BnnHipError(f"{what}: {name} must be a contiguous {dtype} tensor of at least {numel} elements")
+    return t
+
+
+def svgd_dist(bank: torch.Tensor, partials: torch.Tensor, *, members: int):
+    """F23 bnn_svgd_dist: partials[chunk, pair] = the fp32 sum over the chunk's columns of (bank[i] - bank[j])^2, pair (i, j),
+    i < j, at i (2 M - i - 1) / 2 + (j - i - 1); `partials` float32 with svgd_chunks(stride) * M (M - 1) / 2 elements."""
+    lib = L.load()
+    M = int(members)
+    stride = _svgd_rows(bank, M, "svgd_dist", "bank")
+    _svgd_flat(partials, torch.float32, max(1, svgd_chunks(stride) * (M * (M - 1) // 2)), "svgd_dist", "partials")
+    a = L.SvgdDistArgs()
+    a.struct_bytes = C.sizeof(L.SvgdDistArgs)
+    a.members, a.stride, a.bank, a.partials = M, stride, bank.data_ptr(), partials.data_ptr()
+    a._keep = (bank, partials)
+    L.check(lib.bnn_svgd_dist(C.byref(a), _stream()), "bnn_svgd_dist")
+    return partials
+
+
+def svgd_coef(partials: torch.Tensor, coef: torch.Tensor, record: torch.Tensor, *, members: int, chunks: int, grad_scale: float,
+              tau: float, method: int = L.SVGD_SVGD, bandwidth: float = 0.0):
+    """F23 bnn_svgd_coef: the chunk partials -> D2, its median, h (bandwidth 0: median / log(M + 1)), K, r and coef = [A | B]
+    (float32 [M, 2 M]); `record` float64 [svgd_record_doubles(M)]: D2, med, h, r."""
+    lib = L.load()
+    M, chunks = int(members), int(chunks)
+    if not 1 <= M <= L.SVGD_MAX_MEMBERS or chunks < 1:
+        raise BnnHipError(f"svgd_coef: between 1 and {L.SVGD_MAX_MEMBERS} members and chunks >= 1 are required")
+    _svgd_flat(partials, torch.float32, max(1, chunks * (M * (M - 1) // 2)), "svgd_coef", "partials")
+    _svgd_flat(coef, torch.float32, 2 * M * M, "svgd_coef", "coef")
+    _svgd_flat(record, torch.float64, L.svgd_record_doubles(M), "svgd_coef", "record")
+    a = L.SvgdCoefArgs()
+    a.struct_bytes = C.sizeof(L.SvgdCoefArgs)
+    a.members, a.chunks, a.method = M, chunks, int(method)
+    a.grad_scale, a.tau, a.bandwidth = float(grad_scale), float(tau), float(bandwidth)
+    a.partials, a.coef, a.record = partials.data_ptr(), coef.data_ptr(), record.data_ptr()
+    a._keep = (partials, coef, record)
+    L.check(lib.bnn_svgd_coef(C.byref(a), _stream()), "bnn_svgd_coef")
+    return coef, record
+
+
+def svgd_direction(coef: torch.Tensor, bank: torch.Tensor, bucket: torch.Tensor, *, members: int):
+    """F23 bnn_svgd_direction: bucket[:M] <- coef . [bucket[:M] ; bank[:M]] per column, in place (coef float32 [M, 2 M])."""
+    lib = L.load()
+    M = int(members)
+    stride = _svgd_rows(bank, M, "svgd_direction", "bank")
+    if _svgd_rows(bucket, M, "svgd_direction", "bucket") != stride:
+        raise BnnHipError("svgd_direction: the bucket must have the bank's stride")
+    _svgd_flat(coef, torch.float32, 2 * M * M, "svgd_direction", "coef")
+    a = L.SvgdDirectionArgs()
+    a.struct_bytes = C.sizeof(L.SvgdDirectionArgs)
+    a.members, a.stride = M, stride
+    a.coef, a.bank, a.bucket = coef.data_ptr(), bank.data_ptr(), bucket.data_ptr()
+    a._keep = (coef, bank, bucket)
+    L.check(lib.bnn_svgd_direction(C.byref(a), _stream()), "bnn_svgd_direction")
+    return bucket
+
+
 def bank_fwd(x: torch.Tensor, bank: torch.Tensor, w_off: int, b_off: Optional[int], *, out_features: int, members: int,
              first: int = 0, relu: bool = False, math_mode: int = L.MATH_F32, y_dtype=torch.float32, out=None) -> torch.Tensor:
     """F19 bnn_bank_fwd: y[j] = act(x[j or shared] . W[first + j]^T + b[first + j]) for `members` members of `bank` (float32

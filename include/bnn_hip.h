@@ -2863,6 +2863,95 @@ int bnn_swag_step(const bnn_swag_step_args* args, void* stream);
 int bnn_swag_sample(const bnn_swag_sample_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F23  SVGD (Liu & Wang 2016, "Stein Variational Gradient Descent") and the weight-space repulsive ensemble kde-WGD (D'Angelo &
+ * Fortuin 2021, "Repulsive Deep Ensembles are Bayesian"; neither is in the reference): the gradient bucket of F21's step is
+ * rewritten in place into a direction in which every member's gradient is mixed with the others' through an RBF kernel matrix
+ * and a repulsion term keeps the members apart.  Three launches between the last bnn_ens_bwd and the optimiser's launch; no
+ * float atomics, no arrival ticket.
+ *
+ * Definition.  theta_i = row i of the bank buffer [members, stride] (padding included), g_i = row i of the bucket (the gradient
+ * of K6's sum loss), M = members.  With FusedSGMCMC's energy conventions s = dataset_size / (batch_size T) (grad_scale) and
+ * tau' = prior_precision / T (tau), grad U_j = s g_j + tau' theta_j:
+ *     D2_ij = sum_p (theta_i[p] - theta_j[p])^2                  symmetric, the diagonal exactly 0
+ *     med   = the median of all M^2 entries of D2, diagonal included (an even count: the mean of the two middle values)
+ *     h     = bandwidth > 0 ? bandwidth : med / log(M + 1);      h == 0 -> h = 1
+ *     k_ij  = exp(-D2_ij / h),   r_i = sum_j k_ij  (j ascending)
+ *     d     = A g + B theta  per parameter column, the direction the optimiser SUBTRACTS:
+ *       BNN_SVGD_SVGD:  A_ij = s k_ij / M                        B_ij = (tau' k_ij + (2 / h)(k_ij - delta_ij r_i)) / M
+ *       BNN_SVGD_WGD:   A_ij = s delta_ij                        B_ij = tau' delta_ij - (2 / h)(delta_ij - k_ij / r_i)
+ *   so that -d_i = (1 / M) sum_j k_ij [-grad U_j + (2 / h)(theta_i - theta_j)] (SVGD): member i is pushed away from member j.
+ *   M = 1 gives A = [s], B = [tau'] exactly in both methods.
+ *
+ * bnn_svgd_dist — one block per chunk of C = 64 min(BNN_SVGD_CHUNK / 64, ceil(stride / 32768)) columns (whole 64-column tiles,
+ *   at most BNN_SVGD_CHUNK; a smaller bank is cut into about 512 chunks so that the chip is filled) writes partials[chunk][pair], pair (i, j), i < j, at index
+ *   i (2 M - i - 1) / 2 + (j - i - 1): the fp32 sum over the chunk's columns of fma(d, d, .) with d = theta_i[p] - theta_j[p]
+ *   rounded once -- sums of squared differences, never |a|^2 + |b|^2 - 2 a.b.  The longest fp32 addition chain behind a partial
+ *   is L = BNN_SVGD_CHAIN = 129: at most 64 columns of a 64-column tile per thread, the tile sums of the chunk's 64 tiles, and
+ *   the per-thread sums of up to 64 column lanes in lane order (the three never exceed 129 together).  Every term is
+ *   non-negative: a partial is within (L + 2) 2^-24 relative of the exact sum (2 for the rounded difference, squared).
+ *   chunks = ceil(stride / C) = bnn_svgd_chunks(stride) (0 for a stride bnn_svgd_dist refuses); members == 1 writes nothing.
+ *   Errors, in this order: NULL args; ABI; members outside [1, BNN_SVGD_MAX_MEMBERS], stride < 64, not a multiple of 64 or above
+ *   2^34: BNN_ERR_SHAPE; bank, partials NULL: BNN_ERR_NULL; BNN_ERR_ALIGN (bank 16 bytes, partials 4).
+ *
+ * bnn_svgd_coef — ONE block, fp64 throughout: D2_ij = the chunk partials added in chunk order (with at most 512 pairs the
+ *   chunks are split into contiguous ranges whose sums are then added in order); the M^2 entries sorted in LDS, med, h, k, r as above
+ *   (log(M + 1) formed on the host in fp64, exp the device's fp64 exp); A and B formed in fp64 by the expressions above as
+ *   written and rounded to fp32 ONCE; coef = [A | B], fp32 [M, 2 M] row-major.  record (fp64, BNN_SVGD_RECORD_DOUBLES(M)):
+ *   D2 [M, M], med, h, r [M].
+ *   Errors, in this order: NULL args; ABI; members outside [1, BNN_SVGD_MAX_MEMBERS], chunks outside [1, 2^22], grad_scale not
+ *   in (0, inf), tau or bandwidth (0: the median heuristic) not in [0, inf): BNN_ERR_SHAPE; method: BNN_ERR_ENUM; partials, coef,
+ *   record NULL: BNN_ERR_NULL; BNN_ERR_ALIGN (partials, coef 4 bytes, record 8).
+ *
+ * bnn_svgd_direction — bucket[i][p] <- sum_k coef[i][k] v[k][p], v = [bucket ; bank] ([2 M, stride]), for every column p, in
+ *   place, on the exact-fp32 matrix core (v_mfma_f32_16x16x4_f32): per output ONE accumulator that starts at +0 and takes the
+ *   2 M products, padded with zeros to a multiple of 16, in ascending k, four per instruction -- |err| <= (2 M + 2) 2^-24
+ *   sum_k |coef_ik| |v_kp|.  A wave owns 64 columns and reads all 2 M rows of them before it stores any; the bank is not
+ *   written.  Where both operands are zero (the padding columns) the output is exactly zero.
+ *   Errors, in this order: NULL args; ABI; members, stride as bnn_svgd_dist: BNN_ERR_SHAPE; coef, bank, bucket NULL:
+ *   BNN_ERR_NULL; BNN_ERR_ALIGN (coef 4 bytes, bank and bucket 16).
+ * ---------------------------------------------------------------------------------- */
+#define BNN_SVGD_MAX_MEMBERS 64
+#define BNN_SVGD_CHUNK 4096               /* the most columns per block (and per partial) of bnn_svgd_dist */
+#define BNN_SVGD_CHAIN 129                /* L: the longest fp32 addition chain behind a partial */
+#define BNN_SVGD_RECORD_DOUBLES(M) ((M) * (M) + (M) + 2)
+typedef enum { BNN_SVGD_SVGD = 0, BNN_SVGD_WGD = 1 } bnn_svgd_method;
+
+typedef struct bnn_svgd_dist_args {
+  uint32_t struct_bytes;
+  int32_t members;
+  int64_t stride;           /* of the bank: a multiple of 64 */
+  const float* bank;        /* [members, stride] */
+  float* partials;          /* [bnn_svgd_chunks(stride), members (members - 1) / 2] */
+} bnn_svgd_dist_args;
+
+typedef struct bnn_svgd_coef_args {
+  uint32_t struct_bytes;
+  int32_t members;
+  int32_t chunks;           /* rows of partials */
+  int32_t method;           /* bnn_svgd_method */
+  double grad_scale;        /* s */
+  double tau;               /* tau' */
+  double bandwidth;         /* h; 0: the median heuristic */
+  const float* partials;
+  float* coef;              /* [members, 2 members] */
+  double* record;           /* BNN_SVGD_RECORD_DOUBLES(members) */
+} bnn_svgd_coef_args;
+
+typedef struct bnn_svgd_direction_args {
+  uint32_t struct_bytes;
+  int32_t members;
+  int64_t stride;
+  const float* coef;        /* [members, 2 members] */
+  const float* bank;        /* [members, stride] */
+  float* bucket;            /* [members, stride], rewritten in place */
+} bnn_svgd_direction_args;
+
+int32_t bnn_svgd_chunks(int64_t stride);
+int bnn_svgd_dist(const bnn_svgd_dist_args* args, void* stream);
+int bnn_svgd_coef(const bnn_svgd_coef_args* args, void* stream);
+int bnn_svgd_direction(const bnn_svgd_direction_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
