@@ -26,6 +26,9 @@
              moments, the SWA point estimate, SWAG-Diagonal as a BayesianNetwork and low-rank draws into a WeightBank (F22)
 `svgd`       SteinTransform: SVGD / kde-WGD repulsive ensembles -- the members of a DeepEnsemble coupled through an RBF kernel, the
              gradient bucket rewritten into the Stein direction by three launches inside EnsembleTrainStep (F23)
+`ivon`       FusedIVON: the variational online Newton optimiser in K6's captured step -- a weight draw in front of each forward
+             pass, one natural-gradient launch behind the backward pass; the posterior as a BayesianNetwork and as draws into a
+             WeightBank (F24)
 """
 from .runtime import get_math, manual_seed, set_host_eps, set_math, shard_samples  # noqa: F401
 from ._lib import BnnHipError  # noqa: F401
@@ -36,7 +39,8 @@ from .swag import FusedSWAG, SwagPosterior  # noqa: F401
 from .kfac import KronLaplace  # noqa: F401
 from .ensemble import DeepEnsemble, EnsembleTrainStep  # noqa: F401
 from .svgd import SteinTransform  # noqa: F401
+from .ivon import FusedIVON  # noqa: F401
 
 __all__ = ["get_math", "set_math", "manual_seed", "set_host_eps", "shard_samples", "BnnHipError", "ActiveLearner", "ActivePool", "DiagLaplace",
            "FusedSGMCMC", "WeightBank", "KronLaplace", "DeepEnsemble", "EnsembleTrainStep",
-           "FusedSWAG", "SwagPosterior", "SteinTransform"]
+           "FusedSWAG", "SwagPosterior", "SteinTransform", "FusedIVON"]

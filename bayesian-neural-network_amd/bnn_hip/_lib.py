@@ -53,6 +53,7 @@ EXPORTS = (
     "bnn_ens_fwd", "bnn_ens_loss", "bnn_ens_bwd",
     "bnn_swag_step", "bnn_swag_sample",
     "bnn_svgd_chunks", "bnn_svgd_dist", "bnn_svgd_coef", "bnn_svgd_direction",
+    "bnn_ivon_draw", "bnn_ivon_step",
 )
 
 
@@ -707,6 +708,33 @@ class SwagSampleArgs(C.Structure):
                 ("z2", C.c_void_p), ("bank", C.c_void_p)]
 
 
+IVON_MAX_SAMPLES = 8
+IVON_MAX_MEMBERS = 64
+IVON_NOISE_WORD3 = 6
+
+
+class IvonDrawArgs(C.Structure):
+    """bnn_ivon_draw_args (include/bnn_hip.h F24): theta = m + sigma eps into the parameter tensors or members of a weight bank"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_tensors", C.c_int32), ("param", C.c_void_p * SGMCMC_MAX_TENSORS),
+                ("grad", C.c_void_p * SGMCMC_MAX_TENSORS), ("numel", C.c_int64 * SGMCMC_MAX_TENSORS),
+                ("samples", C.c_int32), ("sample", C.c_int32), ("members", C.c_int32), ("first", C.c_int32),
+                ("capacity", C.c_int32), ("eps_mode", C.c_int32), ("sample_base", C.c_uint32), ("reserved", C.c_int32),
+                ("ess", C.c_double), ("weight_decay", C.c_double), ("seed", C.c_uint64), ("mean", C.c_void_p),
+                ("hess", C.c_void_p), ("acc_g", C.c_void_p), ("acc_h", C.c_void_p), ("step", C.c_void_p), ("noise", C.c_void_p),
+                ("bank", C.c_void_p)]
+
+
+class IvonStepArgs(C.Structure):
+    """bnn_ivon_step_args (include/bnn_hip.h F24): the variational online Newton step over every parameter tensor"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("n_tensors", C.c_int32), ("param", C.c_void_p * SGMCMC_MAX_TENSORS),
+                ("grad", C.c_void_p * SGMCMC_MAX_TENSORS), ("numel", C.c_int64 * SGMCMC_MAX_TENSORS),
+                ("samples", C.c_int32), ("eps_mode", C.c_int32), ("lr", C.c_double), ("ess", C.c_double),
+                ("weight_decay", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("loss_scale", C.c_double),
+                ("clip_radius", C.c_double), ("lr_device", C.c_void_p), ("seed", C.c_uint64), ("mean", C.c_void_p),
+                ("hess", C.c_void_p), ("avg_grad", C.c_void_p), ("acc_g", C.c_void_p), ("acc_h", C.c_void_p),
+                ("noise", C.c_void_p), ("step", C.c_void_p), ("beta1_prod", C.c_void_p), ("ticket", C.c_void_p)]
+
+
 SVGD_MAX_MEMBERS = 64
 SVGD_CHUNK = 4096
 SVGD_CHAIN = 129
@@ -1087,6 +1115,9 @@ def _load_real():
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     for name, cls in (("bnn_svgd_dist", SvgdDistArgs), ("bnn_svgd_coef", SvgdCoefArgs), ("bnn_svgd_direction", SvgdDirectionArgs)):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
+    for name, cls in (("bnn_ivon_draw", IvonDrawArgs), ("bnn_ivon_step", IvonStepArgs)):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.POINTER(cls), C.c_void_p]
     lib.bnn_svgd_chunks.restype = C.c_int32

@@ -8,7 +8,11 @@ as a fixed chain of HIP launches, captured once as a hipGraph:
   below's mask read off its saved output, except at layer 0)  ->  bnn_sgd_step / bnn_adam_step.
 
 Three layers: 3 + 1 + 3 + 1 = 8 launches.  The step always trains in train-mode semantics (dropout on), as the
-reference's train_step does after net.train()."""
+reference's train_step does after net.train().
+
+With ivon.FusedIVON the chain runs once per MC sample s = 0 .. S - 1 behind the optimiser's draw launch (opt.perturb(s):
+theta = m + sigma eps into the parameters) and ends in its step launch: 8 S + 1 launches, the sample counter advancing by S.
+The loss returned is then the LAST sample's sum loss at the drawn weights, not the loss at the mean."""
 from __future__ import annotations
 
 import torch
@@ -20,6 +24,7 @@ from .mcdropout import _math, flat_input, layers_of
 from .ops import BnnHipError
 from .optim import FusedAdam, FusedSGD, _sgd_supported
 from .runtime import state
+from .ivon import FusedIVON, default_loss_scale, require_plain_mlp
 from .sgmcmc import FusedSGMCMC
 from .swag import FusedSWAG
 
@@ -30,19 +35,24 @@ class GraphedDenseTrainStep:
     def __init__(self, mlp, optimizer, x: torch.Tensor, y: torch.Tensor, loss=None, capture: bool = True):
         """`x`, `y`: an example minibatch (the shape and dtype of every later one): classification x [B, 1, h, w] with
         int64 labels [B], regression x [B, in] with float32 targets of B * out elements.  `optimizer`: FusedSGD,
-        FusedAdam, sgmcmc.FusedSGMCMC (the sampler in the optimiser's place) or swag.FusedSWAG (SGD that also collects SWAG's
-        moments) with capturable=True over the network's parameters.  `loss`: 'cross_entropy' or 'mse' (sum reduction),
+        FusedAdam, sgmcmc.FusedSGMCMC (the sampler in the optimiser's place), swag.FusedSWAG (SGD that also collects SWAG's
+        moments) or ivon.FusedIVON (variational online Newton: its loss_scale, when None, becomes
+        ivon.default_loss_scale(loss, B, optimizer.sigma)) with capturable=True over the network's parameters.
+        `loss`: 'cross_entropy' or 'mse' (sum reduction),
         by default the reference's for mlp.mode.  `capture=False`: the same launches, run eagerly on every step.
 
         Building the step runs one real warm-up step and then restores the parameters, the optimiser state and the
         sample counter, so the model and the optimiser are left as they were."""
-        if not isinstance(optimizer, (FusedSGD, FusedAdam, FusedSGMCMC, FusedSWAG)):
-            raise BnnHipError("GraphedDenseTrainStep needs FusedSGD, FusedAdam, FusedSGMCMC or FusedSWAG (capturable=True)")
+        if not isinstance(optimizer, (FusedSGD, FusedAdam, FusedSGMCMC, FusedSWAG, FusedIVON)):
+            raise BnnHipError("GraphedDenseTrainStep needs FusedSGD, FusedAdam, FusedSGMCMC, FusedSWAG or FusedIVON "
+                              "(capturable=True)")
         if not all(g.get("capturable") for g in optimizer.param_groups):
             raise BnnHipError("GraphedDenseTrainStep needs a capturable optimiser (capturable=True)")
         if isinstance(optimizer, FusedSGD):
             for g in optimizer.param_groups:
                 _sgd_supported(g)
+        if isinstance(optimizer, FusedIVON):
+            require_plain_mlp(mlp, "GraphedDenseTrainStep")
         if state.shard_samples:
             raise BnnHipError("GraphedDenseTrainStep: MC-sample sharding is not supported; switch it off")
         if loss is None:
@@ -67,6 +77,14 @@ class GraphedDenseTrainStep:
             raise BnnHipError(f"GraphedDenseTrainStep: mse targets must be float32 with {B * C_out} elements")
         self.y = y.clone().contiguous()
         self.math = _math()[0]
+        # MC samples per step: the draws of a FusedIVON; every other optimiser steps on one forward / backward pass
+        self.ivon = isinstance(optimizer, FusedIVON)
+        self.samples = optimizer.param_groups[0]["samples"] if self.ivon else 1
+        if self.ivon:
+            if optimizer._drawn:
+                raise BnnHipError("GraphedDenseTrainStep: the FusedIVON has a step under way; call its step() first")
+            self.loss_scale = optimizer.loss_scale if optimizer.loss_scale is not None else \
+                default_loss_scale(loss, B, optimizer.sigma)
 
         # the parameters, in layer order, and one flat gradient bucket (each slice 256-byte aligned); p.grad are views
         self.params = [t for d in self.layers for t in (d.linear.weight, d.linear.bias) if t is not None]
@@ -106,6 +124,22 @@ class GraphedDenseTrainStep:
 
     # ---- the chain
     def _enqueue(self):
+        if self.ivon:
+            self._attach_grads()                 # perturb(s >= 1) folds the previous sample's gradients
+            for s in range(self.samples):
+                self.opt.perturb(s)
+                self._enqueue_pass()
+            self.opt.step(loss_scale=self.loss_scale)
+            return
+        self._enqueue_pass()
+        self._attach_grads()
+        if isinstance(self.opt, FusedAdam):
+            self.opt._bump = None                # the sample counter advances in the forward, not in Adam's launch
+        self.opt.step()
+
+    def _enqueue_pass(self):
+        """One forward / loss / backward pass at the parameters' current values (a launch per layer each way and the loss
+        launch); the gradients are left in the bucket."""
         with torch.no_grad():
             last = len(self.layers) - 1
             h = self.x
@@ -126,10 +160,6 @@ class GraphedDenseTrainStep:
                               g_b=None if lin.bias is None else self._grad_of[id(lin.bias)],
                               g_x=self.g_hidden[i - 1] if i > 0 else None, gx_mask=below is not None and below.relu,
                               gx_scale=self.scales[i - 1] if i > 0 else 1.0, math_mode=self.math)
-        self._attach_grads()
-        if isinstance(self.opt, FusedAdam):
-            self.opt._bump = None                # the sample counter advances in the forward, not in Adam's launch
-        self.opt.step()
 
     def _attach_grads(self):
         for p, g in zip(self.params, self.grad_views):
@@ -138,7 +168,7 @@ class GraphedDenseTrainStep:
     # ---- the public step
     def step(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """One optimiser step on minibatch (x, y); returns the static 0-dim loss tensor (the reference's loss_info: read
-        it before the next call)."""
+        it before the next call; with a FusedIVON the last sample's sum loss at the drawn weights)."""
         xf = flat_input(self.mlp, x)
         ops.require_device(y)
         if xf.numel() != self.x.numel() or y.numel() != self.y.numel() or y.dtype != self.y.dtype:
@@ -160,5 +190,5 @@ class GraphedDenseTrainStep:
             self.graph.replay()
         else:
             self._enqueue()
-        self._shared.advance(1)
+        self._shared.advance(self.samples)
         return self.loss

@@ -26,6 +26,7 @@ from . import ops
 from .capture import SampleCounter, snapshot, warm_up
 from .mcdropout import _math, flat_input
 from .ops import BnnHipError
+from .ivon import FusedIVON
 from .optim import FusedAdam, FusedSGD, _sgd_supported
 from .runtime import state
 from .sgmcmc import FusedSGMCMC, WeightBank
@@ -106,6 +107,9 @@ class EnsembleTrainStep:
         if isinstance(optimizer, FusedSGMCMC):
             raise BnnHipError("EnsembleTrainStep: FusedSGMCMC is not supported (SG-MCMC chains per member are out of scope); "
                               "use FusedSGD or FusedAdam")
+        if isinstance(optimizer, FusedIVON):
+            raise BnnHipError("EnsembleTrainStep: FusedIVON is not supported (a posterior per member is out of scope); train "
+                              "one network with mlp.graphed_train_step(mlp.ivon(...), x, y), or use FusedSGD or FusedAdam")
         if not isinstance(optimizer, (FusedSGD, FusedAdam)):
             raise BnnHipError("EnsembleTrainStep needs FusedSGD or FusedAdam (capturable=True)")
         if not all(g.get("capturable") for g in optimizer.param_groups):

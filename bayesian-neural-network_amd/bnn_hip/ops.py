@@ -3219,6 +3219,117 @@ def swag_sample(numels: Sequence[int], mean: torch.Tensor, m2: torch.Tensor, dev
     return bank
 
 
+# ---------------------------------------------------------------------------------------------------------------- F24 IVON
+def _ivon_flat(name, what, t, stride, rows=None):
+    shape = (stride,) if rows is None else (rows, stride)
+    if t is None or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+        raise BnnHipError(f"{name}: {what} must be a contiguous float32 {list(shape)} tensor (the bank's layout)")
+    return t.data_ptr()
+
+
+def _ivon_tensors(name, a, params, grads):
+    n = len(params)
+    if not 1 <= n <= L.SGMCMC_MAX_TENSORS:
+        raise BnnHipError(f"{name}: between 1 and {L.SGMCMC_MAX_TENSORS} parameter tensors, got {n}")
+    if grads is not None and len(grads) != n:
+        raise BnnHipError(f"{name}: one gradient tensor per parameter")
+    a.n_tensors = n
+    keep = []
+    for j in range(n):
+        ts = [params[j]] + ([grads[j]] if grads is not None else [])
+        for t in ts:
+            require_device(t)
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != params[j].numel():
+                raise BnnHipError(f"{name}: parameters and gradients must be contiguous float32 of one size")
+        keep += ts
+        a.param[j], a.numel[j] = params[j].data_ptr(), params[j].numel()
+        if grads is not None:
+            a.grad[j] = grads[j].data_ptr()
+    return keep, bank_layout([p.numel() for p in params])[1]
+
+
+def ivon_draw(params, *, hess: torch.Tensor, ess: float, weight_decay: float, samples: int = 1, sample: int = 0, mean=None,
+              step=None, grads=None, acc_g=None, acc_h=None, bank: Optional[torch.Tensor] = None, members: int = 0, first: int = 0,
+              sample_base: int = 0, eps_mode: int = L.EPS_PHILOX, seed: int = 0, noise=None):
+    """F24 bnn_ivon_draw: theta = m + eps / sqrt(ess (hess + weight_decay)) over lists of fp32 tensors in one launch.
+    Training form (`bank` None): draw t * samples + sample (t the device word `step`) into `params`; sample 0 first files the
+    parameters (the mean) into `mean`, sample >= 1 reads the mean there and folds `grads` (the previous sample's) into `acc_g`
+    / `acc_h`.  Bank form: members first .. first + members - 1 of `bank` ([capacity, stride]) around the mean in `params`,
+    member j being draw sample_base + j.  EPS_MEMORY: `noise` [samples, stride] (row `sample`; the fold reads row sample - 1),
+    or [members, stride]."""
+    lib = L.load()
+    S, s, m, first = int(samples), int(sample), int(members), int(first)
+    if not 1 <= S <= L.IVON_MAX_SAMPLES or not 0 <= s < S:
+        raise BnnHipError(f"ivon_draw: samples must lie in [1, {L.IVON_MAX_SAMPLES}] and sample in [0, samples)")
+    if not float(ess) > 0.0 or not float(weight_decay) > 0.0:
+        raise BnnHipError("ivon_draw: ess and weight_decay must be > 0")
+    a = L.IvonDrawArgs()
+    a.struct_bytes = C.sizeof(L.IvonDrawArgs)
+    fold = bank is None and s >= 1
+    keep, stride = _ivon_tensors("ivon_draw", a, params, grads if fold else None)
+    if fold and grads is None:
+        raise BnnHipError("ivon_draw: sample >= 1 folds the previous sample's gradients; pass grads, acc_g and acc_h")
+    require_device(hess, mean, step, acc_g, acc_h, bank, noise)
+    a.samples, a.sample, a.eps_mode = S, s, int(eps_mode)
+    a.ess, a.weight_decay, a.seed = float(ess), float(weight_decay), int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.hess = _ivon_flat("ivon_draw", "hess", hess, stride)
+    if bank is None:
+        a.mean = _ivon_flat("ivon_draw", "mean", mean, stride)
+        if step is None:
+            raise BnnHipError("ivon_draw: the training form needs the step word")
+        a.step = _typed(step, torch.int32, "step", 1).data_ptr()
+        if fold:
+            a.acc_g, a.acc_h = _ivon_flat("ivon_draw", "acc_g", acc_g, stride), _ivon_flat("ivon_draw", "acc_h", acc_h, stride)
+        rows = S
+    else:
+        if not 1 <= m <= L.IVON_MAX_MEMBERS:
+            raise BnnHipError(f"ivon_draw: members must lie in [1, {L.IVON_MAX_MEMBERS}], got {m}")
+        if bank.dtype != torch.float32 or bank.dim() != 2 or bank.shape[1] != stride or not bank.is_contiguous():
+            raise BnnHipError(f"ivon_draw: the bank must be a contiguous float32 [capacity, {stride}] tensor")
+        if first < 0 or first + m > bank.shape[0]:
+            raise BnnHipError(f"ivon_draw: members [{first}, {first + m}) outside the bank's {bank.shape[0]}")
+        a.bank, a.members, a.first, a.capacity = bank.data_ptr(), m, first, bank.shape[0]
+        a.sample_base = int(sample_base) & 0xFFFFFFFF
+        rows = m
+    if eps_mode == L.EPS_MEMORY:
+        a.noise = _ivon_flat("ivon_draw", "noise", noise, stride, rows)
+    a._keep = keep + [hess, mean, step, acc_g, acc_h, bank, noise]
+    L.check(lib.bnn_ivon_draw(C.byref(a), _stream()), "bnn_ivon_draw")
+
+
+def ivon_step(params, grads, *, lr: float, ess: float, weight_decay: float, beta1: float, beta2: float, loss_scale: float,
+              clip_radius: float = float("inf"), samples: int = 1, lr_device=None, mean: torch.Tensor, hess: torch.Tensor,
+              avg_grad: torch.Tensor, acc_g=None, acc_h=None, step: torch.Tensor, beta1_prod: torch.Tensor, ticket: torch.Tensor,
+              eps_mode: int = L.EPS_PHILOX, seed: int = 0, noise=None):
+    """F24 bnn_ivon_step: the variational online Newton step over lists of fp32 tensors in one launch (include/bnn_hip.h F24
+    states the chain).  `lr` is the rate used; `step` a one-element int32 device word (read as uint32), `beta1_prod` a
+    one-element float64 device word (beta1^step), `ticket` 16 zeroed int32 words; `acc_g` / `acc_h` with samples > 1;
+    EPS_MEMORY: `noise` [samples, stride] (the last row is read)."""
+    lib = L.load()
+    S = int(samples)
+    if not 1 <= S <= L.IVON_MAX_SAMPLES:
+        raise BnnHipError(f"ivon_step: samples must lie in [1, {L.IVON_MAX_SAMPLES}], got {samples}")
+    a = L.IvonStepArgs()
+    a.struct_bytes = C.sizeof(L.IvonStepArgs)
+    keep, stride = _ivon_tensors("ivon_step", a, params, grads)
+    require_device(mean, hess, avg_grad, acc_g, acc_h, step, beta1_prod, ticket, lr_device, noise)
+    a.samples, a.eps_mode = S, int(eps_mode)
+    a.lr, a.ess, a.weight_decay, a.beta1, a.beta2 = float(lr), float(ess), float(weight_decay), float(beta1), float(beta2)
+    a.loss_scale, a.clip_radius, a.lr_device = float(loss_scale), float(clip_radius), _ptr(lr_device)
+    a.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    a.mean, a.hess = _ivon_flat("ivon_step", "mean", mean, stride), _ivon_flat("ivon_step", "hess", hess, stride)
+    a.avg_grad = _ivon_flat("ivon_step", "avg_grad", avg_grad, stride)
+    if S > 1:
+        a.acc_g, a.acc_h = _ivon_flat("ivon_step", "acc_g", acc_g, stride), _ivon_flat("ivon_step", "acc_h", acc_h, stride)
+    if eps_mode == L.EPS_MEMORY:
+        a.noise = _ivon_flat("ivon_step", "noise", noise, stride, S)
+    a.step = _typed(step, torch.int32, "step", 1).data_ptr()
+    a.beta1_prod = _typed(beta1_prod, torch.float64, "beta1_prod", 1).data_ptr()
+    a.ticket = _typed(ticket, torch.int32, "ticket", 16).data_ptr()
+    a._keep = keep + [mean, hess, avg_grad, acc_g, acc_h, step, beta1_prod, ticket, lr_device, noise]
+    L.check(lib.bnn_ivon_step(C.byref(a), _stream()), "bnn_ivon_step")
+
+
 # ------------------------------------------------------------------------------------- F23: SVGD / repulsive ensembles
 def svgd_chunks(stride: int) -> int:
     """bnn_svgd_chunks: rows of bnn_svgd_dist's partials for a bank of this stride (whole 64-column tiles per chunk, at most

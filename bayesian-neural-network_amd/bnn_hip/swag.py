@@ -30,6 +30,38 @@ def diag_rho(m2: torch.Tensor, n: int, scale: float = 1.0, var_clamp: float = 1e
     return (s + torch.log(-torch.expm1(-s))).float()
 
 
+def require_three_layers(mlp, layers, who: str):
+    """Refuse a network that is not BayesianNetwork's in -> hidden -> hidden -> classes with ReLUs between the layers."""
+    m = mlp
+    if [(d.relu, d.linear.in_features, d.linear.out_features) for d in layers] != \
+            [(True, m.input_shape, m.hidden_units), (True, m.hidden_units, m.hidden_units), (False, m.hidden_units, m.classes)]:
+        raise BnnHipError(f"{who}: BayesianNetwork has three layers in -> hidden -> hidden -> classes with "
+                          "ReLUs between them; this network has another architecture")
+
+
+def diag_network(mlp, layers, device, means, rhos, *, prior_sigma: float = 1.0, who: str):
+    """A networks.BayesianNetwork on `device` holding a diagonal Gaussian over `mlp`'s parameters: mu = `means` (the bits),
+    rho = `rhos` (both lists in layer order: weight, bias), a N(0, prior_sigma) prior, weight sampling (local_reparam=False).
+    Refuses a network that is not BayesianNetwork's three layers.  SwagPosterior.network and FusedIVON.network build on it."""
+    import networks
+    m = mlp
+    require_three_layers(mlp, layers, who)
+    mp = dict(input_shape=m.input_shape, classes=m.classes, batch_size=m.batch_size, hidden_units=m.hidden_units,
+              mode=m.mode, mu_init=[-0.2, 0.2], rho_init=[-5.0, -4.0], prior_init=[float(prior_sigma)], mixture_prior=False,
+              local_reparam=False)
+    with torch.device(device):
+        net = networks.BayesianNetwork(mp)
+    net.to(device)
+    lays = (net.l1, net.l2, net.l3)
+    mus = [t.data for l in lays for t in (l.weight_mu, l.bias_mu)]
+    rho_params = [t.data for l in lays for t in (l.weight_rho, l.bias_rho)]
+    with torch.no_grad():
+        for mu, rho, a, r in zip(mus, rho_params, means, rhos):
+            mu.copy_(a.view(mu.shape))
+            rho.copy_(r.view(rho.shape))
+    return net
+
+
 class SwagPosterior:
     """The moments of SWAG over `mlp`'s parameters, on the device in the layout of one member of a sgmcmc.WeightBank (element i
     of parameter tensor t at offsets[t] + i): `mean` [stride], `m2` [stride] (Welford: m2 / count is the population variance
@@ -148,29 +180,13 @@ class SwagPosterior:
     def network(self, scale: float = 1.0, var_clamp: float = 1e-30):
         """A networks.BayesianNetwork on the device holding SWAG-Diagonal: mu = the mean (the bits), rho =
         softplus^-1(sqrt(scale * max(m2 / n, var_clamp))) (diag_rho), a N(0, 1) prior, weight sampling (local_reparam=False)."""
-        import networks
-        m = self.mlp
-        if [(d.relu, d.linear.in_features, d.linear.out_features) for d in self.layers] != \
-                [(True, m.input_shape, m.hidden_units), (True, m.hidden_units, m.hidden_units), (False, m.hidden_units, m.classes)]:
-            raise BnnHipError("SwagPosterior.network: BayesianNetwork has three layers in -> hidden -> hidden -> classes with "
-                              "ReLUs between them; this network has another architecture")
+        # (diag_network checks this again; the call here keeps the refusals in their order: the architecture, then the count)
+        require_three_layers(self.mlp, self.layers, "SwagPosterior.network")
         n = self.count()
         if n < 2:
             raise BnnHipError(f"SwagPosterior.network: {n} iterate(s) collected; a variance needs at least 2")
-        mp = dict(input_shape=m.input_shape, classes=m.classes, batch_size=m.batch_size, hidden_units=m.hidden_units,
-                  mode=m.mode, mu_init=[-0.2, 0.2], rho_init=[-5.0, -4.0], prior_init=[1.0], mixture_prior=False,
-                  local_reparam=False)
-        with torch.device(self.device):
-            net = networks.BayesianNetwork(mp)
-        net.to(self.device)
-        lays = (net.l1, net.l2, net.l3)
-        mus = [t.data for l in lays for t in (l.weight_mu, l.bias_mu)]
-        rhos = [t.data for l in lays for t in (l.weight_rho, l.bias_rho)]
-        with torch.no_grad():
-            for mu, rho, a, r in zip(mus, rhos, self.mean_views(), self._views(diag_rho(self.m2, n, scale, var_clamp))):
-                mu.copy_(a.view(mu.shape))
-                rho.copy_(r.view(rho.shape))
-        return net
+        return diag_network(self.mlp, self.layers, self.device, self.mean_views(),
+                            self._views(diag_rho(self.m2, n, scale, var_clamp)), who="SwagPosterior.network")
 
 
 # ---------------------------------------------------------------------------------------------------- the collector

@@ -33,6 +33,7 @@ from bnn_hip import kfac as _kfac
 from bnn_hip import sgmcmc as _sgmcmc
 from bnn_hip import swag as _swag
 from bnn_hip import ensemble as _ensemble
+from bnn_hip import ivon as _ivon
 from bnn_hip.functional import BBBLinearFn as _BBBLinearFn
 from bnn_hip.functional import LayerCall as _LayerCall
 from bnn_hip.functional import LRLinearFn as _LRLinearFn
@@ -457,6 +458,15 @@ class _PlainMLP(nn.Module):
         estimate, `swag.network()` SWAG-Diagonal as a BayesianNetwork and `swag.sample_bank(30).predictive(x)` full SWAG."""
         post = _swag.SwagPosterior(self, rank=int(rank))
         return _swag.FusedSWAG(self.parameters(), lr, swag=post, **kw), post
+
+    def ivon(self, lr, ess, **kw):
+        """Extension (not in the reference): a bnn_hip.ivon.FusedIVON over this network's parameters -- the variational
+        online Newton optimiser (`ess`: the effective sample size, normally the data-set size; `samples`, `hess_init`,
+        `weight_decay`, `beta1`, `beta2`, `clip_radius`, `sigma` for a regression noise).  `step =
+        mlp.graphed_train_step(opt, x, y)` then learns a diagonal Gaussian posterior whose mean the parameters hold;
+        afterwards `opt.network()` is that posterior as a BayesianNetwork, `opt.sample_bank(30).predictive(x)` its ensemble
+        predictive and `opt.variance()` its variances."""
+        return _ivon.FusedIVON(list(self.parameters()), lr, ess, mlp=self, **kw)
 
 
 class MLP(_PlainMLP):

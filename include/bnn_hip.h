@@ -2952,6 +2952,107 @@ int bnn_svgd_coef(const bnn_svgd_coef_args* args, void* stream);
 int bnn_svgd_direction(const bnn_svgd_direction_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * F24  IVON for MLP / MLP_Dropout (Shen et al. 2024, "Variational Learning is Effective for Large Deep Networks"; not in the
+ * reference): natural-gradient variational learning of a diagonal Gaussian N(m, 1 / (ess (h + delta))) per weight at the cost
+ * of an Adam step.  The tensor list is F19's (up to BNN_SGMCMC_MAX_TENSORS fp32 tensors); the state (mean, hess, avg_grad, acc_g,
+ * acc_h: [stride] each) and the rows of noise / bank hold element i of tensor t at off_t + i in the layout of one member of an
+ * F19 bank.  Padding words are never written.  Between steps the parameter tensors hold the mean m.
+ *
+ * Step t = *step (a uint32 word) runs samples s = 0 .. S - 1: bnn_ivon_draw(s) before sample s's forward / backward pass and
+ * bnn_ivon_step after the last.  Host constants, formed in fp64 and rounded once to fp32: ess, delta = weight_decay, beta1,
+ * c1 = (1 - beta1) loss_scale / S, cS = loss_scale / S, rho = 1 - beta2, c2 = 0.5 (1 - beta2)^2, clip_radius, lr.  Everything
+ * per element is fp32 with the multiply-adds written out; sqrt and / are the correctly rounded ones.
+ *       hd = h + delta;   r = sqrt(ess * hd);   sigma = 1 / r                        (draw, fold and step alike)
+ *
+ * bnn_ivon_draw, training form (bank NULL) — theta of draw q = t * S + sample (uint32, wraps) into the parameter tensors:
+ *       m     = sample == 0 ? param : mean;      sample == 0: mean = m  (the mean is filed)
+ *       param = fma(sigma, eps_q, m)
+ *   and for sample >= 1 the fold of the previous sample's gradient g, er = eps_(q-1) * r:
+ *       acc_g = sample == 1 ? g : acc_g + g;     acc_h = sample == 1 ? g * er : fma(g, er, acc_h)
+ *   Reads *step, changes no word.  Traffic at S = 1: reads p, h, writes mean, p: 16 B / parameter.
+ * bnn_ivon_draw, bank form (bank given) — members first .. first + members - 1 of bank [capacity, stride], members <=
+ *   BNN_IVON_MAX_MEMBERS: bank[first + j] = fma(sigma, eps_q, param), q = sample_base + j; the mean is read from the parameter
+ *   tensors (where it lives between steps), m and sigma once per launch whatever `members`.  Reads no word.
+ *   The noise, by eps_mode.  BNN_EPS_PHILOX: eps_q of element i of tensor k from counter (i >> 2, q, k, 6) slot i & 3, key =
+ *   (seed_lo, seed_hi), the map's Box-Muller -- counter word 3 = 6 is a new stream (0 .. 5 taken: F22), BNN_EPS_MAP_VERSION
+ *   stays 2.  BNN_EPS_MEMORY: noise [rows, stride]; the training form reads row `sample` (the fold row sample - 1), the bank
+ *   form row j.  BNN_EPS_ZERO: eps = 0.  Given the same q and noise both forms write the same bits.
+ *   Errors, in this order: NULL args; ABI; n_tensors outside [1, BNN_SGMCMC_MAX_TENSORS], samples outside [1,
+ *   BNN_IVON_MAX_SAMPLES], sample outside [0, samples), (bank form) members outside [1, BNN_IVON_MAX_MEMBERS], first < 0,
+ *   capacity < 1, first + members > capacity, ess <= 0 or NaN, weight_decay <= 0 or NaN, a numel outside [1, 2^34]:
+ *   BNN_ERR_SHAPE; eps_mode: BNN_ERR_ENUM; hess, a param, (training form) mean, step, (sample >= 1) a grad, acc_g, acc_h,
+ *   (BNN_EPS_MEMORY) noise NULL: BNN_ERR_NULL; BNN_ERR_ALIGN (tensors, state, noise and bank 16 bytes, step 4).
+ *
+ * bnn_ivon_step — the natural-gradient step over all tensors in ONE launch, with g the last sample's gradient, q = t * S +
+ *   S - 1 (eps regenerated, theta - m never formed), er = eps_q * r, P = *beta1_prod (fp64, beta1^t) read before the update:
+ *       gs  = S == 1 ? g : acc_g + g;            hs = S == 1 ? g * er : fma(g, er, acc_h)
+ *       gm' = fma(beta1, gm, c1 * gs)
+ *       d   = fma(-cS, hs, h)                                       (h - hhat, hhat = cS hs)
+ *       h'  = fma(c2, (d * d) / hd, fma(-rho, d, h))                (the correction divides by the OLD h + delta)
+ *       ib  = (float)(1 / fma(-P, beta1, 1))                        (fp64, 1 / bc1 with bc1 = 1 - beta1^(t+1); once per thread)
+ *       u   = fma(delta, m, gm' * ib) / (h' + delta);   u = min(max(u, -clip_radius), clip_radius) when clip_radius < inf
+ *       p   = fma(-lr, u, m)                                        m read from mean; lr: *lr_device when given
+ *   Every block reads *step and *beta1_prod before its update; the block that arrives last stores t + 1 and P * beta1 (the
+ *   ticketed hand-off of bnn_swag_step; ticket: 16 zeroed uint32 words, left zeroed).  No pow, no float atomics.
+ *   Traffic at S = 1: reads g, mean, h, gm, writes p, h, gm: 28 B / parameter (bnn_adam_step's).
+ *   Errors, in this order: NULL args; ABI; n_tensors outside [1, BNN_SGMCMC_MAX_TENSORS], samples outside [1,
+ *   BNN_IVON_MAX_SAMPLES], ess <= 0, weight_decay <= 0, lr < 0, beta1 outside [0, 1), beta2 outside [0, 1], loss_scale or
+ *   clip_radius <= 0 (or any of them NaN), a numel outside [1, 2^34]: BNN_ERR_SHAPE; eps_mode: BNN_ERR_ENUM; step,
+ *   beta1_prod, ticket, mean, hess, avg_grad, a param, a grad, (samples > 1) acc_g, acc_h, (BNN_EPS_MEMORY) noise NULL:
+ *   BNN_ERR_NULL; BNN_ERR_ALIGN (tensors, state and noise 16 bytes, beta1_prod 8, words 4).
+ * ---------------------------------------------------------------------------------- */
+#define BNN_IVON_MAX_SAMPLES 8
+#define BNN_IVON_MAX_MEMBERS 64           /* per launch */
+
+typedef struct bnn_ivon_draw_args {
+  uint32_t struct_bytes;
+  int32_t n_tensors;
+  float* param[BNN_SGMCMC_MAX_TENSORS];          /* training form: read at sample 0, written; bank form: the mean, read only */
+  const float* grad[BNN_SGMCMC_MAX_TENSORS];     /* training form, sample >= 1: the previous sample's gradient */
+  int64_t numel[BNN_SGMCMC_MAX_TENSORS];
+  int32_t samples;          /* S */
+  int32_t sample;           /* s; 0 files the mean (training form) */
+  int32_t members, first, capacity;              /* bank form */
+  int32_t eps_mode;         /* bnn_eps_mode */
+  uint32_t sample_base;     /* bank form */
+  int32_t reserved;
+  double ess, weight_decay;
+  uint64_t seed;
+  float* mean;              /* [stride]; training form */
+  const float* hess;        /* [stride] */
+  float* acc_g;             /* [stride]; sample >= 1 */
+  float* acc_h;             /* [stride]; sample >= 1 */
+  const uint32_t* step;     /* device word t; training form */
+  const float* noise;       /* BNN_EPS_MEMORY: [samples, stride] (training form), [members, stride] (bank form) */
+  float* bank;              /* [capacity, stride]: selects the bank form */
+} bnn_ivon_draw_args;
+
+typedef struct bnn_ivon_step_args {
+  uint32_t struct_bytes;
+  int32_t n_tensors;
+  float* param[BNN_SGMCMC_MAX_TENSORS];
+  const float* grad[BNN_SGMCMC_MAX_TENSORS];
+  int64_t numel[BNN_SGMCMC_MAX_TENSORS];
+  int32_t samples;          /* S */
+  int32_t eps_mode;         /* bnn_eps_mode */
+  double lr, ess, weight_decay, beta1, beta2, loss_scale, clip_radius;   /* lr: the rate used (any rescaling done by the caller) */
+  const float* lr_device;   /* optional device float: overrides lr */
+  uint64_t seed;
+  const float* mean;        /* [stride] */
+  float* hess;              /* [stride] */
+  float* avg_grad;          /* [stride] */
+  const float* acc_g;       /* [stride]; samples > 1 */
+  const float* acc_h;       /* [stride]; samples > 1 */
+  const float* noise;       /* BNN_EPS_MEMORY: [samples, stride]; row samples - 1 is read */
+  uint32_t* step;           /* device word t */
+  double* beta1_prod;       /* device fp64 word beta1^t */
+  uint32_t* ticket;         /* 16 device words, zero between launches */
+} bnn_ivon_step_args;
+
+int bnn_ivon_draw(const bnn_ivon_draw_args* args, void* stream);
+int bnn_ivon_step(const bnn_ivon_step_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * bnn_cast_bf16 — fp32 -> bf16 (round to nearest even) of n contiguous elements: the input
  * batch is cast once per ELBO evaluation when bf16 math runs many MC samples, so every
  * layer streams 2-byte activations.  (The reference keeps x in fp32, main.py / class_task.py:71.)
