@@ -192,8 +192,6 @@ __global__ __launch_bounds__(kAcqBlock) void acquire_random_kernel(float* __rest
     if (4u * g + i < N) scores[4u * g + i] = (float)(w[i] >> 8) * 0x1p-24f;          // 24 bits: exact in fp32
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 }  // namespace
 }  // namespace bnn
 

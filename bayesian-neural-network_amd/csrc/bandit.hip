@@ -182,8 +182,6 @@ __global__ __launch_bounds__(kGatherBlock) void bandit_gather_group_kernel(const
 
 using namespace bnn;
 
-static bool misaligned(const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; }
-
 static int check_act(const bnn_bandit_act_args* a) {
   if (!a) return BNN_ERR_NULL;
   if (a->struct_bytes != sizeof(bnn_bandit_act_args)) return BNN_ERR_ABI;

@@ -269,7 +269,6 @@ __global__ __launch_bounds__(kBbBlock) void bb_extend_sampled_kernel(bnn_batchba
   a.offset[m] = (double)E * kLn2d;
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
 bool bad_dims(int C, int S, int N) {
   return C < 2 || C > BNN_BATCHBALD_MAX_CLASSES || S < 1 || S > BNN_BATCHBALD_MAX_SAMPLES || N < 1 || N > BNN_EPOCH_MAX_ROWS;
 }

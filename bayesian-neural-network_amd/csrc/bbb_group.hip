@@ -314,8 +314,6 @@ __global__ __launch_bounds__(kMgThreads) void bbb_group_train_kernel(BgK p) {
 
 using namespace bnn;
 
-static bool bg_misaligned(const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; }
-
 static bool bg_shape_ok(int in_features, int hidden) {
   return in_features >= 1 && in_features <= BNN_MLP_GROUP_MAX_IN && hidden >= 1 && hidden <= BNN_MLP_GROUP_MAX_HIDDEN;
 }
@@ -346,30 +344,30 @@ static int check_bbb_group(const bnn_bbb_group_args* a, bool train) {
   }
   if (!a->agents_host || !a->agents) return BNN_ERR_NULL;
   if (a->agents_bytes != (int64_t)a->n_agents * (int64_t)sizeof(bnn_bbb_group_agent)) return BNN_ERR_SHAPE;
-  if (bg_misaligned(a->agents, 8)) return BNN_ERR_ALIGN;
+  if (misaligned(a->agents, 8)) return BNN_ERR_ALIGN;
   if (a->workspace_bytes < (int64_t)bnn_bbb_group_workspace_bytes(a->in_features, a->hidden)) return BNN_ERR_WORKSPACE;
   for (int g = 0; g < a->n_agents; ++g) {
     const bnn_bbb_group_agent& ag = a->agents_host[g];
     for (int i = 0; i < 12; ++i) {
       if (!ag.param[i]) return BNN_ERR_NULL;
-      if (bg_misaligned(ag.param[i], 4)) return BNN_ERR_ALIGN;
+      if (misaligned(ag.param[i], 4)) return BNN_ERR_ALIGN;
       if (train) {
         if (!ag.exp_avg[i] || !ag.exp_avg_sq[i]) return BNN_ERR_NULL;
-        if (bg_misaligned(ag.exp_avg[i], 4) || bg_misaligned(ag.exp_avg_sq[i], 4)) return BNN_ERR_ALIGN;
+        if (misaligned(ag.exp_avg[i], 4) || misaligned(ag.exp_avg_sq[i], 4)) return BNN_ERR_ALIGN;
       }
     }
     if (!ag.workspace) return BNN_ERR_WORKSPACE;
-    if (bg_misaligned(ag.workspace, 16)) return BNN_ERR_ALIGN;
+    if (misaligned(ag.workspace, 16)) return BNN_ERR_ALIGN;
     if (train) {
       const void* req[] = {ag.step, ag.lr, ag.slab, ag.targets, ag.n_batches, ag.loss_info, ag.sample_counter};
       for (const void* p : req) {
         if (!p) return BNN_ERR_NULL;
-        if (bg_misaligned(p, 4)) return BNN_ERR_ALIGN;
+        if (misaligned(p, 4)) return BNN_ERR_ALIGN;
       }
     } else {
       if (ag.eps_mode != BNN_EPS_PHILOX && ag.eps_mode != BNN_EPS_ZERO) return BNN_ERR_ENUM;
       if (!ag.rows || !ag.outputs || (ag.eps_mode == BNN_EPS_PHILOX && !ag.sample_counter)) return BNN_ERR_NULL;
-      if (bg_misaligned(ag.rows, 4) || bg_misaligned(ag.outputs, 4) || bg_misaligned(ag.sample_counter, 4)) return BNN_ERR_ALIGN;
+      if (misaligned(ag.rows, 4) || misaligned(ag.outputs, 4) || misaligned(ag.sample_counter, 4)) return BNN_ERR_ALIGN;
     }
   }
   return BNN_OK;

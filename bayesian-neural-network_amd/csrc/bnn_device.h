@@ -59,10 +59,11 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& n0, fl
   n1 = rad * __builtin_amdgcn_sinf(u2);
 }
 
-// The four N(0,1) values of epsilon group `group` (see include/bnn_hip.h).
+// The four N(0,1) values of epsilon group `group` (see include/bnn_hip.h).  word3: counter word 3, 0 for the epsilon map and
+// a constant of its own for every other noise stream (the k...Word3 of their files).
 __device__ __forceinline__ void philox_normal4(uint32_t group, uint32_t gsample, uint32_t tensor_id,
-                                               uint32_t k0, uint32_t k1, float out[4]) {
-  const uint4 r = philox4x32<>(make_uint4(group, gsample, tensor_id, 0u), k0, k1);
+                                               uint32_t k0, uint32_t k1, float out[4], uint32_t word3 = 0u) {
+  const uint4 r = philox4x32<>(make_uint4(group, gsample, tensor_id, word3), k0, k1);
   box_muller(r.x, r.y, out[0], out[1]);
   box_muller(r.z, r.w, out[2], out[3]);
 }
@@ -287,6 +288,10 @@ __device__ __forceinline__ T tree_sum(T v, T* part) {
   __syncthreads();
   return r;
 }
+
+// Host: the argument checks of the entry points.  al: a power of two; a null pointer is aligned.
+inline bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
+inline uintptr_t bits(const void* q) { return reinterpret_cast<uintptr_t>(q); }
 
 // Up to MAX tensors cut into chunks, one chunk per block, the chunk -> tensor table riding in the kernel arguments.
 // Host: add() each tensor, then finish(); device: find().  The owner keeps its pointer arrays and its chunk size.

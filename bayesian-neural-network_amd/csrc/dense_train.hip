@@ -15,13 +15,12 @@
 
 #include "bnn_device.h"
 #include "bnn_nll_row.h"
+#include "bnn_stream.h"
 #include "dense_tile.h"
 #include "../../include/bnn_hip.h"
 
 namespace bnn {
 namespace {
-
-constexpr int kSgdChunk = 4096;
 
 struct BwdParams {
   const float* x;
@@ -93,33 +92,29 @@ struct SgdK {
   const float* lr_dev;
 };
 
-// one block = one 4096-element chunk of one tensor; 16-byte accesses
+// one block = one chunk of one tensor (bnn_stream.h)
 __global__ __launch_bounds__(kThreads) void sgd_kernel(const SgdK k) {
+  static_assert(kThreads == 256, "bnn_stream.h's walk");
   long base;
-  const int t = k.list.find((int)blockIdx.x, kSgdChunk, base);
+  const int t = k.list.find((int)blockIdx.x, kStreamChunk, base);
   const long n = k.list.numel[t];
   float* __restrict__ p = k.p[t];
   const float* __restrict__ g = k.g[t];
   const float nlr = -(k.lr_dev ? *k.lr_dev : k.lr);
   const float wd = k.wd;
 #pragma unroll
-  for (int it = 0; it < kSgdChunk / (kThreads * 4); ++it) {
+  for (int it = 0; it < kStreamIters; ++it) {
     const long i = base + ((long)it * kThreads + threadIdx.x) * 4;
     if (i >= n) break;
-    if (i + 3 < n) {
-      const float4 a = *reinterpret_cast<const float4*>(p + i), b = *reinterpret_cast<const float4*>(g + i);
-      float pv[4] = {a.x, a.y, a.z, a.w};
-      const float gv[4] = {b.x, b.y, b.z, b.w};
+    const bool full = i + 3 < n;
+    float pv[4], gv[4];
+    ld4(p, i, n, full, pv);
+    ld4(g, i, n, full, gv);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) pv[j] = __builtin_fmaf(nlr, wd != 0.f ? __builtin_fmaf(wd, pv[j], gv[j]) : gv[j], pv[j]);
-      *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-    } else {
-      for (long j = i; j < n; ++j) p[j] = __builtin_fmaf(nlr, wd != 0.f ? __builtin_fmaf(wd, p[j], g[j]) : g[j], p[j]);
-    }
+    for (int j = 0; j < 4; ++j) pv[j] = __builtin_fmaf(nlr, wd != 0.f ? __builtin_fmaf(wd, pv[j], gv[j]) : gv[j], pv[j]);
+    st4(p, i, n, full, pv);
   }
 }
-
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
 
 }  // namespace
 }  // namespace bnn
@@ -190,7 +185,7 @@ extern "C" int bnn_sgd_step(const bnn_sgd_args* a, void* stream_) {
   }
   for (int t = 0; t < a->n_tensors; ++t) {
     if (!a->param[t] || !a->grad[t]) return BNN_ERR_NULL;
-    const int st = k.list.add(a->numel[t], kSgdChunk);
+    const int st = k.list.add(a->numel[t], kStreamChunk);
     if (st != BNN_OK) return st;
     if (misaligned(a->param[t], 16) || misaligned(a->grad[t], 16)) return BNN_ERR_ALIGN;
     k.p[t] = a->param[t];

@@ -151,7 +151,6 @@ __global__ __launch_bounds__(kThreads) void ens_bwd_kernel(const EnsBwdK p) {
                 [&](int b, int o) { return gz_of(gy[(long)b * p.OUT + o], y, (long)b * p.OUT + o, p.y_scale); });
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
 bool math_ok(int m) { return m == BNN_MATH_F32 || m == BNN_MATH_BF16 || m == BNN_MATH_BF16X3; }
 unsigned xcd_grid(int total) { return 8u * (unsigned)((total + 7) / 8); }      // (xcd_work_item: 8 equal ranges)
 

@@ -125,8 +125,6 @@ __global__ __launch_bounds__(kStageBlock) void epoch_stage_kernel(bnn_epoch_stag
 
 using namespace bnn;
 
-static bool misaligned(const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; }
-
 extern "C" int bnn_epoch_permutation(const bnn_epoch_perm_args* a, void* stream_) {
   if (!a) return BNN_ERR_NULL;
   if (a->struct_bytes != sizeof(bnn_epoch_perm_args)) return BNN_ERR_ABI;

@@ -495,7 +495,6 @@ __global__ __launch_bounds__(256) void flipout_bwd_x_kernel(BwdK p) {
   }
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
 bool bad_features(int v) { return v < 1 || v > BNN_FLIPOUT_MAX_FEATURES; }
 long prepare_blocks(int K, int N) {
   const long items = (long)N * ((K + 3) >> 2) + ((N + 3) >> 2);

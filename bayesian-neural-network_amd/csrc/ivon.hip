@@ -9,55 +9,27 @@
 // with scalar tails, no float atomics.  Per parameter at S = 1 the draw reads p, h and writes mean, p (16 B); the step reads g,
 // mean, h, gm and writes p, h, gm (28 B, bnn_adam_step's).  Per float4 the draw runs one Philox call, 4 sqrt and 4 divisions;
 // the step regenerates the same Philox call (theta - m is never formed) and runs 4 sqrt and 8 divisions.  The step word and the
-// fp64 product beta1^t are advanced by the step launch's last block (optim.hip's ticketed hand-off).
+// fp64 product beta1^t are advanced by the step launch's last block (bnn_stream.h's ticketed hand-off).
 // The step kernel issues a whole chunk's loads ahead of its arithmetic (as bnn_adam_step's unrolled loop does); the draw and
 // the bank kernel make one load / compute / store round per iteration.
 //
 // Every multiply-add below is written out (the build contracts what is left to it): a product that feeds an add is either an
 // explicit fma or does not exist.
 #include "bnn_device.h"
+#include "bnn_stream.h"
 #include "../../include/bnn_hip.h"
 
 namespace bnn {
 namespace {
 
-constexpr int kIvChunk = 4096;
 constexpr uint32_t kIvWord3 = 6u;       // counter word 3 of the IVON noise stream (include/bnn_hip.h F24)
 constexpr int kMaxT = BNN_SGMCMC_MAX_TENSORS;
-
-// the four N(0,1) values of group `group` of tensor `t` of draw q
-__device__ __forceinline__ void ivon_eps4(uint32_t group, uint32_t q, uint32_t t, uint32_t k0, uint32_t k1, float out[4]) {
-  const uint4 r = philox4x32<>(make_uint4(group, q, t, kIvWord3), k0, k1);
-  box_muller(r.x, r.y, out[0], out[1]);
-  box_muller(r.z, r.w, out[2], out[3]);
-}
-
-// elements i .. i + 3 of a tensor of n elements: one 16-byte access when all four exist, scalars (0 beyond n) otherwise
-__device__ __forceinline__ void ld4(const float* __restrict__ src, long i, long n, bool full, float v[4]) {
-  if (full) {
-    const float4 q = *reinterpret_cast<const float4*>(src + i);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = i + j < n ? src[i + j] : 0.f;
-  }
-}
-
-__device__ __forceinline__ void st4(float* __restrict__ dst, long i, long n, bool full, const float v[4]) {
-  if (full) {
-    *reinterpret_cast<float4*>(dst + i) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (i + j < n) dst[i + j] = v[j];
-  }
-}
 
 // the noise of draw q (on chip) or of row `row` of the noise in memory; 0 in BNN_EPS_ZERO
 __device__ __forceinline__ void ivon_noise(int eps_mode, const float* __restrict__ rows, long stride, long row, long i, long n,
                                            bool full, uint32_t q, uint32_t t, uint32_t k0, uint32_t k1, float e[4]) {
   if (eps_mode == BNN_EPS_PHILOX) {
-    ivon_eps4((uint32_t)(i >> 2), q, t, k0, k1, e);
+    philox_normal4((uint32_t)(i >> 2), q, t, k0, k1, e, kIvWord3);
   } else if (eps_mode == BNN_EPS_MEMORY) {
     ld4(rows + row * stride, i, n, full, e);
   } else {
@@ -94,7 +66,7 @@ struct IvDrawK {
 template <bool FOLD>
 __global__ __launch_bounds__(256) void ivon_draw_kernel(const IvDrawK k) {
   long base;
-  const int t = k.list.find((int)blockIdx.x, kIvChunk, base);
+  const int t = k.list.find((int)blockIdx.x, kStreamChunk, base);
   const long n = k.list.numel[t];
   float* __restrict__ p = k.p[t];
   const float* __restrict__ g = k.g[t];
@@ -106,7 +78,7 @@ __global__ __launch_bounds__(256) void ivon_draw_kernel(const IvDrawK k) {
   const uint32_t q = *k.step * k.S + k.s;
   const float ess = k.ess, delta = k.delta;
 #pragma unroll 1
-  for (int it = 0; it < kIvChunk / (256 * 4); ++it) {
+  for (int it = 0; it < kStreamIters; ++it) {
     const long i = base + ((long)it * 256 + threadIdx.x) * 4;
     if (i >= n) break;
     const bool full = i + 3 < n;
@@ -154,7 +126,7 @@ __global__ __launch_bounds__(256) void ivon_draw_kernel(const IvDrawK k) {
 // bank form: members q0 .. q0 + mq - 1 of the launch per block (blockIdx.y takes a group of them)
 __global__ __launch_bounds__(256) void ivon_bank_kernel(const IvDrawK k) {
   long base;
-  const int t = k.list.find((int)blockIdx.x, kIvChunk, base);
+  const int t = k.list.find((int)blockIdx.x, kStreamChunk, base);
   const long n = k.list.numel[t];
   const float* __restrict__ p = k.p[t];
   const float* __restrict__ hess = k.hess + k.off[t];
@@ -164,7 +136,7 @@ __global__ __launch_bounds__(256) void ivon_bank_kernel(const IvDrawK k) {
   const uint32_t mq = k.m - q0 < k.mgroup ? k.m - q0 : k.mgroup;
   const float ess = k.ess, delta = k.delta;
 #pragma unroll 1
-  for (int it = 0; it < kIvChunk / (256 * 4); ++it) {
+  for (int it = 0; it < kStreamIters; ++it) {
     const long i = base + ((long)it * 256 + threadIdx.x) * 4;
     if (i >= n) break;
     const bool full = i + 3 < n;
@@ -214,7 +186,7 @@ struct IvStepK {
 template <bool MULTI, bool CLIP>
 __global__ __launch_bounds__(256) void ivon_step_kernel(const IvStepK k) {
   long base;
-  const int t = k.list.find((int)blockIdx.x, kIvChunk, base);
+  const int t = k.list.find((int)blockIdx.x, kStreamChunk, base);
   const long n = k.list.numel[t];
   float* __restrict__ p = k.p[t];
   const float* __restrict__ g = k.g[t];
@@ -254,13 +226,12 @@ __global__ __launch_bounds__(256) void ivon_step_kernel(const IvStepK k) {
     st4(hess, i, n, full, hv);
     st4(gm, i, n, full, av);
   };
-  constexpr int kIters = kIvChunk / (256 * 4);
-  if (base + kIvChunk <= n) {
+  if (base + kStreamChunk <= n) {
     // a whole chunk (all but a tensor's last): every load of the four iterations is issued before the first result is needed,
     // as bnn_adam_step's unrolled loop does; the stores follow each iteration's arithmetic
-    float gv[kIters][4], mv[kIters][4], hv[kIters][4], av[kIters][4], ag[kIters][4], ah[kIters][4];
+    float gv[kStreamIters][4], mv[kStreamIters][4], hv[kStreamIters][4], av[kStreamIters][4], ag[kStreamIters][4], ah[kStreamIters][4];
 #pragma unroll
-    for (int it = 0; it < kIters; ++it) {
+    for (int it = 0; it < kStreamIters; ++it) {
       const long i = base + ((long)it * 256 + threadIdx.x) * 4;
       ld4(g, i, n, true, gv[it]);
       ld4(mean, i, n, true, mv[it]);
@@ -272,11 +243,11 @@ __global__ __launch_bounds__(256) void ivon_step_kernel(const IvStepK k) {
       }
     }
 #pragma unroll
-    for (int it = 0; it < kIters; ++it)
+    for (int it = 0; it < kStreamIters; ++it)
       finish(base + ((long)it * 256 + threadIdx.x) * 4, true, gv[it], mv[it], hv[it], av[it], ag[it], ah[it]);
   } else {
 #pragma unroll 1
-    for (int it = 0; it < kIters; ++it) {
+    for (int it = 0; it < kStreamIters; ++it) {
       const long i = base + ((long)it * 256 + threadIdx.x) * 4;
       if (i >= n) break;
       const bool full = i + 3 < n;
@@ -292,44 +263,19 @@ __global__ __launch_bounds__(256) void ivon_step_kernel(const IvStepK k) {
       finish(i, full, gv, mv, hv, av, ag, ah);
     }
   }
-  // optim.hip's hand-off: every wave has read the words before thread 0 announces the block; blocks count in 8 groups
-  // (ticket word 1 + blockIdx % 8), each group's last arriver counts once on word 0, the last of those advances the words
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t grp = blockIdx.x & 7u;
-    const uint32_t in_group = (gridDim.x - grp + 7u) >> 3;
-    const uint32_t tk = __hip_atomic_fetch_add(k.ticket + 1 + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tk == in_group - 1u) {
-      k.ticket[1 + grp] = 0u;
-      const uint32_t groups = gridDim.x < 8u ? gridDim.x : 8u;
-      const uint32_t top = __hip_atomic_fetch_add(k.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (top == groups - 1u) {
-        *k.step = step + 1u;
-        *k.prod = prod * k.beta1_d;
-        k.ticket[0] = 0u;
-      }
-    }
-  }
+  last_block(k.ticket, [&] {
+    *k.step = step + 1u;
+    *k.prod = prod * k.beta1_d;
+  });
 }
-
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-uintptr_t bits(const void* q) { return reinterpret_cast<uintptr_t>(q); }
 
 // the chunk list and the state offsets of a tensor list; BNN_OK or the refusal
 template <class K>
-int lay_out(K& k, int n_tensors, const int64_t* numel, long& stride) {
-  stride = 0;
+int lay_out(K& k, int n_tensors, const int64_t* numel) {
   for (int t = 0; t < kMaxT; ++t) {
-    k.p[t] = nullptr; k.g[t] = nullptr; k.off[t] = 0;
+    k.p[t] = nullptr; k.g[t] = nullptr;
   }
-  for (int t = 0; t < n_tensors; ++t) {
-    if (numel[t] > ((int64_t)1 << 34)) return BNN_ERR_SHAPE;
-    const int st = k.list.add(numel[t], kIvChunk);
-    if (st != BNN_OK) return st;
-    k.off[t] = stride;
-    stride += (numel[t] + 63) / 64 * 64;
-  }
-  return BNN_OK;
+  return state_offsets(k.list, n_tensors, numel, k.off, k.stride);
 }
 
 }  // namespace
@@ -349,8 +295,7 @@ extern "C" int bnn_ivon_draw(const bnn_ivon_draw_args* a, void* stream_) {
     return BNN_ERR_SHAPE;
   if (!(a->ess > 0.0) || !(a->weight_decay > 0.0)) return BNN_ERR_SHAPE;
   IvDrawK k;
-  long stride;
-  const int st = lay_out(k, a->n_tensors, a->numel, stride);
+  const int st = lay_out(k, a->n_tensors, a->numel);
   if (st != BNN_OK) return st;
   if ((unsigned)a->eps_mode > (unsigned)BNN_EPS_ZERO) return BNN_ERR_ENUM;
   const bool mem = a->eps_mode == BNN_EPS_MEMORY, fold = !bank && a->sample >= 1;
@@ -369,7 +314,7 @@ extern "C" int bnn_ivon_draw(const bnn_ivon_draw_args* a, void* stream_) {
   k.S = (uint32_t)a->samples; k.s = (uint32_t)a->sample;
   k.m = bank ? (uint32_t)a->members : 0u; k.first = bank ? (uint32_t)a->first : 0u; k.sample_base = a->sample_base;
   k.k0 = (uint32_t)a->seed; k.k1 = (uint32_t)(a->seed >> 32);
-  k.eps_mode = a->eps_mode; k.stride = stride;
+  k.eps_mode = a->eps_mode;
   k.mean = bank ? nullptr : a->mean; k.hess = a->hess;
   k.acc_g = fold ? a->acc_g : nullptr; k.acc_h = fold ? a->acc_h : nullptr;
   k.step = bank ? nullptr : a->step; k.noise = mem ? a->noise : nullptr; k.bank = a->bank;
@@ -400,8 +345,7 @@ extern "C" int bnn_ivon_step(const bnn_ivon_step_args* a, void* stream_) {
       !(a->beta2 >= 0.0 && a->beta2 <= 1.0) || !(a->loss_scale > 0.0) || !(a->clip_radius > 0.0))
     return BNN_ERR_SHAPE;
   IvStepK k;
-  long stride;
-  const int st = lay_out(k, a->n_tensors, a->numel, stride);
+  const int st = lay_out(k, a->n_tensors, a->numel);
   if (st != BNN_OK) return st;
   if ((unsigned)a->eps_mode > (unsigned)BNN_EPS_ZERO) return BNN_ERR_ENUM;
   const bool mem = a->eps_mode == BNN_EPS_MEMORY, multi = a->samples > 1;
@@ -424,7 +368,7 @@ extern "C" int bnn_ivon_step(const bnn_ivon_step_args* a, void* stream_) {
   k.rho = (float)rho; k.c2 = (float)(0.5 * rho * rho); k.clip = (float)a->clip_radius;
   k.beta1_d = a->beta1; k.lr_dev = a->lr_device;
   k.S = (uint32_t)a->samples; k.k0 = (uint32_t)a->seed; k.k1 = (uint32_t)(a->seed >> 32);
-  k.eps_mode = a->eps_mode; k.stride = stride;
+  k.eps_mode = a->eps_mode;
   k.mean = a->mean; k.hess = a->hess; k.gm = a->avg_grad;
   k.acc_g = multi ? a->acc_g : nullptr; k.acc_h = multi ? a->acc_h : nullptr; k.noise = mem ? a->noise : nullptr;
   k.step = a->step; k.prod = a->beta1_prod; k.ticket = a->ticket;

@@ -372,9 +372,7 @@ __device__ __forceinline__ void fetch_seg(const NoiseOpnd& q, int K, int r0, int
   float n[12];
 #pragma unroll
   for (int gi = 0; gi < 3; ++gi) {
-    const uint4 w = philox4x32<>(make_uint4(g0 + (uint32_t)gi, q.sample, q.layer, kKfacWord3), q.k0, q.k1);
-    box_muller(w.x, w.y, n[4 * gi], n[4 * gi + 1]);
-    box_muller(w.z, w.w, n[4 * gi + 2], n[4 * gi + 3]);
+    philox_normal4(g0 + (uint32_t)gi, q.sample, q.layer, q.k0, q.k1, n + 4 * gi, kKfacWord3);
   }
   const double g = q.lg[r];
 #pragma unroll
@@ -441,8 +439,6 @@ __global__ __launch_bounds__(kThreads) void kfac_sample_w_kernel(SampleParams p)
     }
   });
 }
-
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
 
 long tiles(long n) { return (n + kT - 1) / kT; }
 

@@ -522,8 +522,6 @@ __global__ __launch_bounds__(kThreads) void laplace_glm_sample_kernel(const floa
   }
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 }  // namespace
 }  // namespace bnn
 

@@ -258,8 +258,6 @@ __global__ void dropout_mask_kernel(float* __restrict__ mask, uint32_t k0, uint3
   }
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 // Argument checks and the launch geometry of bnn_dense_fwd (a pure function of the arguments' values and alignment).
 struct DenseLaunch {
   int big;          // 128 x 128 tiles (bf16 math only)

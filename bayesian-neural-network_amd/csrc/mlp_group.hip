@@ -160,8 +160,6 @@ __global__ __launch_bounds__(kMgThreads) void mlp_group_train_kernel(const bnn_m
 
 using namespace bnn;
 
-static bool mg_misaligned(const void* p, uintptr_t al) { return (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; }
-
 // The shared shape and the host copy of the agent blocks (include/bnn_hip.h F6); train additionally needs the optimiser
 // and minibatch pointers, fwd the rows and outputs.
 static int check_mlp_group(const bnn_mlp_group_args* a, bool train) {
@@ -182,26 +180,26 @@ static int check_mlp_group(const bnn_mlp_group_args* a, bool train) {
   }
   if (!a->agents_host || !a->agents) return BNN_ERR_NULL;
   if (a->agents_bytes != (int64_t)a->n_agents * (int64_t)sizeof(bnn_mlp_group_agent)) return BNN_ERR_SHAPE;
-  if (mg_misaligned(a->agents, 8)) return BNN_ERR_ALIGN;
+  if (misaligned(a->agents, 8)) return BNN_ERR_ALIGN;
   for (int g = 0; g < a->n_agents; ++g) {
     const bnn_mlp_group_agent& ag = a->agents_host[g];
     for (int i = 0; i < 6; ++i) {
       if (!ag.param[i]) return BNN_ERR_NULL;
-      if (mg_misaligned(ag.param[i], 4)) return BNN_ERR_ALIGN;
+      if (misaligned(ag.param[i], 4)) return BNN_ERR_ALIGN;
       if (train) {
         if (!ag.exp_avg[i] || !ag.exp_avg_sq[i]) return BNN_ERR_NULL;
-        if (mg_misaligned(ag.exp_avg[i], 4) || mg_misaligned(ag.exp_avg_sq[i], 4)) return BNN_ERR_ALIGN;
+        if (misaligned(ag.exp_avg[i], 4) || misaligned(ag.exp_avg_sq[i], 4)) return BNN_ERR_ALIGN;
       }
     }
     if (train) {
       const void* req[] = {ag.step, ag.lr, ag.slab, ag.targets, ag.n_batches, ag.loss};
       for (const void* p : req) {
         if (!p) return BNN_ERR_NULL;
-        if (mg_misaligned(p, 4)) return BNN_ERR_ALIGN;
+        if (misaligned(p, 4)) return BNN_ERR_ALIGN;
       }
     } else {
       if (!ag.rows || !ag.outputs) return BNN_ERR_NULL;
-      if (mg_misaligned(ag.rows, 4) || mg_misaligned(ag.outputs, 4)) return BNN_ERR_ALIGN;
+      if (misaligned(ag.rows, 4) || misaligned(ag.outputs, 4)) return BNN_ERR_ALIGN;
     }
   }
   return BNN_OK;

@@ -7,12 +7,12 @@
 // chunk -> tensor table rides in the kernel arguments; 16-byte accesses.
 #include "bnn_device.h"
 #include "bnn_nll_row.h"
+#include "bnn_stream.h"
 #include "../../include/bnn_hip.h"
 #include <math.h>
+#include <type_traits>
 
 namespace bnn {
-
-constexpr int kAdamChunk = 4096;
 
 struct AdamK {
   float* p[BNN_ADAM_MAX_TENSORS];
@@ -35,39 +35,31 @@ __global__ void adam_tick_kernel(uint32_t* step) { *step += 1u; }
 // GBF16: the gradients arrive in bf16 (a data-parallel step's all-reduced 2-byte bucket)
 template <bool GBF16>
 __global__ __launch_bounds__(256) void adam_kernel(const AdamK k) {
+  using G = typename std::conditional<GBF16, __bf16, float>::type;
   long base;
-  const int t = k.list.find((int)blockIdx.x, kAdamChunk, base);
+  const int t = k.list.find((int)blockIdx.x, kStreamChunk, base);
   const long n = k.list.numel[t];
   float* __restrict__ p = k.p[t];
-  const float* __restrict__ g = k.g[t];
-  const __bf16* __restrict__ g16 = reinterpret_cast<const __bf16*>(k.g[t]);
-  auto ld_g4 = [&](long i) -> float4 {
-    if (!GBF16) return *reinterpret_cast<const float4*>(g + i);
-    const bf16x4 h = *reinterpret_cast<const bf16x4*>(g16 + i);
-    return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
-  };
-  auto ld_g1 = [&](long i) -> float { return GBF16 ? (float)g16[i] : g[i]; };
+  const G* __restrict__ g = reinterpret_cast<const G*>(k.g[t]);
   float* __restrict__ m = k.m[t];
   float* __restrict__ v = k.v[t];
   // a whole chunk (all but the last block of a tensor): its 16 loads go out before anything else -- the double-precision
   // bias corrections below are a few hundred instructions per thread, and behind them the first load round trip of every
   // wave was exposed at the head of the launch
-  constexpr int kIt = kAdamChunk / (256 * 4);
-  const bool whole = base + kAdamChunk <= n;
-  float4 qa[kIt], qb[kIt], qc[kIt], qd[kIt];
+  const bool whole = base + kStreamChunk <= n;
+  float pw[kStreamIters][4], gw[kStreamIters][4], mw[kStreamIters][4], vw[kStreamIters][4];
   if (whole) {
 #pragma unroll
-    for (int it = 0; it < kIt; ++it) {
+    for (int it = 0; it < kStreamIters; ++it) {
       const long i = base + ((long)it * 256 + threadIdx.x) * 4;
-      qa[it] = *reinterpret_cast<const float4*>(p + i);
-      qb[it] = ld_g4(i);
-      qc[it] = *reinterpret_cast<const float4*>(m + i);
-      qd[it] = *reinterpret_cast<const float4*>(v + i);
+      ld4(p, i, n, true, pw[it]);
+      ld4(g, i, n, true, gw[it]);
+      ld4(m, i, n, true, mw[it]);
+      ld4(v, i, n, true, vw[it]);
     }
   }
   const double lr = k.lr_dev ? (double)*k.lr_dev : k.lr;
-  // with a ticket word every block reads the old step and uses step + 1; the block that arrives last (all have
-  // read it by then) stores it: the optimiser step is ONE launch, nobody waits
+  // with a ticket word every block reads the old step and uses step + 1; the launch's last block stores it (last_block)
   const uint32_t step = k.step_dev ? *k.step_dev + (k.ticket ? 1u : 0u) : k.step;
   // bias corrections in double, as torch computes them on the host (1 - beta ** step)
   const double bc1 = 1.0 - pow(k.beta1, (double)step);
@@ -75,45 +67,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamK k) {
   const float step_size = (float)(lr / bc1);
   const float sqrt_bc2 = (float)sqrt(bc2);
   const float omb1 = k.omb1, omb2 = k.omb2;
-  if (whole) {
-#pragma unroll
-    for (int it = 0; it < kIt; ++it) {
-      const long i = base + ((long)it * 256 + threadIdx.x) * 4;
-      float pv[4] = {qa[it].x, qa[it].y, qa[it].z, qa[it].w}, gv[4] = {qb[it].x, qb[it].y, qb[it].z, qb[it].w};
-      float mv[4] = {qc[it].x, qc[it].y, qc[it].z, qc[it].w}, vv[4] = {qd[it].x, qd[it].y, qd[it].z, qd[it].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float gg = k.wd != 0.f ? __builtin_fmaf(k.wd, pv[j], gv[j]) : gv[j];
-        mv[j] = __builtin_fmaf(gg - mv[j], omb1, mv[j]);           // the arithmetic of the general loop below
-        vv[j] = __builtin_fmaf(vv[j], k.beta2f, omb2 * gg * gg);
-        const float denom = __builtin_sqrtf(vv[j]) / sqrt_bc2 + k.eps;
-        pv[j] = pv[j] - step_size * (mv[j] / denom);
-      }
-      *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-      *reinterpret_cast<float4*>(m + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-      *reinterpret_cast<float4*>(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-    }
-  } else
-#pragma unroll
-  for (int it = 0; it < kAdamChunk / (256 * 4); ++it) {
-    const long i = base + ((long)it * 256 + threadIdx.x) * 4;
-    if (i >= n) break;
-    float pv[4], gv[4], mv[4], vv[4];
-    const bool full = i + 3 < n;
-    if (full) {
-      const float4 a = *reinterpret_cast<const float4*>(p + i), b = ld_g4(i);
-      const float4 c = *reinterpret_cast<const float4*>(m + i), d = *reinterpret_cast<const float4*>(v + i);
-      pv[0] = a.x; pv[1] = a.y; pv[2] = a.z; pv[3] = a.w;
-      gv[0] = b.x; gv[1] = b.y; gv[2] = b.z; gv[3] = b.w;
-      mv[0] = c.x; mv[1] = c.y; mv[2] = c.z; mv[3] = c.w;
-      vv[0] = d.x; vv[1] = d.y; vv[2] = d.z; vv[3] = d.w;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool ok = i + j < n;
-        pv[j] = ok ? p[i + j] : 0.f; gv[j] = ok ? ld_g1(i + j) : 0.f; mv[j] = ok ? m[i + j] : 0.f; vv[j] = ok ? v[i + j] : 0.f;
-      }
-    }
+  // the arithmetic and the stores of one float4 whose operands are loaded; `full`: all four elements exist
+  auto finish = [&](const long i, const bool full, float pv[4], const float gv[4], float mv[4], float vv[4]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float gg = k.wd != 0.f ? __builtin_fmaf(k.wd, pv[j], gv[j]) : gv[j];
@@ -124,37 +79,33 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamK k) {
       const float denom = __builtin_sqrtf(vv[j]) / sqrt_bc2 + k.eps;
       pv[j] = pv[j] - step_size * (mv[j] / denom);
     }
-    if (full) {
-      *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-      *reinterpret_cast<float4*>(m + i) = make_float4(mv[0], mv[1], mv[2], mv[3]);
-      *reinterpret_cast<float4*>(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-    } else {
+    st4(p, i, n, full, pv);
+    st4(m, i, n, full, mv);
+    st4(v, i, n, full, vv);
+  };
+  if (whole) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (i + j < n) { p[i + j] = pv[j]; m[i + j] = mv[j]; v[i + j] = vv[j]; }
+    for (int it = 0; it < kStreamIters; ++it)
+      finish(base + ((long)it * 256 + threadIdx.x) * 4, true, pw[it], gw[it], mw[it], vw[it]);
+  } else {
+#pragma unroll
+    for (int it = 0; it < kStreamIters; ++it) {
+      const long i = base + ((long)it * 256 + threadIdx.x) * 4;
+      if (i >= n) break;
+      const bool full = i + 3 < n;
+      float pv[4], gv[4], mv[4], vv[4];
+      ld4(p, i, n, full, pv);
+      ld4(g, i, n, full, gv);
+      ld4(m, i, n, full, mv);
+      ld4(v, i, n, full, vv);
+      finish(i, full, pv, gv, mv, vv);
     }
   }
-  // every wave of the block has read *step_dev (top of the kernel) before thread 0 announces the block's arrival:
-  // the last arriver overwrites the word, and a wave that had not loaded it yet would use step + 2
-  if (k.ticket) __syncthreads();
-  if (k.ticket && threadIdx.x == 0) {
-    // two-level arrival count: device-scope atomics on ONE word serialise at the memory side (1170 of them were a
-    // ~4 us tail on this 24 us kernel); blocks count in 8 groups (word 1 + blockIdx % 8), each group's last arriver
-    // counts once on word 0
-    const uint32_t g = blockIdx.x & 7u;
-    const uint32_t in_group = (gridDim.x - g + 7u) >> 3;
-    const uint32_t tk = __hip_atomic_fetch_add(k.ticket + 1 + g, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tk == in_group - 1u) {
-      k.ticket[1 + g] = 0u;                               // ready for the next launch
-      const uint32_t groups = gridDim.x < 8u ? gridDim.x : 8u;
-      const uint32_t top = __hip_atomic_fetch_add(k.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (top == groups - 1u) {
-        *k.step_dev = step;
-        if (k.bump) *k.bump += k.bump_by;
-        k.ticket[0] = 0u;
-      }
-    }
-  }
+  if (k.ticket)
+    last_block(k.ticket, [&] {
+      *k.step_dev = step;
+      if (k.bump) *k.bump += k.bump_by;
+    });
 }
 
 // one thread per (sample, batch row)
@@ -184,7 +135,7 @@ extern "C" int bnn_adam_step(const bnn_adam_args* a, void* stream_) {
   }
   for (int t = 0; t < a->n_tensors; ++t) {
     if (!a->param[t] || !a->grad[t] || !a->exp_avg[t] || !a->exp_avg_sq[t]) return BNN_ERR_NULL;
-    const int st = k.list.add(a->numel[t], kAdamChunk);
+    const int st = k.list.add(a->numel[t], kStreamChunk);
     if (st != BNN_OK) return st;
     const uintptr_t al = reinterpret_cast<uintptr_t>(a->param[t]) | reinterpret_cast<uintptr_t>(a->grad[t]) |
                          reinterpret_cast<uintptr_t>(a->exp_avg[t]) | reinterpret_cast<uintptr_t>(a->exp_avg_sq[t]);

@@ -235,8 +235,6 @@ __global__ __launch_bounds__(kHistBlock) void hist_fold_kernel(HistK k) {
   }
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 // the argument checks shared by the query and the launch; fills the kernels' block (first_block) on success
 int hist_plan(const bnn_param_hist_args* a, HistK& k) {
   if (!a) return BNN_ERR_NULL;

@@ -208,8 +208,6 @@ __global__ __launch_bounds__(kPredBlock) void mc_predictive_quantile_kernel(cons
 
 using namespace bnn;
 
-static bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 extern "C" int bnn_mc_predictive(const bnn_mc_predictive_args* a, void* stream_) {
   if (!a) return BNN_ERR_NULL;
   if (a->struct_bytes != sizeof(bnn_mc_predictive_args)) return BNN_ERR_ABI;

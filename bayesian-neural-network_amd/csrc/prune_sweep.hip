@@ -240,8 +240,6 @@ __global__ __launch_bounds__(kTailBlock) void prune_tail_kernel(bnn_prune_tail_a
   }
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 constexpr size_t kSelStateBytes = (sizeof(SelState) + 15) & ~size_t(15);
 
 }  // namespace

@@ -225,8 +225,6 @@ __global__ __launch_bounds__(kThreads) void pruned_fwd_kernel(PrunedParams p) {
   }
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 template <typename T, typename YT>
 void launch_levels(const PrunedParams& p, int levels, dim3 grid, hipStream_t st) {
   switch (levels) {

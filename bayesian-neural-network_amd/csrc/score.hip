@@ -347,8 +347,6 @@ __global__ __launch_bounds__(kScoreBlock) void mc_score_fold_kernel(const unsign
 }
 static_assert(kMaxWords <= kScoreBlock, "the fold is one word per thread");
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 bool shape_ok(int G, int B, int C) {
   return G > 0 && B > 0 && C > 0 && (int64_t)G * B <= INT32_MAX && (int64_t)B * C <= INT32_MAX && (int64_t)G * B * C <= ((int64_t)1 << 40);
 }

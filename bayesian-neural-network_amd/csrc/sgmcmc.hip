@@ -5,7 +5,7 @@
 //
 // The step is pure streaming like Adam's: SGLD reads p, g and writes p (12 B / parameter), SGHMC adds v read and written
 // (20 B), a collecting step 4 B more; the noise is generated on chip.  One block = one 4096-element chunk of one tensor,
-// 16-byte accesses, the step word advanced by the launch's last block (optim.hip's ticketed hand-off).
+// 16-byte accesses, the step word advanced by the launch's last block (bnn_stream.h's ticketed hand-off).
 //
 // The bank forward is K5's product per member: dense_tile.h's 64 x 64 tile core (the same stage image, the same MFMA chain
 // over 32-wide k stages as K5, so a member's output equals bnn_dense_fwd on that member's weights bit for bit), one tile of
@@ -13,21 +13,14 @@
 // is ordered (member, column tile, row tile) and dealt to the XCDs in contiguous ranges, so that the row tiles that share a
 // weight tile run on one XCD and meet in its L2.
 #include "bnn_device.h"
+#include "bnn_stream.h"
 #include "dense_tile.h"
 #include "../../include/bnn_hip.h"
 
 namespace bnn {
 namespace {
 
-constexpr int kSgChunk = 4096;
 constexpr uint32_t kSgWord3 = 3u;       // counter word 3 of the SG-MCMC noise stream (include/bnn_hip.h F19)
-
-// the four N(0,1) values of elements 4 group .. 4 group + 3 of tensor t at chain step k
-__device__ __forceinline__ void sgmcmc_eps4(uint32_t group, uint32_t k, uint32_t t, uint32_t k0, uint32_t k1, float out[4]) {
-  const uint4 r = philox4x32<>(make_uint4(group, k, t, kSgWord3), k0, k1);
-  box_muller(r.x, r.y, out[0], out[1]);
-  box_muller(r.z, r.w, out[2], out[3]);
-}
 
 struct SgK {
   float* p[BNN_SGMCMC_MAX_TENSORS];
@@ -57,7 +50,7 @@ __device__ __forceinline__ void sg_update(float& p, float& v, float g, float e, 
 template <bool MOM>
 __global__ __launch_bounds__(256) void sgmcmc_kernel(const SgK k) {
   long base;
-  const int t = k.list.find((int)blockIdx.x, kSgChunk, base);
+  const int t = k.list.find((int)blockIdx.x, kStreamChunk, base);
   const long n = k.list.numel[t];
   float* __restrict__ p = k.p[t];
   const float* __restrict__ g = k.g[t];
@@ -71,76 +64,33 @@ __global__ __launch_bounds__(256) void sgmcmc_kernel(const SgK k) {
   float* __restrict__ slot = collect ? k.bank + (long)(collected % k.capacity) * k.stride + k.off[t] : nullptr;
   const float a = row.x, b = row.y, c = row.z;
 #pragma unroll
-  for (int it = 0; it < kSgChunk / (256 * 4); ++it) {
+  for (int it = 0; it < kStreamIters; ++it) {
     const long i = base + ((long)it * 256 + threadIdx.x) * 4;
     if (i >= n) break;
     const bool full = i + 3 < n;
     float pv[4], gv[4], vv[4] = {0.f, 0.f, 0.f, 0.f}, ev[4] = {0.f, 0.f, 0.f, 0.f};
-    if (full) {
-      const float4 q = *reinterpret_cast<const float4*>(p + i), r = *reinterpret_cast<const float4*>(g + i);
-      pv[0] = q.x; pv[1] = q.y; pv[2] = q.z; pv[3] = q.w;
-      gv[0] = r.x; gv[1] = r.y; gv[2] = r.z; gv[3] = r.w;
-      if (MOM) {
-        const float4 m = *reinterpret_cast<const float4*>(v + i);
-        vv[0] = m.x; vv[1] = m.y; vv[2] = m.z; vv[3] = m.w;
-      }
-      if (k.eps_mode == BNN_EPS_MEMORY) {
-        const float4 m = *reinterpret_cast<const float4*>(ep + i);
-        ev[0] = m.x; ev[1] = m.y; ev[2] = m.z; ev[3] = m.w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool ok = i + j < n;
-        pv[j] = ok ? p[i + j] : 0.f;
-        gv[j] = ok ? g[i + j] : 0.f;
-        if (MOM) vv[j] = ok ? v[i + j] : 0.f;
-        if (k.eps_mode == BNN_EPS_MEMORY) ev[j] = ok ? ep[i + j] : 0.f;
-      }
-    }
-    if (k.eps_mode == BNN_EPS_PHILOX) sgmcmc_eps4((uint32_t)(i >> 2), step, (uint32_t)t, k.k0, k.k1, ev);
+    ld4(p, i, n, full, pv);
+    ld4(g, i, n, full, gv);
+    if (MOM) ld4(v, i, n, full, vv);
+    if (k.eps_mode == BNN_EPS_MEMORY) ld4(ep, i, n, full, ev);
+    if (k.eps_mode == BNN_EPS_PHILOX) philox_normal4((uint32_t)(i >> 2), step, (uint32_t)t, k.k0, k.k1, ev, kSgWord3);
 #pragma unroll
     for (int j = 0; j < 4; ++j) sg_update(pv[j], vv[j], gv[j], ev[j], k.grad_scale, k.tau, a, b, c);
-    if (full) {
-      const float4 q = make_float4(pv[0], pv[1], pv[2], pv[3]);
-      *reinterpret_cast<float4*>(p + i) = q;
-      if (MOM) *reinterpret_cast<float4*>(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-      if (collect) *reinterpret_cast<float4*>(slot + i) = q;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (i + j < n) {
-          p[i + j] = pv[j];
-          if (MOM) v[i + j] = vv[j];
-          if (collect) slot[i + j] = pv[j];
-        }
-    }
+    st4(p, i, n, full, pv);
+    if (MOM) st4(v, i, n, full, vv);
+    if (collect) st4(slot, i, n, full, pv);
   }
-  // optim.hip's hand-off: every wave has read the words before thread 0 announces the block; blocks count in 8 groups
-  // (ticket word 1 + blockIdx % 8), each group's last arriver counts once on word 0, the last of those advances the words
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t grp = blockIdx.x & 7u;
-    const uint32_t in_group = (gridDim.x - grp + 7u) >> 3;
-    const uint32_t tk = __hip_atomic_fetch_add(k.ticket + 1 + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tk == in_group - 1u) {
-      k.ticket[1 + grp] = 0u;
-      const uint32_t groups = gridDim.x < 8u ? gridDim.x : 8u;
-      const uint32_t top = __hip_atomic_fetch_add(k.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (top == groups - 1u) {
-        *k.step = step + 1u;
-        if (collect) *k.collected = collected + 1u;
-        k.ticket[0] = 0u;
-      }
-    }
-  }
+  last_block(k.ticket, [&] {
+    *k.step = step + 1u;
+    if (collect) *k.collected = collected + 1u;
+  });
 }
 
 __global__ void sgmcmc_noise_kernel(float* __restrict__ out, uint32_t k0, uint32_t k1, uint32_t tensor, uint32_t step, long numel) {
   const long groups = (numel + 3) >> 2;
   for (long gi = (long)blockIdx.x * blockDim.x + threadIdx.x; gi < groups; gi += (long)gridDim.x * blockDim.x) {
     float e[4];
-    sgmcmc_eps4((uint32_t)gi, step, tensor, k0, k1, e);
+    philox_normal4((uint32_t)gi, step, tensor, k0, k1, e, kSgWord3);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       if (4 * gi + j < numel) out[4 * gi + j] = e[j];
@@ -225,8 +175,6 @@ __global__ __launch_bounds__(kThreads) void bank_fwd_kernel(const BankK k) {
   });
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 template <typename T, typename XT, typename YT>
 void launch_bank(const BankK& k, hipStream_t st) {
   const unsigned blocks = 8u * (unsigned)((k.total + 7) / 8);      // (xcd_work_item: 8 equal ranges)
@@ -256,17 +204,10 @@ extern "C" int bnn_sgmcmc_step(const bnn_sgmcmc_args* a, void* stream_) {
   if (a->n_tensors <= 0 || a->n_tensors > BNN_SGMCMC_MAX_TENSORS || a->table_rows <= 0) return BNN_ERR_SHAPE;
   if (a->bank && a->capacity <= 0) return BNN_ERR_SHAPE;
   SgK k;
-  long off = 0;
   for (int t = 0; t < BNN_SGMCMC_MAX_TENSORS; ++t) {
-    k.p[t] = nullptr; k.g[t] = nullptr; k.v[t] = nullptr; k.eps[t] = nullptr; k.off[t] = 0;
+    k.p[t] = nullptr; k.g[t] = nullptr; k.v[t] = nullptr; k.eps[t] = nullptr;
   }
-  for (int t = 0; t < a->n_tensors; ++t) {
-    if (a->numel[t] > ((int64_t)1 << 34)) return BNN_ERR_SHAPE;      // (the stream's group index is 32 bits)
-    const int st = k.list.add(a->numel[t], kSgChunk);
-    if (st != BNN_OK) return st;
-    k.off[t] = off;
-    off += (a->numel[t] + 63) / 64 * 64;
-  }
+  if (const int st = state_offsets(k.list, a->n_tensors, a->numel, k.off, k.stride); st != BNN_OK) return st;
   if ((unsigned)a->eps_mode > (unsigned)BNN_EPS_ZERO) return BNN_ERR_ENUM;
   if (!a->table || !a->step || !a->ticket || (a->bank && !a->collected)) return BNN_ERR_NULL;
   const bool mom = a->momentum[0] != nullptr;
@@ -285,7 +226,7 @@ extern "C" int bnn_sgmcmc_step(const bnn_sgmcmc_args* a, void* stream_) {
   k.L = (uint32_t)a->table_rows; k.burn_in = a->burn_in; k.capacity = a->bank ? (uint32_t)a->capacity : 1u;
   k.k0 = (uint32_t)a->seed; k.k1 = (uint32_t)(a->seed >> 32);
   k.eps_mode = a->eps_mode; k.grad_scale = a->grad_scale; k.tau = a->tau;
-  k.stride = off; k.bank = a->bank; k.step = a->step; k.collected = a->collected; k.ticket = a->ticket;
+  k.bank = a->bank; k.step = a->step; k.collected = a->collected; k.ticket = a->ticket;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
   if (mom) hipLaunchKernelGGL(sgmcmc_kernel<true>, dim3((unsigned)chunks), dim3(256), 0, stream, k);
   else hipLaunchKernelGGL(sgmcmc_kernel<false>, dim3((unsigned)chunks), dim3(256), 0, stream, k);

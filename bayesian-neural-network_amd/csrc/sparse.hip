@@ -247,8 +247,6 @@ __global__ __launch_bounds__(256) void sparse_fwd_kernel(bnn_sparse_fwd_args a, 
   }
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 // rows of a group: the largest of 32, 16, 8, 4 that gives the launch >= 1024 blocks (4 if none does)
 int row_group(int out, long other_blocks) {
   for (int rg = kMaxRG; rg > 4; rg >>= 1)

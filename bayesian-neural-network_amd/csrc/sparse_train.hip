@@ -447,8 +447,6 @@ __global__ __launch_bounds__(256) void sparse_sigma_kernel(const bnn_sparse_sigm
     sigma[i] = (!keep || keep[i]) ? softplus(rho[i]) : 0.f;
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 // columns of a group: the largest of 32, 16, 8, 4 that gives the launch >= 1024 blocks (4 if none does)
 int col_group(int in, long other_blocks) {
   for (int cg = kMaxCG; cg > 4; cg >>= 1)

@@ -41,8 +41,6 @@ long chunk_columns(long stride) {
   return 64 * (tiles < kSvChunk / kSvTile ? tiles : (long)(kSvChunk / kSvTile));
 }
 
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
-
 __host__ __device__ inline int pair_index(int i, int j, int M) { return i * (2 * M - i - 1) / 2 + (j - i - 1); }   // i < j
 
 // ------------------------------------------------------------------------------------------------------------- distances

@@ -6,19 +6,19 @@
 //
 // The step is pure streaming like bnn_sgd_step: p, g read and p written (12 B / parameter), + 8 B with a momentum buffer,
 // + 16 B (mean, m2 read and written) + 4 B (one row of D) on a collecting step.  One block = one 4096-element chunk of one
-// tensor, 16-byte accesses, the step and count words advanced by the launch's last block (optim.hip's ticketed hand-off).
+// tensor, 16-byte accesses, the step and count words advanced by the launch's last block (bnn_stream.h's ticketed hand-off).
 //
 // The draw holds a thread's float4 of mean, sqrt(var) and the Keff rows of D in registers and loops over the members:
 // (2 + Keff + m) * 4 B per element and launch whatever m; per member and float4 one Philox call, 4 (Keff + 2) fmas and one
 // 16-byte store.  z2 (m x Keff, shared by every element) is formed once per block into LDS.  A network of few chunks has its
 // members split over blockIdx.y (each group re-reads the moments, out of the caches at that size) so that the grid fills the chip.
 #include "bnn_device.h"
+#include "bnn_stream.h"
 #include "../../include/bnn_hip.h"
 
 namespace bnn {
 namespace {
 
-constexpr int kSwChunk = 4096;
 constexpr uint32_t kSwWord3 = 5u;       // counter word 3 of the SWAG noise streams (include/bnn_hip.h F22)
 constexpr int kMaxT = BNN_SGMCMC_MAX_TENSORS;
 
@@ -43,7 +43,7 @@ struct SwStepK {
 template <bool MOM>
 __global__ __launch_bounds__(256) void swag_step_kernel(const SwStepK k) {
   long base;
-  const int t = k.list.find((int)blockIdx.x, kSwChunk, base);
+  const int t = k.list.find((int)blockIdx.x, kStreamChunk, base);
   const long n = k.list.numel[t];
   float* __restrict__ p = k.p[t];
   const float* __restrict__ g = k.g[t];
@@ -60,36 +60,17 @@ __global__ __launch_bounds__(256) void swag_step_kernel(const SwStepK k) {
   const float nlr = -(k.lr_dev ? *k.lr_dev : k.lr);
   const float wd = k.wd, mu = k.mu;
 #pragma unroll
-  for (int it = 0; it < kSwChunk / (256 * 4); ++it) {
+  for (int it = 0; it < kStreamIters; ++it) {
     const long i = base + ((long)it * 256 + threadIdx.x) * 4;
     if (i >= n) break;
     const bool full = i + 3 < n;
     float pv[4], gv[4], vv[4] = {0.f, 0.f, 0.f, 0.f}, av[4] = {0.f, 0.f, 0.f, 0.f}, sv[4] = {0.f, 0.f, 0.f, 0.f}, dv[4];
-    if (full) {
-      const float4 q = *reinterpret_cast<const float4*>(p + i), w = *reinterpret_cast<const float4*>(g + i);
-      pv[0] = q.x; pv[1] = q.y; pv[2] = q.z; pv[3] = q.w;
-      gv[0] = w.x; gv[1] = w.y; gv[2] = w.z; gv[3] = w.w;
-      if (MOM) {
-        const float4 m = *reinterpret_cast<const float4*>(v + i);
-        vv[0] = m.x; vv[1] = m.y; vv[2] = m.z; vv[3] = m.w;
-      }
-      if (collect) {
-        const float4 a = *reinterpret_cast<const float4*>(mean + i), s = *reinterpret_cast<const float4*>(m2 + i);
-        av[0] = a.x; av[1] = a.y; av[2] = a.z; av[3] = a.w;
-        sv[0] = s.x; sv[1] = s.y; sv[2] = s.z; sv[3] = s.w;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const bool ok = i + j < n;
-        pv[j] = ok ? p[i + j] : 0.f;
-        gv[j] = ok ? g[i + j] : 0.f;
-        if (MOM) vv[j] = ok ? v[i + j] : 0.f;
-        if (collect) {
-          av[j] = ok ? mean[i + j] : 0.f;
-          sv[j] = ok ? m2[i + j] : 0.f;
-        }
-      }
+    ld4(p, i, n, full, pv);
+    ld4(g, i, n, full, gv);
+    if (MOM) ld4(v, i, n, full, vv);
+    if (collect) {
+      ld4(mean, i, n, full, av);
+      ld4(m2, i, n, full, sv);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -104,46 +85,18 @@ __global__ __launch_bounds__(256) void swag_step_kernel(const SwStepK k) {
         sv[j] = __builtin_fmaf(d, dv[j], sv[j]);
       }
     }
-    if (full) {
-      *reinterpret_cast<float4*>(p + i) = make_float4(pv[0], pv[1], pv[2], pv[3]);
-      if (MOM) *reinterpret_cast<float4*>(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-      if (collect) {
-        *reinterpret_cast<float4*>(mean + i) = make_float4(av[0], av[1], av[2], av[3]);
-        *reinterpret_cast<float4*>(m2 + i) = make_float4(sv[0], sv[1], sv[2], sv[3]);
-        if (row) *reinterpret_cast<float4*>(row + i) = make_float4(dv[0], dv[1], dv[2], dv[3]);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (i + j < n) {
-          p[i + j] = pv[j];
-          if (MOM) v[i + j] = vv[j];
-          if (collect) {
-            mean[i + j] = av[j];
-            m2[i + j] = sv[j];
-            if (row) row[i + j] = dv[j];
-          }
-        }
+    st4(p, i, n, full, pv);
+    if (MOM) st4(v, i, n, full, vv);
+    if (collect) {
+      st4(mean, i, n, full, av);
+      st4(m2, i, n, full, sv);
+      if (row) st4(row, i, n, full, dv);
     }
   }
-  // optim.hip's hand-off: every wave has read the words before thread 0 announces the block; blocks count in 8 groups
-  // (ticket word 1 + blockIdx % 8), each group's last arriver counts once on word 0, the last of those advances the words
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t grp = blockIdx.x & 7u;
-    const uint32_t in_group = (gridDim.x - grp + 7u) >> 3;
-    const uint32_t tk = __hip_atomic_fetch_add(k.ticket + 1 + grp, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tk == in_group - 1u) {
-      k.ticket[1 + grp] = 0u;
-      const uint32_t groups = gridDim.x < 8u ? gridDim.x : 8u;
-      const uint32_t top = __hip_atomic_fetch_add(k.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (top == groups - 1u) {
-        *k.step = step + 1u;
-        if (collect) *k.count = cnt + 1u;
-        k.ticket[0] = 0u;
-      }
-    }
-  }
+  last_block(k.ticket, [&] {
+    *k.step = step + 1u;
+    if (collect) *k.count = cnt + 1u;
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------- the draw
@@ -164,19 +117,12 @@ struct SwSampleK {
   float c_lr[BNN_SWAG_MAX_RANK + 1];
 };
 
-// the four N(0,1) values of group `group` of stream `t` (a tensor, or BNN_SGMCMC_MAX_TENSORS for z2) of draw q
-__device__ __forceinline__ void swag_eps4(uint32_t group, uint32_t q, uint32_t t, uint32_t k0, uint32_t k1, float out[4]) {
-  const uint4 r = philox4x32<>(make_uint4(group, q, t, kSwWord3), k0, k1);
-  box_muller(r.x, r.y, out[0], out[1]);
-  box_muller(r.z, r.w, out[2], out[3]);
-}
-
 // KB: a compile-time bound of the rank (a multiple of 4): the rows of D a thread holds are registers, never an indexed array
 template <int KB>
 __global__ __launch_bounds__(256) void swag_sample_kernel(const SwSampleK k) {
   __shared__ float4 z2s[BNN_SWAG_MAX_MEMBERS][BNN_SWAG_MAX_RANK / 4];
   long base;
-  const int t = k.list.find((int)blockIdx.x, kSwChunk, base);
+  const int t = k.list.find((int)blockIdx.x, kStreamChunk, base);
   const long n = k.list.numel[t];
   const uint32_t cnt = *k.count;
   const uint32_t Keff = k.low_rank ? (cnt < k.K ? cnt : k.K) : 0u;
@@ -191,7 +137,7 @@ __global__ __launch_bounds__(256) void swag_sample_kernel(const SwSampleK k) {
       const uint32_t qq = w / (uint32_t)(KB / 4), q = q0 + qq, gq = w % (uint32_t)(KB / 4);
       float e[4] = {0.f, 0.f, 0.f, 0.f};
       if (k.eps_mode == BNN_EPS_PHILOX) {
-        swag_eps4(gq, k.sample_base + q, (uint32_t)kMaxT, k.k0, k.k1, e);
+        philox_normal4(gq, k.sample_base + q, (uint32_t)kMaxT, k.k0, k.k1, e, kSwWord3);   // stream kMaxT: z2
       } else if (k.eps_mode == BNN_EPS_MEMORY) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -207,26 +153,19 @@ __global__ __launch_bounds__(256) void swag_sample_kernel(const SwSampleK k) {
   const float* __restrict__ z1 = k.z1 + k.off[t];
   float* __restrict__ out = k.bank + (long)k.first * k.stride + k.off[t];
 #pragma unroll 1
-  for (int it = 0; it < kSwChunk / (256 * 4); ++it) {
+  for (int it = 0; it < kStreamIters; ++it) {
     const long i = base + ((long)it * 256 + threadIdx.x) * 4;
     if (i >= n) break;
     const bool full = i + 3 < n;
     float av[4], cs[4];
     float4 D[KB > 0 ? KB : 1];
+    ld4(mean, i, n, full, av);
+    ld4(m2, i, n, full, cs);
     if (full) {
-      const float4 a = *reinterpret_cast<const float4*>(mean + i), s = *reinterpret_cast<const float4*>(m2 + i);
-      av[0] = a.x; av[1] = a.y; av[2] = a.z; av[3] = a.w;
-      cs[0] = s.x; cs[1] = s.y; cs[2] = s.z; cs[3] = s.w;
 #pragma unroll
       for (int j = 0; j < KB; ++j)
         if ((uint32_t)j < Keff) D[j] = *reinterpret_cast<const float4*>(dev + (long)j * k.stride + i);
     } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const bool ok = i + e < n;
-        av[e] = ok ? mean[i + e] : 0.f;
-        cs[e] = ok ? m2[i + e] : 0.f;
-      }
 #pragma unroll
       for (int j = 0; j < KB; ++j)
         if ((uint32_t)j < Keff) {
@@ -239,7 +178,6 @@ __global__ __launch_bounds__(256) void swag_sample_kernel(const SwSampleK k) {
 #pragma unroll 1
     for (uint32_t qq = 0; qq < mq; ++qq) {
       const uint32_t q = q0 + qq;
-      float* __restrict__ dst = out + (long)q * k.stride + i;
       float th[4];
       if (k.eps_mode == BNN_EPS_ZERO) {
 #pragma unroll
@@ -247,16 +185,9 @@ __global__ __launch_bounds__(256) void swag_sample_kernel(const SwSampleK k) {
       } else {
         float z[4];
         if (k.eps_mode == BNN_EPS_PHILOX) {
-          swag_eps4((uint32_t)(i >> 2), k.sample_base + q, (uint32_t)t, k.k0, k.k1, z);
+          philox_normal4((uint32_t)(i >> 2), k.sample_base + q, (uint32_t)t, k.k0, k.k1, z, kSwWord3);
         } else {
-          const float* __restrict__ zr = z1 + (long)q * k.stride + i;
-          if (full) {
-            const float4 zz = *reinterpret_cast<const float4*>(zr);
-            z[0] = zz.x; z[1] = zz.y; z[2] = zz.z; z[3] = zz.w;
-          } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) z[e] = i + e < n ? zr[e] : 0.f;
-          }
+          ld4(z1 + (long)q * k.stride, i, n, full, z);
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) th[e] = __builtin_fmaf(cs[e], z[e], av[e]);
@@ -283,18 +214,10 @@ __global__ __launch_bounds__(256) void swag_sample_kernel(const SwSampleK k) {
           for (int e = 0; e < 4; ++e) th[e] = __builtin_fmaf(clr, acc[e], th[e]);
         }
       }
-      if (full) {
-        *reinterpret_cast<float4*>(dst) = make_float4(th[0], th[1], th[2], th[3]);
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (i + e < n) dst[e] = th[e];
-      }
+      st4(out + (long)q * k.stride, i, n, full, th);
     }
   }
 }
-
-bool misaligned(const void* q, uintptr_t al) { return (reinterpret_cast<uintptr_t>(q) & (al - 1)) != 0; }
 
 template <int KB>
 void launch_sample(const SwSampleK& k, int chunks, hipStream_t st) {
@@ -313,17 +236,10 @@ extern "C" int bnn_swag_step(const bnn_swag_step_args* a, void* stream_) {
     return BNN_ERR_SHAPE;
   if (!(a->momentum_factor >= 0.0) || !(a->weight_decay >= 0.0) || !(a->lr >= 0.0)) return BNN_ERR_SHAPE;
   SwStepK k;
-  long off = 0;
   for (int t = 0; t < BNN_SGMCMC_MAX_TENSORS; ++t) {
-    k.p[t] = nullptr; k.g[t] = nullptr; k.v[t] = nullptr; k.off[t] = 0;
+    k.p[t] = nullptr; k.g[t] = nullptr; k.v[t] = nullptr;
   }
-  for (int t = 0; t < a->n_tensors; ++t) {
-    if (a->numel[t] > ((int64_t)1 << 34)) return BNN_ERR_SHAPE;
-    const int st = k.list.add(a->numel[t], kSwChunk);
-    if (st != BNN_OK) return st;
-    k.off[t] = off;
-    off += (a->numel[t] + 63) / 64 * 64;
-  }
+  if (const int st = state_offsets(k.list, a->n_tensors, a->numel, k.off, k.stride); st != BNN_OK) return st;
   if (!a->step || !a->count || !a->ticket || !a->mean || !a->m2 || (a->rank > 0 && !a->dev)) return BNN_ERR_NULL;
   const bool mom = a->momentum[0] != nullptr;
   uintptr_t al = reinterpret_cast<uintptr_t>(a->mean) | reinterpret_cast<uintptr_t>(a->m2) |
@@ -337,7 +253,7 @@ extern "C" int bnn_swag_step(const bnn_swag_step_args* a, void* stream_) {
     return BNN_ERR_ALIGN;
   const int chunks = k.list.finish();
   k.lr = (float)a->lr; k.mu = (float)a->momentum_factor; k.wd = (float)a->weight_decay; k.lr_dev = a->lr_device;
-  k.start = a->start; k.every = a->every; k.K = (uint32_t)a->rank; k.stride = off;
+  k.start = a->start; k.every = a->every; k.K = (uint32_t)a->rank;
   k.mean = a->mean; k.m2 = a->m2; k.dev = a->rank > 0 ? a->dev : nullptr;
   k.step = a->step; k.count = a->count; k.ticket = a->ticket;
   hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
@@ -355,15 +271,7 @@ extern "C" int bnn_swag_sample(const bnn_swag_sample_args* a, void* stream_) {
       (long)a->first + a->members > a->capacity || (a->low_rank && a->rank == 0) || !(a->var_clamp >= 0.f))
     return BNN_ERR_SHAPE;
   SwSampleK k;
-  long off = 0;
-  for (int t = 0; t < BNN_SGMCMC_MAX_TENSORS; ++t) k.off[t] = 0;
-  for (int t = 0; t < a->n_tensors; ++t) {
-    if (a->numel[t] > ((int64_t)1 << 34)) return BNN_ERR_SHAPE;
-    const int st = k.list.add(a->numel[t], kSwChunk);
-    if (st != BNN_OK) return st;
-    k.off[t] = off;
-    off += (a->numel[t] + 63) / 64 * 64;
-  }
+  if (const int st = state_offsets(k.list, a->n_tensors, a->numel, k.off, k.stride); st != BNN_OK) return st;
   if ((unsigned)a->eps_mode > (unsigned)BNN_EPS_ZERO) return BNN_ERR_ENUM;
   const bool mem = a->eps_mode == BNN_EPS_MEMORY, lowr = a->low_rank != 0;
   if (!a->mean || !a->m2 || !a->count || !a->bank || (lowr && !a->dev) || (mem && !a->z1) || (mem && lowr && !a->z2))
@@ -375,7 +283,7 @@ extern "C" int bnn_swag_sample(const bnn_swag_sample_args* a, void* stream_) {
   const int chunks = k.list.finish();
   k.mean = a->mean; k.m2 = a->m2; k.dev = lowr ? a->dev : nullptr; k.count = a->count;
   k.z1 = mem ? a->z1 : nullptr; k.z2 = mem && lowr ? a->z2 : nullptr;
-  k.bank = a->bank; k.stride = off;
+  k.bank = a->bank;
   // a small network has few chunks: the members are then split over blockIdx.y (halved while under two blocks per CU and two
   // members per block), each group re-reading the moments -- out of L2 / the Infinity Cache at that size.  Speed only: a
   // member's values do not depend on the split.

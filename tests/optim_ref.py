@@ -66,7 +66,7 @@ import torch
 U = 2.0 ** -24
 TINY = 2.0 ** -150
 F32, F64 = np.float32, np.float64
-CHUNK = 4096              # kAdamChunk, kSgdChunk
+CHUNK = 4096              # kStreamChunk (csrc/bnn_stream.h)
 MAX_TENSORS = 16          # BNN_ADAM_MAX_TENSORS, BNN_SGD_MAX_TENSORS
 GUARD = 64                # floats of sentinel before and after every tensor
 SENTINEL = 0xFFC5A5A5     # a NaN with a payload: an out-of-range READ shows as well (0xFFC5 is a bf16 NaN too)

@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 import bnn_hip
 import ivon_ref as R
+import optim_ref as O
 from bnn_hip import _lib as L
 from bnn_hip import ivon, ops, sgmcmc
 from bnn_hip.ops import BnnHipError
@@ -138,6 +139,24 @@ def test_draw_and_step_on_given_noise_bit_for_bit(dev, S, clip, lr_word):
         u = np.concatenate([(ch.mean[sl] - ch.p[t].reshape(-1)) / np.float32(ch.lr) for t, sl in enumerate(ch.sl)])
         at = np.isclose(np.abs(u), 0.05, rtol=1e-4)
         assert 0.02 < at.mean() < 0.98, at.mean()
+
+
+@pytest.mark.parametrize("blocks", sorted(O.GRIDS))
+@pytest.mark.parametrize("S", [1, 2])
+def test_draw_and_step_on_given_noise_bit_for_bit_at_every_grid(dev, blocks, S):
+    """The step launch's last block (csrc/bnn_stream.h: 8 ticket groups, then word 0) at grids of 1, 2, 7, 8, 9, 16 and 17
+    blocks.  Three steps: after every launch the state is the restated chain's (_Device.check: the parameters, mean, hess,
+    avg_grad, the accumulators, the step word, the bits of the fp64 product, the zeroed ticket), the step word has advanced
+    by exactly one per step launch and by nothing in a draw launch, and the product by one factor beta1."""
+    numels = O.GRIDS[blocks]
+    assert len(O.chunk_table(numels)) == blocks
+    rng, ch = _chain(numels, S, True, 6, 5)
+    d = _Device(dev, ch)
+    for k in range(3):
+        prod = ch.prod
+        _one_step(dev, rng, ch, d, numels, S, True, False, k)
+        assert sgmcmc._read_word(d.step) == 5 + k + 1 == ch.t and float(d.prod.item()) == ch.prod == prod * HYPER["beta1"], k
+        assert not d.ticket.any(), k
 
 
 def test_sixteen_tensors(dev):

@@ -12,6 +12,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import bnn_hip
+import optim_ref as O
 import sgmcmc_ref as R
 from bnn_hip import _lib as L
 from bnn_hip import ops, sgmcmc
@@ -113,6 +114,38 @@ def test_update_rule_bit_for_bit(dev, friction):
     ops.sgmcmc_step(b, dg, table=dtab, step=s2, ticket=t2, grad_scale=468.75, tau=0.5, eps_mode=L.EPS_MEMORY, momenta=bm, noise=zeros)
     for t in range(len(NUMELS)):
         assert torch.equal(a[t], b[t]) and not torch.equal(a[t], zp[t]) and (not mom or torch.equal(am[t], bm[t]))
+
+
+@pytest.mark.parametrize("blocks", sorted(O.GRIDS))
+@pytest.mark.parametrize("friction", [None, 0.3])
+def test_update_rule_bit_for_bit_at_every_grid(dev, friction, blocks):
+    """The launch's last block (csrc/bnn_stream.h: 8 ticket groups, then word 0) at grids of 1, 2, 7, 8, 9, 16 and 17 blocks.
+    Three launches, flags [0, 1, 1] behind a burn-in of 1 (one launch that does not collect, two that do, capacity 2): after
+    every launch the parameters, the momenta and the ring are the restated chain's, the step word has advanced by exactly one,
+    the collected word is the chain's and every ticket word is zero."""
+    numels = O.GRIDS[blocks]
+    assert len(O.chunk_table(numels)) == blocks
+    tab = R.table([0.013, 0.0021, 0.0034], temperature=0.9, friction=friction, flags=[0, 1, 1])
+    hp, dp = _tensors(dev, numels, 1, 0.3)
+    mom = friction is not None
+    dm = [torch.zeros_like(p) for p in dp] if mom else None
+    hbank = np.full((2, R.layout(numels)[1]), 7.0, dtype=np.float32)
+    dbank = torch.from_numpy(hbank.copy()).to(dev)
+    ch = R.Chain(hp, tab, grad_scale=468.75, tau=0.5, momentum=mom, burn_in=1, bank=hbank)
+    step, collected, ticket = _words(dev)
+    dtab = torch.from_numpy(tab).to(dev)
+    for k in range(3):
+        hg, dg = _tensors(dev, numels, 10 + k, 0.01)
+        he, de = _tensors(dev, numels, 20 + k)
+        ch.step(hg, he)
+        ops.sgmcmc_step(dp, dg, table=dtab, step=step, ticket=ticket, grad_scale=468.75, tau=0.5, eps_mode=L.EPS_MEMORY,
+                        momenta=dm, noise=de, burn_in=1, collected=collected, bank=dbank)
+        for t in range(len(numels)):
+            assert _same(dp[t], ch.p[t]), (k, t)
+            assert not mom or _same(dm[t], ch.v[t]), (k, t)
+        assert _same(dbank, hbank), k
+        assert sgmcmc._read_word(step) == k + 1 == ch.k and sgmcmc._read_word(collected) == k == ch.collected, k
+        assert not ticket.any(), k
 
 
 # ---------------------------------------------------------------------------------------------- 3. PHILOX = MEMORY

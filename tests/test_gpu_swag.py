@@ -11,6 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import bnn_hip
+import optim_ref as O
 import swag_ref as R
 from bnn_hip import _lib as L
 from bnn_hip import ops, sgmcmc, swag
@@ -99,6 +100,36 @@ def test_step_bit_for_bit(dev, K, momentum, wd):
     assert ch.collected_at == list(range(2, K + 4))
     if K:
         assert not np.isin(SENTINEL, hdev[:, :1]) and (hdev[:, 1:64] == SENTINEL).all()      # (every row written, no padding)
+
+
+@pytest.mark.parametrize("blocks", sorted(O.GRIDS))
+@pytest.mark.parametrize("momentum", [False, True])
+def test_step_bit_for_bit_at_every_grid(dev, blocks, momentum):
+    """The launch's last block (csrc/bnn_stream.h: 8 ticket groups, then word 0) at grids of 1, 2, 7, 8, 9, 16 and 17 blocks.
+    Three launches, start 1, every 1, rank 2 (one launch that does not collect, two that do): after every launch the
+    parameters, the momenta, the moments and the ring are the restated chain's, the step word has advanced by exactly one, the
+    count word is the chain's and every ticket word is zero."""
+    numels = O.GRIDS[blocks]
+    assert len(O.chunk_table(numels)) == blocks
+    lr, mu, wd, K = 0.05, 0.9, 1e-3, 2
+    hp, dp = _tensors(dev, numels, 1, 0.3)
+    hmean, hm2, hdev = _moment_buffers(numels, K)
+    dmean, dm2, ddev = _to(dev, hmean), _to(dev, hm2), _to(dev, hdev)
+    dm = [torch.zeros_like(p) for p in dp] if momentum else None
+    ch = R.Chain(hp, lr=lr, mu=mu, wd=wd, momentum=momentum, start=1, every=1, rank=K, mean=hmean, m2=hm2, dev=hdev)
+    step, count, ticket = _words(dev)
+    for k in range(3):
+        hg, dg = _tensors(dev, numels, 10 + k, 0.05)
+        ch.step(hg)
+        ops.swag_step(dp, dg, lr=lr, momentum=mu, weight_decay=wd, momenta=dm, start=1, every=1, mean=dmean, m2=dm2, dev=ddev,
+                      step=step, count=count, ticket=ticket)
+        for t in range(len(numels)):
+            assert _same(dp[t], ch.p[t]), (k, t)
+            assert not momentum or _same(dm[t], ch.v[t]), (k, t)
+        assert _same(dmean, hmean) and _same(dm2, hm2) and _same(ddev, hdev), k
+        assert sgmcmc._read_word(step) == k + 1 == ch.k and sgmcmc._read_word(count) == k == ch.n, k
+        assert not ticket.any(), k
+    assert ch.collected_at == [1, 2]
 
 
 def test_step_with_sixteen_tensors(dev):
