@@ -1,6 +1,7 @@
 """Training MLP / MLP_Dropout on the device (bnn_dense_fwd -> bnn_dense_loss -> bnn_dense_bwd -> bnn_sgd_step /
 bnn_adam_step, bnn_hip.dense_train.GraphedDenseTrainStep) against fp64 restatements on the restated dropout masks,
-against itself (graph replays vs eager launches) and against the reference's PyTorch loop."""
+against itself (graph replays vs eager launches) and against the reference's PyTorch loop.
+Layer-level accuracy of bnn_dense_fwd / bnn_dense_bwd, element by element, lives in tests/test_gpu_dense_layer.py."""
 import numpy as np
 import pytest
 import torch

@@ -1,6 +1,7 @@
 """MC dropout of MLP_Dropout on the device (bnn_dense_fwd / bnn_dropout_mask, MLP_Dropout.mc_forward / predict_mc /
 predictive / predictive_graph) against the numpy restatement of the kind-3 dropout map and fp64 torch forwards that
-apply the restated masks."""
+apply the restated masks.
+Layer-level accuracy of bnn_dense_fwd, element by element, lives in tests/test_gpu_dense_layer.py."""
 import numpy as np
 import pytest
 import torch
